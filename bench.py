@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- forecast-steps/sec (train) of the StemGNN hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps and prints the result line (the throughput, `ms_per_step`, the
+schedule self-check of engine.TrainStep).  `--dump-outputs DIR` writes what the last timed step left to its caller -- the
+loss, the updated parameters and the RMSprop state -- as float32 .npy files; the inputs depend only on the arguments, so two
+builds can be compared output for output.  Everything else the line can carry (described below: roofline objects, CPU
+baseline, side sections, the 20-step figure, the all-reduce timings) takes runs of its own and is measured with `--full` only.
 
 N > 1: one rank per GPU over RCCL.  Started under torch.distributed.run (RANK / WORLD_SIZE in the environment) it is
 one rank; started plainly with --gpus N it re-launches itself through torch.distributed.run with N ranks on 127.0.0.1.
@@ -17,7 +23,7 @@ carries the same step with the GLU forward and data-gradient products as split-b
 kernels (`bf16x2`, csrc/glu_fused_bf16.h; <= 3e-5 model-level error against north_star's 1e-4 bar) with its own `roofline`
 objects, and `bf16x3`; `--dtype bf16x2` makes that the main line instead.
 
-Rank 0 prints ONE JSON line: the throughput, a `roofline` object for the MFMA GEMM family with the largest summed GPU
+Rank 0 prints ONE JSON line: the throughput and, with `--full`, a `roofline` object for the MFMA GEMM family with the largest summed GPU
 time per step (each family timed live with HIP events on the launch stream; `roofline_families` lists all of them),
 at N=1 a `cpu_baseline` object (the real reference when /root/reference is mounted, else the oracle port, timed on this
 box's host cores) and `other_configs`: short single-GPU runs of the per-GPU shards of BASELINE.json configs[0],[2],[3],[4],
@@ -406,10 +412,28 @@ def cpu_baseline(cfg, budget_s=20.0):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-def run_training(cfg, steps, warmup, dev, world, rank, graph=True, T=12672, collective=None, extra=None, short=0):
+def dump_outputs(out_dir, model, opt, stepper):
+    """What the last train step hands its caller, as float32 .npy files: the loss, every parameter (model.parameters()
+    order, flattened and concatenated) and the RMSprop square averages (the optimizer's flat buffer) -- ~10 MB at the
+    headline shape."""
+    import numpy as np
+    import torch
+
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": stepper.loss, "params": torch.cat([p.detach().reshape(-1) for p in model.parameters()]),
+              "rmsprop_square_avg": opt.square_avg}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
+def run_training(cfg, steps, warmup, dev, world, rank, graph=True, T=12672, collective=None, extra=None, short=0,
+                 allreduce_timing=False, dump_dir=None):
     """Build model + resident series, run warmup + `steps` timed train steps; returns (elapsed_s, mode, final_loss).
     extra: a dict that receives `schedule` (engine.TrainStep's start-up self-check) and, with short > 0, `short_ms_per_step`:
-    a second timed region of `short` steps right behind the first (the driver's command line is --steps 20)."""
+    a second timed region of `short` steps right behind the first (the driver's command line is --steps 20).
+    allreduce_timing: with a process group, time the step's collectives on their own into extra["allreduce"].
+    dump_dir: rank 0 writes the last timed step's outputs there (dump_outputs) before anything else runs."""
     import torch
     import torch.distributed as dist
     from stemgnn_amd import Model, ops
@@ -455,6 +479,8 @@ def run_training(cfg, steps, warmup, dev, world, rank, graph=True, T=12672, coll
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, model, opt, stepper)
     if short:
         if dist.is_initialized():
             dist.barrier()
@@ -467,7 +493,7 @@ def run_training(cfg, steps, warmup, dev, world, rank, graph=True, T=12672, coll
             extra["short_ms_per_step"] = (time.perf_counter() - t1) / short * 1e3
     if extra is not None:
         extra["schedule"] = dict(stepper.schedule)
-    if dist.is_initialized() and extra is not None and stepper.bucket is not None:
+    if allreduce_timing and dist.is_initialized() and extra is not None and stepper.bucket is not None:
         # the data-parallel step's collectives alone, eager, on every rank together (outside the timed region; the gradient
         # buffer holds zeros after the fused optimizer step): the head range [0, split) is the one all-reduce the step EXPOSES
         # (behind the GRU weight gradients), the tail range rides on the side branch under the GRU recurrence
@@ -767,6 +793,10 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss, parameters and RMSprop state "
+                                                          "as float32 DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: roofline objects, "
+                                                        "CPU baseline, side sections, 20-step figure, all-reduce timings")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true", help="skip every side section (other_configs, dtype / spectral variants)")
     ap.add_argument("--no-roofline", action="store_true",
@@ -821,7 +851,8 @@ def main():
     extra = {}
     elapsed, mode, final_loss = run_training(cfg, args.steps, args.warmup, dev, world, rank, graph=not args.no_graph,
                                              collective=True if (world > 1 or launched) else None, extra=extra,
-                                             short=20 if args.steps > 20 else 0)
+                                             short=20 if args.full and args.steps > 20 else 0, allreduce_timing=args.full,
+                                             dump_dir=args.dump_outputs)
     out = {
         "metric": "forecast-steps/sec (train)", "value": world * cfg["B"] * cfg["H"] / (elapsed / args.steps),
         "unit": "forecast-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -847,15 +878,15 @@ def main():
         out["ms_per_step_20_steps"] = extra["short_ms_per_step"]
     if rank == 0:
         print("bench headline (complete line follows on stdout): " + json.dumps(out), file=sys.stderr, flush=True)
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             out["roofline"], out["roofline_families"], out["roofline_mfma"], out["gru"] = roofline_objects(cfg)
             out["gru"]["critical_us"] = out["gru"]["fwd_us"] + out["gru"]["bwd_incl_weight_grads_us"]
             out["gru"]["share_of_step"] = out["gru"]["critical_us"] / (out["ms_per_step"] * 1e3)
             out["step_roofline"] = step_roofline(cfg, out["ms_per_step"])
         solo = world == 1 and not launched
-        if solo and not args.no_cpu_baseline:
+        if args.full and solo and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg)
-        if solo and not args.no_other_configs:
+        if args.full and solo and not args.no_other_configs:
             torch.cuda.empty_cache()
             for name in SECTIONS:
                 out[name] = run_section_child(name, args)

@@ -6,6 +6,7 @@ Writes tests/golden/data/<case>.npz:
   norm_{z_score,min_max}  ForecastDataset(...).data (float64), x_end_idx, sample windows, de_normalized()
   metrics                 utils.math_utils.evaluate (all four axis variants, raw and normalised)
   rolling                 models.handler.inference with a stub model whose output is shorter than the horizon
+  random_inputs           ForecastDataset / evaluate / de_normalized on random series (NaN runs, constant columns)
   train_e2e               models.handler.train (3 epochs, RMSProp + ExponentialLR, validate every epoch) on a tiny
                           synthetic CSV with the reference Model at dropout 0: initial/final state_dict, batch order,
                           per-step losses, per-epoch validation metrics
@@ -181,6 +182,50 @@ def case_train(fd, hd, name="train_e2e", T=150, N=8, W=6, H=3, multi=2, bs=16, e
           "val mae", [float(m["mae"]) for m in log["metrics"]])
 
 
+def case_random(fd, mu, trials=12):
+    """Random series (NaN runs, constant columns, several window / horizon / interval settings) through the reference's
+    ForecastDataset (every normalisation, every item), all four evaluate() variants and de_normalized()."""
+    import warnings
+    rng = np.random.default_rng(11)
+    out = {"trials": np.int64(trials)}
+    for trial in range(trials):
+        T, N = int(rng.integers(12, 60)), int(rng.integers(1, 7))
+        W, H = int(rng.integers(1, 6)), int(rng.integers(1, 5))
+        interval = int(rng.integers(1, 4))
+        raw = rng.normal(size=(T, N)) * rng.uniform(0.5, 4.0, size=N) + rng.uniform(-3, 3, size=N)
+        raw[rng.random((T, N)) < 0.1] = np.nan
+        raw[:, 0] = np.where(np.isnan(raw[:, 0]), 1.0, raw[:, 0])         # column 0 keeps at least ... all values
+        if N > 1 and trial % 3 == 0:
+            raw[:, 1] = 2.5                                                # std == 0 / max == min
+        p = f"t{trial}_"
+        out.update({p + "cfg": np.array([W, H, interval], np.int64), p + "raw": raw})
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            out[p + "filled"] = np.asarray(fd.ForecastDataset(raw, W, H).data, np.float64)
+            for method in ("z_score", "min_max", None):
+                ds = fd.ForecastDataset(raw, window_size=W, horizon=H, normalize_method=method, interval=interval)
+                q = f"{p}{method}_"
+                out[q + "data"] = np.asarray(ds.data, np.float64)
+                out[q + "x_end_idx"] = np.asarray(ds.x_end_idx, np.int64)
+                items = [ds[i] for i in range(len(ds))]
+                out[q + "x"] = np.stack([x.numpy() for x, _ in items])
+                out[q + "y"] = np.stack([y.numpy() for _, y in items])
+            C = int(rng.integers(1, 9))
+            t = rng.normal(size=(C, H, N)).astype(np.float32)
+            t[rng.random(t.shape) < 0.05] = 0.0
+            f = (t + rng.normal(size=t.shape) * 0.3).astype(np.float32).astype(np.float64)
+            out.update({p + "target": t, p + "forecast": f})
+            with np.errstate(divide="ignore", invalid="ignore"):
+                for bs in (0, 1):
+                    for bn in (0, 1):
+                        for nm, v in zip(("mape", "mae", "rmse"), mu.evaluate(t, f, by_step=bool(bs), by_node=bool(bn))):
+                            out[f"{p}eval_s{bs}n{bn}_{nm}"] = np.asarray(v)
+            stat = {"mean": rng.normal(size=N).tolist(), "std": rng.uniform(0.5, 2, size=N).tolist()}
+            out.update({p + "stat_mean": np.array(stat["mean"]), p + "stat_std": np.array(stat["std"]),
+                        p + "denorm": np.asarray(fd.de_normalized(t, "z_score", dict(stat)))})
+    save("random_inputs", **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     fd, mu, hd = load_reference_packages()
@@ -188,6 +233,7 @@ if __name__ == "__main__":
     case_norm(fd, "min_max")
     case_metrics(fd, mu)
     case_rolling(fd, hd)
+    case_random(fd, mu)
     case_train(fd, hd)
     # the headline shape (PEMS07: N=228, W=12, H=3, multi=5, batch 32): 2 epochs of the reference's handler.train
     case_train(fd, hd, name="train_pems07", T=500, N=228, W=12, H=3, multi=5, bs=32, epochs=2, ntrain=350, lr=1e-4,

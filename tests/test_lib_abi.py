@@ -4,10 +4,12 @@ import ctypes
 import os
 import re
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "stemgnn_hip.h")
+GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
 
 
 def declared_symbols():
@@ -124,11 +126,10 @@ def test_constructor_accepts_any_stack_count_like_the_reference(stack_cnt):
     keys = list(m.state_dict().keys())
     assert sum(k.startswith(f"stock_block.{stack_cnt - 1}.") for k in keys) > 0
     m.eval(); m.train()
-    from oracle import ref_shim
-    if ref_shim.reference_available():
-        ref = ref_shim.load_reference_model_module().Model(6, stack_cnt, 4, 2, horizon=2)
-        assert [(k, tuple(v.shape)) for k, v in ref.state_dict().items()] == \
-               [(k, tuple(v.shape)) for k, v in m.state_dict().items()]
+    # the reference's own state_dict for the same constructor call (tests/golden/make_golden.py run_stack_case)
+    z = np.load(os.path.join(GOLDEN_DIR, "ref_init", f"stack{stack_cnt}.npz"))
+    assert [(k, tuple(z["shape." + k])) for k in z["keys"].tolist()] == \
+           [(k, tuple(v.shape)) for k, v in m.state_dict().items()]
 
 
 def test_model_constructor_rejects_shapes_outside_the_fc_tail_range(lib):

@@ -32,6 +32,16 @@ def relerr(got, ref):
     return num / den if den > 0 else num
 
 
+def sign_sketch(a, k=64, seed=7):
+    """k random +-1 projections of a flattened tensor (float64), the signs from oracle/detrand.py.  For a difference d
+    of two tensors, mean(sketch(d)^2) estimates ||d||_2^2 without bias, and with k = 64 it falls below a quarter of it
+    with negligible probability -- so a fixture can pin a large tensor through k numbers (||d||_inf <= ||d||_2)."""
+    from oracle.detrand import det_uniform
+    flat = torch.as_tensor(a).double().reshape(-1).numpy()
+    signs = np.where(det_uniform((k, flat.size), seed) >= 0, 1.0, -1.0)
+    return signs @ flat
+
+
 def synthetic_series(T, N, seed):
     """sin(2 pi t / p_n + phi_n) * a_n + c_n + noise (SURVEY 8d shape), float64, from the deterministic generators of
     oracle/detrand.py (so a fixture can name a seed instead of carrying the series)."""

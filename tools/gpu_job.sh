@@ -3,7 +3,7 @@
 #     bash tools/gpu_job.sh <tag> <stage> [<stage> ...]
 # stages (outputs under gpurun_out/<tag>/):
 #   tests[=<pytest -k expr>]   the -m gpu tier (or a subset)
-#   bench[=<extra args>]       the default bench line -> bench.json
+#   bench[=<extra args>]       the full bench line (--full) -> bench.json
 #   prof                       rocprofv3 kernel trace of IN-STEP launches only (--no-roofline: no isolated timing loops)
 #                              -> kernel_stats.txt (us / step) + step_timeline.txt
 #   prof_iso                   kernel trace of the isolated GEMM-family loops only (tools/family_time.py)
@@ -24,7 +24,7 @@ for STAGE in "$@"; do
       else timeout 2400 python -m pytest tests -m gpu -x -q --durations=15 > $OUT/pytest.log 2>&1; fi
       echo "pytest rc=$?" >> $OUT/pytest.log; tail -6 $OUT/pytest.log ;;
     bench)
-      timeout 900 python bench.py $ARG > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+      timeout 900 python bench.py --full $ARG > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
       python tools/bench_brief.py $OUT/bench.json ;;
     prof)
       ( cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof -- $BENCH_PROF > $R/$OUT/prof.log 2>&1 )
