@@ -341,6 +341,33 @@ int stemgnn_block_wgrad_split(const float* const* params_host, const float* pack
                               float* scratch, float* gradpart, int nsplit, int cu_percent, int B, int N, int W,
                               int multi, int splits, void* stream);
 
+/* ---- inference forward (no saved activations; Model.predict / engine.ForecastStep) ----------------------------------
+ * The _infer entries run the same kernels and arithmetic as their training counterparts -- bit-identical outputs -- without the
+ * stores only the backward pass reads: no GRU `reserve`, no GLU gates, no layer-0 / layer-1 GLU outputs where the fused kernels
+ * keep them in LDS, no ig / fs of the heads.  One block's intermediate tensors live in a caller-owned workspace `ws` of
+ * ws_floats floats (layout: G [M,3W] | layer-2 GLU outputs [M,CP2[0]] | [M,CP2[1]] | optional ping-pong slabs 4 x [M,CP]);
+ * it is reusable for block 1 once block 0's heads have run (stream order).
+ * stemgnn_infer_workspace_floats: the size for the exact-fp32 and the bf16x2 forms (the ping-pong slabs are included where a
+ * per-layer GLU launch or the per-stage heads path runs at this shape, or STEMGNN_GLU_FUSED=0);
+ * stemgnn_infer_workspace_split_floats: the same for one arithmetic (splits 0, 2, 3 as stemgnn_spectral_glu_fwd_split; 3
+ * always needs the slabs).  A workspace smaller than the path the call takes needs returns SG_EINVAL.
+ * stemgnn_gru_fwd_infer      == stemgnn_gru_fwd without `reserve` (h_ext is written as ever: the attention reads it)
+ * stemgnn_spectral_glu_fwd_infer / _split_infer == stemgnn_spectral_glu_fwd / _split, reading G from ws and writing the
+ *                               layer-2 outputs into ws
+ * stemgnn_igft_heads_fwd_infer == stemgnn_igft_heads_fwd reading the layer-2 outputs from ws
+ * The GFT writes G with stemgnn_gft_fwd(..., G = ws, ...) (offset 0 of the workspace). */
+size_t stemgnn_infer_workspace_floats(int B, int N, int W, int multi);
+size_t stemgnn_infer_workspace_split_floats(int B, int N, int W, int multi, int splits);
+int stemgnn_gru_fwd_infer(const float* x, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                          int B, int S, int Hd, int W, float* scratch, float* h_ext, int* status, void* stream);
+int stemgnn_spectral_glu_fwd_infer(const float* packed, float* ws, size_t ws_floats, int B, int N, int W, int multi,
+                                   void* stream);
+int stemgnn_spectral_glu_fwd_split_infer(const float* packed, const float* split, float* ws, size_t ws_floats, int B, int N,
+                                         int W, int multi, int splits, void* stream);
+int stemgnn_igft_heads_fwd_infer(const float* const* params_host, const float* packed, float* ws, size_t ws_floats,
+                                 const float* X, long xs_b, long xs_n, long xs_t, float* forecast, int accumulate,
+                                 float* backcast, int B, int N, int W, int multi, void* stream);
+
 /* ---- callers on either side of the blocks, fused ------------------------------------------------
  * fc tail (models/base_model.py:97-101,174-179): fsum [B*N, W] (block forecast sum) ->
  * forecast [B,H,N] = Linear(W,H)(LeakyReLU_0.01(Linear(W,W)(fsum))) permuted.  stemgnn_fc_tail_supported(W,H)
@@ -416,6 +443,11 @@ int stemgnn_mse_bwd(const float* forecast, const float* target, size_t n, const 
  * L > W (which the reference fails on with a shape error) returns SG_EINVAL. */
 int stemgnn_roll_window(const float* inputs, const float* forecast, float* inputs_next, float* forecast_steps,
                         int B, int W, int L, int N, int step, int horizon, void* stream);
+/* engine.ForecastStep's result slabs: out_forecast / out_target [capacity, H, N] rows pos[0] + b := forecast / target [B, H, N]
+ * row b, with pos (int64[1]) read on the device -- the window queue's position before the batch's gather; rows outside
+ * [0, capacity) are dropped. */
+int stemgnn_forecast_store(const float* forecast, const float* target, const long long* pos, float* out_forecast,
+                           float* out_target, int B, int H, int N, long capacity, void* stream);
 /* evaluate() (utils/math_utils.py:24-74) with the optional de_normalized() (forecast_dataloader.py:25-38) in front:
  * target / forecast [count,H,N] fp32, v -> v*mul[n] + add[n] in fp64 when mul != NULL (z_score: std, mean; min_max:
  * max-min+1e-8, min).  out (fp64) = overall[3] | by_node[3][N] | by_step[3][H] | by_step_node[3][H][N], each triple

@@ -79,6 +79,7 @@ SIGNATURES = {
     "stemgnn_mse_fwd": (c_int, [_P, _P, c_size_t, _P, _P, _P, _P]),
     "stemgnn_mse_bwd": (c_int, [_P, _P, c_size_t, _P, _P, _P]),
     "stemgnn_roll_window": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "stemgnn_forecast_store": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_long, _P]),
     "stemgnn_eval_scratch_doubles": (c_size_t, [c_long, c_int, c_int]),
     "stemgnn_eval_out_doubles": (c_size_t, [c_int, c_int]),
     "stemgnn_eval_metrics": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, _P, _P, _P]),
@@ -106,6 +107,13 @@ SIGNATURES = {
                                       _P, _P]),
     "stemgnn_fc_tail_train_rows": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
     "stemgnn_fc_tail_train_finish": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "stemgnn_infer_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "stemgnn_infer_workspace_split_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "stemgnn_gru_fwd_infer": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "stemgnn_spectral_glu_fwd_infer": (c_int, [_P, _P, c_size_t, c_int, c_int, c_int, c_int, _P]),
+    "stemgnn_spectral_glu_fwd_split_infer": (c_int, [_P, _P, _P, c_size_t, c_int, c_int, c_int, c_int, c_int, _P]),
+    "stemgnn_igft_heads_fwd_infer": (c_int, [_PP, _P, _P, c_size_t, _P, c_long, c_long, c_long, _P, c_int, _P,
+                                             c_int, c_int, c_int, c_int, _P]),
     "stemgnn_block_wgrad": (c_int, [_PP, _P, _P, _P, c_long, c_long, c_long, _P, c_int, _P, _P, c_int, c_int,
                                     c_int, c_int, c_int, c_int, _P]),
     "stemgnn_block_wgrad_split": (c_int, [_PP, _P, _P, _P, c_long, c_long, c_long, _P, c_int, _P, _P, c_int, c_int,

@@ -233,6 +233,28 @@ class Model(nn.Module):
             raise _lib.StemGNNHipError(f"fc tail: time_step={self.time_step}, horizon={self.horizon} outside the HIP kernels' "
                                        "range (time_step <= 64, horizon <= 32); stemgnn_amd has no torch fallback")
 
+    def predict(self, x):
+        """Inference forward: ``(forecast [B,H,N], attention [N,N])``, bit-identical to ``self.eval(); self(x)`` under
+        ``torch.no_grad()``, with nothing stored for a backward pass (ops.forecast_forward: the _infer kernels of
+        include/stemgnn_hip.h).  Eval semantics whatever ``self.training`` is (no dropout); ``self.training``, the dropout
+        stream and ``self.hot_state`` are neither read nor changed, so a call between two training steps leaves training
+        bit for bit as it was.  The weights are packed on every call (FusedRMSprop writes parameters through raw pointers:
+        a cache keyed on torch's version counters would not see it)."""
+        self._require_fc_tail()
+        if not x.is_cuda:
+            raise _lib.StemGNNHipError(
+                f"input is on {x.device}: stemgnn_amd.Model runs only on a HIP device (no CPU fallback)")
+        if self.stack_cnt > 2:        # the reference's failures for other stack counts, as in hot_path
+            raise AttributeError("'NoneType' object has no attribute 'unsqueeze'")
+        if self.stack_cnt < 2:
+            raise IndexError("list index out of range")
+        g = self.GRU
+        blocks = self.stock_block[0].hip_params() + self.stock_block[1].hip_params()
+        with torch.no_grad():
+            return ops.forecast_forward(x, (g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0), self.weight_key,
+                                        self.weight_query, self.multi_layer, self.alpha, self.dropout_rate, blocks,
+                                        (self.fc[0].weight, self.fc[0].bias, self.fc[2].weight, self.fc[2].bias))
+
     def forward(self, x):
         self._require_fc_tail()
         fsum, attention, _ = self.hot_path(x)

@@ -182,7 +182,9 @@ struct GftBwdDt2Op {
 // forward: out = (x Wl + bl) * sigmoid(x Wr + br).  Packed "pair" columns: within a 32-column MFMA tile lanes
 // 0-15 hold the linear_left result and lanes 16-31 the linear_right result of the SAME 16 channels, so one
 // cross-lane exchange (lane ^ 16) brings u and v together; left lanes store `out`, right lanes store the gate.
-struct GluFwdEpi {
+// GATE = false: the inference forward (stemgnn_spectral_glu_fwd_infer) -- `out` only, `gate` is not read
+template <bool GATE = true>
+struct GluFwdEpiT {
   static constexpr bool WHOLE = true;
   const float* bp[2];
   float* out[2];
@@ -203,7 +205,7 @@ struct GluFwdEpi {
     const bool live = hi ? live1 : live0;
     const int c = (col0 >> 1) + (lane & 31);
     float* po = out[r] + c;
-    float* pg = gate[r] + c;
+    float* pg = GATE ? gate[r] + c : nullptr;
     const int ld = cp[r];
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
@@ -218,12 +220,13 @@ struct GluFwdEpi {
         const int row = row0 + i * 32 + g2_row_of(reg, lane);
         if (live && row < M) {
           po[(size_t)row * ld] = u * g;
-          pg[(size_t)row * ld] = g;
+          if constexpr (GATE) pg[(size_t)row * ld] = g;
         }
       }
     }
   }
 };
+using GluFwdEpi = GluFwdEpiT<true>;
 
 // data gradient of layer l -> d(pre-activation) of layer l-1 in pair order:
 //   d = dX[row][c];  left: d * gate ; right: d * out * (1 - gate)       (GLU backward)
@@ -576,14 +579,79 @@ extern "C" int stemgnn_gft_bwd_dt2(const float* X0, long xs0_b, long xs0_n, long
   return 0;
 }
 
+// Where the GLU forward reads G and writes each layer's out / gate: the saved-activation layout of the training forward, or
+// the inference workspace (sg_infer_layout: no gates; layers 0 / 1 through the ping-pong slabs, used by the per-layer launches
+// only -- the fused kernels keep those two layers in LDS)
+struct GluFwdBufs {
+  const float* G;
+  float* out[2][3];
+  float* gate[2][3];
+};
+static GluFwdBufs glu_bufs_saved(const SgDims& d, float* saved) {
+  const SgSavedLayout S = sg_saved_layout(d);
+  GluFwdBufs b;
+  b.G = saved + S.G;
+  for (int r = 0; r < 2; ++r)
+    for (int l = 0; l < 3; ++l) { b.out[r][l] = saved + S.out[r][l]; b.gate[r][l] = saved + S.gate[r][l]; }
+  return b;
+}
+static GluFwdBufs glu_bufs_infer(const SgDims& d, float* ws, bool pp) {
+  const SgInferLayout I = sg_infer_layout(d, pp);
+  GluFwdBufs b;
+  b.G = ws + I.G;
+  for (int r = 0; r < 2; ++r) {
+    b.out[r][0] = pp ? ws + I.pp[r][0] : nullptr;
+    b.out[r][1] = pp ? ws + I.pp[r][1] : nullptr;
+    b.out[r][2] = ws + I.out2[r];
+    for (int l = 0; l < 3; ++l) b.gate[r][l] = nullptr;
+  }
+  return b;
+}
+// per-layer GLU launches (fp32, or split-bf16 for layers 1 / 2 when the plane sets fpl[r * 3 + l] are given); INF: no gate stores
+template <bool INF>
+static int glu_fwd_layers(const SgDims& d, const float* packed, const unsigned short* const* fpl, int splits,
+                          const GluFwdBufs& bf, hipStream_t st) {
+  const SgPackedLayout P = sg_packed_layout(d);
+  using Epi = GluFwdEpiT<!INF>;
+  for (int l = 0; l < 3; ++l) {
+    G2Args g;
+    G2SArgs gs;
+    Epi e;
+    for (int r = 0; r < 2; ++r) {
+      g.A[r] = l == 0 ? bf.G : bf.out[r][l - 1];
+      g.lda[r] = l == 0 ? d.KG : d.CP;
+      g.B[r] = packed + P.w[r][l];
+      g.ldb[r] = sg_glu_np(d, l, r);
+      g.M[r] = d.M; g.N[r] = sg_glu_np(d, l, r); g.K[r] = sg_glu_kin(d, l);
+      if (fpl) {
+        gs.A[r] = g.A[r]; gs.lda[r] = g.lda[r]; gs.P[r] = fpl[r * 3 + l];
+        gs.M[r] = g.M[r]; gs.N[r] = g.N[r]; gs.K[r] = g.K[r]; gs.Kp[r] = g2s_pad32(g.K[r]);
+      }
+      e.bp[r] = packed + P.b[r][l];
+      e.out[r] = bf.out[r][l];
+      e.gate[r] = bf.gate[r][l];
+      e.cp[r] = sg_glu_cp(d, l, r);
+    }
+    g.nsplit = 1; g.chunk = (sg_glu_kin(d, l) + 15) & ~15; g.b_ones_col = -1;
+    if (fpl && l > 0 && g2s_ok(gs, 2)) {
+      SG_TRY((g2s_launch<Epi>(gs, e, 2, splits, st)));
+      continue;
+    }
+    if (sg_glu_kin(d, l) > SG_LONG_K) SG_TRY((g2_launch<Epi, true, false, 64, true>(g, e, 2, st)));
+    else SG_TRY((g2_launch<Epi, true, false, 64>(g, e, 2, st)));
+  }
+  return 0;
+}
+
 // m_pick: the row count the block height (64 / 96 rows) is chosen for -- d.M itself, or the REAL launch's row count when this
-// call is its warm-up (stemgnn_spectral_glu_fwd_warm); fused_only: do nothing where the fused kernel does not apply
-static int glu_fwd_impl(const float* packed, float* saved, int B, int N, int W, int multi, void* stream, int m_pick,
+// call is its warm-up (stemgnn_spectral_glu_fwd_warm); fused_only: do nothing where the fused kernel does not apply.
+// INF: the inference forward (bf: sg_infer_layout); returns SG_EINVAL where it would need the ping-pong slabs and has none.
+template <bool INF = false>
+static int glu_fwd_impl(const float* packed, const GluFwdBufs& bf, int B, int N, int W, int multi, void* stream, int m_pick,
                         bool fused_only) {
-  if (!packed || !saved || B <= 0 || N <= 0 || W <= 0 || multi <= 0) return SG_EINVAL;
+  if (!packed || !bf.G || B <= 0 || N <= 0 || W <= 0 || multi <= 0) return SG_EINVAL;
   const SgDims d = sg_dims(B, N, W, multi);
   const SgPackedLayout P = sg_packed_layout(d);
-  const SgSavedLayout S = sg_saved_layout(d);
   hipStream_t st = (hipStream_t)stream;
   // One launch for the three layers (csrc/glu_fused.h: activations of a 64-row block resident in LDS, weights on a
   // direct-to-LDS ring) where the padded channel count is <= 256; STEMGNN_GLU_FUSED=0 keeps the three per-layer launches
@@ -595,14 +663,14 @@ static int glu_fwd_impl(const float* packed, float* saved, int B, int N, int W, 
     const int mt = fmode == 3 && gg.ok3 ? 3 : (fmode == 2 ? 2 : gf_pick_mt(m_pick > 0 ? m_pick : d.M, sg_num_cus(), gg.ok3));
     if (fused_only && d.M != 4 * 32 * mt) return SG_EINVAL;
     GfArgs a;
-    a.G = saved + S.G; a.KG = d.KG; a.KP0 = gg.kp[0]; a.KA = gg.KA; a.M = d.M; a.ns = gg.ns;
+    a.G = bf.G; a.KG = d.KG; a.KP0 = gg.kp[0]; a.KA = gg.KA; a.M = d.M; a.ns = gg.ns;
     a.nrb = (d.M + 32 * mt - 1) / (32 * mt);
     for (int l = 0; l < 3; ++l) {
       a.nst[l] = gg.nst[l];
       for (int r = 0; r < 2; ++r) {
         a.bias[r][l] = packed + P.b[r][l];
-        a.out[r][l] = saved + S.out[r][l];
-        a.gate[r][l] = saved + S.gate[r][l];
+        a.out[r][l] = bf.out[r][l];
+        a.gate[r][l] = bf.gate[r][l];
         a.cp[r][l] = sg_glu_cp(d, l, r);
       }
     }
@@ -612,8 +680,8 @@ static int glu_fwd_impl(const float* packed, float* saved, int B, int N, int W, 
     static SgDynLds guard[6];
 #define GF_LAUNCH(MT_, H01, H2, GI)                                                                          \
     do {                                                                                                    \
-      SG_TRY(sg_ensure_dyn_lds((const void*)sg_glu_fused_fwd_kernel<MT_, H01, H2>, lds, guard[GI]));         \
-      hipLaunchKernelGGL((sg_glu_fused_fwd_kernel<MT_, H01, H2>), grid, dim3(256), lds, st, a);              \
+      SG_TRY(sg_ensure_dyn_lds((const void*)sg_glu_fused_fwd_kernel<MT_, H01, H2, INF>, lds, guard[GI]));    \
+      hipLaunchKernelGGL((sg_glu_fused_fwd_kernel<MT_, H01, H2, INF>), grid, dim3(256), lds, st, a);         \
     } while (0)
     if (mt == 3) {
       if (gg.hp[0] == 1) GF_LAUNCH(3, 1, 1, 3);
@@ -629,30 +697,14 @@ static int glu_fwd_impl(const float* packed, float* saved, int B, int N, int W, 
     return 0;
   }
   if (fused_only) return 0;
-  for (int l = 0; l < 3; ++l) {
-    G2Args g;
-    GluFwdEpi e;
-    for (int r = 0; r < 2; ++r) {
-      g.A[r] = l == 0 ? saved + S.G : saved + S.out[r][l - 1];
-      g.lda[r] = l == 0 ? d.KG : d.CP;
-      g.B[r] = packed + P.w[r][l];
-      g.ldb[r] = sg_glu_np(d, l, r);
-      g.M[r] = d.M; g.N[r] = sg_glu_np(d, l, r); g.K[r] = sg_glu_kin(d, l);
-      e.bp[r] = packed + P.b[r][l];
-      e.out[r] = saved + S.out[r][l];
-      e.gate[r] = saved + S.gate[r][l];
-      e.cp[r] = sg_glu_cp(d, l, r);
-    }
-    g.nsplit = 1; g.chunk = (sg_glu_kin(d, l) + 15) & ~15; g.b_ones_col = -1;
-    if (sg_glu_kin(d, l) > SG_LONG_K) SG_TRY((g2_launch<GluFwdEpi, true, false, 64, true>(g, e, 2, st)));
-    else SG_TRY((g2_launch<GluFwdEpi, true, false, 64>(g, e, 2, st)));
-  }
-  return 0;
+  if (INF && !bf.out[0][0]) return SG_EINVAL;           // per-layer launches need the ping-pong slabs
+  return glu_fwd_layers<INF>(d, packed, nullptr, 0, bf, st);
 }
 
 extern "C" int stemgnn_spectral_glu_fwd(const float* packed, float* saved, int B, int N, int W, int multi,
                                         void* stream) {
-  return glu_fwd_impl(packed, saved, B, N, W, multi, stream, 0, false);
+  if (!saved) return SG_EINVAL;
+  return glu_fwd_impl(packed, glu_bufs_saved(sg_dims(B, N, W, multi), saved), B, N, W, multi, stream, 0, false);
 }
 
 // ---- split-bf16 variant of the GLU forward / data-gradient layers (STEMGNN_DTYPE=bf16x3 | bf16x2, csrc/gemm2s.h) ------
@@ -758,13 +810,14 @@ extern "C" int stemgnn_glu_split_panels(const float* packed, float* split, int W
   return 0;
 }
 
-// forward of the three GLU layers with layers 1, 2 on the split-bf16 kernel (same saved out / gate as the fp32 entry)
-extern "C" int stemgnn_spectral_glu_fwd_split(const float* packed, const float* split, float* saved, int B, int N, int W,
-                                              int multi, int splits, void* stream) {
-  if (!packed || !split || !saved || B <= 0 || N <= 0 || W <= 0 || multi <= 0 || splits < 2 || splits > 3) return SG_EINVAL;
+// forward of the three GLU layers with layers 1, 2 on the split-bf16 kernel (same saved out / gate as the fp32 entry);
+// INF: the inference forward into the workspace `bf` describes (see glu_fwd_impl)
+template <bool INF = false>
+static int glu_fwd_split_impl(const float* packed, const float* split, const GluFwdBufs& bf, int B, int N, int W, int multi,
+                              int splits, void* stream) {
+  if (!packed || !split || !bf.G || B <= 0 || N <= 0 || W <= 0 || multi <= 0 || splits < 2 || splits > 3) return SG_EINVAL;
   const SgDims d = sg_dims(B, N, W, multi);
   const SgPackedLayout P = sg_packed_layout(d);
-  const SgSavedLayout S = sg_saved_layout(d);
   const G2SLayout L = g2s_layout(d, splits);
   const unsigned short* base = reinterpret_cast<const unsigned short*>(split);
   hipStream_t st = (hipStream_t)stream;
@@ -773,24 +826,24 @@ extern "C" int stemgnn_spectral_glu_fwd_split(const float* packed, const float* 
     // ONE launch for the three layers on the bf16 matrix pipe (csrc/glu_fused_bf16.h): activations of a 64-row block resident
     // in LDS as two bf16 planes, pre-split weights on the direct-to-LDS ring; saved out / gate are fp32 as ever
     GbArgs a;
-    a.G = saved + S.G; a.KG = d.KG; a.LDK = gb.LDK; a.M = d.M; a.ns = gb.ns;
+    a.G = bf.G; a.KG = d.KG; a.LDK = gb.LDK; a.M = d.M; a.ns = gb.ns;
     a.nrb = (d.M + GB_BM - 1) / GB_BM;
     for (int l = 0; l < 3; ++l) {
       a.nst[l] = gb.nst[l]; a.kp[l] = gb.kp[l];
       for (int r = 0; r < 2; ++r) {
         a.bias[r][l] = packed + P.b[r][l];
-        a.out[r][l] = saved + S.out[r][l];
-        a.gate[r][l] = saved + S.gate[r][l];
+        a.out[r][l] = bf.out[r][l];
+        a.gate[r][l] = bf.gate[r][l];
         a.cp[r][l] = sg_glu_cp(d, l, r);
       }
     }
     for (int r = 0; r < 2; ++r) a.wf[r] = base + L.FS[r];
     const dim3 grid(8 * ((a.nrb + 3) / 4));
     static SgDynLds guard[3];
-#define GB_LAUNCH(H01, H2, GI)                                                                               \
-    do {                                                                                                    \
-      SG_TRY(sg_ensure_dyn_lds((const void*)sg_glu_fused_fwd_bf16_kernel<H01, H2>, gb.lds_bytes, guard[GI])); \
-      hipLaunchKernelGGL((sg_glu_fused_fwd_bf16_kernel<H01, H2>), grid, dim3(256), gb.lds_bytes, st, a);     \
+#define GB_LAUNCH(H01, H2, GI)                                                                                    \
+    do {                                                                                                         \
+      SG_TRY(sg_ensure_dyn_lds((const void*)sg_glu_fused_fwd_bf16_kernel<H01, H2, INF>, gb.lds_bytes, guard[GI])); \
+      hipLaunchKernelGGL((sg_glu_fused_fwd_bf16_kernel<H01, H2, INF>), grid, dim3(256), gb.lds_bytes, st, a);     \
     } while (0)
     if (gb.hp[0] == 1) GB_LAUNCH(1, 1, 0);
     else if (gb.hp[2] == 1) GB_LAUNCH(2, 1, 1);
@@ -800,32 +853,16 @@ extern "C" int stemgnn_spectral_glu_fwd_split(const float* packed, const float* 
     return 0;
   }
   if (splits == 2 && g_planes_skipped.load(std::memory_order_relaxed) && gb.ok && gq_geom(d).ok) return SG_EINVAL;   // see dgrad_split
-  for (int l = 0; l < 3; ++l) {
-    G2Args g;
-    G2SArgs gs;
-    GluFwdEpi e;
-    for (int r = 0; r < 2; ++r) {
-      g.A[r] = l == 0 ? saved + S.G : saved + S.out[r][l - 1];
-      g.lda[r] = l == 0 ? d.KG : d.CP;
-      g.B[r] = packed + P.w[r][l];
-      g.ldb[r] = sg_glu_np(d, l, r);
-      g.M[r] = d.M; g.N[r] = sg_glu_np(d, l, r); g.K[r] = sg_glu_kin(d, l);
-      gs.A[r] = g.A[r]; gs.lda[r] = g.lda[r]; gs.P[r] = base + L.F[r][l];
-      gs.M[r] = g.M[r]; gs.N[r] = g.N[r]; gs.K[r] = g.K[r]; gs.Kp[r] = g2s_pad32(g.K[r]);
-      e.bp[r] = packed + P.b[r][l];
-      e.out[r] = saved + S.out[r][l];
-      e.gate[r] = saved + S.gate[r][l];
-      e.cp[r] = sg_glu_cp(d, l, r);
-    }
-    g.nsplit = 1; g.chunk = (sg_glu_kin(d, l) + 15) & ~15; g.b_ones_col = -1;
-    if (l > 0 && g2s_ok(gs, 2)) {
-      SG_TRY((g2s_launch<GluFwdEpi>(gs, e, 2, splits, st)));
-      continue;
-    }
-    if (sg_glu_kin(d, l) > SG_LONG_K) SG_TRY((g2_launch<GluFwdEpi, true, false, 64, true>(g, e, 2, st)));
-    else SG_TRY((g2_launch<GluFwdEpi, true, false, 64>(g, e, 2, st)));
-  }
-  return 0;
+  if (INF && !bf.out[0][0]) return SG_EINVAL;           // per-layer launches need the ping-pong slabs
+  const unsigned short* fpl[6];
+  for (int r = 0; r < 2; ++r)
+    for (int l = 0; l < 3; ++l) fpl[r * 3 + l] = base + L.F[r][l];
+  return glu_fwd_layers<INF>(d, packed, fpl, splits, bf, st);
+}
+extern "C" int stemgnn_spectral_glu_fwd_split(const float* packed, const float* split, float* saved, int B, int N, int W,
+                                              int multi, int splits, void* stream) {
+  if (!saved) return SG_EINVAL;
+  return glu_fwd_split_impl(packed, split, glu_bufs_saved(sg_dims(B, N, W, multi), saved), B, N, W, multi, splits, stream);
 }
 
 // Warm-up of the fused forward (round 6).  The FIRST launch of the fused three-layer kernel in a step runs ~12 us longer than
@@ -854,7 +891,8 @@ extern "C" int stemgnn_spectral_glu_fwd_warm(const float* packed, const float* s
   const int fmode = ef ? atoi(ef) : 1;
   if (!gg.ok || fmode == 0 || (((uintptr_t)packed) & 15) != 0) return 0;
   const int mt = fmode == 3 && gg.ok3 ? 3 : (fmode == 2 ? 2 : gf_pick_mt(d.M, sg_num_cus(), gg.ok3));
-  return glu_fwd_impl(packed, saved, 1, 4 * 32 * mt, W, multi, stream, d.M, true);
+  return glu_fwd_impl(packed, glu_bufs_saved(sg_dims(1, 4 * 32 * mt, W, multi), saved), 1, 4 * 32 * mt, W, multi, stream, d.M,
+                      true);
 }
 
 // data-gradient chain of the three GLU layers (= stemgnn_spectral_glu_bwd with parts = 1) with the two d(pre-activation)
@@ -1066,63 +1104,135 @@ extern "C" int stemgnn_spectral_glu_bwd(const float* packed, const float* saved,
   return 0;
 }
 
-extern "C" int stemgnn_igft_heads_fwd(const float* const* params_host, const float* packed, float* saved,
-                                      const float* X, long xs_b, long xs_n, long xs_t,
-                                      float* forecast, int accumulate, float* backcast,
-                                      int B, int N, int W, int multi, void* stream) {
-  if (!params_host || !packed || !saved || !X || !forecast || B <= 0 || N <= 0 || W <= 0 || multi <= 0)
-    return SG_EINVAL;
+// 1 where the heads forward runs as ONE fused kernel (heads.h), 0 where it takes the per-stage GEMMs (ig / fs through memory)
+static bool heads_fused_ok(const SgDims& d) {
+  return hd_fwd_lds_floats(d.KF, d.WmP, d.W) * sizeof(float) <= (size_t)150 * 1024 && d.KF <= SG_LONG_K;
+}
+// a3[r]: the last GLU layer's outputs; ig / fs: where the per-stage path passes them between its GEMMs.  SAVE = false: the
+// inference forward -- the fused kernel keeps ig / fs in LDS (ig / fs are then only used by the per-stage path)
+template <bool SAVE = true>
+static int heads_fwd_impl(const float* const* params_host, const float* packed, const float* const (&a3)[2], float* ig, float* fs,
+                          const float* X, long xs_b, long xs_n, long xs_t, float* forecast, int accumulate, float* backcast,
+                          int B, int N, int W, int multi, void* stream) {
   const SgDims d = sg_dims(B, N, W, multi);
   const SgPackedLayout P = sg_packed_layout(d);
-  const SgSavedLayout S = sg_saved_layout(d);
   hipStream_t st = (hipStream_t)stream;
   const int has_bc = backcast != nullptr;
   if (has_bc && (!params_host[5] || !params_host[6])) return SG_EINVAL;
   // one fused kernel per block (csrc/heads.h) when the 32-row block fits the LDS budget; STEMGNN_HEADS_FUSED=0 and large
   // W*multi take the three descriptor GEMMs below
   const size_t hd_bytes = hd_fwd_lds_floats(d.KF, d.WmP, W) * sizeof(float);
-  if (hd_bytes <= (size_t)150 * 1024 && d.KF <= SG_LONG_K) {
+  if (heads_fused_ok(d)) {
     HeadsFwdArgs a;
-    for (int r = 0; r < 2; ++r) { a.a3[r] = saved + S.out[r][2]; a.cp2[r] = d.CP2[r]; }
+    for (int r = 0; r < 2; ++r) { a.a3[r] = a3[r]; a.cp2[r] = d.CP2[r]; }
     a.wfold = packed + P.wfold;
     a.Fw = params_host[1]; a.Fb = params_host[2]; a.FRw = params_host[3]; a.FRb = params_host[4];
     a.BCw = params_host[5]; a.BCb = params_host[6]; a.BSw = params_host[7]; a.BSb = params_host[8];
     a.X = HdXView{X, xs_b, xs_n, xs_t, N};
-    a.ig = saved + S.ig; a.fs = saved + S.fs; a.forecast = forecast; a.backcast = backcast;
+    a.ig = ig; a.fs = fs; a.forecast = forecast; a.backcast = backcast;
     a.M = d.M; a.W = W; a.Wm = d.Wm; a.WmP = d.WmP; a.KF = d.KF; a.accumulate = accumulate; a.has_bc = has_bc;
     a.lda = hd_lda(d.KF); a.ldi = d.WmP + 1;
     // eight waves, one 16-row tile each (heads.h); STEMGNN_HEADS_FWD_WAVES=4: both row tiles per wave (rounds 3-5)
     static const int waves_env = getenv("STEMGNN_HEADS_FWD_WAVES") ? atoi(getenv("STEMGNN_HEADS_FWD_WAVES")) : 8;
     if (waves_env == 8) {
       static SgDynLds lds_guard8;
-      SG_TRY(sg_ensure_dyn_lds((const void*)sg_heads_fwd_kernel<8>, hd_bytes, lds_guard8));
-      hipLaunchKernelGGL(sg_heads_fwd_kernel<8>, dim3((d.M + HD_RB - 1) / HD_RB), dim3(512), hd_bytes, st, a);
+      SG_TRY(sg_ensure_dyn_lds((const void*)sg_heads_fwd_kernel<8, SAVE>, hd_bytes, lds_guard8));
+      hipLaunchKernelGGL((sg_heads_fwd_kernel<8, SAVE>), dim3((d.M + HD_RB - 1) / HD_RB), dim3(512), hd_bytes, st, a);
     } else {
       static SgDynLds lds_guard;
-      SG_TRY(sg_ensure_dyn_lds((const void*)sg_heads_fwd_kernel<4>, hd_bytes, lds_guard));
-      hipLaunchKernelGGL(sg_heads_fwd_kernel<4>, dim3((d.M + HD_RB - 1) / HD_RB), dim3(256), hd_bytes, st, a);
+      SG_TRY(sg_ensure_dyn_lds((const void*)sg_heads_fwd_kernel<4, SAVE>, hd_bytes, lds_guard));
+      hipLaunchKernelGGL((sg_heads_fwd_kernel<4, SAVE>), dim3((d.M + HD_RB - 1) / HD_RB), dim3(256), hd_bytes, st, a);
     }
     SG_TRY(hipGetLastError());
     return 0;
   }
   {
     IgftOp op;
-    for (int r = 0; r < 2; ++r) { op.a3[r] = saved + S.out[r][2]; op.cp2[r] = d.CP2[r]; }
-    op.wfold = packed + P.wfold; op.ig = saved + S.ig; op.M = d.M; op.Wm = d.Wm; op.WmP = d.WmP;
+    if (!ig || !fs) return SG_EINVAL;
+    for (int r = 0; r < 2; ++r) { op.a3[r] = a3[r]; op.cp2[r] = d.CP2[r]; }
+    op.wfold = packed + P.wfold; op.ig = ig; op.M = d.M; op.Wm = d.Wm; op.WmP = d.WmP;
     if (d.KF > SG_LONG_K) SG_TRY((sg_launch_gemm<IgftOp, 32, 64, true, false, false, 64, true>(op, d.M, d.Wm, 1, st)));
     else SG_TRY((sg_launch_gemm<IgftOp, 32, 64, true, false, false, 64>(op, d.M, d.Wm, 1, st)));
   }
   {
-    Head1Op op{saved + S.ig, XView{X, xs_b, xs_n, xs_t, N},
+    Head1Op op{ig, XView{X, xs_b, xs_n, xs_t, N},
                params_host[1], params_host[2], params_host[5], params_host[6], params_host[7], params_host[8],
-               saved + S.fs, backcast, d.M, W, d.Wm, has_bc};
+               fs, backcast, d.M, W, d.Wm, has_bc};
     SG_TRY((sg_launch_gemm<Head1Op, 32, 64, true, true, false, 64>(op, d.M, d.Wm + (has_bc ? W : 0), 1, st)));
   }
   {
-    Head2Op op{saved + S.fs, params_host[3], params_host[4], forecast, d.M, W, d.Wm, accumulate};
+    Head2Op op{fs, params_host[3], params_host[4], forecast, d.M, W, d.Wm, accumulate};
     SG_TRY((sg_launch_gemm<Head2Op, 64, 32, true, true, false>(op, d.M, W, 1, st)));
   }
   return 0;
+}
+
+extern "C" int stemgnn_igft_heads_fwd(const float* const* params_host, const float* packed, float* saved,
+                                      const float* X, long xs_b, long xs_n, long xs_t,
+                                      float* forecast, int accumulate, float* backcast,
+                                      int B, int N, int W, int multi, void* stream) {
+  if (!params_host || !packed || !saved || !X || !forecast || B <= 0 || N <= 0 || W <= 0 || multi <= 0)
+    return SG_EINVAL;
+  const SgSavedLayout S = sg_saved_layout(sg_dims(B, N, W, multi));
+  const float* const a3[2] = {saved + S.out[0][2], saved + S.out[1][2]};
+  return heads_fwd_impl<true>(params_host, packed, a3, saved + S.ig, saved + S.fs, X, xs_b, xs_n, xs_t, forecast, accumulate,
+                              backcast, B, N, W, multi, stream);
+}
+
+// ---- inference forward of one StockBlock (stemgnn_*_infer): the training kernels without the stores only the backward reads --
+// The ping-pong slabs of the workspace are needed where a per-layer GLU launch (no fused kernel for this shape, or
+// STEMGNN_GLU_FUSED=0) or the per-stage heads path runs.  Both fused GLU forms (exact fp32 and split-bf16 bf16x2) are asked, so
+// one size serves either arithmetic; splits = 3 (bf16x3) always runs per-layer launches.
+static bool infer_needs_pp(const SgDims& d, int splits) {
+  const char* ef = getenv("STEMGNN_GLU_FUSED");
+  const bool fused_on = !(ef && atoi(ef) == 0);
+  const bool glu_fused = fused_on && gf_geom(d).ok && gb_geom(d).ok && splits != 3;
+  return !glu_fused || !heads_fused_ok(d);
+}
+static size_t infer_ws_floats(int B, int N, int W, int multi, int splits) {
+  if (B <= 0 || N <= 0 || W <= 0 || multi <= 0) return 0;
+  const SgDims d = sg_dims(B, N, W, multi);
+  return sg_infer_layout(d, infer_needs_pp(d, splits)).total;
+}
+extern "C" size_t stemgnn_infer_workspace_floats(int B, int N, int W, int multi) { return infer_ws_floats(B, N, W, multi, 0); }
+extern "C" size_t stemgnn_infer_workspace_split_floats(int B, int N, int W, int multi, int splits) {
+  if (splits != 0 && splits != 2 && splits != 3) return 0;
+  return infer_ws_floats(B, N, W, multi, splits);
+}
+// the workspace's buffer set: the ping-pong slabs are used when the caller's buffer holds them (ws_floats covers the layout with
+// them); a buffer sized without them is only accepted while the fused forms apply (else the GLU / heads entries return SG_EINVAL)
+static bool infer_ws_ok(const SgDims& d, size_t ws_floats, bool* pp) {
+  *pp = ws_floats >= sg_infer_layout(d, true).total;
+  return ws_floats >= sg_infer_layout(d, false).total;
+}
+extern "C" int stemgnn_spectral_glu_fwd_infer(const float* packed, float* ws, size_t ws_floats, int B, int N, int W, int multi,
+                                              void* stream) {
+  if (!packed || !ws || B <= 0 || N <= 0 || W <= 0 || multi <= 0) return SG_EINVAL;
+  const SgDims d = sg_dims(B, N, W, multi);
+  bool pp = false;
+  if (!infer_ws_ok(d, ws_floats, &pp)) return SG_EINVAL;
+  return glu_fwd_impl<true>(packed, glu_bufs_infer(d, ws, pp), B, N, W, multi, stream, 0, false);
+}
+extern "C" int stemgnn_spectral_glu_fwd_split_infer(const float* packed, const float* split, float* ws, size_t ws_floats, int B,
+                                                    int N, int W, int multi, int splits, void* stream) {
+  if (!packed || !split || !ws || B <= 0 || N <= 0 || W <= 0 || multi <= 0 || splits < 2 || splits > 3) return SG_EINVAL;
+  const SgDims d = sg_dims(B, N, W, multi);
+  bool pp = false;
+  if (!infer_ws_ok(d, ws_floats, &pp)) return SG_EINVAL;
+  return glu_fwd_split_impl<true>(packed, split, glu_bufs_infer(d, ws, pp), B, N, W, multi, splits, stream);
+}
+extern "C" int stemgnn_igft_heads_fwd_infer(const float* const* params_host, const float* packed, float* ws, size_t ws_floats,
+                                            const float* X, long xs_b, long xs_n, long xs_t, float* forecast, int accumulate,
+                                            float* backcast, int B, int N, int W, int multi, void* stream) {
+  if (!params_host || !packed || !ws || !X || !forecast || B <= 0 || N <= 0 || W <= 0 || multi <= 0) return SG_EINVAL;
+  const SgDims d = sg_dims(B, N, W, multi);
+  bool pp = false;
+  if (!infer_ws_ok(d, ws_floats, &pp)) return SG_EINVAL;
+  const SgInferLayout I = sg_infer_layout(d, pp);
+  const float* const a3[2] = {ws + I.out2[0], ws + I.out2[1]};
+  // per-stage path: ig / fs in the (by then free) ping-pong slabs of branch 0, M x CP >= M x Wm each
+  return heads_fwd_impl<false>(params_host, packed, a3, pp ? ws + I.pp[0][0] : nullptr, pp ? ws + I.pp[0][1] : nullptr, X, xs_b,
+                               xs_n, xs_t, forecast, accumulate, backcast, B, N, W, multi, stream);
 }
 
 // fixed-order reduce of the heads' split slabs; which: bit 0 Wfold, 1 FR, 2 F, 3 BC, 4 BS (BC / BS only with a backcast head)

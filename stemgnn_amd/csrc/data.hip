@@ -267,6 +267,33 @@ extern "C" int stemgnn_roll_window(const float* inputs, const float* forecast, f
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// result slabs of a replayed rolling forecast (engine.ForecastStep): rows pos[0] + b of out_forecast / out_target [capacity, H, N]
+// := forecast / target [b] -- the position is the window queue's, read on the device (no per-batch host copy)
+__global__ void sg_forecast_store_kernel(const float* __restrict__ forecast, const float* __restrict__ target,
+                                         const long long* __restrict__ pos, float* __restrict__ out_f, float* __restrict__ out_t,
+                                         int HN, long capacity) {
+  const int b = blockIdx.y;
+  const long long row = pos[0] + b;
+  if (row < 0 || row >= capacity) return;
+  const bool tgt = blockIdx.z != 0;
+  const float* src = (tgt ? target : forecast) + (size_t)b * HN;
+  float* dst = (tgt ? out_t : out_f) + (size_t)row * HN;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < HN; i += gridDim.x * blockDim.x) dst[i] = src[i];
+}
+
+extern "C" int stemgnn_forecast_store(const float* forecast, const float* target, const long long* pos, float* out_forecast,
+                                      float* out_target, int B, int H, int N, long capacity, void* stream) {
+  if (!forecast || !target || !pos || !out_forecast || !out_target || B <= 0 || H <= 0 || N <= 0 || capacity <= 0)
+    return SG_EINVAL;
+  const int HN = H * N;
+  const unsigned gx = (unsigned)((HN + 255) / 256 < 64 ? (HN + 255) / 256 : 64);
+  hipLaunchKernelGGL(sg_forecast_store_kernel, dim3(gx, B, 2), dim3(256), 0, (hipStream_t)stream, forecast, target, pos,
+                     out_forecast, out_target, HN, capacity);
+  SG_TRY(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // evaluate(): target / forecast [count, H, N] fp32 (the reference holds the same values in float64 arrays,
 // handler.py:50); optional de-normalisation v*mul[n] + add[n] in fp64 with separate multiply and add roundings
 // (numpy: `data * std + mean`).  Per element: ape = min?(|f-t|/|t| + 1e-5, 5) (NaN kept), ae = |f-t|, se = (f-t)^2.

@@ -164,7 +164,9 @@ __device__ __forceinline__ void gf_stage(const float* __restrict__ Aq, const flo
   }
 }
 
-template <int MT, int HP, bool LAST>
+// INF: the inference forward (stemgnn_spectral_glu_fwd_infer) -- the same arithmetic with only the last layer's `out` stored
+// (no gate at all; layers 0 / 1 live in LDS only)
+template <int MT, int HP, bool LAST, bool INF = false>
 __device__ __forceinline__ void gf_layer(float* As, GfRing& rg, int& rbuf, int nst, int lane, int wave,
                                          const float (&bl)[2], const float (&br)[2], float* __restrict__ outp,
                                          float* __restrict__ gatep, int cp, int M, int m0, int KA) {
@@ -217,7 +219,7 @@ __device__ __forceinline__ void gf_layer(float* As, GfRing& rg, int& rbuf, int n
     // per store pair); the ragged last block takes the predicated form
     float* po = outp + (size_t)m0 * cp + c;
     float* pg = gatep + (size_t)m0 * cp + c;
-    if (!(GF_ABL & 1) && live) {
+    if (!(GF_ABL & 1) && (!INF || LAST) && live) {
       if (full) {
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg)
@@ -225,7 +227,7 @@ __device__ __forceinline__ void gf_layer(float* As, GfRing& rg, int& rbuf, int n
           for (int i = 0; i < MT; ++i) {
             const size_t off = (size_t)T::row(i, reg, lane) * cp;
             GF_ST(&po[off], o[reg][i]);
-            GF_ST(&pg[off], gs[reg][i]);
+            if constexpr (!INF) GF_ST(&pg[off], gs[reg][i]);
           }
       } else {
 #pragma unroll
@@ -235,7 +237,7 @@ __device__ __forceinline__ void gf_layer(float* As, GfRing& rg, int& rbuf, int n
             const int rl = T::row(i, reg, lane);
             if (m0 + rl < M) {
               GF_ST(&po[(size_t)rl * cp], o[reg][i]);
-              GF_ST(&pg[(size_t)rl * cp], gs[reg][i]);
+              if constexpr (!INF) GF_ST(&pg[(size_t)rl * cp], gs[reg][i]);
             }
           }
       }
@@ -247,7 +249,7 @@ __device__ __forceinline__ void gf_layer(float* As, GfRing& rg, int& rbuf, int n
   }
 }
 
-template <int MT, int HP01, int HP2>
+template <int MT, int HP01, int HP2, bool INF = false>
 static __global__ __launch_bounds__(256, 1) void sg_glu_fused_fwd_kernel(const GfArgs g) {
   using T = GfTile<MT>;
   extern __shared__ __attribute__((aligned(16))) float gf_lds[];   // ONE array: As[KA][LDA] then the ring
@@ -309,9 +311,9 @@ static __global__ __launch_bounds__(256, 1) void sg_glu_fused_fwd_kernel(const G
     for (int h = 0; h < 2; ++h) asm volatile("" : "+v"(bl[l][h]), "+v"(br[l][h]));
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // (the first stage's barrier publishes the buffer)
   int rbuf = 0;
-  gf_layer<MT, HP01, false>(As, rg, rbuf, g.nst[0], lane, wave, bl[0], br[0], g.out[r][0], g.gate[r][0], g.cp[r][0], M, m0, g.KA);
-  gf_layer<MT, HP01, false>(As, rg, rbuf, g.nst[1], lane, wave, bl[1], br[1], g.out[r][1], g.gate[r][1], g.cp[r][1], M, m0, g.KA);
-  gf_layer<MT, HP2, true>(As, rg, rbuf, g.nst[2], lane, wave, bl[2], br[2], g.out[r][2], g.gate[r][2], g.cp[r][2], M, m0, g.KA);
+  gf_layer<MT, HP01, false, INF>(As, rg, rbuf, g.nst[0], lane, wave, bl[0], br[0], g.out[r][0], g.gate[r][0], g.cp[r][0], M, m0, g.KA);
+  gf_layer<MT, HP01, false, INF>(As, rg, rbuf, g.nst[1], lane, wave, bl[1], br[1], g.out[r][1], g.gate[r][1], g.cp[r][1], M, m0, g.KA);
+  gf_layer<MT, HP2, true, INF>(As, rg, rbuf, g.nst[2], lane, wave, bl[2], br[2], g.out[r][2], g.gate[r][2], g.cp[r][2], M, m0, g.KA);
   gf_wait_vm<0>();                                         // the run-ahead DMA pieces must not outlive the workgroup's LDS
 }
 

@@ -234,7 +234,8 @@ __device__ __forceinline__ void gb_write_operand(unsigned short* __restrict__ a0
     }
 }
 
-template <int HP, bool LAST>
+// INF: the inference forward (stemgnn_spectral_glu_fwd_split_infer) -- only the last layer's `out` is stored
+template <int HP, bool LAST, bool INF = false>
 __device__ __forceinline__ void gb_layer(unsigned short* Ab, int LDK, GfRing& rg, int& rbuf, int nk, int lane, int wave,
                                          const float (&bl)[2], const float (&br)[2], GbPend<HP>& next, int kcap) {
   const int fi = lane & 31, fk = (lane >> 5) << 3;
@@ -277,20 +278,24 @@ __device__ __forceinline__ void gb_layer(unsigned short* Ab, int LDK, GfRing& rg
         const float u = acc[i][h][0][reg] + bl[h], v = acc[i][h][1][reg] + br[h];
         next.gs[h][i][reg] = (GB_ABL & 16) ? v : gb_sigmoid(v);
         next.o[h][i][reg] = u * next.gs[h][i][reg];
+        // INF: with its store gone, hipcc would contract the product into the operand split's remainder o - bf16(o) (an FMA
+        // with a different rounding than the training kernel's multiply then subtract): keep the rounded product
+        if constexpr (INF) asm volatile("" : "+v"(next.o[h][i][reg]));
       }
     if constexpr (!LAST) {
       if (c < kcap && !(GB_ABL & 8)) gb_write_operand(Ab + c, plane_stride, LDK, next.o[h], lane);   // (columns beyond the next K: never read)
     }
   }
 #pragma unroll
-  for (int e = 0; e < GbPend<HP>::N; ++e) next.store(e);
+  for (int e = 0; e < GbPend<HP>::N; ++e)
+    if (!INF || (LAST && (e & 1) == 0)) next.store(e);        // (e & 1: the gate half of the pending values)
   if constexpr (!LAST) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // published by the next layer's first barrier
   if (GB_ABL & 1) {
     if (acc[0][0][0][0] + acc[1][HP - 1][1][7] == 1.2345e-30f) Ab[0] = 1;    // keep the accumulators alive
   }
 }
 
-template <int HP01, int HP2>
+template <int HP01, int HP2, bool INF = false>
 static __global__ __launch_bounds__(256, 1) void sg_glu_fused_fwd_bf16_kernel(const GbArgs g) {
   extern __shared__ __attribute__((aligned(16))) float gb_lds[];   // ONE array: the two activation planes, then the ring
   unsigned short* Ab = reinterpret_cast<unsigned short*>(gb_lds);
@@ -354,9 +359,9 @@ static __global__ __launch_bounds__(256, 1) void sg_glu_fused_fwd_bf16_kernel(co
   p0.init(g.out[r][0], g.gate[r][0], g.cp[r][0], M, m0, lane, wave);
   p1.init(g.out[r][1], g.gate[r][1], g.cp[r][1], M, m0, lane, wave);
   p2.init(g.out[r][2], g.gate[r][2], g.cp[r][2], M, m0, lane, wave);
-  gb_layer<HP01, false>(Ab, LDK, rg, rbuf, g.kp[0] / 16, lane, wave, bl[0], br[0], p0, g.kp[1]);
-  gb_layer<HP01, false>(Ab, LDK, rg, rbuf, g.kp[1] / 16, lane, wave, bl[1], br[1], p1, g.kp[2]);
-  gb_layer<HP2, true>(Ab, LDK, rg, rbuf, g.kp[2] / 16, lane, wave, bl[2], br[2], p2, 0);
+  gb_layer<HP01, false, INF>(Ab, LDK, rg, rbuf, g.kp[0] / 16, lane, wave, bl[0], br[0], p0, g.kp[1]);
+  gb_layer<HP01, false, INF>(Ab, LDK, rg, rbuf, g.kp[1] / 16, lane, wave, bl[1], br[1], p1, g.kp[2]);
+  gb_layer<HP2, true, INF>(Ab, LDK, rg, rbuf, g.kp[2] / 16, lane, wave, bl[2], br[2], p2, 0);
   gf_wait_vm<0>();                                         // the run-ahead DMA pieces must not outlive the workgroup's LDS
 }
 

@@ -150,6 +150,8 @@ __global__ void gru_transpose_kernel(const float* __restrict__ w, float* __restr
 
 // ---- forward recurrence: one workgroup (16 waves) per batch row ---------------------------------------------
 // dynamic LDS: h[Hd] | part[ks][3][Hd]
+// RS = false: the inference form (stemgnn_gru_fwd_infer) -- the same arithmetic without the `reserve` stores
+template <bool RS>
 __global__ __launch_bounds__(1024) void gru_fwd_kernel(const float* __restrict__ gi, const float* __restrict__ w_hhT,
                                                        const float* __restrict__ b_hh, int B, int S, int Hd,
                                                        float* __restrict__ h_all, float* __restrict__ reserve) {
@@ -201,8 +203,10 @@ __global__ __launch_bounds__(1024) void gru_fwd_kernel(const float* __restrict__
       const float z = gru_sigmoid(gip[Hd + i] + g1);
       const float n = tanhf(gip[2 * Hd + i] + r * g2);
       const float hn = (1.f - z) * n + z * hs[i];
-      float* rs = reserve + row * 4 * Hd;
-      rs[i] = r; rs[Hd + i] = z; rs[2 * Hd + i] = n; rs[3 * Hd + i] = g2;
+      if constexpr (RS) {
+        float* rs = reserve + row * 4 * Hd;
+        rs[i] = r; rs[Hd + i] = z; rs[2 * Hd + i] = n; rs[3 * Hd + i] = g2;
+      }
       h_all[row * Hd + i] = hn;
       hs[i] = hn;      // hs[i] is only read by this thread in this phase; phase 1 readers are past the barrier
     }
@@ -362,7 +366,7 @@ __device__ __forceinline__ void gru_cluster_ids(int B, int P, int& b, int& p) {
 }
 
 // forward.  dynamic LDS: hs[Hd] | part[ksf][3][U]
-template <int KC>
+template <int KC, bool RS = true>
 __global__ __launch_bounds__(1024) void gru_fwd_cluster_kernel(const float* __restrict__ gi, const float* __restrict__ w_hh,
                                                                const float* __restrict__ b_hh, int B, int S, int Hd, int P,
                                                                gru_u64* __restrict__ xbuf, int* __restrict__ status,
@@ -433,8 +437,10 @@ __global__ __launch_bounds__(1024) void gru_fwd_cluster_kernel(const float* __re
       const float z = gru_sigmoid(gp1 + g1);
       const float n = tanhf(gp2 + r * g2);
       const float hn = (1.f - z) * n + z * hs[gu];
-      float* rs = reserve + row * 4 * Hd;
-      rs[gu] = r; rs[Hd + gu] = z; rs[2 * Hd + gu] = n; rs[3 * Hd + gu] = g2;
+      if constexpr (RS) {
+        float* rs = reserve + row * 4 * Hd;
+        rs[gu] = r; rs[Hd + gu] = z; rs[2 * Hd + gu] = n; rs[3 * Hd + gu] = g2;
+      }
       h_all[row * Hd + gu] = hn;
       hs[gu] = hn;
       if (P > 1 && s + 1 < S) gru_publish(xbuf + ((size_t)((s + 1) & 1) * B + b) * Hd + gu, (unsigned)(s + 1), hn);
@@ -972,10 +978,11 @@ extern "C" int stemgnn_gru_bwd_cus(int B, int Hd) {
   return B * (P > 0 ? P : 1);
 }
 
-extern "C" int stemgnn_gru_fwd(const float* x, const float* w_ih, const float* w_hh, const float* b_ih,
-                               const float* b_hh, int B, int S, int Hd, int W, float* scratch, float* h_ext,
-                               float* reserve, int* status, void* stream) {
-  if (!x || !w_ih || !w_hh || !b_ih || !b_hh || !scratch || !h_ext || !reserve || !status || B <= 0 || S <= 0 ||
+// RS = false: the inference forward -- the same launches and arithmetic, no `reserve` stores (reserve may be NULL)
+template <bool RS>
+static int gru_fwd_impl(const float* x, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, int B,
+                        int S, int Hd, int W, float* scratch, float* h_ext, float* reserve, int* status, void* stream) {
+  if (!x || !w_ih || !w_hh || !b_ih || !b_hh || !scratch || !h_ext || (RS && !reserve) || !status || B <= 0 || S <= 0 ||
       Hd <= 0 || W <= 0)
     return SG_EINVAL;
   hipStream_t st = (hipStream_t)stream;
@@ -1012,7 +1019,7 @@ extern "C" int stemgnn_gru_fwd(const float* x, const float* w_ih, const float* w
   }
   if (use_wide) {
     float* xb = scratch + ((((size_t)3 * Hd * Hd + (size_t)3 * S * B * Hd) + 3) & ~(size_t)3);      // 16-byte aligned
-    SG_TRY(gru_wide_fwd(gi, w_hh, b_hh, B, S, Hd, wide, xb, status, h_all, reserve, st));
+    SG_TRY(gru_wide_fwd<RS>(gi, w_hh, b_hh, B, S, Hd, wide, xb, status, h_all, reserve, st));
     return 0;
   }
   if (P2 > 0) {
@@ -1033,7 +1040,7 @@ extern "C" int stemgnn_gru_fwd(const float* x, const float* w_ih, const float* w
     const int UF = (Hd + PF - 1) / PF;
     const int KF = UF <= 32 ? 32 : (UF <= 34 ? 34 : (UF <= 40 ? 40 : (UF <= 48 ? 48 : (UF <= 58 ? 58 : 64))));
     const dim3 grid4(8 * ((B + 7) / 8) * PF);
-#define GRU_F4K(PP, KK) hipLaunchKernelGGL((gru_fwd_cluster4_kernel<PP, KK>), grid4, dim3((PP + 2) * 64), 0, st, gi, w_hh, \
+#define GRU_F4K(PP, KK) hipLaunchKernelGGL((gru_fwd_cluster4_kernel<PP, KK, RS>), grid4, dim3((PP + 2) * 64), 0, st, gi, w_hh, \
                                            b_hh, B, S, Hd, xbuf, status, h_all, reserve, xid, allow_fast)
 #define GRU_F4(PP) do { if (KF == 32) GRU_F4K(PP, 32); else if (KF == 34) GRU_F4K(PP, 34); else if (KF == 40) GRU_F4K(PP, 40); \
                         else if (KF == 48) GRU_F4K(PP, 48); else if (KF == 58) GRU_F4K(PP, 58); else GRU_F4K(PP, 64); } while (0)
@@ -1051,7 +1058,7 @@ extern "C" int stemgnn_gru_fwd(const float* x, const float* w_ih, const float* w
     if (P > 1) SG_TRY(sg_zero_async(xbuf, (size_t)2 * B * Hd * sizeof(gru_u64), st));   // tags := 0 every launch
     const size_t lds = (size_t)(Hd + GRU_KC + c.ksf * 3 * c.U) * sizeof(float);
     const dim3 grid(8 * ((B + 7) / 8) * P);
-    hipLaunchKernelGGL(gru_fwd_cluster_kernel<GRU_KC>, grid, dim3(1024), lds, st, gi, w_hh, b_hh, B, S, Hd, P, xbuf,
+    hipLaunchKernelGGL((gru_fwd_cluster_kernel<GRU_KC, RS>), grid, dim3(1024), lds, st, gi, w_hh, b_hh, B, S, Hd, P, xbuf,
                        status, h_all, reserve);
     SG_TRY(hipGetLastError());
     return 0;
@@ -1063,9 +1070,20 @@ extern "C" int stemgnn_gru_fwd(const float* x, const float* w_ih, const float* w
   const int ks = nub >= 16 ? 1 : 16 / nub;
   const size_t lds = (size_t)(Hd + ks * 3 * Hd) * sizeof(float);
   if (lds > 64 * 1024) return SG_EINVAL;
-  hipLaunchKernelGGL(gru_fwd_kernel, dim3(B), dim3(1024), lds, st, gi, w_hhT, b_hh, B, S, Hd, h_all, reserve);
+  hipLaunchKernelGGL(gru_fwd_kernel<RS>, dim3(B), dim3(1024), lds, st, gi, w_hhT, b_hh, B, S, Hd, h_all, reserve);
   SG_TRY(hipGetLastError());
   return 0;
+}
+
+extern "C" int stemgnn_gru_fwd(const float* x, const float* w_ih, const float* w_hh, const float* b_ih,
+                               const float* b_hh, int B, int S, int Hd, int W, float* scratch, float* h_ext,
+                               float* reserve, int* status, void* stream) {
+  return gru_fwd_impl<true>(x, w_ih, w_hh, b_ih, b_hh, B, S, Hd, W, scratch, h_ext, reserve, status, stream);
+}
+extern "C" int stemgnn_gru_fwd_infer(const float* x, const float* w_ih, const float* w_hh, const float* b_ih,
+                                     const float* b_hh, int B, int S, int Hd, int W, float* scratch, float* h_ext,
+                                     int* status, void* stream) {
+  return gru_fwd_impl<false>(x, w_ih, w_hh, b_ih, b_hh, B, S, Hd, W, scratch, h_ext, nullptr, status, stream);
 }
 
 // weight-gradient GEMMs of the rows [row0, row0 + rows) of the recurrence: dW_hh | db_hh and dW_ih | db_ih as split slabs

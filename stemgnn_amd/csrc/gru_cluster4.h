@@ -139,7 +139,7 @@ constexpr int GRU4_WMAX = 16;            // window lengths up to this have dW_ih
 #ifndef GRU_CHORE_SLEEP_B
 #define GRU_CHORE_SLEEP_B 10
 #endif
-template <int P, int KU>
+template <int P, int KU, bool RS = true>     // RS = false: no `reserve` stores (stemgnn_gru_fwd_infer)
 __global__ __launch_bounds__((P + 2) * 64) void gru_fwd_cluster4_kernel(const float* __restrict__ gi, const float* __restrict__ w_hh,
                                                                         const float* __restrict__ b_hh, int B, int S, int Hd,
                                                                         gru_u64* __restrict__ xbuf, int* __restrict__ status,
@@ -224,8 +224,10 @@ __global__ __launch_bounds__((P + 2) * 64) void gru_fwd_cluster4_kernel(const fl
       }
       if (s >= 2 && lane_ok) {
         const size_t rw = (size_t)(s - 2) * B + b;
-        float* rs = reserve + rw * 4 * Hd + gu;
-        rs[0] = r; rs[Hd] = z; rs[2 * Hd] = n; rs[3 * Hd] = g2;
+        if constexpr (RS) {
+          float* rs = reserve + rw * 4 * Hd + gu;
+          rs[0] = r; rs[Hd] = z; rs[2 * Hd] = n; rs[3 * Hd] = g2;
+        }
         h_all[rw * Hd + gu] = hn;
       }
       gru_lds_barrier();                                 // #s
@@ -234,9 +236,11 @@ __global__ __launch_bounds__((P + 2) * 64) void gru_fwd_cluster4_kernel(const fl
     for (int t = (S >= 2 ? S - 2 : S - 1); t < S; ++t) {
       const size_t rw = (size_t)t * B + b;
       if (lane_ok) {
-        float* rs = reserve + rw * 4 * Hd + gu;
-        rs[0] = stash[t & 1][0][lane]; rs[Hd] = stash[t & 1][1][lane]; rs[2 * Hd] = stash[t & 1][2][lane];
-        rs[3 * Hd] = stash[t & 1][3][lane];
+        if constexpr (RS) {
+          float* rs = reserve + rw * 4 * Hd + gu;
+          rs[0] = stash[t & 1][0][lane]; rs[Hd] = stash[t & 1][1][lane]; rs[2 * Hd] = stash[t & 1][2][lane];
+          rs[3 * Hd] = stash[t & 1][3][lane];
+        }
         h_all[rw * Hd + gu] = stash[t & 1][4][lane];
       }
     }

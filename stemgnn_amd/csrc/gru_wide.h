@@ -86,7 +86,7 @@ __device__ __forceinline__ gw_f4 gw_load(__amdgpu_buffer_rsrc_t r, int group, in
 
 // ---- forward ---------------------------------------------------------------------------------------------------
 // MT = 16-row MFMA tiles covering the 3U gate rows, GW = 16-unit groups per wave (<= GW * 8 * 16 hidden units)
-template <int MT, int GW, bool MASK>
+template <int MT, int GW, bool MASK, bool RS = true>     // RS = false: no `reserve` stores (stemgnn_gru_fwd_infer)
 __global__ __launch_bounds__(GW_NW * 64) void gru_fwd_wide_kernel(
     const float* __restrict__ gi, const float* __restrict__ w_hh, const float* __restrict__ b_hh, int B, int b0, int Bc,
     int S, int Hd, int U, int KG, float* __restrict__ hx, unsigned* __restrict__ flags, int* __restrict__ status,
@@ -228,8 +228,10 @@ __global__ __launch_bounds__(GW_NW * 64) void gru_fwd_wide_kernel(
     GW_ACC(c_sync2, t5, t4);
     if (tid == 0 && s + 1 < S) __hip_atomic_store(flags + (size_t)p * GW_FS, (unsigned)(s + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (gate) {                                            // saved tensors: off the critical path, after the flag
-      float* rsv = reserve + row * 4 * Hd;
-      rsv[gu] = r; rsv[Hd + gu] = z; rsv[2 * Hd + gu] = n; rsv[3 * Hd + gu] = g2;
+      if constexpr (RS) {
+        float* rsv = reserve + row * 4 * Hd;
+        rsv[gu] = r; rsv[Hd + gu] = z; rsv[2 * Hd + gu] = n; rsv[3 * Hd + gu] = g2;
+      }
       h_all[row * Hd + gu] = hn;
     }
   }
@@ -394,6 +396,7 @@ static inline int gru_wide_plan(int Hd, int pmax, GruWide* out) {
   return g.P;
 }
 
+template <bool RS = true>
 static inline hipError_t gru_wide_fwd(const float* gi, const float* w_hh, const float* b_hh, int B, int S, int Hd,
                                       const GruWide& g, float* xbuf, int* status, float* h_all, float* reserve,
                                       hipStream_t st) {
@@ -403,7 +406,7 @@ static inline hipError_t gru_wide_fwd(const float* gi, const float* w_hh, const 
     const int Bc = B - b0 < GW_BP ? B - b0 : GW_BP;
     hipError_t e = sg_zero_async(xbuf, ((size_t)2 * 3 * g.KG * 256 + (size_t)1024 * GW_FS) * sizeof(float), st);
     if (e != hipSuccess) return e;
-#define GWF2(MT_, GW_, MK_) hipLaunchKernelGGL((gru_fwd_wide_kernel<MT_, GW_, MK_>), dim3(g.P), dim3(GW_NW * 64), 0, st, gi, w_hh, \
+#define GWF2(MT_, GW_, MK_) hipLaunchKernelGGL((gru_fwd_wide_kernel<MT_, GW_, MK_, RS>), dim3(g.P), dim3(GW_NW * 64), 0, st, gi, w_hh, \
                                                b_hh, B, b0, Bc, S, Hd, g.U, g.KG, hx, flags, status, h_all, reserve)
 #define GWF(MT_, GW_) do { if (Bc <= 8) GWF2(MT_, GW_, true); else GWF2(MT_, GW_, false); } while (0)
     if (g.GWf <= 8) { if (g.MT == 1) GWF(1, 8); else if (g.MT == 2) GWF(2, 8); else GWF(3, 8); }

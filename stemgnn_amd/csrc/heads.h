@@ -112,7 +112,8 @@ __device__ __forceinline__ float hd_sigmoid(float v) { return __frcp_rn(1.f + __
 
 // NW = 4: a wave owns both 16-row tiles of its column tiles (rounds 3-5).  NW = 8: one row tile each -- half the MFMA chain
 // and half the epilogue stores per wave in every phase of this one-workgroup-per-CU, latency-bound kernel.
-template <int NW>
+// SAVE = false: the inference forward (stemgnn_igft_heads_fwd_infer) -- ig / fs stay in LDS, no global stores of them
+template <int NW, bool SAVE = true>
 __global__ __launch_bounds__(NW * 64) void sg_heads_fwd_kernel(const HeadsFwdArgs g) {
   constexpr int NT = NW * 64;
   constexpr bool SPLIT = NW == 8;
@@ -190,10 +191,10 @@ __global__ __launch_bounds__(NW * 64) void sg_heads_fwd_kernel(const HeadsFwdArg
       const int r0 = rh * 16 + kq * 4 + reg, r1 = 16 + r0;
       if (col < Wm) {
         igs[r0 * ldi + col] = c0[reg];
-        if (m0 + r0 < M) g.ig[(size_t)(m0 + r0) * Wm + col] = c0[reg];
+        if (SAVE && m0 + r0 < M) g.ig[(size_t)(m0 + r0) * Wm + col] = c0[reg];
         if constexpr (!SPLIT) {
           igs[r1 * ldi + col] = c1[reg];
-          if (m0 + r1 < M) g.ig[(size_t)(m0 + r1) * Wm + col] = c1[reg];
+          if (SAVE && m0 + r1 < M) g.ig[(size_t)(m0 + r1) * Wm + col] = c1[reg];
         }
       }
     }
@@ -214,11 +215,11 @@ __global__ __launch_bounds__(NW * 64) void sg_heads_fwd_kernel(const HeadsFwdArg
       if (col < Wm) {
         const float s0 = hd_sigmoid(c0[reg] + bias);
         fss[r0 * ldi + col] = s0;
-        if (m0 + r0 < M) g.fs[(size_t)(m0 + r0) * Wm + col] = s0;
+        if (SAVE && m0 + r0 < M) g.fs[(size_t)(m0 + r0) * Wm + col] = s0;
         if constexpr (!SPLIT) {
           const float s1 = hd_sigmoid(c1[reg] + bias);
           fss[r1 * ldi + col] = s1;
-          if (m0 + r1 < M) g.fs[(size_t)(m0 + r1) * Wm + col] = s1;
+          if (SAVE && m0 + r1 < M) g.fs[(size_t)(m0 + r1) * Wm + col] = s1;
         }
       }
     }

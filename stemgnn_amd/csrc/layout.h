@@ -266,6 +266,28 @@ SG_HD SgSavedLayout sg_saved_layout(const SgDims& d) {
   return L;
 }
 
+// ---- inference workspace of one StockBlock forward (floats; the stemgnn_*_infer entry points) ----------------------
+// Only what the forward itself reads again: G, the last GLU layer's outputs (the heads' input) and, where a per-layer GLU
+// launch or the per-stage heads path runs, two ping-pong slabs per branch for the layer-0 / layer-1 outputs (the per-stage
+// heads reuse pp[0][0] / pp[0][1] for ig / fs once the GLU stack is done).  The slabs sit at the end, so the offsets of G and
+// out2 do not depend on whether they are present.
+struct SgInferLayout {
+  size_t G;              // M x KG
+  size_t out2[2];        // M x CP2[r]
+  size_t pp[2][2];       // [branch][slot] M x CP (only with pp)
+  size_t total;
+};
+SG_HD SgInferLayout sg_infer_layout(const SgDims& d, bool pp) {
+  SgInferLayout L;
+  size_t off = 0, M = (size_t)d.M;
+  L.G = off; off += M * d.KG;
+  for (int r = 0; r < 2; ++r) { L.out2[r] = off; off += M * d.CP2[r]; }
+  for (int r = 0; r < 2; ++r)
+    for (int k = 0; k < 2; ++k) { L.pp[r][k] = off; if (pp) off += M * d.CP; }
+  L.total = off;
+  return L;
+}
+
 // ---- backward scratch of one StockBlock (floats) ------------------------------------------------
 struct SgScratchLayout {
   size_t dpF;            // M x Wm

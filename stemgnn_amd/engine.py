@@ -664,3 +664,119 @@ class TrainStep:
         if reset:
             self.loss_sum.zero_()
         return v
+
+
+class ForecastStep:
+    """The inference counterpart of TrainStep: the rolling forecast of one batch (what trainer.rolling_forecast does per
+    loader batch, models/handler.py:41-65) as ONE captured hipGraph, replayed per batch.
+
+    A replay gathers the next batch_size windows of the loaded order through the device-side queue
+    (stemgnn_window_gather_queue), runs Model.predict on them and ceil(horizon / H) - 1 more rounds of roll_window + predict
+    until `horizon` steps exist, then writes forecast and target into the result slabs [count, horizon, N] at the queue
+    position (stemgnn_forecast_store): no per-batch index or tensor copy from the host.  A ragged last batch runs the same
+    code eagerly.  Model.predict neither reads nor changes the model's training state, so a pass can sit between two
+    TrainStep replays.
+
+        fs = ForecastStep(model, batch_size, window, horizon, series, order_capacity)
+        fs.load_order(hi_all)              # window-end rows, int64
+        while fs.remaining: fs.run_next()
+        forecast, target = fs.result()     # rolling_forecast's format: [count, horizon, N] each
+    """
+
+    def __init__(self, model, batch_size, window, horizon, series, order_capacity, graph=True):
+        self.model = model
+        self.B, self.W, self.horizon = int(batch_size), int(window), int(horizon)
+        if series is None or series.dim() != 2:
+            raise ValueError("ForecastStep needs the resident series [T, N]")
+        self.series = series
+        self.N = int(series.shape[1])
+        dev = series.device
+        self.device = dev
+        cap = max(int(order_capacity), self.B)
+        self.order = torch.full((cap,), self.W, dtype=torch.int64, device=dev)   # every slot a valid window end
+        self.queue = torch.zeros(4, dtype=torch.int64, device=dev)              # {position, arrival ticket, count, wrap}
+        self._q_header = torch.zeros(4, dtype=torch.int64).pin_memory()
+        self.pos = torch.zeros(1, dtype=torch.int64, device=dev)                # queue position of the batch in flight
+        self.x = torch.zeros(self.B, self.W, self.N, device=dev)
+        self.y = torch.zeros(self.B, self.horizon, self.N, device=dev)
+        self.steps = torch.zeros(self.B, self.horizon, self.N, device=dev)
+        self.out_forecast = torch.zeros(cap, self.horizon, self.N, device=dev)
+        self.out_target = torch.zeros(cap, self.horizon, self.N, device=dev)
+        self.want_graph = bool(graph)
+        self._replay = None
+        self._armed = False
+        self._n = 0
+        self._done = 0
+
+    def _set_queue(self, position, count, wrap=0):
+        h = self._q_header
+        h[0], h[1], h[2], h[3] = int(position), 0, int(count), int(wrap)
+        self.queue.copy_(h, non_blocking=False)
+
+    def _roll(self, window, steps):
+        """Rolling inference of one batch (trainer.rolling_forecast's inner loop) into `steps`."""
+        done = 0
+        while done < self.horizon:
+            out, _ = self.model.predict(window)
+            window = ops.roll_window(window, out, steps, done, self.horizon)
+            done += min(self.horizon - done, out.shape[1])
+
+    def _body(self):
+        self.pos.copy_(self.queue[:1])                  # device-side position before the gather advances it
+        ops.window_gather_queue(self.series, self.order, self.queue, self.B, self.W, self.horizon, self.x, self.y)
+        self._roll(self.x, self.steps)
+        ops.forecast_store(self.steps, self.y, self.pos, self.out_forecast, self.out_target)
+
+    def _arm(self):
+        """Capture the replay.  The capture's warm-up runs read the order in wrap mode; the iterator is put back afterwards
+        and the batch is then run for real (the warm-up writes land in rows the pass overwrites)."""
+        self._armed = True
+        if not self.want_graph:
+            return
+        keep = self.queue.clone()
+        self._set_queue(0, self.order.numel(), wrap=1)
+        try:
+            self._replay = capture(self._body, warmups=1)
+        finally:
+            self.queue.copy_(keep)
+
+    @property
+    def remaining(self):
+        return self._n - self._done
+
+    def load_order(self, hi_all):
+        """Window-end rows of the pass (int64, any device); results go to rows 0 .. count-1 of the slabs in this order."""
+        hi_all = hi_all.reshape(-1)
+        n = hi_all.numel()
+        if n > self.order.numel():
+            raise ValueError(f"load_order: {n} windows exceed order_capacity {self.order.numel()}")
+        self.order[:n].copy_(hi_all)
+        self._set_queue(0, n)
+        self._n, self._done = n, 0
+
+    def run_next(self):
+        """Rolling forecast of the next batch_size windows (fewer for the ragged last batch, which runs eagerly)."""
+        left = self._n - self._done
+        if left <= 0:
+            raise IndexError("run_next: the loaded order is exhausted")
+        if left < self.B:
+            p = self._done
+            hi = self.order[p:p + left]
+            x, y = ops.window_gather(self.series, hi, self.W, self.horizon)
+            steps = torch.empty(left, self.horizon, self.N, device=self.device)
+            self._roll(x, steps)
+            self.out_forecast[p:p + left].copy_(steps)
+            self.out_target[p:p + left].copy_(y)
+            self._done = self._n
+            return
+        if not self._armed:
+            self._arm()
+        if self._replay is not None:
+            self._replay()
+        else:
+            self._body()
+        self._done += self.B
+
+    def result(self):
+        """(forecast, target) [count, horizon, N] of the windows run so far, in load_order's order (views of the slabs)."""
+        return self.out_forecast[:self._done], self.out_target[:self._done]

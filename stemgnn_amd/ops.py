@@ -1021,6 +1021,99 @@ class SpectralHotPath(torch.autograd.Function):
 # ---------------------------------------------------------------------------------------------------------------
 # data path either side of the hot path: thin wrappers over csrc/data.hip
 
+def forecast_forward(x, gru_params, wk, wq, multi, alpha, drop_p, block_params, fc_params):
+    """Inference forward of Model (reference models/base_model.py:136-179 in eval mode) without autograd and without the
+    tensors only a backward pass reads: the GRU recurrence without its gate reserve (stemgnn_gru_fwd_infer), attention /
+    Laplacian with training = 0, Chebyshev basis (eigen route under STEMGNN_SPECTRAL=eig), both StockBlocks on the _infer
+    entries (one workspace of stemgnn_infer_workspace_split_floats floats, reused by block 1), then the fc tail kernel.
+    Same kernels and arithmetic as SpectralHotPath.forward in eval mode: bit-identical outputs.  The weights are packed
+    on every call, as in training.  x [B,W,N]; gru_params = (weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0);
+    block_params = 2 x 33 block tensors; fc_params = (fc.0.weight, fc.0.bias, fc.2.weight, fc.2.bias).
+    Returns (forecast [B,H,N], attention [N,N])."""
+    lib = _lib.load()
+    w_ih, w_hh, b_ih, b_hh = (t.contiguous() for t in gru_params)
+    for name, t in (("x", x), ("GRU.weight_ih_l0", w_ih), ("GRU.weight_hh_l0", w_hh), ("weight_key", wk),
+                    ("weight_query", wq)):
+        _require_gpu(t, name)
+    assert len(block_params) == 2 * _lib.SG_BLOCK_NPARAMS
+    x = x.contiguous()
+    B, W, N = x.shape
+    Hd = w_hh.shape[1]
+    if Hd != N:
+        raise _lib.StemGNNHipError(f"GRU hidden size {Hd} != units {N}")
+    dev, f32 = x.device, torch.float32
+    st = _stream()
+    # GRU (reference :137) -> h [N,B,N] = h_ext[1:]
+    h_ext = torch.empty(N + 1, B, Hd, device=dev, dtype=f32)
+    gscr = torch.empty(lib.stemgnn_gru_fwd_scratch_floats(B, N, Hd), device=dev, dtype=f32)
+    _lib.check(lib.stemgnn_gru_fwd_infer(x.data_ptr(), w_ih.data_ptr(), w_hh.data_ptr(), b_ih.data_ptr(), b_hh.data_ptr(),
+                                         B, N, Hd, W, gscr.data_ptr(), h_ext.data_ptr(), gru_status(dev).data_ptr(), st),
+               "gru_fwd_infer")
+    del gscr                        # (stream-ordered reuse by the caching allocator: lowers the call's peak)
+    # attention + Laplacian (eval: no dropout) and the spectral basis
+    mul_L = torch.empty(4, N, N, device=dev, dtype=f32)
+    attention = torch.empty(N, N, device=dev, dtype=f32)
+    attn_saved = torch.empty(lib.stemgnn_attn_saved_floats(B, N), device=dev, dtype=f32)
+    _lib.check(lib.stemgnn_attn_laplacian_fwd(h_ext[1:].data_ptr(), wk.data_ptr(), wq.data_ptr(), float(alpha), float(drop_p),
+                                              0, None, B, N, attn_saved.data_ptr(), attention.data_ptr(), mul_L.data_ptr(), 3,
+                                              st), "attn_laplacian_fwd")
+    if os.environ.get("STEMGNN_SPECTRAL", "cheb") == "eig":
+        lam = torch.empty(N, device=dev, dtype=f32)
+        U = torch.empty(N, N, device=dev, dtype=f32)
+        escr = torch.empty(lib.stemgnn_eigh_scratch_floats(N), device=dev, dtype=f32)
+        _lib.check(lib.stemgnn_eigh_fwd(mul_L.data_ptr(), lam.data_ptr(), U.data_ptr(), escr.data_ptr(), N, 0, st), "eigh_fwd")
+    else:
+        _lib.check(lib.stemgnn_cheb_fwd(mul_L.data_ptr(), N, st), "cheb_fwd")
+    del attn_saved
+    # both StockBlocks through one inference workspace (G | layer-2 GLU outputs | ping-pong slabs where needed)
+    splits = glu_splits()
+    tables = dft_tables(W, multi, dev)
+    n_ws = lib.stemgnn_infer_workspace_split_floats(B, N, W, multi, splits)
+    ws = torch.empty(n_ws, device=dev, dtype=f32)
+    fsum = torch.empty(B, N, W, device=dev, dtype=f32)
+    backcast = torch.empty(B, N, W, device=dev, dtype=f32)
+    n_packed = lib.stemgnn_packed_floats(W, multi)
+    blocks = [list(block_params[:33]), list(block_params[33:])]
+    xviews = [(x, W * N, 1, N), (backcast, N * W, W, 1)]   # X[b,n,t] strides of block 0 / block 1
+    for s in range(2):
+        blk = [None if p is None else p.contiguous() for p in blocks[s]]
+        parr = _lib.ptr_array(blk)
+        X, sb, sn, stt = xviews[s]
+        pk = torch.empty(n_packed, device=dev, dtype=f32)
+        _pack_block(lib, parr, tables, pk, W, multi, splits, st)
+        _lib.check(lib.stemgnn_gft_fwd(mul_L.data_ptr(), X.data_ptr(), sb, sn, stt, ws.data_ptr(), B, N, W, st), "gft_fwd")
+        if splits:
+            sp = _split_panels(lib, pk, W, multi, splits, dev, st)
+            _lib.check(lib.stemgnn_spectral_glu_fwd_split_infer(pk.data_ptr(), sp.data_ptr(), ws.data_ptr(), n_ws, B, N, W,
+                                                                multi, splits, st), "spectral_glu_fwd_split_infer")
+        else:
+            _lib.check(lib.stemgnn_spectral_glu_fwd_infer(pk.data_ptr(), ws.data_ptr(), n_ws, B, N, W, multi, st),
+                       "spectral_glu_fwd_infer")
+        _lib.check(lib.stemgnn_igft_heads_fwd_infer(parr, pk.data_ptr(), ws.data_ptr(), n_ws, X.data_ptr(), sb, sn, stt,
+                                                    fsum.data_ptr(), int(s == 1), backcast.data_ptr() if s == 0 else None,
+                                                    B, N, W, multi, st), "igft_heads_fwd_infer")
+    # fc tail (:175-179) -> [B,H,N]
+    w0, b0, w2, b2 = (t.contiguous() for t in fc_params)
+    H = w2.shape[0]
+    forecast = torch.empty(B, H, N, device=dev, dtype=f32)
+    _lib.check(lib.stemgnn_fc_tail_fwd(fsum.data_ptr(), w0.data_ptr(), b0.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                                       B, N, W, H, forecast.data_ptr(), st), "fc_tail_fwd")
+    return forecast, attention
+
+
+def forecast_store(forecast, target, pos, out_forecast, out_target):
+    """Result slabs of engine.ForecastStep: out_*[pos + b] = forecast / target[b] with the row position read on the device
+    (pos: int64[1]); rows at or beyond the slabs' capacity are dropped."""
+    lib = _lib.load()
+    B, H, N = forecast.shape
+    if target.shape != forecast.shape or out_forecast.shape[1:] != (H, N) or out_target.shape != out_forecast.shape:
+        raise _lib.StemGNNHipError("forecast_store: shape mismatch")
+    if pos.dtype != torch.int64 or pos.device != forecast.device:
+        raise _lib.StemGNNHipError("forecast_store: pos must be an int64 tensor on the forecast's device")
+    _lib.check(lib.stemgnn_forecast_store(forecast.data_ptr(), target.data_ptr(), pos.data_ptr(), out_forecast.data_ptr(),
+                                          out_target.data_ptr(), B, H, N, out_forecast.shape[0], _stream()), "forecast_store")
+
+
 class MSELossFn(torch.autograd.Function):
     """nn.MSELoss(reduction='mean') of the driver (reference models/handler.py:140,162) as two fixed-order kernels."""
 

@@ -26,7 +26,7 @@ import torch
 
 from . import ops
 from .base_model import Model
-from .engine import TrainStep
+from .engine import ForecastStep, TrainStep
 from .forecast_dataloader import ForecastDataset, WindowLoader, denorm_coefficients
 from .math_utils import Scores
 from .optim import FusedAdam, FusedRMSprop
@@ -74,6 +74,21 @@ def rolling_forecast(model, loader, horizon):
             targets.append(target)
     model.train(was_training)
     return torch.cat(forecasts), torch.cat(targets)
+
+
+def rolling_forecast_graph(model, dataset, horizon, batch_size):
+    """rolling_forecast(model, WindowLoader(dataset, batch_size), horizon) on engine.ForecastStep: each full batch is one
+    hipGraph replay of window gather -> Model.predict -> roll_window rounds -> result slabs; the ragged last batch runs
+    eagerly.  Same (forecast, target) [count, horizon, N], bit for bit; the model's training state is left untouched.
+    The dataset's horizon (its target length) must equal `horizon`."""
+    if int(dataset.horizon) != int(horizon):
+        raise ValueError(f"rolling_forecast_graph: dataset horizon {dataset.horizon} != horizon {horizon}")
+    n = len(dataset)
+    step = ForecastStep(model, batch_size, dataset.window_size, horizon, dataset.data, order_capacity=n)
+    step.load_order(dataset.hi_all)
+    while step.remaining > 0:
+        step.run_next()
+    return step.result()
 
 
 def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=None):
