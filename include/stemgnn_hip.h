@@ -341,6 +341,21 @@ int stemgnn_block_wgrad_split(const float* const* params_host, const float* pack
                               float* scratch, float* gradpart, int nsplit, int cu_percent, int B, int N, int W,
                               int multi, int splits, void* stream);
 
+/* Which launch path each stage of one StockBlock takes at a shape (host only, no GPU work): a bitmask of SG_PATH_*, asked
+ * through the same predicates the launchers use, for buffers allocated the way the model allocates them (each its own
+ * 256-byte aligned allocation).  splits: 0 exact fp32, 2 / 3 the split-bf16 GLU forms (STEMGNN_DTYPE=bf16x2 / bf16x3).
+ * Environment switches count as the launchers read them.  SG_EINVAL for a bad argument.  Tests use it to prove that their
+ * shapes reach every path (a moved threshold fails on the CPU instead of silently dropping coverage). */
+#define SG_PATH_GLU_FWD_FUSED   1    /* GLU forward: one fused three-layer launch (else per-layer launches)            */
+#define SG_PATH_GLU_DGRAD_FUSED 2    /* GLU data-gradient chain: one fused launch (else per-layer launches)           */
+#define SG_PATH_HEADS_FWD_FUSED 4    /* IGFT + heads forward: one fused kernel (else the per-stage GEMMs)             */
+#define SG_PATH_HEADS_BWD_FUSED 8    /* heads backward, data part: one fused kernel (else the per-stage GEMMs)        */
+#define SG_PATH_HEADS_BWD_16W   16   /* ... that kernel at 16 waves per workgroup (KF > 128; else 4)                  */
+#define SG_PATH_LONG_K          32   /* K of the folded IGFT GEMM > 640: the long-K (two-level) instantiations        */
+#define SG_PATH_WGRAD_FUSED     64   /* block 0's weight gradients in one fused launch (else the per-stage slab path) */
+#define SG_PATH_GLU_WGRAD_FUSED 128  /* the six GLU products alone fit that kernel (what the slab path's GLU part asks) */
+int stemgnn_block_paths(int B, int N, int W, int multi, int splits);
+
 /* ---- inference forward (no saved activations; Model.predict / engine.ForecastStep) ----------------------------------
  * The _infer entries run the same kernels and arithmetic as their training counterparts -- bit-identical outputs -- without the
  * stores only the backward pass reads: no GRU `reserve`, no GLU gates, no layer-0 / layer-1 GLU outputs where the fused kernels

@@ -264,12 +264,14 @@ def hot_path(gru_out, x, sd, alpha=0.2, drop_mask=None, drop_p=0.0, spectral="ch
     return f0 + f1, A_s, mul_L                            # :174
 
 
-def model_forward(x, sd, alpha=0.2, drop_mask=None, drop_p=0.0, spectral="cheb", kink_pos=None):
-    """models/base_model.py:167-179.  x [B,W,N] -> (forecast [B,H,N] (or [B,1,N] if H==1), attention [N,N])."""
+def model_forward(x, sd, alpha=0.2, drop_mask=None, drop_p=0.0, spectral="cheb", kink_pos=None, fc_kink_pos=None):
+    """models/base_model.py:167-179.  x [B,W,N] -> (forecast [B,H,N] (or [B,1,N] if H==1), attention [N,N]).
+    ``fc_kink_pos`` (bool [B,N,W], optional): as ``kink_pos``, for the fc tail's LeakyReLU (which side of 0 each
+    pre-activation is taken to be on)."""
     gru_out = gru_front(x, sd)
     fsum, A_s, _ = hot_path(gru_out, x, sd, alpha, drop_mask, drop_p, spectral, kink_pos)
     y = F.linear(fsum, sd["fc.0.weight"], sd["fc.0.bias"])               # :175
-    y = F.leaky_relu(y, 0.01)
+    y = F.leaky_relu(y, 0.01) if fc_kink_pos is None else torch.where(fc_kink_pos, y, 0.01 * y)
     y = F.linear(y, sd["fc.2.weight"], sd["fc.2.bias"])
     if y.shape[-1] == 1:                                                 # :176-177
         return y.unsqueeze(1).squeeze(-1), A_s

@@ -10,6 +10,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STEMGNN_HIP_LIB", os.path.join(_HERE, "libstemgnn_hip.so"))   # override: A/B builds only
 SG_BLOCK_NPARAMS = 33
 SG_EINVAL = -10001
+# bits of stemgnn_block_paths (SG_PATH_* in include/stemgnn_hip.h)
+SG_PATH = {"glu_fwd_fused": 1, "glu_dgrad_fused": 2, "heads_fwd_fused": 4, "heads_bwd_fused": 8, "heads_bwd_16w": 16,
+           "long_k": 32, "wgrad_fused": 64, "glu_wgrad_fused": 128}
 
 _P = c_void_p          # device pointer
 _PP = POINTER(c_void_p)  # host array of device pointers
@@ -94,6 +97,7 @@ SIGNATURES = {
     "stemgnn_glu_split_floats": (c_size_t, [c_int, c_int, c_int]),
     "stemgnn_glu_split_panels": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "stemgnn_glu_fused_bf16_ok": (c_int, [c_int, c_int, c_int]),
+    "stemgnn_block_paths": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "stemgnn_spectral_glu_fwd_split": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "stemgnn_glu_warm_saved_floats": (c_size_t, [c_int, c_int]),
     "stemgnn_spectral_glu_fwd_warm": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),

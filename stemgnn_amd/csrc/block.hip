@@ -643,6 +643,22 @@ static int glu_fwd_layers(const SgDims& d, const float* packed, const unsigned s
   return 0;
 }
 
+// ---- which launch path a shape takes (the launchers below and stemgnn_block_paths ask the same predicates) ----------
+// STEMGNN_GLU_FUSED, read per call: 0 off, 1 auto, 2 / 3: force 64- / 96-row workgroups of the fused GLU kernels (tests)
+static int glu_fused_mode() {
+  const char* ef = getenv("STEMGNN_GLU_FUSED");
+  return ef ? atoi(ef) : 1;
+}
+static inline bool sg_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// fp32 GLU forward: ONE fused three-layer launch (csrc/glu_fused.h), else three per-layer launches
+static bool glu_fwd_fused_ok(const SgDims& d, int fmode, const void* packed) {
+  return gf_geom(d).ok && fmode != 0 && sg_aligned16(packed);
+}
+// fp32 GLU data-gradient chain: ONE fused launch layer 2 -> 1 -> 0 -> dG (csrc/glu_fused.h), else per-layer launches
+static bool glu_dgrad_fused_ok(const SgDims& d, int dmode, const void* packed, const void* scratch) {
+  return gd_geom(d).ok && dmode != 0 && sg_aligned16(packed) && sg_aligned16(scratch);
+}
+
 // m_pick: the row count the block height (64 / 96 rows) is chosen for -- d.M itself, or the REAL launch's row count when this
 // call is its warm-up (stemgnn_spectral_glu_fwd_warm); fused_only: do nothing where the fused kernel does not apply.
 // INF: the inference forward (bf: sg_infer_layout); returns SG_EINVAL where it would need the ping-pong slabs and has none.
@@ -657,9 +673,8 @@ static int glu_fwd_impl(const float* packed, const GluFwdBufs& bf, int B, int N,
   // direct-to-LDS ring) where the padded channel count is <= 256; STEMGNN_GLU_FUSED=0 keeps the three per-layer launches
   // (read per call, so a test can compare the two on the same buffers).
   const GfGeom gg = gf_geom(d);
-  const char* ef = getenv("STEMGNN_GLU_FUSED");
-  const int fmode = ef ? atoi(ef) : 1;                  // 0 off, 1 auto, 2 / 3: force 64- / 96-row workgroups (tests)
-  if (gg.ok && fmode != 0 && (((uintptr_t)packed) & 15) == 0) {
+  const int fmode = glu_fused_mode();                   // 0 off, 1 auto, 2 / 3: force 64- / 96-row workgroups (tests)
+  if (glu_fwd_fused_ok(d, fmode, packed)) {
     const int mt = fmode == 3 && gg.ok3 ? 3 : (fmode == 2 ? 2 : gf_pick_mt(m_pick > 0 ? m_pick : d.M, sg_num_cus(), gg.ok3));
     if (fused_only && d.M != 4 * 32 * mt) return SG_EINVAL;
     GfArgs a;
@@ -738,6 +753,12 @@ static inline G2SLayout g2s_layout(const SgDims& d, int S) {
   for (int r = 0; r < 2; ++r) { L.DS[r] = off; off += S == 2 ? gq_stream_elems(d, r) : 0; }
   L.total = off;
   return L;
+}
+// split-bf16 GLU forward (bf16x2): ONE fused three-layer launch (csrc/glu_fused_bf16.h), else per-layer split launches
+static bool glu_fwd_fused_bf16_ok(const SgDims& d, int splits) { return splits == 2 && gb_geom(d).ok && gb_enabled(); }
+// split-bf16 GLU data-gradient chain (bf16x2): ONE fused launch, else per-layer split launches + the fp32 layer-0 product
+static bool glu_dgrad_fused_bf16_ok(const SgDims& d, int splits, const void* scratch) {
+  return splits == 2 && gq_geom(d).ok && gb_enabled() && sg_aligned16(scratch);
 }
 extern "C" size_t stemgnn_glu_split_floats(int W, int multi, int splits) {
   if (W <= 0 || multi <= 0 || splits < 2 || splits > 3) return 0;
@@ -822,7 +843,7 @@ static int glu_fwd_split_impl(const float* packed, const float* split, const Glu
   const unsigned short* base = reinterpret_cast<const unsigned short*>(split);
   hipStream_t st = (hipStream_t)stream;
   const GbGeom gb = gb_geom(d);
-  if (splits == 2 && gb.ok && gb_enabled()) {
+  if (glu_fwd_fused_bf16_ok(d, splits)) {
     // ONE launch for the three layers on the bf16 matrix pipe (csrc/glu_fused_bf16.h): activations of a 64-row block resident
     // in LDS as two bf16 planes, pre-split weights on the direct-to-LDS ring; saved out / gate are fp32 as ever
     GbArgs a;
@@ -887,9 +908,8 @@ extern "C" int stemgnn_spectral_glu_fwd_warm(const float* packed, const float* s
   }
   const SgDims d = sg_dims(B, N, W, multi);
   const GfGeom gg = gf_geom(d);
-  const char* ef = getenv("STEMGNN_GLU_FUSED");
-  const int fmode = ef ? atoi(ef) : 1;
-  if (!gg.ok || fmode == 0 || (((uintptr_t)packed) & 15) != 0) return 0;
+  const int fmode = glu_fused_mode();
+  if (!glu_fwd_fused_ok(d, fmode, packed)) return 0;
   const int mt = fmode == 3 && gg.ok3 ? 3 : (fmode == 2 ? 2 : gf_pick_mt(d.M, sg_num_cus(), gg.ok3));
   return glu_fwd_impl(packed, glu_bufs_saved(sg_dims(1, 4 * 32 * mt, W, multi), saved), 1, 4 * 32 * mt, W, multi, stream, d.M,
                       true);
@@ -909,7 +929,7 @@ extern "C" int stemgnn_spectral_glu_dgrad_split(const float* packed, const float
   const unsigned short* base = reinterpret_cast<const unsigned short*>(split);
   hipStream_t st = (hipStream_t)stream;
   const GqGeom gq = gq_geom(d);
-  if (splits == 2 && gq.ok && gb_enabled() && (((uintptr_t)scratch) & 15) == 0) {
+  if (glu_dgrad_fused_bf16_ok(d, splits, scratch)) {
     // ONE launch for layer 2 -> 1 -> 0's d(pre-activation) -> dG on the bf16 matrix pipe (csrc/glu_fused_bf16.h)
     GqArgs a;
     a.CP = d.CP; a.KG = d.KG; a.M = d.M; a.LDK = gq.LDK; a.nrb = (d.M + GB_BM - 1) / GB_BM;
@@ -972,6 +992,26 @@ extern "C" int stemgnn_spectral_glu_dgrad_split(const float* packed, const float
   return 0;
 }
 
+// the six GLU weight-gradient products as the fused weight-gradient kernel's list (csrc/wgrad.h); true where that kernel can
+// take them (its DMA path's 16-byte rules, at most SG_WG_MAX_TILES output tiles), else they run as per-layer slab GEMMs
+static bool glu_wgrad_list(const SgDims& d, const float* saved, const float* scratch, float* gradpart, const SgGradLayout& Gl,
+                           WgGemm (&wq)[6]) {
+  const SgSavedLayout S = sg_saved_layout(d);
+  const SgScratchLayout C = sg_scratch_layout(d);
+  bool ok = true;
+  for (int l = 0; l < 3; ++l)
+    for (int r = 0; r < 2; ++r) {
+      WgGemm& q = wq[l * 2 + r];
+      q.A = scratch + C.dact[r][l]; q.lda = sg_glu_np(d, l, r);
+      q.B = l == 0 ? saved + S.G : saved + S.out[r][l - 1]; q.ldb = l == 0 ? d.KG : d.CP;
+      q.out = gradpart + Gl.w[r][l];
+      q.Mi = sg_glu_np(d, l, r); q.Nj = sg_glu_kin(d, l) + 1; q.ones_col = sg_glu_kin(d, l);
+      q.ldo = q.Nj; q.out_bias = nullptr;
+      ok = ok && wg_gemm_ok(q);
+    }
+  return ok && wg_tiles_fit(wq, 6);
+}
+
 extern "C" int stemgnn_spectral_glu_bwd(const float* packed, const float* saved, float* scratch,
                                         float* gradpart, int nsplit, int parts, int B, int N, int W, int multi,
                                         void* stream) {
@@ -991,28 +1031,13 @@ extern "C" int stemgnn_spectral_glu_bwd(const float* packed, const float* saved,
   // take the round-1 path: per layer a split-M slab GEMM, then one reduce over the GLU slabs.  Either way slab 0 of
   // every GLU region holds the complete gradient when this function returns.
   WgGemm wq[6];
-  bool fused = (parts & 2) != 0;
-  if (parts & 2) {
-    for (int l = 0; l < 3; ++l)
-      for (int r = 0; r < 2; ++r) {
-        WgGemm& q = wq[l * 2 + r];
-        q.A = scratch + C.dact[r][l]; q.lda = sg_glu_np(d, l, r);
-        q.B = l == 0 ? saved + S.G : saved + S.out[r][l - 1]; q.ldb = l == 0 ? d.KG : d.CP;
-        q.out = gradpart + Gl.w[r][l];
-        q.Mi = sg_glu_np(d, l, r); q.Nj = sg_glu_kin(d, l) + 1; q.ones_col = sg_glu_kin(d, l);
-        q.ldo = q.Nj; q.out_bias = nullptr;
-        fused = fused && wg_gemm_ok(q);
-      }
-    fused = fused && wg_tiles_fit(wq, 6);
-  }
+  const bool fused = (parts & 2) != 0 && glu_wgrad_list(d, saved, scratch, gradpart, Gl, wq);
   // data-gradient chain: ONE launch for layer 2 -> 1 -> 0's d(pre-activation) (csrc/glu_fused.h, operand resident in LDS,
   // weights on the direct-to-LDS ring) where the padded channel count is <= 256; STEMGNN_GLU_FUSED=0 keeps the two
   // per-layer launches and the GluDgrad0Op product.
   const GdGeom gdg = gd_geom(d);
-  const char* efd = getenv("STEMGNN_GLU_FUSED");
-  const int dmode = efd ? atoi(efd) : 1;                // 0 off, 1 auto, 2 / 3: force 64- / 96-row workgroups (tests)
-  const bool fused_dgrad = (parts & 1) && gdg.ok && dmode != 0 && (((uintptr_t)packed) & 15) == 0 &&
-                           (((uintptr_t)scratch) & 15) == 0;
+  const int dmode = glu_fused_mode();                   // 0 off, 1 auto, 2 / 3: force 64- / 96-row workgroups (tests)
+  const bool fused_dgrad = (parts & 1) && glu_dgrad_fused_ok(d, dmode, packed, scratch);
   if (fused_dgrad) {
     const int mt = dmode == 3 && gdg.ok3 ? 3 : (dmode == 2 ? 2 : gf_pick_mt(d.M, sg_num_cus(), gdg.ok3));
     GdArgs a;
@@ -1250,6 +1275,20 @@ static hipError_t heads_reduce(const SgDims& d, const SgGradLayout& G, float* gr
   return sg_reduce_slabs(gradpart, R, nsplit, st);
 }
 
+// 1 where the data part of the heads backward runs as ONE fused kernel (heads.h), 0 where it takes the per-stage launches
+// (d(sigmoid) of the backcast, dpF, dig and the last GLU layer's d(pre-activation) through memory)
+static bool heads_bwd_fused_ok(const SgDims& d) {
+  return hd_bwd_lds_floats(d.WmP, d.W) * sizeof(float) <= (size_t)150 * 1024 && d.Wm <= SG_LONG_K;
+}
+// waves per workgroup of the fused heads backward.  Its d(pre-activation) phase's column tiles over 16 waves (one tile each),
+// 8 (two) or 4 (four: rounds 3-5): the kernel is one workgroup per CU and latency-bound, a wave's epilogue loads / stores are
+// what shrinks (2 launches per step: 53.2 / 44.1 / 40.9 us at 4 / 8 / 16 waves); STEMGNN_HEADS_BWD_WAVES = 4 | 8 | 16, read
+// once per process.  KF <= 128 always takes 4.
+static int heads_bwd_waves(const SgDims& d) {
+  static const int waves_env = getenv("STEMGNN_HEADS_BWD_WAVES") ? atoi(getenv("STEMGNN_HEADS_BWD_WAVES")) : 16;
+  return (waves_env == 16 || waves_env == 8) && d.KF > 128 ? waves_env : 4;
+}
+
 extern "C" int stemgnn_igft_heads_bwd(const float* const* params_host, const float* packed, const float* saved,
                                       const float* X, long xs_b, long xs_n, long xs_t,
                                       const float* dforecast, const float* dbackcast, const float* backcast,
@@ -1272,7 +1311,7 @@ extern "C" int stemgnn_igft_heads_bwd(const float* const* params_host, const flo
   bool fused_data = false;
   {
     const size_t hb = hd_bwd_lds_floats(d.WmP, W) * sizeof(float);
-    if ((parts & 1) && hb <= (size_t)150 * 1024 && d.Wm <= SG_LONG_K) {
+    if ((parts & 1) && heads_bwd_fused_ok(d)) {
       HeadsBwdArgs a;
       a.dfo = dforecast; a.dbc = dbackcast; a.bc = backcast; a.fs = saved + S.fs; a.wfold = packed + P.wfold;
       a.Fw = params_host[1]; a.FRw = params_host[3]; a.BCw = params_host[5];
@@ -1283,15 +1322,12 @@ extern "C" int stemgnn_igft_heads_bwd(const float* const* params_host, const flo
       a.dpF = dpF; a.dpB = dpB; a.dig = dig;
       a.M = d.M; a.W = W; a.Wm = d.Wm; a.WmP = d.WmP; a.KF = d.KF; a.has_bc = has_bc;
       a.ldi = d.WmP + 1; a.ldw = ((W + 3) & ~3) + 1;
-      // the d(pre-activation) phase's column tiles over 16 waves (one tile each), 8 (two) or 4 (four: rounds 3-5): the
-      // kernel is one workgroup per CU and latency-bound, a wave's epilogue loads / stores are what shrinks
-      // (2 launches per step: 53.2 / 44.1 / 40.9 us at 4 / 8 / 16 waves); STEMGNN_HEADS_BWD_WAVES = 4 | 8 | 16
-      static const int waves_env = getenv("STEMGNN_HEADS_BWD_WAVES") ? atoi(getenv("STEMGNN_HEADS_BWD_WAVES")) : 16;
-      if (waves_env == 16 && d.KF > 128) {
+      const int waves = heads_bwd_waves(d);
+      if (waves == 16) {
         static SgDynLds lds_guard16;
         SG_TRY(sg_ensure_dyn_lds((const void*)sg_heads_bwd_kernel<16>, hb, lds_guard16));
         hipLaunchKernelGGL(sg_heads_bwd_kernel<16>, dim3((d.M + HD_RB - 1) / HD_RB), dim3(1024), hb, st, a);
-      } else if (waves_env == 8 && d.KF > 128) {
+      } else if (waves == 8) {
         static SgDynLds lds_guard8;
         SG_TRY(sg_ensure_dyn_lds((const void*)sg_heads_bwd_kernel<8>, hb, lds_guard8));
         hipLaunchKernelGGL(sg_heads_bwd_kernel<8>, dim3((d.M + HD_RB - 1) / HD_RB), dim3(512), hb, st, a);
@@ -1391,21 +1427,14 @@ extern "C" int stemgnn_shortcut_dx(const float* scratch, const float* bs_w, floa
   return 0;
 }
 
-static int block_wgrad_impl(const float* const* params_host, const float* packed, const float* saved,
-                            const float* X, long xs_b, long xs_n, long xs_t, const float* dforecast, int has_bc,
-                            float* scratch, float* gradpart, int nsplit, int cu_percent, int B, int N, int W,
-                            int multi, void* stream, int splits) {
-  if (!params_host || !packed || !saved || !X || !dforecast || !scratch || !gradpart || nsplit <= 0 || B <= 0 || N <= 0 ||
-      W <= 0 || multi <= 0)
-    return SG_EINVAL;
-  const SgDims d = sg_dims(B, N, W, multi);
+// every weight-gradient product of one StockBlock but the short-cut head's as the fused weight-gradient kernel's list (n of
+// them); true where ONE launch of that kernel takes them all, false where the per-stage slab GEMMs run instead (shapes
+// outside the DMA path's 16-byte rules or with more than SG_WG_MAX_TILES output tiles)
+static bool block_wgrad_list(const SgDims& d, const float* saved, const float* scratch, const float* dforecast, float* gradpart,
+                             const SgGradLayout& Gl, int has_bc, WgGemm* q, int* n_out) {
   const SgSavedLayout S = sg_saved_layout(d);
   const SgScratchLayout C = sg_scratch_layout(d);
-  const SgGradLayout Gl = sg_grad_layout(d, nsplit);
-  hipStream_t st = (hipStream_t)stream;
-  has_bc = has_bc ? 1 : 0;
-  if (has_bc && !params_host[5]) return SG_EINVAL;
-  WgGemm q[WG_MAXG];
+  const int W = d.W;
   int n = 0;
   bool ok = true;
   auto add = [&](const float* A, int lda, int Mi, const float* Bp, int ldb, int ncolB, bool ones, float* out, int ldo) {
@@ -1418,7 +1447,6 @@ static int block_wgrad_impl(const float* const* params_host, const float* packed
     for (int r = 0; r < 2; ++r)
       add(scratch + C.dact[r][l], sg_glu_np(d, l, r), sg_glu_np(d, l, r), l == 0 ? saved + S.G : saved + S.out[r][l - 1],
           l == 0 ? d.KG : d.CP, sg_glu_kin(d, l), true, gradpart + Gl.w[r][l], sg_glu_kin(d, l) + 1);
-  const int n_glu = n;
   // FR: dfo^T [fs | 1]; F: dpF^T [ig | 1]; BC: dpB^T [ig | 1]; Wfold: [Re3 | Im3]^T dig  (one product per branch)
   add(dforecast, W, W, saved + S.fs, d.Wm, d.Wm, true, gradpart + Gl.fr, d.Wm + 1);
   add(scratch + C.dpF, d.Wm, d.Wm, saved + S.ig, d.Wm, d.Wm, true, gradpart + Gl.fc, d.Wm + 1);
@@ -1426,7 +1454,26 @@ static int block_wgrad_impl(const float* const* params_host, const float* packed
   for (int r = 0; r < 2; ++r)
     add(saved + S.out[r][2], d.CP2[r], d.CP2[r], scratch + C.dig, d.Wm, d.Wm, false,
         gradpart + Gl.wfold + (r ? (size_t)d.CP2[0] * d.WmP : 0), d.WmP);
-  ok = ok && wg_tiles_fit(q, n);
+  *n_out = n;
+  return ok && wg_tiles_fit(q, n);
+}
+
+static int block_wgrad_impl(const float* const* params_host, const float* packed, const float* saved,
+                            const float* X, long xs_b, long xs_n, long xs_t, const float* dforecast, int has_bc,
+                            float* scratch, float* gradpart, int nsplit, int cu_percent, int B, int N, int W,
+                            int multi, void* stream, int splits) {
+  if (!params_host || !packed || !saved || !X || !dforecast || !scratch || !gradpart || nsplit <= 0 || B <= 0 || N <= 0 ||
+      W <= 0 || multi <= 0)
+    return SG_EINVAL;
+  const SgDims d = sg_dims(B, N, W, multi);
+  const SgScratchLayout C = sg_scratch_layout(d);
+  const SgGradLayout Gl = sg_grad_layout(d, nsplit);
+  hipStream_t st = (hipStream_t)stream;
+  has_bc = has_bc ? 1 : 0;
+  if (has_bc && !params_host[5]) return SG_EINVAL;
+  WgGemm q[WG_MAXG];
+  int n = 0;
+  const bool ok = block_wgrad_list(d, saved, scratch, dforecast, gradpart, Gl, has_bc, q, &n);
   if (!ok) {     // shapes outside the DMA path's 16-byte rules or with more tiles than CUs: the per-stage slab GEMMs (each leaves slab 0 complete)
     const int rc = stemgnn_igft_heads_bwd(params_host, packed, saved, X, xs_b, xs_n, xs_t, dforecast,
                                           has_bc ? dforecast : nullptr, has_bc ? dforecast : nullptr, scratch, gradpart,
@@ -1434,7 +1481,6 @@ static int block_wgrad_impl(const float* const* params_host, const float* packed
     if (rc) return rc;
     return stemgnn_spectral_glu_bwd(packed, saved, scratch, gradpart, nsplit, 2, B, N, W, multi, stream);
   }
-  (void)n_glu;
   SG_TRY(wg_launch(q, n, d.M, gradpart + Gl.wg_ws, reinterpret_cast<unsigned*>(gradpart + Gl.wg_cnt), Gl.wg_smax, st, true,
                    cu_percent, false, nullptr, nullptr, splits == 2));
   if (has_bc) {  // BS: -dpB^T [X | 1] on the descriptor GEMM (X is a strided view), 32 tiny slabs + their reduce
@@ -1471,4 +1517,33 @@ extern "C" int stemgnn_block_wgrad_split(const float* const* params_host, const 
   if (splits != 0 && splits != 2) return SG_EINVAL;
   return block_wgrad_impl(params_host, packed, saved, X, xs_b, xs_n, xs_t, dforecast, has_bc, scratch, gradpart, nsplit,
                           cu_percent, B, N, W, multi, stream, splits);
+}
+
+// ---- launch-path query (tests): the same predicates the launchers above ask, on buffers the way the model allocates them --
+// Every buffer (packed weights, saved activations, scratch, gradient partials, d(forecast)) is its own allocation on a
+// 256-byte aligned base, as torch's are, so only the layout offsets inside each decide the 16-byte rules.  Environment
+// switches count as the launchers see them (STEMGNN_GLU_FUSED per call, STEMGNN_HEADS_BWD_WAVES once per process).
+extern "C" int stemgnn_block_paths(int B, int N, int W, int multi, int splits) {
+  if (B <= 0 || N <= 0 || W <= 0 || multi <= 0 || (splits != 0 && splits != 2 && splits != 3)) return SG_EINVAL;
+  const SgDims d = sg_dims(B, N, W, multi);
+  float* const base = reinterpret_cast<float*>((uintptr_t)256);     // never dereferenced
+  const int nsplit = 32;                                             // ops.py's _NSPLIT (only the outputs' offsets depend on it)
+  const SgGradLayout Gl = sg_grad_layout(d, nsplit);
+  const int mode = glu_fused_mode();
+  int bits = 0;
+  if (splits == 0 ? glu_fwd_fused_ok(d, mode, base) : glu_fwd_fused_bf16_ok(d, splits)) bits |= SG_PATH_GLU_FWD_FUSED;
+  if (splits == 0 ? glu_dgrad_fused_ok(d, mode, base, base) : glu_dgrad_fused_bf16_ok(d, splits, base))
+    bits |= SG_PATH_GLU_DGRAD_FUSED;
+  if (heads_fused_ok(d)) bits |= SG_PATH_HEADS_FWD_FUSED;
+  if (heads_bwd_fused_ok(d)) {
+    bits |= SG_PATH_HEADS_BWD_FUSED;
+    if (heads_bwd_waves(d) == 16) bits |= SG_PATH_HEADS_BWD_16W;
+  }
+  if (d.KF > SG_LONG_K) bits |= SG_PATH_LONG_K;
+  WgGemm q[WG_MAXG];
+  int n = 0;
+  if (block_wgrad_list(d, base, base, base, base, Gl, 1, q, &n)) bits |= SG_PATH_WGRAD_FUSED;
+  WgGemm wq[6];
+  if (glu_wgrad_list(d, base, base, base, Gl, wq)) bits |= SG_PATH_GLU_WGRAD_FUSED;
+  return bits;
 }

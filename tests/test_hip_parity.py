@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from oracle import stemgnn_oracle as O
-from tests.util import golden_cases, hash_seed, load_golden, relerr
+from tests.util import golden_cases, hash_seed, kink_audit, load_golden, relerr
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -350,13 +350,8 @@ def test_large_config_shapes(N, W, multi, H, B, dtype, monkeypatch):
     # asserted to be of rounding class; a logit is "near the kink" when it is smaller than twice that error
     ek, eq = float((key.double() - key64).abs().max()), float((query.double() - query64).abs().max())
     assert relerr(key, key64) < 2e-5 and relerr(query, query64) < 2e-5, (relerr(key, key64), relerr(query, query64))
-    near = logit64.abs() <= 2 * (ek + eq)
-    flips = pos_impl != (logit64 > 0)
-    n_near, n_flip = int(near.sum()), int(flips.sum())
-    print(f"kink audit: key/query fp32 error {ek:.2e}/{eq:.2e}; {n_near} of {logit64.numel()} logits within twice that "
-          f"of 0, {n_flip} decision flips")
-    assert n_near <= max(16, int(2e-5 * logit64.numel())), n_near
-    assert n_flip <= max(8, int(5e-7 * logit64.numel())) and bool((flips & ~near).sum() == 0), (n_flip, int((flips & ~near).sum()))
+    flips = kink_audit(pos_impl, logit64, ek + eq, f"attention logits, key/query fp32 error {ek:.2e}/{eq:.2e}")
+    n_flip = int(flips.sum())
     # -- 1. independent comparison
     _, t_forecast, t_att, t_grads = O.loss_and_grads(x64, y64, sd64)
     rows = [("forecast", relerr(forecast, t_forecast)), ("attention", relerr(att, t_att))]

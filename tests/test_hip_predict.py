@@ -43,8 +43,21 @@ def test_predict_equals_eval_forward(N, W, multi, H, B, dtype, monkeypatch):
 
 
 @pytest.mark.parametrize("N,W,multi,H,B", [(140, 12, 5, 3, 16),      # ECG
-                                           (2048, 48, 2, 3, 2)])     # wide GRU, per-layer GLU, per-stage heads
+                                           (2048, 48, 2, 3, 2)])     # wide GRU, per-layer GLU (KF = 400: fused heads)
 def test_predict_equals_eval_forward_more_shapes(N, W, multi, H, B):
+    _check_equal(N, W, multi, H, B)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16x2"])
+@pytest.mark.parametrize("N,W,multi,H,B", [(40, 64, 3, 8, 4),        # KF = 784 > 640: per-stage inference heads, long K
+                                           (7, 64, 9, 4, 2)])        # per-stage heads forward and backward
+def test_predict_equals_eval_forward_per_stage_heads(N, W, multi, H, B, dtype, monkeypatch):
+    """The per-stage heads of the inference forward keep ig / fs in branch 0's ping-pong slabs of the workspace
+    (stemgnn_igft_heads_fwd_infer); the training forward keeps them in the saved activations."""
+    from stemgnn_amd import _lib
+
+    assert not _lib.load().stemgnn_block_paths(B, N, W, multi, 0) & _lib.SG_PATH["heads_fwd_fused"]
+    monkeypatch.setenv("STEMGNN_DTYPE", dtype)
     _check_equal(N, W, multi, H, B)
 
 

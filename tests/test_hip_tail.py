@@ -9,7 +9,11 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-@pytest.mark.parametrize("B,N,W,H", [(32, 228, 12, 3), (5, 33, 12, 1), (3, 50, 28, 28), (2, 7, 5, 2), (300, 3, 16, 4)])
+# the limits of the fc tail kernels' range (time_step 64, horizon 32) and its small end (W = 1, H = 1, B = 1, N = 1)
+LIMIT_SHAPES = [(2, 7, 64, 32), (1, 1, 1, 1), (4, 3, 64, 1), (3, 5, 1, 32)]
+
+
+@pytest.mark.parametrize("B,N,W,H", [(32, 228, 12, 3), (5, 33, 12, 1), (3, 50, 28, 28), (2, 7, 5, 2), (300, 3, 16, 4)] + LIMIT_SHAPES)
 def test_fc_tail_fwd_bwd_vs_torch(B, N, W, H):
     from stemgnn_amd.ops import FcTail
 
@@ -163,7 +167,7 @@ def test_train_step_queue_mode_equals_per_step_indices():
     assert torch.equal(outs[0][0], outs[1][0]) and outs[0][1] == outs[1][1]
 
 
-@pytest.mark.parametrize("B,N,W,H", [(32, 228, 12, 3), (5, 33, 12, 1), (3, 50, 8, 4), (16, 64, 48, 12)])
+@pytest.mark.parametrize("B,N,W,H", [(32, 228, 12, 3), (5, 33, 12, 1), (3, 50, 8, 4), (16, 64, 48, 12)] + LIMIT_SHAPES)
 def test_fused_train_tail_matches_separate_stages(B, N, W, H):
     """stemgnn_fc_tail_train (fc fwd + MSE + both backwards, 2 launches) == FcTail -> MSELoss -> backward (5 launches):
     loss, d(loss)/d(fsum) and the four fc gradients, also with a non-unit upstream gradient."""
@@ -197,7 +201,7 @@ def test_fused_train_tail_matches_separate_stages(B, N, W, H):
     assert float(out) == float(l2) and abs(float(acc) - float(l2)) < 1e-12
 
 
-@pytest.mark.parametrize("B,N,W,H", [(32, 228, 12, 3), (5, 33, 12, 1), (3, 50, 28, 28)])
+@pytest.mark.parametrize("B,N,W,H", [(32, 228, 12, 3), (5, 33, 12, 1), (3, 50, 28, 28)] + LIMIT_SHAPES)
 def test_fc_tail_train_in_two_calls_equals_the_one_call(B, N, W, H):
     """Round 6: stemgnn_fc_tail_train_rows + _finish (the step queues `_finish` on the side branch: nothing on the backward's
     chain reads the loss or the fc gradients) are the one call's two launches: bit-identical loss, loss accumulator, d(fsum) and

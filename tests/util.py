@@ -52,3 +52,20 @@ def synthetic_series(T, N, seed):
     a = det_uniform((N,), seed + 2, 0.5, 3.0).astype(np.float64)
     c = det_uniform((N,), seed + 3, -2.0, 8.0).astype(np.float64)
     return np.sin(2 * np.pi * t / p + phi) * a + c + 0.1 * det_normalish((T, N), seed + 4).astype(np.float64)
+
+
+def kink_audit(pos_impl, ref64, err, what):
+    """LeakyReLU-kink audit of one set of pre-activations: `pos_impl` the implementation's decisions (which side of 0 it took
+    each value to be on), `ref64` the fp64 oracle's values, `err` the implementation's measured (rounding-class) evaluation
+    error of them.  A value is "near the kink" when it is smaller than twice that error; the decisions may differ from the
+    fp64 ones on at most a handful of values, and only near the kink.  Returns the flips (where they differ)."""
+    ref64 = ref64.double().cpu()
+    pos_impl = pos_impl.cpu()
+    near = ref64.abs() <= 2 * err
+    flips = pos_impl != (ref64 > 0)
+    n_near, n_flip = int(near.sum()), int(flips.sum())
+    print(f"kink audit ({what}): fp32 error {err:.2e}; {n_near} of {ref64.numel()} values within twice that of 0, "
+          f"{n_flip} decision flips")
+    assert n_near <= max(16, int(2e-5 * ref64.numel())), n_near
+    assert n_flip <= max(8, int(5e-7 * ref64.numel())) and bool((flips & ~near).sum() == 0), (n_flip, int((flips & ~near).sum()))
+    return flips
