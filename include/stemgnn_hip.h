@@ -162,8 +162,8 @@ int stemgnn_gru_bwd_cus(int B, int Hd);
 int stemgnn_gru_fwd(const float* x, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
                     int B, int S, int Hd, int W, float* scratch, float* h_ext, float* reserve, int* status,
                     void* stream);
-/* dh_all [S,B,Hd] = gradient of every output step -> dw_ih, dw_hh, db_ih, db_hh (x gets no gradient); everything is
- * ordered on `stream` (the side-stream schedules of round 2 were measured slower and removed in round 4). */
+/* dh_all [S,B,Hd] = gradient of every output step -> dw_ih, dw_hh, db_ih, db_hh (x's gradient: stemgnn_gru_input_grad behind
+ * it); everything is ordered on `stream` (the side-stream schedules of round 2 were measured slower and removed in round 4). */
 int stemgnn_gru_bwd(const float* dh_all, const float* x, const float* w_hh, const float* h_ext,
                     const float* reserve, int B, int S, int Hd, int W, float* scratch,
                     float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, int* status, void* stream);
@@ -220,6 +220,21 @@ int stemgnn_gru_bwd_rank2_finish(const float* dkey, const float* dquery, const f
                                  const float* w_hh, const float* h_ext, const float* reserve, int B, int S, int Hd, int W,
                                  float* scratch, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, int* status,
                                  unsigned* ctl, void* side_stream, void* stream);
+/* Weights-off backward (no GRU parameter needs a gradient): the recurrence alone, on the plain kernels -- no dW_hh product, no
+ * dW_ih accumulation, no reduce launch.  Same arguments as stemgnn_gru_bwd / stemgnn_gru_bwd_rank2_dq without the four weight
+ * outputs (and without the dW_hh flags); the gate gradients in `scratch` carry the same bits as from those calls.
+ * stemgnn_gru_bwd_rank2_recur: nchunk > 0 -- dquery is followed by the attention backward's per-chunk partials, summed in the
+ * fill launch as in stemgnn_gru_bwd_rank2_dq; nchunk == 0 -- dquery is already summed. */
+int stemgnn_gru_bwd_recur(const float* dh_all, const float* x, const float* w_hh, const float* h_ext, const float* reserve,
+                          int B, int S, int Hd, int W, float* scratch, int* status, void* stream);
+int stemgnn_gru_bwd_rank2_recur(const float* dkey, float* dquery, int nchunk, const float* wk, const float* wq, const float* x,
+                                const float* w_hh, const float* h_ext, const float* reserve, int B, int S, int Hd, int W,
+                                float* scratch, int* status, void* stream);
+/* Gradient of the GRU's input (gi = x W_ih^T + b_ih): dx[b][t][s] = sum_j dgi[s*B + b][j] W_ih[j][t], x's own [B, W, S] layout
+ * (written, not accumulated).  `scratch` is the scratch of an earlier stemgnn_gru_bwd, _rank2, _rank2_dq, _rank2_begin (+ its
+ * _finish), _recur or _rank2_recur call on the same stream, whose gate gradients dgi [S*B, 3 Hd] sit at its offset 0.  Exact
+ * fp32 on the MFMA core, one fixed summation order: bit-identical from launch to launch. */
+int stemgnn_gru_input_grad(const float* scratch, const float* w_ih, int B, int S, int Hd, int W, float* dx, void* stream);
 
 /* ---- weight packing (per StockBlock, once per optimizer step) -----------------------------------
  * Folds the length-W DFT (:49-51) into the first GLU layer, drops the dead C2R bins,

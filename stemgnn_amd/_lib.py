@@ -65,6 +65,9 @@ SIGNATURES = {
     "stemgnn_gru_bwd_ctl_words": (c_size_t, [c_int]),
     "stemgnn_gru_bwd_rank2_begin": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "stemgnn_gru_bwd_rank2_finish": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "stemgnn_gru_bwd_recur": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "stemgnn_gru_bwd_rank2_recur": (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "stemgnn_gru_input_grad": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "stemgnn_keyquery_wgrad": (c_int, [_P, _P, _P, _P, c_int, c_int, _P]),
     "stemgnn_attn_dquery_reduce": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
     "stemgnn_keyquery_wgrad2": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P]),

@@ -70,6 +70,28 @@ struct GruGiOp {
   __device__ void epi(int, int i, int j, float v) const { gi[(size_t)i * 3 * Hd + j] = v + b_ih[j]; }
 };
 
+// ---- input gradient (the transpose of the projection): dx[b][t][s] = sum_j dgi[(s,b)][j] W_ih[j][t] -------------------------
+// Reads the gate gradients [S*B, 3 Hd] a backward call left at offset 0 of its scratch.  The GEMM's rows run (b, s) with s
+// fastest, so the epilogue's 16-row runs of a column land on consecutive s of x's own [B, W, S] layout (no transpose pass).
+struct GruDxOp {
+  const float *dgi, *w_ih;
+  float* dx;
+  int B, S, Hd, W;
+  __device__ bool setup(int, int& M, int& N, int& K0, int& K1) const {
+    M = S * B; N = W; K0 = 0; K1 = 3 * Hd;
+    return true;
+  }
+  __device__ float a(int, int i, int k) const {
+    const int b = i / S, s = i - b * S;
+    return dgi[((size_t)s * B + b) * 3 * Hd + k];
+  }
+  __device__ float b(int, int k, int j) const { return w_ih[(size_t)k * W + j]; }
+  __device__ void epi(int, int i, int j, float v) const {
+    const int b = i / S, s = i - b * S;
+    dx[((size_t)b * W + j) * S + s] = v;
+  }
+};
+
 // The same projection as a streaming kernel (round 6): with K = W = 12 the product is 20 MB of stores and 60 MFLOP at PEMS07 --
 // an output-bound outer-product-like op, not a GEMM.  A thread owns FOUR consecutive output columns (its 4 x W weights and
 // bias stay in registers), a workgroup 16 consecutive (s, b) rows whose W input values sit in LDS (broadcast reads); every
@@ -1124,7 +1146,7 @@ static int gru_bwd_impl(const float* dh_all, const float* dkey, const float* dqu
                         const float* x, const float* w_hh, const float* h_ext, const float* reserve, int B, int S, int Hd,
                         int W, float* scratch, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, int* status,
                         void* stream, int stages = 3, void* side = nullptr, unsigned* ctl = nullptr, int dq_nchunk = 0,
-                        int wg_split = 0);
+                        int wg_split = 0, bool no_wgrad = false);
 extern "C" int stemgnn_gru_bwd(const float* dh_all, const float* x, const float* w_hh, const float* h_ext,
                                const float* reserve, int B, int S, int Hd, int W, float* scratch, float* dw_ih,
                                float* dw_hh, float* db_ih, float* db_hh, int* status, void* stream) {
@@ -1165,6 +1187,33 @@ extern "C" int stemgnn_gru_bwd_rank2_dq(const float* dkey, float* dquery, int nc
   if (!dkey || !dquery || nchunk <= 0 || (flags & ~1) || !wk || !wq || !stemgnn_gru_bwd_rank2_ok(B, Hd)) return SG_EINVAL;
   return gru_bwd_impl(nullptr, dkey, dquery, wk, wq, x, w_hh, h_ext, reserve, B, S, Hd, W, scratch, dw_ih, dw_hh, db_ih, db_hh,
                       status, stream, 3, nullptr, nullptr, nchunk, flags & 1);
+}
+// Weights-off backward: only the recurrence runs (the gate gradients land in `scratch` for stemgnn_gru_input_grad)
+extern "C" int stemgnn_gru_bwd_recur(const float* dh_all, const float* x, const float* w_hh, const float* h_ext,
+                                     const float* reserve, int B, int S, int Hd, int W, float* scratch, int* status,
+                                     void* stream) {
+  if (!dh_all) return SG_EINVAL;
+  return gru_bwd_impl(dh_all, nullptr, nullptr, nullptr, nullptr, x, w_hh, h_ext, reserve, B, S, Hd, W, scratch, nullptr, nullptr,
+                      nullptr, nullptr, status, stream, 3, nullptr, nullptr, 0, 0, true);
+}
+extern "C" int stemgnn_gru_bwd_rank2_recur(const float* dkey, float* dquery, int nchunk, const float* wk, const float* wq,
+                                           const float* x, const float* w_hh, const float* h_ext, const float* reserve, int B,
+                                           int S, int Hd, int W, float* scratch, int* status, void* stream) {
+  if (!dkey || !dquery || nchunk < 0 || !wk || !wq || !stemgnn_gru_bwd_rank2_ok(B, Hd)) return SG_EINVAL;
+  return gru_bwd_impl(nullptr, dkey, dquery, wk, wq, x, w_hh, h_ext, reserve, B, S, Hd, W, scratch, nullptr, nullptr, nullptr,
+                      nullptr, status, stream, 3, nullptr, nullptr, nchunk, 0, true);
+}
+// dx [B, W, S] from the gate gradients an earlier backward call (any of the entries above) left in the same `scratch`, on the
+// exact-fp32 MFMA core: one workgroup per 32 output rows, all of K = 3 Hd in fixed order (two-level accumulation, 128-deep
+// K tiles: K reaches 6144 at hidden 2048), no split, no atomics -- the same bits on every launch.
+extern "C" int stemgnn_gru_input_grad(const float* scratch, const float* w_ih, int B, int S, int Hd, int W, float* dx,
+                                      void* stream) {
+  if (!scratch || !w_ih || !dx || B <= 0 || S <= 0 || Hd <= 0 || W <= 0) return SG_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  GruDxOp op{scratch, w_ih, dx, B, S, Hd, W};
+  if (W <= 32) SG_TRY((sg_launch_gemm<GruDxOp, 32, 32, true, false, false, 128, true>(op, S * B, W, 1, st)));
+  else SG_TRY((sg_launch_gemm<GruDxOp, 32, 64, true, false, false, 128, true>(op, S * B, W, 1, st)));
+  return 0;
 }
 // ---- dW_hh beside the recurrence ------------------------------------------------------------------------------------------
 // The two-level K partition of the dW_hh launch (wgrad.h): a pure function of the shape, used by the plain launch too, so
@@ -1238,9 +1287,9 @@ extern "C" int stemgnn_gru_bwd_rank2_finish(const float* dkey, const float* dque
 static int gru_bwd_impl(const float* dh_all, const float* dkey, const float* dquery, const float* wk, const float* wq,
                         const float* x, const float* w_hh, const float* h_ext, const float* reserve, int B, int S, int Hd,
                         int W, float* scratch, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh, int* status,
-                        void* stream, int stages, void* side, unsigned* ctl, int dq_nchunk, int wg_split) {
-  if ((!dh_all && !dkey) || !x || !w_hh || !h_ext || !reserve || !scratch || !dw_ih || !dw_hh || !db_ih || !db_hh || !status ||
-      B <= 0 || S <= 0 || Hd <= 0 || W <= 0)
+                        void* stream, int stages, void* side, unsigned* ctl, int dq_nchunk, int wg_split, bool no_wgrad) {
+  if ((!dh_all && !dkey) || !x || !w_hh || !h_ext || !reserve || !scratch ||
+      (!no_wgrad && (!dw_ih || !dw_hh || !db_ih || !db_hh)) || !status || B <= 0 || S <= 0 || Hd <= 0 || W <= 0)
     return SG_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const float* h_all = h_ext + (size_t)B * Hd;
@@ -1251,7 +1300,9 @@ static int gru_bwd_impl(const float* dh_all, const float* dkey, const float* dqu
   const int P2 = gru_pick_P2(B, Hd);
   const int P = P2 > 0 ? 0 : gru_pick_P(B, Hd);
   bool fold_ih = false, hh_fused = false, cnt_zeroed = false, ih_reduced = false;
-  const bool run_rec = (stages & 1) != 0, run_wg = (stages & 2) != 0;
+  // no_wgrad (stemgnn_gru_bwd_recur / _rank2_recur): the recurrence alone, on the plain kernels (stages == 3: no progress
+  // publishing, no store wave), no dW_ih fold, no weight-gradient or reduce launch
+  const bool run_rec = (stages & 1) != 0, run_wg = (stages & 2) != 0 && !no_wgrad;
   const bool split_call = stages != 3;                   // begin / finish: only where stemgnn_gru_bwd_overlap_ok (the callers check)
   bool dq_pending = dq_nchunk > 0 && run_rec;            // dquery arrives as per-chunk partials: summed in the fill launch where
   GruWide dq_probe;
@@ -1322,7 +1373,7 @@ static int gru_bwd_impl(const float* dh_all, const float* dkey, const float* dqu
       const bool v4 = P2 <= 4 || P2 == 6;
       // dW_ih | db_ih accumulated by the chore wave while the gate gradients pass through it: one slab per batch row
       // instead of the split-K GEMM behind the recurrence
-      fold_ih = v4 && W <= GRU4_WMAX;
+      fold_ih = v4 && W <= GRU4_WMAX && !no_wgrad;
       float* ih_slab = fold_ih ? p_ih : nullptr;
       if (run_rec) {
 #define GRU_B4KS(PP, KK, SWV) do { const size_t hog = gru_lds_hog4<PP>((const void*)gru_bwd_cluster4_kernel<PP, KK, 1, SWV>); \

@@ -315,14 +315,32 @@ class GruFront(torch.autograd.Function):
             dh_all = dh_all.contiguous()
         scratch = torch.empty(lib.stemgnn_gru_bwd_scratch_floats(B, S, Hd, W), device=dev, dtype=f32)
         prm = ctx.gru_params
-        direct = ctx.state.direct and all(p.grad is not None and p.grad.is_contiguous() for p in prm)
+        # frozen GRU (no parameter needs a gradient): the recurrence alone (stemgnn_gru_bwd_recur / _rank2_recur) -- its gate
+        # gradients are all the input gradient below needs
+        frozen = not any(ctx.needs_input_grad[1:5])
+        direct = not frozen and ctx.state.direct and all(p.grad is not None and p.grad.is_contiguous() for p in prm)
         if direct:
             dw_ih, dw_hh, db_ih, db_hh = (p.grad for p in prm)
-        else:
+        elif not frozen:
             dw_ih, dw_hh = torch.empty_like(w_ih), torch.empty_like(w_hh)
             db_ih = torch.empty(3 * Hd, device=dev, dtype=f32)
             db_hh = torch.empty(3 * Hd, device=dev, dtype=f32)
-        if factors is not None:
+        if frozen:
+            if factors is not None:
+                attn_scratch, fb, fn, wk, wq, after, dq_chunks = factors
+                base = attn_scratch.data_ptr() + 4 * fn * fn
+                ctx.state.gru_ctl_zeroed = False
+                _lib.check(lib.stemgnn_gru_bwd_rank2_recur(base, base + 4 * fb * fn, dq_chunks, wk.data_ptr(), wq.data_ptr(),
+                                                           x.data_ptr(), w_hh.data_ptr(), h_ext.data_ptr(), reserve.data_ptr(),
+                                                           B, S, Hd, W, scratch.data_ptr(), gru_status(dev).data_ptr(),
+                                                           _stream()), "gru_bwd_rank2_recur")
+                if after is not None:
+                    after()             # dwk / dwq on the side stream
+            else:
+                _lib.check(lib.stemgnn_gru_bwd_recur(dh_all.data_ptr(), x.data_ptr(), w_hh.data_ptr(), h_ext.data_ptr(),
+                                                     reserve.data_ptr(), B, S, Hd, W, scratch.data_ptr(),
+                                                     gru_status(dev).data_ptr(), _stream()), "gru_bwd_recur")
+        elif factors is not None:
             # SpectralHotPath.backward stopped at dkey | dquery: dh[s,b,i] = dkey[b,i] wk[s] + dquery[b,i] wq[s] is formed
             # inside the recurrence (the [N,B,N] gradient tensor is never written; `dh_all` is a zero-stride placeholder)
             attn_scratch, fb, fn, wk, wq, after, dq_chunks = factors
@@ -362,10 +380,16 @@ class GruFront(torch.autograd.Function):
                                            reserve.data_ptr(), B, S, Hd, W, scratch.data_ptr(), dw_ih.data_ptr(),
                                            dw_hh.data_ptr(), db_ih.data_ptr(), db_hh.data_ptr(),
                                            gru_status(dev).data_ptr(), _stream()), "gru_bwd")
+        dx = None
+        if ctx.needs_input_grad[0]:
+            # x [B,W,S] through the input projection, from the gate gradients the call above left at offset 0 of `scratch`
+            dx = torch.empty(B, W, S, device=dev, dtype=f32)
+            _lib.check(lib.stemgnn_gru_input_grad(scratch.data_ptr(), w_ih.data_ptr(), B, S, Hd, W, dx.data_ptr(), _stream()),
+                       "gru_input_grad")
         ctx.state.join()                # the spectral blocks' weight gradients (side stream) overlapped this recurrence
-        if direct:
-            return None, None, None, None, None, None
-        return None, dw_ih, dw_hh, db_ih, db_hh, None
+        if direct or frozen:
+            return dx, None, None, None, None, None
+        return dx, dw_ih, dw_hh, db_ih, db_hh, None
 
 
 class FcTail(torch.autograd.Function):
@@ -820,9 +844,13 @@ class SpectralHotPath(torch.autograd.Function):
         xviews = [(x, W * N, 1, N), (backcast, N * W, W, 1)]
         grads = [[None] * 33, [None] * 33]
         direct_idx = set()
+        # frozen parameter groups (no tensor of the group needs a gradient) get no buffers and no weight-gradient launches
+        nig = ctx.needs_input_grad
+        live = [any(nig[10 + 33 * s + i] for i, p in enumerate(blocks[s]) if p is not None) for s in (0, 1)]
+        kq_live = nig[2] or nig[3]
         for s in (1, 0):
             for i, p in enumerate(blocks[s]):
-                if p is None or (s == 1 and i in (7, 8)):   # block 1's short-cut is unused (:73-74) -> grad None
+                if p is None or (s == 1 and i in (7, 8)) or not live[s]:   # block 1's short-cut is unused (:73-74) -> grad None
                     continue
                 if state.direct and p.grad is not None and p.grad.is_contiguous():
                     grads[s][i] = p.grad          # written in place by the unpack kernel
@@ -834,7 +862,7 @@ class SpectralHotPath(torch.autograd.Function):
         # chain -- in particular the latency-bound GRU recurrence, which leaves half of the CUs idle; whoever
         # consumes the gradients (optimizer / all-reduce, or GruFront.backward at the latest) joins the stream.
         n_block_grads = sum(g is not None for blk in grads for g in blk)
-        overlap = state.overlap and len(direct_idx) == n_block_grads
+        overlap = state.overlap and n_block_grads > 0 and len(direct_idx) == n_block_grads
         side = _side_stream(dev) if overlap else None
         main = torch.cuda.current_stream()
         keep = []
@@ -916,8 +944,9 @@ class SpectralHotPath(torch.autograd.Function):
             heads(st)
             glu(st)
             if not overlap:
-                wgrad(st, 100)
-                unpack(st)
+                if live[s]:
+                    wgrad(st, 100)
+                    unpack(st)
                 _lib.check(lib.stemgnn_gft_bwd(
                     mul_L.data_ptr(), X.data_ptr(), sb, sn, stt, dG.data_ptr(),
                     dbackcast.data_ptr() if s == 1 else None, dmul_L.data_ptr(), int(s == 0), B, N, W, st), "gft_bwd")
@@ -936,6 +965,8 @@ class SpectralHotPath(torch.autograd.Function):
                 with torch.cuda.stream(side):
                     sst = side.cuda_stream
                     for ss in (0, 1):
+                        if not live[ss]:
+                            continue
                         _h, _g, w2, u2 = (heads, glu, wgrad, unpack) if ss == 0 else stage_fns(1)
                         w2(sst, _wg_cu(ss, B, N))
                         u2(sst)
@@ -950,6 +981,17 @@ class SpectralHotPath(torch.autograd.Function):
                     if state.block_grads_hook is not None:
                         state.block_grads_hook()         # data-parallel: reduce the finished range under the GRU recurrence
                 keep.append(bufs)                        # alive until the join
+        dX0 = None
+        if nig[1]:
+            # d(loss)/dx through block 0 (x is its input X, :169): the GFT adjoint sum_k T_k^T dG0_k (:63) minus the short-cut
+            # head's direct term (:70-71), from block 0's heads data part still in scratch0 -- written [B,N,W], handed out as
+            # x's [B,W,N] view.  The GRU's share comes from GruFront.backward; autograd adds the two.
+            X, sb, sn, stt = xviews[0]
+            dX0 = torch.empty(B, N, W, device=dev, dtype=f32)
+            _lib.check(lib.stemgnn_gft_bwd(mul_L.data_ptr(), X.data_ptr(), sb, sn, stt, scratch0[off_dG:].data_ptr(),
+                                           dX0.data_ptr(), None, 0, B, N, W, st), "gft_bwd dX")
+            _lib.check(lib.stemgnn_shortcut_dx(scratch0.data_ptr(), blocks[0][7].data_ptr(), dX0.data_ptr(), B, N, W, multi, st),
+                       "shortcut_dx")
         if overlap:
             state.pending = (side, (keep, packed, saved, split, backcast, dfsum, dbackcast))
         dL = torch.empty(N, N, device=dev, dtype=f32)
@@ -961,9 +1003,15 @@ class SpectralHotPath(torch.autograd.Function):
         # the critical chain, dwk / dwq come from a small kernel of their own on the side stream
         factored = ctx.factored and ctx.needs_input_grad[0] and bool(lib.stemgnn_gru_bwd_rank2_ok(B, N))
         dh = torch.empty(1, device=dev, dtype=f32).expand(N, B, N) if factored else torch.empty_like(h)   # placeholder: never read
-        kq_direct = state.direct and wk.grad is not None and wq.grad is not None
-        dwk = wk.grad if kq_direct else torch.empty_like(wk)
-        dwq = wq.grad if kq_direct else torch.empty_like(wq)
+        kq_direct = kq_live and state.direct and wk.grad is not None and wq.grad is not None
+        if kq_live:
+            dwk = wk.grad if kq_direct else torch.empty_like(wk)
+            dwq = wq.grad if kq_direct else torch.empty_like(wq)
+        elif factored:
+            dwk = dwq = None            # frozen key / query: the factored attention backward forms neither
+        else:
+            dwk, dwq = torch.empty(2, N, device=dev, dtype=f32)       # written on the way to dh, never read
+        _ptr = lambda t: None if t is None else t.data_ptr()
         attn_scratch = torch.empty(lib.stemgnn_attn_scratch_floats(B, N, _NCHUNK), device=dev, dtype=f32)
         use_drop = training and drop_p > 0.0
         # exact mode: d(loss_global)/dA = mean over ranks of the local dA, and the flat gradient bucket is AVERAGED later,
@@ -974,11 +1022,13 @@ class SpectralHotPath(torch.autograd.Function):
         # on the side branch sum their own copy (same fixed order, same bits)
         follower = bool(overlap and ctx.factored and state.gru_ctl_zeroed and lib.stemgnn_gru_bwd_overlap_ok(B, N, N, W))
         dq_parts = bool(factored and overlap and kq_direct and not follower)      # (the follower's _begin call takes dquery reduced)
+        if not kq_live:                 # frozen key / query: nothing else reads dquery -- the GRU backward's fill launch sums it
+            dq_parts = bool(factored and not follower)
         for part in ((3,) if exact is None else (1, 2)):
             _lib.check(lib.stemgnn_attn_laplacian_bwd(
                 dL.data_ptr(), h.data_ptr(), wk.data_ptr(), wq.data_ptr(), alpha, drop_p, int(training),
                 seed.data_ptr() if use_drop else None, B, N, attn_saved.data_ptr(), attn_scratch.data_ptr(), _NCHUNK,
-                None if factored else dh.data_ptr(), dwk.data_ptr(), dwq.data_ptr(),
+                None if factored else dh.data_ptr(), _ptr(dwk), _ptr(dwq),
                 part | ((4 | (8 if dq_parts else 0)) if factored and part != 1 else 0), st), "attn_laplacian_bwd")
             if exact is not None and part == 1:
                 _all_reduce_mean(attn_scratch[:N * N], exact)
@@ -1008,14 +1058,15 @@ class SpectralHotPath(torch.autograd.Function):
                 if state.side_probe is not None:
                     state.side_probe.append(kq_wgrad)
             state.dh_factors = (attn_scratch, B, N, wk, wq, after, _NCHUNK if dq_parts else 0)
-            if after is None:
+            if after is None and kq_live:
                 _lib.check(lib.stemgnn_keyquery_wgrad(h.data_ptr(), attn_scratch.data_ptr(), dwk.data_ptr(), dwq.data_ptr(),
                                                       B, N, st), "keyquery_wgrad")
         for s_, i_ in direct_idx:
             grads[s_][i_] = None                  # already in p.grad: nothing for autograd to accumulate
-        if kq_direct:
+        if kq_direct or not kq_live:
             dwk = dwq = None
-        return (dh, None, dwk, dwq, None, None, None, None, None, None, *grads[0], *grads[1])
+        dx = dX0.permute(0, 2, 1) if dX0 is not None else None
+        return (dh, dx, dwk, dwq, None, None, None, None, None, None, *grads[0], *grads[1])
 
 
 # ---------------------------------------------------------------------------------------------------------------
