@@ -13,6 +13,7 @@
 #include "gemm2.h"
 #include "gemm2s.h"
 #include "gemm_core.h"
+#include "gemm_phased.h"
 #include "layout.h"
 #include "reduce.h"
 #include "wgrad.h"
@@ -174,6 +175,107 @@ struct GftBwdDt2Op {
     return X[blk].at(bb, j, t);
   }
   __device__ void epi(int, int i, int j, float v) const { dT[(size_t)i * N + j] = v; }
+};
+
+// ---- the same products in phased form (gemm_phased.h): same sums; offsets split into a row and a column part, so the
+// (kq, n) / (b, t) decompositions are done once per thread and tile row / column; 32-bit offsets (sg_phased_fits) --------
+struct XViewI {
+  const float* p;
+  int sb, sn, st;
+};
+// every offset the phased ops form stays below 2^31: the two dG slabs and the strided X view
+static inline bool sg_phased_fits(int B, int N, int W, long xs_b, long xs_n, long xs_t) {
+  if (xs_b < 0 || xs_n < 0 || xs_t < 0) return false;
+  const long lim = 1L << 31;
+  if (xs_b >= lim || xs_n >= lim || xs_t >= lim) return false;
+  return 2L * B * N * 3 * W < lim && (B - 1) * xs_b + (N - 1) * xs_n + (W - 1) * xs_t < lim;
+}
+
+template <bool XKF>    // XKF: X is contiguous along the node axis (the reduction axis here)
+struct GftFwdPhOp {
+  static constexpr int NZ = 1, NPH = 1;
+  template <int Z, int P> static constexpr bool akf() { return true; }
+  template <int Z, int P> static constexpr bool bkf() { return XKF; }
+  GftFwdOp o;
+  XViewI X;
+  __device__ bool setup(int, int& M, int& Nn, int& K) const {
+    M = 3 * o.N; Nn = o.B * o.W; K = o.N;
+    return true;
+  }
+  template <int Z, int P> __device__ int arow(int i) const { return i * o.N; }
+  template <int Z, int P> __device__ int acol(int k) const { return k; }
+  template <int Z, int P> __device__ float aval(int off) const { return o.T[off]; }
+  template <int Z, int P> __device__ int brow(int k) const { return k * X.sn; }
+  template <int Z, int P> __device__ int bcol(int j) const {
+    int bb, t;
+    o.dW.divmod(j, bb, t);
+    return bb * X.sb + t * X.st;
+  }
+  template <int Z, int P> __device__ float bval(int off) const { return X.p[off]; }
+  __device__ void epi(int z, int i, int j, float v) const { o.epi(z, i, j, v); }
+};
+
+struct GftBwdDxPhOp {
+  static constexpr int NZ = 1, NPH = 1;
+  template <int Z, int P> static constexpr bool akf() { return false; }
+  template <int Z, int P> static constexpr bool bkf() { return false; }
+  GftBwdDxOp o;
+  __device__ bool setup(int, int& M, int& Nn, int& K) const {
+    M = o.N; Nn = o.B * o.W; K = 3 * o.N;
+    return true;
+  }
+  template <int Z, int P> __device__ int arow(int i) const { return i; }
+  template <int Z, int P> __device__ int acol(int k) const { return k * o.N; }
+  template <int Z, int P> __device__ float aval(int off) const { return o.T[off]; }
+  template <int Z, int P> __device__ int brow(int k) const {
+    int kq, n;
+    o.dN.divmod(k, kq, n);
+    return n * (3 * o.W) + kq * o.W;
+  }
+  template <int Z, int P> __device__ int bcol(int j) const {
+    int bb, t;
+    o.dW.divmod(j, bb, t);
+    return bb * (o.N * 3 * o.W) + t;
+  }
+  template <int Z, int P> __device__ float bval(int off) const { return o.dG[off] + o.dG[off + o.slab]; }
+  __device__ void epi(int z, int i, int j, float v) const { o.epi(z, i, j, v); }
+};
+
+// phase 0 = block 0's (b, t) range, phase 1 = block 1's; each block's X is walked along ITS contiguous axis
+template <bool X0KF, bool X1KF>    // XnKF: block n's X is contiguous along t (the reduction axis here)
+struct GftBwdDt2PhOp {
+  static constexpr int NZ = 1, NPH = 2;
+  template <int Z, int P> static constexpr bool akf() { return true; }
+  template <int Z, int P> static constexpr bool bkf() { return P == 0 ? X0KF : X1KF; }
+  GftBwdDt2Op o;
+  XViewI X[2];
+  __device__ bool setup(int, int& M, int& Nn, int& K) const {
+    M = 3 * o.N; Nn = o.N; K = 2 * o.B * o.W;
+    return true;
+  }
+  __device__ int pend() const { return o.B * o.W; }
+  template <int Z, int P> __device__ int arow(int i) const {
+    int kq, n;
+    o.dN.divmod(i, kq, n);
+    return n * (3 * o.W) + kq * o.W;
+  }
+  template <int Z, int P> __device__ int acol(int k) const {
+    int bb, t;
+    o.dW.divmod(k - P * o.B * o.W, bb, t);
+    return bb * (o.N * 3 * o.W) + t;
+  }
+  template <int Z, int P> __device__ float aval(int off) const {
+    const float* g = o.dG[P];
+    return g[off] + g[off + o.slab];
+  }
+  template <int Z, int P> __device__ int brow(int k) const {
+    int bb, t;
+    o.dW.divmod(k - P * o.B * o.W, bb, t);
+    return bb * X[P].sb + t * X[P].st;
+  }
+  template <int Z, int P> __device__ int bcol(int j) const { return j * X[P].sn; }
+  template <int Z, int P> __device__ float bval(int off) const { return X[P].p[off]; }
+  __device__ void epi(int z, int i, int j, float v) const { o.epi(z, i, j, v); }
 };
 
 // =================================================================================================
@@ -532,6 +634,12 @@ extern "C" int stemgnn_gft_fwd(const float* mul_L, const float* X, long xs_b, lo
   GftFwdOp op{mul_L + (size_t)N * N, XView{X, xs_b, xs_n, xs_t, N}, G, B, N, W, sg_div(N), sg_div(W)};
   hipStream_t st = (hipStream_t)stream;
   if (N <= 512) {       // latency-bound at small N: half as many load -> LDS -> MFMA rounds
+    if (sg_graph_phased() && sg_phased_fits(B, N, W, xs_b, xs_n, xs_t)) {
+      const XViewI xi{X, (int)xs_b, (int)xs_n, (int)xs_t};
+      if (xs_n == 1) SG_TRY((sg_launch_phased<GftFwdPhOp<true>>(GftFwdPhOp<true>{op, xi}, 3 * N, B * W, st)));
+      else SG_TRY((sg_launch_phased<GftFwdPhOp<false>>(GftFwdPhOp<false>{op, xi}, 3 * N, B * W, st)));
+      return 0;
+    }
     if (xs_n == 1) SG_TRY((sg_launch_gemm<GftFwdOp, 32, 32, true, true, false, 128, true>(op, 3 * N, B * W, 1, st)));
     else SG_TRY((sg_launch_gemm<GftFwdOp, 32, 32, true, false, false, 128, true>(op, 3 * N, B * W, 1, st)));
     return 0;
@@ -550,7 +658,9 @@ extern "C" int stemgnn_gft_bwd(const float* mul_L, const float* X, long xs_b, lo
   if (!sg_div_ok(3L * N + 128, N) || !sg_div_ok((long)B * W + 128, W)) return SG_EINVAL;
   if (dX) {
     GftBwdDxOp op{mul_L + (size_t)N * N, dG, dX, B, N, W, (size_t)B * N * 3 * W, sg_div(N), sg_div(W)};
-    if (bk128) SG_TRY((sg_launch_gemm<GftBwdDxOp, 32, 32, false, false, false, 128, true>(op, N, B * W, 1, st)));
+    if (bk128 && sg_graph_phased() && sg_phased_fits(B, N, W, 0, 0, 0))
+      SG_TRY((sg_launch_phased<GftBwdDxPhOp>(GftBwdDxPhOp{op}, N, B * W, st)));
+    else if (bk128) SG_TRY((sg_launch_gemm<GftBwdDxOp, 32, 32, false, false, false, 128, true>(op, N, B * W, 1, st)));
     else SG_TRY((sg_launch_gemm<GftBwdDxOp, 32, 32, false, false, false, 64, true>(op, N, B * W, 1, st)));
   }
   if (!dmul_L) return 0;                         // data gradient only (the caller runs the dT product elsewhere)
@@ -574,6 +684,15 @@ extern "C" int stemgnn_gft_bwd_dt2(const float* X0, long xs0_b, long xs0_n, long
   if (!sg_div_ok(3L * N + 128, N) || !sg_div_ok(2L * B * W + 128, W)) return SG_EINVAL;
   GftBwdDt2Op op{{dG0, dG1}, {XView{X0, xs0_b, xs0_n, xs0_t, N}, XView{X1, xs1_b, xs1_n, xs1_t, N}}, dmul_L + (size_t)N * N,
                  B, N, W, (size_t)B * N * 3 * W, sg_div(N), sg_div(W)};
+  if (N <= 512 && sg_graph_phased() && sg_phased_fits(B, N, W, xs0_b, xs0_n, xs0_t) && sg_phased_fits(B, N, W, xs1_b, xs1_n, xs1_t)) {
+    const XViewI x0{X0, (int)xs0_b, (int)xs0_n, (int)xs0_t}, x1{X1, (int)xs1_b, (int)xs1_n, (int)xs1_t};
+    const bool k0 = xs0_t == 1, k1 = xs1_t == 1;       // a block whose X is t-contiguous is walked along the reduction axis
+    if (k0 && k1) SG_TRY((sg_launch_phased<GftBwdDt2PhOp<true, true>>(GftBwdDt2PhOp<true, true>{op, {x0, x1}}, 3 * N, N, st)));
+    else if (k0) SG_TRY((sg_launch_phased<GftBwdDt2PhOp<true, false>>(GftBwdDt2PhOp<true, false>{op, {x0, x1}}, 3 * N, N, st)));
+    else if (k1) SG_TRY((sg_launch_phased<GftBwdDt2PhOp<false, true>>(GftBwdDt2PhOp<false, true>{op, {x0, x1}}, 3 * N, N, st)));
+    else SG_TRY((sg_launch_phased<GftBwdDt2PhOp<false, false>>(GftBwdDt2PhOp<false, false>{op, {x0, x1}}, 3 * N, N, st)));
+    return 0;
+  }
   if (N <= 512) SG_TRY((sg_launch_gemm<GftBwdDt2Op, 32, 32, true, false, false, 128, true>(op, 3 * N, N, 1, st)));
   else SG_TRY((sg_launch_gemm<GftBwdDt2Op, 32, 32, true, false, false, 64, true>(op, 3 * N, N, 1, st)));
   return 0;

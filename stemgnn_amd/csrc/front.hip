@@ -13,6 +13,7 @@
 #include "../../include/stemgnn_hip.h"
 #include "dq_reduce.h"
 #include "gemm_core.h"
+#include "gemm_phased.h"
 #include "layout.h"
 
 #define SG_TRY(e)                                \
@@ -644,6 +645,27 @@ struct ChebBwd2Op {
   }
 };
 
+// The first backward product in phased form (gemm_phased.h): same sums, each z loaded along its contiguous axis.
+// z = 0: both operands k-contiguous; z = 1: L^T and dT3 are i / j-contiguous.  (ChebBwd2Op -- k < N k-contiguous, k >= N
+// i / j-contiguous, the boundary inside a K tile -- measured slower in phased form and stays on the core: DESIGN section 8)
+struct ChebBwd1PhOp {
+  static constexpr int NZ = 2, NPH = 1;
+  template <int Z, int P> static constexpr bool akf() { return Z == 0; }
+  template <int Z, int P> static constexpr bool bkf() { return Z == 0; }
+  ChebBwd1Op o;
+  __device__ bool setup(int, int& M, int& Nn, int& K) const {
+    M = o.N; Nn = o.N; K = o.N;
+    return true;
+  }
+  template <int Z, int P> __device__ int arow(int i) const { return Z == 0 ? i * o.N : i; }
+  template <int Z, int P> __device__ int acol(int k) const { return Z == 0 ? k : k * o.N; }
+  template <int Z, int P> __device__ float aval(int off) const { return (Z == 0 ? o.dT3 : o.L)[off]; }
+  template <int Z, int P> __device__ int brow(int k) const { return Z == 0 ? k : k * o.N; }
+  template <int Z, int P> __device__ int bcol(int j) const { return Z == 0 ? j * o.N : j; }
+  template <int Z, int P> __device__ float bval(int off) const { return (Z == 0 ? o.T2 : o.dT3)[off]; }
+  __device__ void epi(int z, int i, int j, float v) const { o.epi(z, i, j, v); }
+};
+
 // =================================================================================================
 // host side
 // =================================================================================================
@@ -825,8 +847,9 @@ extern "C" int stemgnn_cheb_bwd(const float* mul_L, const float* dmul_L, float* 
   float* dT2p = scratch + nn;
   ChebBwd1Op op1{mul_L + nn, mul_L + 2 * nn, dmul_L + nn, dmul_L + 2 * nn, dmul_L + 3 * nn, dLp, dT2p, N};
   if (N <= 512) {
-    SG_TRY((sg_launch_gemm<ChebBwd1Op, 32, 32, true, true, false, 128, true>(op1, N, N, 2, st)));
     ChebBwd2Op op2b{mul_L + nn, dT2p, dLp, dL, N};
+    if (sg_graph_phased()) SG_TRY((sg_launch_phased<ChebBwd1PhOp>(ChebBwd1PhOp{op1}, N, N, st)));
+    else SG_TRY((sg_launch_gemm<ChebBwd1Op, 32, 32, true, true, false, 128, true>(op1, N, N, 2, st)));
     SG_TRY((sg_launch_gemm<ChebBwd2Op, 32, 32, true, true, false, 128, true>(op2b, N, N, 1, st)));
     return 0;
   }
