@@ -159,6 +159,39 @@ size_t stemgnn_gru_bwd_scratch_floats(int B, int S, int Hd, int W);
 /* CUs (one workgroup each) the backward recurrence occupies for its whole run at this shape: a caller that overlaps other
  * kernels with it on another stream sizes them for the remaining CUs. */
 int stemgnn_gru_bwd_cus(int B, int Hd);
+/* The launch plan of the GRU front at a shape (host only, no GPU work): the one function stemgnn_gru_fwd / _fwd_infer,
+ * every stemgnn_gru_bwd* entry, stemgnn_gru_bwd_rank2_ok and stemgnn_gru_bwd_cus take their decisions from, written out as
+ * SG_GRU_PATH_WORDS ints.  cus > 0: the plan for a device with that many CUs; cus <= 0: the current device.  Parts that
+ * look at pointers (16-byte alignment of the projection's output, the fused weight-gradient kernel's operand rules) are
+ * answered for buffers that are each their own 256-byte aligned allocation, as the model's are.  Environment switches
+ * count as the launchers read them.  SG_EINVAL for a bad argument.  Tests use it to prove that their shapes reach every
+ * kernel family and instantiation (a moved threshold fails on the CPU instead of silently dropping coverage). */
+#define SG_GRU_PATH_WORDS 16
+#define SG_GRU_FWD_FAMILY   0    /* SG_GRU_FAM_*                                                                          */
+#define SG_GRU_FWD_P        1    /* workgroups per batch row of the forward cluster (0: wide / streaming)                 */
+#define SG_GRU_FWD_K        2    /* unrolled mat-vec length KF of gru_fwd_cluster4_kernel (0 elsewhere)                   */
+#define SG_GRU_GI_STREAM    3    /* input projection: 1 the streaming kernel (W == 12, Hd % 4 == 0), 0 the GEMM           */
+#define SG_GRU_BWD_FAMILY   4    /* SG_GRU_FAM_*                                                                          */
+#define SG_GRU_BWD_P        5    /* workgroups per batch row of the backward cluster (0: wide / streaming)                */
+#define SG_GRU_BWD_KU       6    /* unrolled mat-vec length KU of gru_bwd_cluster4 / cluster2_kernel (0 elsewhere)        */
+#define SG_GRU_BWD_SLICES   7    /* owner slices per mat-vec wave (1 or 2; 0 outside the wave-level clusters)             */
+#define SG_GRU_IH_FOLDED    8    /* dW_ih | db_ih accumulated inside the recurrence (else the split-K GEMM)               */
+#define SG_GRU_HH_FORM      9    /* SG_GRU_HH_*                                                                           */
+#define SG_GRU_IH_SLABS     10   /* slabs the dW_ih | db_ih sum adds up: B when folded, else the split count 32           */
+#define SG_GRU_RANK2_OK     11   /* == stemgnn_gru_bwd_rank2_ok(B, Hd)                                                    */
+#define SG_GRU_WIDE_PASSES  12   /* wide cluster: 16-row passes over the batch, ceil(B / 16) (0: not wide)                */
+#define SG_GRU_WIDE_MT      13   /* wide cluster: 16-row MFMA tiles of a workgroup's 3 U gate rows                        */
+#define SG_GRU_WIDE_GWF     14   /* wide cluster: forward instantiation, 16-unit groups per wave (8 or 16)                */
+#define SG_GRU_WIDE_GWB     15   /* wide cluster: backward instantiation (24 or 48)                                       */
+#define SG_GRU_FAM_STREAM   0    /* one workgroup per batch row, W_hh streamed from L2 every step                         */
+#define SG_GRU_FAM_CLUSTER1 1    /* round-1 cluster (LDS staging), STEMGNN_GRU_CLUSTER=1 and hidden < 64                  */
+#define SG_GRU_FAM_CLUSTER2 2    /* backward only: gru_bwd_cluster2_kernel (P = 5, 8)                                     */
+#define SG_GRU_FAM_CLUSTER4 3    /* wave-specialised per-row cluster (gru_cluster4.h)                                     */
+#define SG_GRU_FAM_WIDE     4    /* one MFMA cluster for all batch rows (gru_wide.h)                                      */
+#define SG_GRU_HH_SLABS     0    /* dW_hh | db_hh as 32 split-K slabs + the fixed-order reduce                            */
+#define SG_GRU_HH_TILES     1    /* fused weight-gradient kernel, tile list (<= 64 output tiles)                          */
+#define SG_GRU_HH_FLAT      2    /* fused weight-gradient kernel, flat work list (> 64 output tiles)                      */
+int stemgnn_gru_paths(int B, int S, int Hd, int W, int cus, int* out /* [SG_GRU_PATH_WORDS] */);
 int stemgnn_gru_fwd(const float* x, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
                     int B, int S, int Hd, int W, float* scratch, float* h_ext, float* reserve, int* status,
                     void* stream);

@@ -13,6 +13,21 @@ SG_EINVAL = -10001
 # bits of stemgnn_block_paths (SG_PATH_* in include/stemgnn_hip.h)
 SG_PATH = {"glu_fwd_fused": 1, "glu_dgrad_fused": 2, "heads_fwd_fused": 4, "heads_bwd_fused": 8, "heads_bwd_16w": 16,
            "long_k": 32, "wgrad_fused": 64, "glu_wgrad_fused": 128}
+# words of stemgnn_gru_paths (SG_GRU_* in include/stemgnn_hip.h), the kernel families and the dW_hh forms
+SG_GRU_PATH_WORDS = 16
+SG_GRU_WORD = {"fwd_family": 0, "fwd_P": 1, "fwd_K": 2, "gi_stream": 3, "bwd_family": 4, "bwd_P": 5, "bwd_KU": 6,
+               "bwd_slices": 7, "ih_folded": 8, "hh_form": 9, "ih_slabs": 10, "rank2_ok": 11, "wide_passes": 12,
+               "wide_MT": 13, "wide_GWf": 14, "wide_GWb": 15}
+SG_GRU_FAM = {"stream": 0, "cluster1": 1, "cluster2": 2, "cluster4": 3, "wide": 4}
+SG_GRU_HH = {"slabs": 0, "tiles": 1, "flat": 2}
+
+
+def gru_paths(B, S, Hd, W, cus=0):
+    """stemgnn_gru_paths as a dict of SG_GRU_WORD names (cus = 0: the current device); raises on SG_EINVAL."""
+    out = (c_int * SG_GRU_PATH_WORDS)()
+    check(load().stemgnn_gru_paths(B, S, Hd, W, cus, out), "stemgnn_gru_paths")
+    return {k: int(out[i]) for k, i in SG_GRU_WORD.items()}
+
 
 _P = c_void_p          # device pointer
 _PP = POINTER(c_void_p)  # host array of device pointers
@@ -56,6 +71,7 @@ SIGNATURES = {
     "stemgnn_gru_fwd_scratch_floats": (c_size_t, [c_int, c_int, c_int]),
     "stemgnn_gru_bwd_scratch_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
     "stemgnn_gru_bwd_cus": (c_int, [c_int, c_int]),
+    "stemgnn_gru_paths": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_int)]),
     "stemgnn_gru_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "stemgnn_gru_bwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
     "stemgnn_gru_bwd_rank2_ok": (c_int, [c_int, c_int]),

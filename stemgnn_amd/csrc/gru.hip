@@ -899,6 +899,7 @@ extern "C" size_t stemgnn_gru_reserve_floats(int B, int S, int Hd) { return (siz
 #define GRU_KC 48       // resident weights per lane (registers); the per-step loops are fully unrolled over it
 // Workgroups of a cluster kernel poll each other, so ALL of them must be resident at once: one per CU.  The bound is the
 // current device's CU count (queried once per device, never assumed) minus 1/8 slack for CUs another stream may hold.
+static int gru_limit_of_cus(int cus) { return cus - cus / 8; }
 static int gru_resident_limit() {
   static int cached_dev = -1, cached = 0;
   int dev = 0;
@@ -906,22 +907,22 @@ static int gru_resident_limit() {
   if (dev != cached_dev) {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    cached = cus - cus / 8;
+    cached = gru_limit_of_cus(cus);
     cached_dev = dev;
   }
   return cached;
 }
-static int gru_pick_P(int B, int Hd) {
+static int gru_pick_P(int B, int Hd, int limit) {
   const char* e = getenv("STEMGNN_GRU_CLUSTER");
   if (e && atoi(e) == 0) return 0;                 // 0: streaming kernels, 1: cluster v1, 2 / unset: v2 then v1
   for (int P = 1; P <= 8; P *= 2) {
     const GruCluster c = gru_cluster_geom(Hd, P);
-    if (c.ksf >= 1 && c.ksb >= 1 && c.kcf <= GRU_KC && c.kcb <= GRU_KC && B * P <= gru_resident_limit()) return P;
+    if (c.ksf >= 1 && c.ksb >= 1 && c.kcf <= GRU_KC && c.kcb <= GRU_KC && B * P <= limit) return P;
   }
   return 0;
 }
 // v2 cluster (wave-level exchange): P in {1,2,4,5} with U = ceil(Hd/P) <= 64; 0 = not applicable
-static int gru_pick_P2(int B, int Hd) {
+static int gru_pick_P2(int B, int Hd, int limit) {
   const char* e = getenv("STEMGNN_GRU_CLUSTER");
   if (e && atoi(e) != 2) return 0;
   // P workgroups per batch row: the slice U = ceil(Hd/P) must fit the 64 lanes, all B*P workgroups must be
@@ -930,7 +931,7 @@ static int gru_pick_P2(int B, int Hd) {
   static const int cand[6] = {1, 2, 4, 5, 6, 8};
   for (int i = 0; i < 6; ++i) {
     const int P = cand[i];
-    if ((Hd + P - 1) / P <= 64 && B * P <= gru_resident_limit()) return P;
+    if ((Hd + P - 1) / P <= 64 && B * P <= limit) return P;
   }
   return 0;
 }
@@ -959,7 +960,7 @@ static size_t gru_xbuf_floats(int B, int Hd) {     // u64 granules, 2 parities (
   return a > b ? a : b;
 }
 // wide cluster (gru_wide.h): hidden sizes beyond the per-row clusters; STEMGNN_GRU_WIDE=0 disables, =1 forces it
-static int gru_pick_wide(int B, int Hd, int P2, GruWide* g) {
+static int gru_pick_wide(int B, int Hd, int P2, int limit, GruWide* g) {
   const char* e = getenv("STEMGNN_GRU_WIDE");
   const int mode = e ? atoi(e) : -1;
   if (mode == 0) return 0;
@@ -967,7 +968,111 @@ static int gru_pick_wide(int B, int Hd, int P2, GruWide* g) {
   if (c && atoi(c) == 0 && mode != 1) return 0;
   if (P2 > 0 && mode != 1) return 0;                 // the per-row clusters are faster where they fit
   (void)B;
-  return gru_wide_plan(Hd, gru_resident_limit(), g);
+  return gru_wide_plan(Hd, limit, g);
+}
+
+// ---- the launch plan: every decision of the host entry points below, as ONE function of the shape and the resident limit ----
+// (stemgnn_gru_paths writes it out for the tests; the launchers read nothing but this struct, so what a test is told is
+// what runs)
+static int gru_gi_stream_env() {
+  static const int on = !(getenv("STEMGNN_GRU_GI_STREAM") && atoi(getenv("STEMGNN_GRU_GI_STREAM")) == 0);
+  return on;
+}
+// the dW_hh | db_hh product as the fused weight-gradient kernel sees it: rows 0..2Hd-1 of dgh are dgi's r, z gates, rows
+// 2Hd..3Hd-1 = dghn; h_prev of row (s, b) is row (s, b) of h_ext (slab 0 = zeros)
+static void gru_hh_gemms(WgGemm* q, const float* dgi, const float* dghn, const float* h_ext, float* dw_hh, float* db_hh,
+                         int Hd) {
+  q[0].A = dgi;  q[0].lda = 3 * Hd; q[0].Mi = 2 * Hd; q[0].out = dw_hh; q[0].out_bias = db_hh;
+  q[1].A = dghn; q[1].lda = Hd;     q[1].Mi = Hd;     q[1].out = dw_hh + (size_t)2 * Hd * Hd; q[1].out_bias = db_hh + 2 * Hd;
+  for (int r = 0; r < 2; ++r) { q[r].B = h_ext; q[r].ldb = Hd; q[r].Nj = Hd + 1; q[r].ones_col = Hd; q[r].ldo = Hd; }
+}
+// which form computes it: the fused kernel when the 16-byte rules hold (Hd % 4 == 0 for aligned buffers) and its partial
+// tiles fit the slab region -- the tile list up to 64 output tiles, the flat work list beyond (hidden > 512: 216 tiles at
+// 1024, 816 at 2048; arrival counters at the end of the slab region) -- otherwise 32 slabs + the reduce
+struct GruHhForm { int form, ntiles, smax; size_t ws_use; };
+static GruHhForm gru_hh_form(WgGemm* q, int Hd) {
+  GruHhForm f{SG_GRU_HH_SLABS, 0, 0, 0};
+  const bool ok = wg_gemm_ok(q[0]) && wg_gemm_ok(q[1]);
+  f.ntiles = wg_tile_index(q, 2);
+  const size_t ws_floats = (size_t)GRU_NSPLIT * 3 * Hd * (Hd + 1);
+  if (!ok) return f;
+  if (f.ntiles > 64) {
+    const size_t ncnt = ((size_t)f.ntiles + 63) & ~(size_t)63;
+    const size_t ws_use = (ws_floats - ncnt) & ~(size_t)3;
+    const int smax_big = (int)(ws_use / ((size_t)f.ntiles * WG_TILE_FLOATS));
+    if (smax_big >= 1) { f.form = SG_GRU_HH_FLAT; f.smax = smax_big > 8 ? 8 : smax_big; f.ws_use = ws_use; }
+    return f;
+  }
+  const int smax_ws = (int)(ws_floats / ((size_t)f.ntiles * WG_TILE_FLOATS));
+  if (smax_ws >= 1) { f.form = SG_GRU_HH_TILES; f.smax = smax_ws > 32 ? 32 : smax_ws; }
+  return f;
+}
+struct GruPlan {
+  int fwd_family, PF, KF, gi_stream;            // gi_stream: by shape; the launcher adds the 16-byte check of its own pointer
+  int bwd_family, P, KU, slices, fold_ih, hh_form, ih_sum, rank2_ok;
+  GruWide wide;                                 // valid where the family is SG_GRU_FAM_WIDE
+};
+static GruPlan gru_plan(int B, int S, int Hd, int W, int limit) {
+  GruPlan p{};
+  const int P2 = gru_pick_P2(B, Hd, limit);
+  if (gru_pick_wide(B, Hd, P2, limit, &p.wide) > 0) {
+    p.fwd_family = p.bwd_family = SG_GRU_FAM_WIDE;
+  } else if (P2 > 0) {
+    // Wave-specialised forward (gru_cluster4.h): P + 2 waves per workgroup, so every P <= 8 fits; its cluster size may
+    // differ from the backward's (the backward shares the chip with the side-stream weight-gradient GEMMs, the forward
+    // has it to itself).  Default: 7 workgroups per batch row when B * 7 of them are resident (224 of the 256 CUs at batch
+    // 32: the mat-vec slices shrink to 33 columns; measured 1.4985 -> 1.4850 ms per step at PEMS07, P = 5 / 6: 1.509 /
+    // 1.491), else the backward's P.
+    p.fwd_family = SG_GRU_FAM_CLUSTER4;
+    p.PF = P2;
+    {
+      const int want = 7, uw = (Hd + want - 1) / want;
+      // 7 workgroups per row = 9 waves = three on one SIMD = 168 registers per lane: slices of <= 40 columns only
+      if (uw <= 40 && B * want <= limit) p.PF = want;
+    }
+    const int UF = (Hd + p.PF - 1) / p.PF;
+    p.KF = UF <= 32 ? 32 : (UF <= 34 ? 34 : (UF <= 40 ? 40 : (UF <= 48 ? 48 : (UF <= 58 ? 58 : 64))));
+    // P <= 4 and P = 6 (hidden 321..384: PEMS03, two owner slices per mat-vec wave) run the wave-specialised backward
+    // (gru_cluster4.h); P = 5 and P = 8 keep the round-1 layout (17 waves / register budget)
+    const bool v4 = P2 <= 4 || P2 == 6;
+    p.bwd_family = v4 ? SG_GRU_FAM_CLUSTER4 : SG_GRU_FAM_CLUSTER2;
+    p.P = P2;
+    p.KU = gru_pick_KU(Hd, P2);
+    if (P2 == 6 && p.KU < 58) p.KU = 58;                   // the two-slice form is instantiated at 58 and 64 only
+    p.slices = (P2 == 6 || P2 == 8) ? 2 : 1;
+    // dW_ih | db_ih accumulated by the chore wave while the gate gradients pass through it: one slab per batch row
+    // instead of the split-K GEMM behind the recurrence
+    p.fold_ih = v4 && W <= GRU4_WMAX;
+    p.rank2_ok = v4;                                        // the factored output gradient: the same kernels only
+  } else {
+    const int P = gru_pick_P(B, Hd, limit);
+    p.fwd_family = p.bwd_family = P > 0 ? SG_GRU_FAM_CLUSTER1 : SG_GRU_FAM_STREAM;
+    p.PF = p.P = P;
+  }
+  p.gi_stream = gru_gi_stream_env() && p.fwd_family != SG_GRU_FAM_WIDE && W == 12 && (Hd & 3) == 0;
+  p.ih_sum = p.fold_ih ? B : GRU_NSPLIT;
+  {
+    float* const base = reinterpret_cast<float*>((uintptr_t)256);     // never dereferenced: every buffer its own allocation
+    WgGemm q[2];
+    gru_hh_gemms(q, base, base + (size_t)3 * S * B * Hd, base, base, base, Hd);
+    p.hh_form = gru_hh_form(q, Hd).form;
+  }
+  return p;
+}
+extern "C" int stemgnn_gru_paths(int B, int S, int Hd, int W, int cus, int* out) {
+  if (B <= 0 || S <= 0 || Hd <= 0 || W <= 0 || !out) return SG_EINVAL;
+  const GruPlan p = gru_plan(B, S, Hd, W, cus > 0 ? gru_limit_of_cus(cus) : gru_resident_limit());
+  const bool wide = p.fwd_family == SG_GRU_FAM_WIDE;
+  out[SG_GRU_FWD_FAMILY] = p.fwd_family; out[SG_GRU_FWD_P] = p.PF; out[SG_GRU_FWD_K] = p.KF;
+  out[SG_GRU_GI_STREAM] = p.gi_stream;
+  out[SG_GRU_BWD_FAMILY] = p.bwd_family; out[SG_GRU_BWD_P] = p.P; out[SG_GRU_BWD_KU] = p.KU;
+  out[SG_GRU_BWD_SLICES] = p.slices; out[SG_GRU_IH_FOLDED] = p.fold_ih; out[SG_GRU_HH_FORM] = p.hh_form;
+  out[SG_GRU_IH_SLABS] = p.ih_sum; out[SG_GRU_RANK2_OK] = p.rank2_ok;
+  out[SG_GRU_WIDE_PASSES] = wide ? (B + GW_BP - 1) / GW_BP : 0;
+  out[SG_GRU_WIDE_MT] = wide ? p.wide.MT : 0;
+  out[SG_GRU_WIDE_GWF] = wide ? gru_wide_gwf_class(p.wide) : 0;
+  out[SG_GRU_WIDE_GWB] = wide ? gru_wide_gwb_class(p.wide) : 0;
+  return 0;
 }
 
 extern "C" size_t stemgnn_gru_fwd_scratch_floats(int B, int S, int Hd) {
@@ -992,12 +1097,9 @@ extern "C" size_t stemgnn_gru_bwd_ctl_words(int S) { return S > 0 ? gru_ovl_word
 // it on another stream should leave out when it sizes that work (ops.py: the second fused weight-gradient launch)
 extern "C" int stemgnn_gru_bwd_cus(int B, int Hd) {
   if (B <= 0 || Hd <= 0) return 0;
-  const int P2 = gru_pick_P2(B, Hd);
-  GruWide wide;
-  if (gru_pick_wide(B, Hd, P2, &wide) > 0) return wide.P;
-  if (P2 > 0) return B * P2;
-  const int P = gru_pick_P(B, Hd);
-  return B * (P > 0 ? P : 1);
+  const GruPlan pl = gru_plan(B, Hd, Hd, 1, gru_resident_limit());
+  if (pl.bwd_family == SG_GRU_FAM_WIDE) return pl.wide.P;
+  return B * (pl.P > 0 ? pl.P : 1);
 }
 
 // RS = false: the inference forward -- the same launches and arithmetic, no `reserve` stores (reserve may be NULL)
@@ -1008,15 +1110,14 @@ static int gru_fwd_impl(const float* x, const float* w_ih, const float* w_hh, co
       Hd <= 0 || W <= 0)
     return SG_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const int P2 = gru_pick_P2(B, Hd);
-  GruWide wide;
-  const bool use_wide = gru_pick_wide(B, Hd, P2, &wide) > 0;
+  const GruPlan pl = gru_plan(B, S, Hd, W, gru_resident_limit());
+  const bool use_wide = pl.fwd_family == SG_GRU_FAM_WIDE, use_c4 = pl.fwd_family == SG_GRU_FAM_CLUSTER4;
   float* h_all = h_ext + (size_t)B * Hd;                                  // steps 0..S-1
   float* w_hhT = scratch;
   float* gi = scratch + (size_t)3 * Hd * Hd;
   gru_u64* xbuf2 = (gru_u64*)(scratch + ((((size_t)3 * Hd * Hd + (size_t)3 * S * B * Hd) + 1) & ~(size_t)1));
   size_t zn0 = 0, zn1 = 0;
-  if (!use_wide && P2 > 0) {
+  if (use_c4) {
     // per-row clusters: slab 0 (h_{-1} = 0) and the exchange granules (tags := 0 every launch) are zeroed ahead of the
     // recurrence INSIDE the projection GEMM's launch (GruGiOp::setup: every workgroup clears a share) instead of fill
     // nodes / a zeroing kernel of their own (each costs ~5 us of launch latency on the step's critical path).  (Round 3's
@@ -1027,8 +1128,7 @@ static int gru_fwd_impl(const float* x, const float* w_ih, const float* w_hh, co
   } else {
     SG_TRY(sg_zero_async(h_ext, (size_t)B * Hd * sizeof(float), st));    // slab 0: h_{-1} = 0
   }
-  static const int gi_stream = !(getenv("STEMGNN_GRU_GI_STREAM") && atoi(getenv("STEMGNN_GRU_GI_STREAM")) == 0);
-  if (gi_stream && !use_wide && W == 12 && (Hd & 3) == 0 && (reinterpret_cast<uintptr_t>(gi) & 15) == 0) {
+  if (pl.gi_stream && (reinterpret_cast<uintptr_t>(gi) & 15) == 0) {           // (the plan: W == 12, Hd % 4 == 0, not wide)
     const int ncg = 3 * Hd / 4;
     hipLaunchKernelGGL(gru_gi_stream_kernel<12>, dim3((S * B + GI_RB - 1) / GI_RB, (ncg + GI_NT - 1) / GI_NT), dim3(GI_NT), 0,
                        st, x, w_ih, b_ih, gi, B, S, Hd, reinterpret_cast<unsigned*>(h_ext), reinterpret_cast<unsigned*>(xbuf2),
@@ -1041,26 +1141,14 @@ static int gru_fwd_impl(const float* x, const float* w_ih, const float* w_hh, co
   }
   if (use_wide) {
     float* xb = scratch + ((((size_t)3 * Hd * Hd + (size_t)3 * S * B * Hd) + 3) & ~(size_t)3);      // 16-byte aligned
-    SG_TRY(gru_wide_fwd<RS>(gi, w_hh, b_hh, B, S, Hd, wide, xb, status, h_all, reserve, st));
+    SG_TRY(gru_wide_fwd<RS>(gi, w_hh, b_hh, B, S, Hd, pl.wide, xb, status, h_all, reserve, st));
     return 0;
   }
-  if (P2 > 0) {
+  if (use_c4) {
     gru_u64* xbuf = xbuf2;                                                          // zeroed inside the projection GEMM's launch above
     gru_u64* xid = xbuf + (size_t)2 * B * Hd;                                       // P XCC-id granules per batch row
     static const int allow_fast = !(getenv("STEMGNN_GRU_FAST_XCD") && atoi(getenv("STEMGNN_GRU_FAST_XCD")) == 0);
-    // Wave-specialised forward (gru_cluster4.h): P + 2 waves per workgroup, so every P <= 8 fits; its cluster size may
-    // differ from the backward's (the backward shares the chip with the side-stream weight-gradient GEMMs, the forward
-    // has it to itself).  Default: 7 workgroups per batch row when B * 7 of them are resident (224 of the 256 CUs at batch
-    // 32: the mat-vec slices shrink to 33 columns; measured 1.4985 -> 1.4850 ms per step at PEMS07, P = 5 / 6: 1.509 /
-    // 1.491), else the backward's P.
-    int PF = P2;
-    {
-      const int want = 7, uw = (Hd + want - 1) / want;
-      // 7 workgroups per row = 9 waves = three on one SIMD = 168 registers per lane: slices of <= 40 columns only
-      if (uw <= 40 && B * want <= gru_resident_limit()) PF = want;
-    }
-    const int UF = (Hd + PF - 1) / PF;
-    const int KF = UF <= 32 ? 32 : (UF <= 34 ? 34 : (UF <= 40 ? 40 : (UF <= 48 ? 48 : (UF <= 58 ? 58 : 64))));
+    const int PF = pl.PF, KF = pl.KF;                    // wave-specialised forward (gru_cluster4.h), sizes: gru_plan
     const dim3 grid4(8 * ((B + 7) / 8) * PF);
 #define GRU_F4K(PP, KK) hipLaunchKernelGGL((gru_fwd_cluster4_kernel<PP, KK, RS>), grid4, dim3((PP + 2) * 64), 0, st, gi, w_hh, \
                                            b_hh, B, S, Hd, xbuf, status, h_all, reserve, xid, allow_fast)
@@ -1073,8 +1161,8 @@ static int gru_fwd_impl(const float* x, const float* w_ih, const float* w_hh, co
     SG_TRY(hipGetLastError());
     return 0;
   }
-  const int P = gru_pick_P(B, Hd);
-  if (P > 0) {
+  if (pl.fwd_family == SG_GRU_FAM_CLUSTER1) {
+    const int P = pl.PF;
     const GruCluster c = gru_cluster_geom(Hd, P);
     gru_u64* xbuf = (gru_u64*)(scratch + ((((size_t)3 * Hd * Hd + (size_t)3 * S * B * Hd) + 1) & ~(size_t)1));   // 8-B aligned
     if (P > 1) SG_TRY(sg_zero_async(xbuf, (size_t)2 * B * Hd * sizeof(gru_u64), st));   // tags := 0 every launch
@@ -1134,10 +1222,7 @@ static int gru_wgrad_rows(const float* dgi, const float* dghn, const float* h_ex
 // factored output gradient (stemgnn_gru_bwd_rank2): supported by the wave-specialised per-row cluster kernels only
 extern "C" int stemgnn_gru_bwd_rank2_ok(int B, int Hd) {
   if (B <= 0 || Hd <= 0) return 0;
-  const int P2 = gru_pick_P2(B, Hd);
-  GruWide wide;
-  if (gru_pick_wide(B, Hd, P2, &wide) > 0) return 0;
-  return (P2 >= 1 && P2 <= 4) || P2 == 6;
+  return gru_plan(B, Hd, Hd, 1, gru_resident_limit()).rank2_ok;
 }
 // stages: 1 = the recurrence (fill + kernel), 2 = the weight gradients, 3 = both on `stream`.  1 and 2 as SEPARATE calls
 // (stemgnn_gru_bwd_rank2_begin / _finish) = the dW_hh product overlapped with the recurrence: 1 makes the kernel publish
@@ -1297,16 +1382,17 @@ static int gru_bwd_impl(const float* dh_all, const float* dkey, const float* dqu
   float* dghn = dgi + (size_t)3 * S * B * Hd;
   float* p_hh = dghn + (size_t)S * B * Hd;
   float* p_ih = p_hh + (size_t)GRU_NSPLIT * 3 * Hd * (Hd + 1);
-  const int P2 = gru_pick_P2(B, Hd);
-  const int P = P2 > 0 ? 0 : gru_pick_P(B, Hd);
-  bool fold_ih = false, hh_fused = false, cnt_zeroed = false, ih_reduced = false;
+  const GruPlan pl = gru_plan(B, S, Hd, W, gru_resident_limit());
+  const bool row_cluster = pl.bwd_family == SG_GRU_FAM_CLUSTER4 || pl.bwd_family == SG_GRU_FAM_CLUSTER2;
+  const int P2 = row_cluster ? pl.P : 0;
+  const bool fold_ih = pl.fold_ih && !no_wgrad;
+  bool hh_fused = false, cnt_zeroed = false, ih_reduced = false;
   // no_wgrad (stemgnn_gru_bwd_recur / _rank2_recur): the recurrence alone, on the plain kernels (stages == 3: no progress
   // publishing, no store wave), no dW_ih fold, no weight-gradient or reduce launch
   const bool run_rec = (stages & 1) != 0, run_wg = (stages & 2) != 0 && !no_wgrad;
   const bool split_call = stages != 3;                   // begin / finish: only where stemgnn_gru_bwd_overlap_ok (the callers check)
   bool dq_pending = dq_nchunk > 0 && run_rec;            // dquery arrives as per-chunk partials: summed in the fill launch where
-  GruWide dq_probe;
-  if (dq_pending && !(P2 > 0 && gru_pick_wide(B, Hd, P2, &dq_probe) <= 0)) {   // the per-row clusters run, by a launch of its own elsewhere
+  if (dq_pending && !row_cluster) {   // the per-row clusters run, by a launch of its own elsewhere
     float* dq = const_cast<float*>(dquery);
     hipLaunchKernelGGL(sg_gru_dq_reduce_kernel, dim3((unsigned)(((size_t)B * Hd + 255) / 256)), dim3(256), 0, st,
                        dq + (size_t)B * Hd, dq, B, Hd, dq_nchunk);
@@ -1320,11 +1406,10 @@ static int gru_bwd_impl(const float* dh_all, const float* dkey, const float* dqu
   unsigned* ovl_cntA = ovl_claim + GRU_OVL_CLAIMS;
   unsigned* ovl_qhead = ovl_cntA + 64;
   const int ovl_ts = 4;                                  // time steps per progress chunk
-  GruWide wide;
-  if (gru_pick_wide(B, Hd, P2, &wide) > 0) {
+  if (pl.bwd_family == SG_GRU_FAM_WIDE) {
     float* xb = scratch + ((((size_t)(p_ih - scratch) + (size_t)gru_ih_slabs(B) * 3 * Hd * (W + 1)) + 3) & ~(size_t)3);
-    if (run_rec) SG_TRY(gru_wide_bwd(dh_all, w_hh, h_all, reserve, B, S, Hd, wide, xb, status, dgi, dghn, st));
-  } else if (P2 > 0) {
+    if (run_rec) SG_TRY(gru_wide_bwd(dh_all, w_hh, h_all, reserve, B, S, Hd, pl.wide, xb, status, dgi, dghn, st));
+  } else if (row_cluster) {
     // (Round 2 also built two overlap schedules for the weight-gradient tail -- time segments of the recurrence and a
     // progress mark released by a spin kernel -- which were parity-tested, measured SLOWER inside the hipGraph step
     // (profiles/r02_gru_segments.md) and removed in round 4; the recurrence runs as ONE launch over all S steps.)
@@ -1359,7 +1444,7 @@ static int gru_bwd_impl(const float* dh_all, const float* dkey, const float* dqu
     unsigned* kprog = split_call ? ovl_prog : nullptr;   // the recurrence publishes its progress only for a reader beside it
     static const int allow_fast = !(getenv("STEMGNN_GRU_FAST_XCD") && atoi(getenv("STEMGNN_GRU_FAST_XCD")) == 0);
     const dim3 grid(8 * ((B + 7) / 8) * P2);
-    const int KU2 = gru_pick_KU(Hd, P2);
+    const int KU2 = pl.KU;
     {
       const int s_hi = S - 1, s_lo = 0, s_mark = -1;       // the whole range in one launch, no progress mark
 #define GRU_B2K(PP, KK, OO) do { const size_t hog = gru_lds_hog<PP>((const void*)gru_bwd_cluster2_kernel<PP, KK, OO>); \
@@ -1368,12 +1453,7 @@ static int gru_bwd_impl(const float* dh_all, const float* dkey, const float* dqu
                        xid0, allow_fast); } while (0)
 #define GRU_B2(PP, OO) do { if (KU2 == 32) GRU_B2K(PP, 32, OO); else if (KU2 == 48) GRU_B2K(PP, 48, OO); \
                             else if (KU2 == 58) GRU_B2K(PP, 58, OO); else GRU_B2K(PP, 64, OO); } while (0)
-      // P <= 4 and P = 6 (hidden 321..384: PEMS03, two owner slices per mat-vec wave) run the wave-specialised backward
-      // (gru_cluster4.h); P = 5 and P = 8 keep the round-1 layout (17 waves / register budget)
-      const bool v4 = P2 <= 4 || P2 == 6;
-      // dW_ih | db_ih accumulated by the chore wave while the gate gradients pass through it: one slab per batch row
-      // instead of the split-K GEMM behind the recurrence
-      fold_ih = v4 && W <= GRU4_WMAX && !no_wgrad;
+      const bool v4 = pl.bwd_family == SG_GRU_FAM_CLUSTER4;      // (which P runs which kernel, and fold_ih: gru_plan)
       float* ih_slab = fold_ih ? p_ih : nullptr;
       if (run_rec) {
 #define GRU_B4KS(PP, KK, SWV) do { const size_t hog = gru_lds_hog4<PP>((const void*)gru_bwd_cluster4_kernel<PP, KK, 1, SWV>); \
@@ -1401,7 +1481,8 @@ static int gru_bwd_impl(const float* dh_all, const float* dkey, const float* dqu
       SG_TRY(hipGetLastError());
       }
     }
-  } else if (P > 0) {
+  } else if (pl.bwd_family == SG_GRU_FAM_CLUSTER1) {
+    const int P = pl.P;
     const GruCluster c = gru_cluster_geom(Hd, P);
     gru_u64* xbuf = (gru_u64*)(scratch + ((((size_t)(p_ih - scratch) + (size_t)gru_ih_slabs(B) * 3 * Hd * (W + 1)) + 1) & ~(size_t)1));
     if (P > 1) SG_TRY(sg_zero_async(xbuf, (size_t)2 * B * 3 * Hd * sizeof(gru_u64), st));
@@ -1427,33 +1508,20 @@ static int gru_bwd_impl(const float* dh_all, const float* dkey, const float* dqu
     // green, but SLOWER than slabs + reduce: backward incl. weight gradients 0.836 -> 0.863 ms at N=358, B=32.)
     {
       WgGemm q[2];
-      q[0].A = dgi;  q[0].lda = 3 * Hd; q[0].Mi = 2 * Hd; q[0].out = dw_hh; q[0].out_bias = db_hh;
-      q[1].A = dghn; q[1].lda = Hd;     q[1].Mi = Hd;     q[1].out = dw_hh + (size_t)2 * Hd * Hd; q[1].out_bias = db_hh + 2 * Hd;
-      bool ok = true;
-      for (int r = 0; r < 2; ++r) {
-        q[r].B = h_ext; q[r].ldb = Hd; q[r].Nj = Hd + 1; q[r].ones_col = Hd; q[r].ldo = Hd;
-        ok = ok && wg_gemm_ok(q[r]);
-      }
-      const int ntiles = wg_tile_index(q, 2);
-      const size_t ws_floats = (size_t)GRU_NSPLIT * 3 * Hd * (Hd + 1);
+      gru_hh_gemms(q, dgi, dghn, h_ext, dw_hh, db_hh, Hd);
+      const GruHhForm hf = gru_hh_form(q, Hd);             // with this call's own pointers (the plan's answer: aligned ones)
+      const int ntiles = hf.ntiles;
       // the sum of the dW_ih | db_ih slabs rides along in the same launch (extra workgroups): no reduce launch on the tail
       WgExtra ex;
-      ex.part = p_ih; ex.out_w = dw_ih; ex.out_b = db_ih; ex.rows = 3 * Hd; ex.cols = W; ex.nsplit = B;
+      ex.part = p_ih; ex.out_w = dw_ih; ex.out_b = db_ih; ex.rows = 3 * Hd; ex.cols = W; ex.nsplit = pl.ih_sum;
       const WgExtra* exr = fold_ih ? &ex : nullptr;
-      if (ok && ntiles > 64) {
-        // hidden > 512: hundreds of tiles (216 at 1024, 816 at 2048) -- the flat work list of wgrad.h; arrival counters at
-        // the end of the slab region (which is 32 full copies of dW_hh: far more than the few partial tiles per output tile)
-        const size_t ncnt = ((size_t)ntiles + 63) & ~(size_t)63;
-        const size_t ws_use = (ws_floats - ncnt) & ~(size_t)3;
-        const int smax_big = (int)(ws_use / ((size_t)ntiles * WG_TILE_FLOATS));
-        if (smax_big >= 1) {
-          SG_TRY(wg_launch(q, 2, S * B, p_hh, reinterpret_cast<unsigned*>(p_hh + ws_use), smax_big > 8 ? 8 : smax_big, st, true,
-                           100, true));
-          hh_fused = true;
-        }
+      if (hf.form == SG_GRU_HH_FLAT) {
+        // hidden > 512: the flat work list of wgrad.h; arrival counters at the end of the slab region (which is 32 full
+        // copies of dW_hh: far more than the few partial tiles per output tile)
+        SG_TRY(wg_launch(q, 2, S * B, p_hh, reinterpret_cast<unsigned*>(p_hh + hf.ws_use), hf.smax, st, true, 100, true));
+        hh_fused = true;
       }
-      const int smax_ws = (int)(ws_floats / ((size_t)ntiles * WG_TILE_FLOATS));
-      if (ok && smax_ws >= 1 && ntiles <= 64) {
+      if (hf.form == SG_GRU_HH_TILES) {
         // arrival counters: the last 64 words of the 16-byte aligned part of the scratch tail (>= 128 spare floats)
         const size_t tail = (gru_bwd_scratch_base(B, S, Hd, W) - 64) & ~(size_t)3;
         unsigned* cnt = ctl ? ctl + gru_ovl_words(S) : reinterpret_cast<unsigned*>(scratch + tail);
@@ -1470,7 +1538,7 @@ static int gru_bwd_impl(const float* dh_all, const float* dkey, const float* dqu
           const int tmo = getenv("STEMGNN_GRU_WHH_TIMEOUT") ? atoi(getenv("STEMGNN_GRU_WHH_TIMEOUT")) : 4000;
           tl.timeout = (unsigned)(tmo < 0 ? 0 : tmo);
         }
-        const int smax = smax_ws > 32 ? 32 : smax_ws;
+        const int smax = hf.smax;
         if (split_call) {
           if (!two || !side) return SG_EINVAL;
           hipStream_t sd = (hipStream_t)side;
@@ -1509,7 +1577,7 @@ static int gru_bwd_impl(const float* dh_all, const float* dkey, const float* dqu
     J.part[1] = p_hh + (size_t)GRU_NSPLIT * n0; J.out_w[1] = dw_hh + (size_t)2 * Hd * Hd; J.out_b[1] = db_hh + 2 * Hd;
     J.rows[1] = Hd; J.cols[1] = Hd;
     J.part[2] = p_ih; J.out_w[2] = dw_ih; J.out_b[2] = db_ih; J.rows[2] = 3 * Hd; J.cols[2] = W;
-    J.nsplit[0] = J.nsplit[1] = GRU_NSPLIT; J.nsplit[2] = fold_ih ? B : GRU_NSPLIT;
+    J.nsplit[0] = J.nsplit[1] = GRU_NSPLIT; J.nsplit[2] = fold_ih ? pl.ih_sum : GRU_NSPLIT;
     if (hh_fused) J.rows[0] = J.rows[1] = 0;           // dw_hh / db_hh are complete already
     if (hh_fused && ih_reduced) return 0;              // ... and so are dw_ih / db_ih (WgExtra)
     size_t nmax = n0;

@@ -395,6 +395,9 @@ static inline int gru_wide_plan(int Hd, int pmax, GruWide* out) {
   *out = g;
   return g.P;
 }
+// the instantiation a geometry runs on: 16-unit groups per wave of the forward (8 / 16) and the backward (24 / 48) kernel
+static inline int gru_wide_gwf_class(const GruWide& g) { return g.GWf <= 8 ? 8 : 16; }
+static inline int gru_wide_gwb_class(const GruWide& g) { return g.GWb <= 24 ? 24 : 48; }
 
 template <bool RS = true>
 static inline hipError_t gru_wide_fwd(const float* gi, const float* w_hh, const float* b_hh, int B, int S, int Hd,
@@ -409,7 +412,7 @@ static inline hipError_t gru_wide_fwd(const float* gi, const float* w_hh, const 
 #define GWF2(MT_, GW_, MK_) hipLaunchKernelGGL((gru_fwd_wide_kernel<MT_, GW_, MK_, RS>), dim3(g.P), dim3(GW_NW * 64), 0, st, gi, w_hh, \
                                                b_hh, B, b0, Bc, S, Hd, g.U, g.KG, hx, flags, status, h_all, reserve)
 #define GWF(MT_, GW_) do { if (Bc <= 8) GWF2(MT_, GW_, true); else GWF2(MT_, GW_, false); } while (0)
-    if (g.GWf <= 8) { if (g.MT == 1) GWF(1, 8); else if (g.MT == 2) GWF(2, 8); else GWF(3, 8); }
+    if (gru_wide_gwf_class(g) == 8) { if (g.MT == 1) GWF(1, 8); else if (g.MT == 2) GWF(2, 8); else GWF(3, 8); }
     else            { if (g.MT == 1) GWF(1, 16); else if (g.MT == 2) GWF(2, 16); else GWF(3, 16); }
 #undef GWF2
 #undef GWF
@@ -430,7 +433,7 @@ static inline hipError_t gru_wide_bwd(const float* dout, const float* w_hh, cons
     if (e != hipSuccess) return e;
 #define GWB(GW_) hipLaunchKernelGGL((gru_bwd_wide_kernel<GW_>), dim3(g.P), dim3(GW_NW * 64), 0, st, dout, w_hh, h_all, reserve, \
                                     B, b0, Bc, S, Hd, g.U, g.KG, hx, flags, status, dgi, dghn)
-    if (g.GWb <= 24) GWB(24); else GWB(48);
+    if (gru_wide_gwb_class(g) == 24) GWB(24); else GWB(48);
 #undef GWB
     e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -54,6 +54,12 @@ SWEEP_CASES = [
     (172, 48, 4, 7, 14), (84, 7, 11, 1, 5), (91, 23, 5, 26, 12), (67, 54, 12, 10, 1),
 ]
 
+# the model behind the GRU front's batch-size fallbacks (csrc/gru.hip's residency rule B * P <= 224; the plan of each is
+# pinned on the CPU by tests/test_gru_paths.py): batch 64 at PEMS07's N -> the wide cluster in four passes and the
+# materialised-dh attention backward; N = 400 -> the P = 8 kernels; batch 40 -> the B > 32 forward cluster and per-row dW_ih
+# slabs; batch 225 at a hidden size below 64 -> the streaming kernels
+GRU_FALLBACK_CASES = [(228, 12, 5, 3, 64), (400, 12, 5, 3, 4), (60, 12, 5, 3, 40), (40, 8, 2, 4, 225)]
+
 # the N <= 256 single-workgroup branches once more through the direct eigensolver route (csrc/eigh.hip)
 EIG_CASES = [(256, 12, 5, 3, 2), (257, 12, 5, 3, 2)]
 
@@ -166,6 +172,12 @@ def test_edge_shape_matches_fp64_oracle(N, W, multi, H, B, dtype, monkeypatch):
 @pytest.mark.parametrize("dtype", ["f32", "bf16x2"])
 @pytest.mark.parametrize("N,W,multi,H,B", SWEEP_CASES)
 def test_sweep_shape_matches_fp64_oracle(N, W, multi, H, B, dtype, monkeypatch):
+    _check_case((N, W, multi, H, B), dtype, monkeypatch)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16x2"])
+@pytest.mark.parametrize("N,W,multi,H,B", GRU_FALLBACK_CASES)
+def test_gru_fallback_shape_matches_fp64_oracle(N, W, multi, H, B, dtype, monkeypatch):
     _check_case((N, W, multi, H, B), dtype, monkeypatch)
 
 
