@@ -62,6 +62,9 @@ int stemgnn_make_tables_host(int W, int multi, float* tables_host);
  * parts    bit 0: attention (-> A | deg, contiguous N*N + N floats at saved + 3*B*N), bit 1: Laplacian from (A, deg);
  *          3 = both.  The batch mean (:140) is the ONE cross-sample reduction of the path: a data-parallel caller that
  *          wants single-process semantics for a split batch runs part 1, averages A | deg over the ranks, runs part 2.
+ * Limits:  0 <= drop_p < 1 (forward and backward), and the attention part keeps four rows of N floats plus one float per
+ *          batch of a chunk in 64 KiB of LDS: ceil(B / min(B, 8)) + 4 N <= 16384, i.e. N <= 4095 for B <= 32 (N <= 4094 up to
+ *          B = 64).  A larger N returns SG_EINVAL before anything is launched.
  */
 int stemgnn_attn_laplacian_fwd(const float* h, const float* wk, const float* wq, float alpha,
                                float drop_p, int training, const uint64_t* seed,

@@ -22,6 +22,7 @@
     if (_e != hipSuccess) return -(int)_e;       \
   } while (0)
 
+constexpr size_t SG_ATTN_FWD_LDS_BYTES = 64 * 1024;   // dynamic LDS of sg_attention_fwd_kernel: (ceil(B / min(B, 8)) + 4 N) floats
 constexpr int ATTN_NBC = 8;     // batch chunks of the attention forward (more waves; partial sums reduced in fixed order)
 
 // ---- Philox4x32-10 ------------------------------------------------------------------------------------
@@ -290,8 +291,15 @@ __global__ __launch_bounds__(256) void sg_laplacian_fused_kernel(const float* __
     const int i = i0 + r, j = j0 + tx;
     if (i < N && j < N) {
       const size_t o = (size_t)i * N + j;
-      const float a = own[u] * invB;
-      const float sy = 0.5f * (a + tT[tx][r]);
+      float a, sy;
+      {
+        // no fma(own, invB, partner): contracted, element (i, j) would add the rounded partner to its own unrounded product
+        // and (j, i) the other way round.  Uncontracted, attention_out is bitwise symmetric and has the bits of
+        // sg_laplacian_fwd_kernel (which reads the rounded A back) for every B
+#pragma clang fp contract(off)
+        a = own[u] * invB;
+        sy = 0.5f * (a + tT[tx][r]);
+      }
       const float di = sdeg[0][r], dj = sdeg[1][tx];
       const float dhi = 1.f / (sqrtf(di) + 1e-7f), dhj = 1.f / (sqrtf(dj) + 1e-7f);
       const float qv = (i == j ? di : 0.f) - sy;
@@ -681,7 +689,11 @@ extern "C" int stemgnn_attn_laplacian_fwd(const float* h, const float* wk, const
                                           float* saved, float* attention_out, float* mul_L, int parts, void* stream) {
   if (!h || !wk || !wq || !saved || !attention_out || !mul_L || B <= 0 || N <= 0 || (parts & 3) == 0) return SG_EINVAL;
   if (training && drop_p > 0.f && !seed) return SG_EINVAL;
-  if (drop_p < 0.f || drop_p >= 1.f) return SG_EINVAL;
+  if (!(drop_p >= 0.f && drop_p < 1.f)) return SG_EINVAL;
+  const int nbc = B < ATTN_NBC ? B : ATTN_NBC;
+  const int bn = (B + nbc - 1) / nbc;
+  const size_t lds = ((size_t)bn + (size_t)4 * N) * sizeof(float);
+  if ((parts & 1) && lds > SG_ATTN_FWD_LDS_BYTES) return SG_EINVAL;      // refused before anything is launched
   hipStream_t st = (hipStream_t)stream;
   float* key = saved;
   float* query = key + (size_t)B * N;
@@ -693,10 +705,6 @@ extern "C" int stemgnn_attn_laplacian_fwd(const float* h, const float* wk, const
     SG_TRY(hipGetLastError());
     float* Apart = deg + N;
     float* degpart = Apart + (size_t)ATTN_NBC * N * N;
-    const int nbc = B < ATTN_NBC ? B : ATTN_NBC;
-    const int bn = (B + nbc - 1) / nbc;
-    const size_t lds = (size_t)(bn + 4 * N) * sizeof(float);
-    if (lds > 64 * 1024) return SG_EINVAL;
     hipLaunchKernelGGL(sg_attention_fwd_kernel, dim3((N + 3) / 4, (B + bn - 1) / bn), dim3(256), lds, st, key, query, alpha,
                        drop_p, training, seed, B, N, bn, rowsum, Apart, degpart);
     SG_TRY(hipGetLastError());
@@ -728,6 +736,7 @@ extern "C" int stemgnn_attn_laplacian_bwd(const float* dL, const float* h, const
       N <= 0 || nchunk <= 0 || (parts & 3) == 0)
     return SG_EINVAL;
   if (training && drop_p > 0.f && !seed) return SG_EINVAL;
+  if (!(drop_p >= 0.f && drop_p < 1.f)) return SG_EINVAL;                // as the forward: keep_scale = 1 / (1 - p) is inf at 1
   hipStream_t st = (hipStream_t)stream;
   const float* key = saved;
   const float* query = key + (size_t)B * N;
