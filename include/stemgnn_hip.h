@@ -81,6 +81,18 @@ int stemgnn_attn_laplacian_bwd(const float* dL, const float* h, const float* wk,
                                float alpha, float drop_p, int training, const uint64_t* seed,
                                int B, int N, const float* saved, float* scratch, int nchunk,
                                float* dh, float* dwk, float* dwq, int parts, void* stream);
+/* The same with an external gradient for the RETURNED attention: dA_ext [N,N] fp32 row-major = d(loss)/d(attention_out)
+ * (a penalty on the learned graph, an edge's saliency).  Its adjoint through the symmetrisation (:143) and the batch mean (:140)
+ * joins inside the Laplacian backward's own launch:
+ *     dA / B = ((dd_i - dq_ij / 2) + (dA_ext[i][j] + dA_ext[j][i]) / 2) / B
+ * -- no extra launch on the chain; with dA_ext all zeros the outputs have the bits of stemgnn_attn_laplacian_bwd's.
+ * dL == NULL: attention-only backward (nothing reached mul_L): a small seed kernel writes dA / B = (dA_ext + dA_ext^T) / 2 / B
+ * in place of the Laplacian backward.  dA_ext == NULL: exactly stemgnn_attn_laplacian_bwd.  Both NULL: SG_EINVAL.
+ * parts, the scratch layout (stemgnn_attn_scratch_floats) and every other argument: as stemgnn_attn_laplacian_bwd. */
+int stemgnn_attn_laplacian_bwd_ext(const float* dL, const float* dA_ext, const float* h, const float* wk, const float* wq,
+                                   float alpha, float drop_p, int training, const uint64_t* seed,
+                                   int B, int N, const float* saved, float* scratch, int nchunk,
+                                   float* dh, float* dwk, float* dwq, int parts, void* stream);
 /* test hook: write the 0/1 keep-mask [B,N,N] the kernels above generate for `seed`. */
 int stemgnn_dropout_mask(float drop_p, const uint64_t* seed, int B, int N, float* mask, void* stream);
 /* One step of a model's dropout stream (nn.Dropout draws a fresh mask per forward, models/base_model.py:101,142): used[0..1] :=

@@ -214,17 +214,21 @@ class Model(nn.Module):
         return SpectralHotPath.apply(h, x, self.weight_key, self.weight_query, self.multi_layer, self.alpha,
                                      self.dropout_rate, self.training, seed, hs, *params)
 
-    def loss(self, x, target, loss_out=None, accum=None, unit_grad=False):
+    def loss(self, x, target, loss_out=None, accum=None, unit_grad=False, return_attention=False):
         """MSE training loss of one batch, ``nn.MSELoss()(self(x)[0], target)`` (models/handler.py:161-162), with the fc tail,
         the loss and both their backwards fused into one autograd node (two launches instead of five; forecast itself is
         not materialised).  `loss_out` / `accum`: optional static float32 scalar to write the loss into / float64 scalar
         that receives += loss.  `unit_grad`: the caller promises ``loss.backward()`` with an upstream gradient of 1 (what
         the driver does), which lets direct-gradient mode write the fc gradients in place (only honoured while autograd is
-        recording: a logging call under ``torch.no_grad()`` never touches ``p.grad``)."""
+        recording: a logging call under ``torch.no_grad()`` never touches ``p.grad``).  `return_attention`: return
+        ``(loss, attention)`` from the same hot-path call -- attention [N,N] is differentiable, so a penalty on the learned
+        graph rides on this fused node: ``torch.autograd.backward([loss, penalty], [one, one])`` (engine.TrainStep's
+        ``attention_penalty``) or ``(loss + penalty).backward()`` without `unit_grad`."""
         self._require_fc_tail()
-        fsum, _attention, _ = self.hot_path(x)
-        return FcTailMse.apply(fsum, target, self.fc[0].weight, self.fc[0].bias, self.fc[2].weight, self.fc[2].bias,
+        fsum, attention, _ = self.hot_path(x)
+        loss = FcTailMse.apply(fsum, target, self.fc[0].weight, self.fc[0].bias, self.fc[2].weight, self.fc[2].bias,
                                self.hot_state, loss_out, accum, bool(unit_grad) and torch.is_grad_enabled())
+        return (loss, attention) if return_attention else loss
 
     def _require_fc_tail(self):
         """The fc tail kernels (csrc/tail.hip) keep both weight matrices of a row block in LDS: time_step <= 64 and

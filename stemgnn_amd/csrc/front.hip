@@ -318,9 +318,15 @@ __global__ __launch_bounds__(256) void sg_laplacian_fused_kernel(const float* __
 // annihilates exactly (sum_j p_j = 1); adding it in fp32 only injects eps*|dd_i| noise into a difference of O(1/N)
 // terms (at N=2048 that noise is the whole 1e-4 budget of d weight_key/query), so it is dropped.  With dropout the
 // mask makes the term non-constant and it is kept.
+// EXT: an external gradient G = d(loss)/d(attention) [N,N] for the RETURNED attention 0.5 (A + A^T) (models/base_model.py:143
+// after the batch mean of :140) joins at this point: dAB[i][j] = ((dd_i - dq_ij / 2) + (G[i][j] + G[j][i]) / 2) / B.  G enters
+// AFTER the degree term, so with_degree == 0 stays valid as it is; a row-constant G (A.sum(): G = 1) is annihilated by the
+// softmax backward exactly as dd_i is -- it is not special-cased, the result is rounding noise around zero, as in the
+// reference.  G == 0 leaves the bits of the plain kernel (x + 0 = x).
+template <bool EXT>
 __global__ __launch_bounds__(256) void sg_laplacian_bwd_kernel(const float* __restrict__ dL, const float* __restrict__ A,
                                                                const float* __restrict__ deg, float* __restrict__ dAB,
-                                                               int B, int N, int with_degree) {
+                                                               int B, int N, int with_degree, const float* __restrict__ G) {
   __builtin_amdgcn_s_setprio(SG_CHAIN_PRIO);      // see gemm_core.h: these run beside the weight-gradient launch
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = blockIdx.x * 4 + wave;
@@ -334,12 +340,14 @@ __global__ __launch_bounds__(256) void sg_laplacian_bwd_kernel(const float* __re
     // round 6: every load of the row -- dL and A along the row and down the column, the degrees -- is issued BEFORE the first
     // use and kept in registers for the second pass (the two passes re-read the same elements; as two loops of four dependent
     // rounds each the kernel was ~8 L2 round trips long: 11.8 us for 0.4 MB).  Same operations in the same order.
-    float a_ij[4], a_ji[4], l_ij[4], l_ji[4], dg[4];
+    float a_ij[4], a_ji[4], l_ij[4], l_ji[4], dg[4], g_ij[4], g_ji[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int j = lane + 64 * t, jj = j < N ? j : N - 1;
       l_ij[t] = dL[(size_t)i * N + jj]; l_ji[t] = dL[(size_t)jj * N + i];
       dg[t] = deg[jj];
+      g_ij[t] = EXT ? G[(size_t)i * N + jj] : 0.f;      // part of the same up-front batch: no round trip of their own
+      g_ji[t] = EXT ? G[(size_t)jj * N + i] : 0.f;
       a_ij[t] = with_degree ? A[(size_t)i * N + jj] : 0.f;
       a_ji[t] = with_degree ? A[(size_t)jj * N + i] : 0.f;
     }
@@ -364,7 +372,8 @@ __global__ __launch_bounds__(256) void sg_laplacian_bwd_kernel(const float* __re
       if (j < N) {
         const float dhj = 1.f / (sqrtf(dg[t]) + 1e-7f);
         const float dq = (l_ij[t] + l_ji[t]) * dhi * dhj;
-        dAB[(size_t)i * N + j] = (dd - 0.5f * dq) * invB;
+        const float v = dd - 0.5f * dq;
+        dAB[(size_t)i * N + j] = (EXT ? v + 0.5f * (g_ij[t] + g_ji[t]) : v) * invB;
       }
     }
     return;
@@ -383,7 +392,35 @@ __global__ __launch_bounds__(256) void sg_laplacian_bwd_kernel(const float* __re
   for (int j = lane; j < N; j += 64) {
     const float dhj = 1.f / (sqrtf(deg[j]) + 1e-7f);
     const float dq = (dL[(size_t)i * N + j] + dL[(size_t)j * N + i]) * dhi * dhj;
-    dAB[(size_t)i * N + j] = (dd - 0.5f * dq) * invB;
+    const float v = dd - 0.5f * dq;
+    dAB[(size_t)i * N + j] = (EXT ? v + 0.5f * (G[(size_t)i * N + j] + G[(size_t)j * N + i]) : v) * invB;
+  }
+}
+
+// The seed of an attention-only backward (no gradient reaches mul_L: dL == 0, hence no Laplacian and no degree term):
+// dAB = (G + G^T) / 2 / B.  32 x 32 tiles, the transposed operand through LDS so that both reads run along rows.
+__global__ __launch_bounds__(256) void sg_attention_seed_kernel(const float* __restrict__ G, float* __restrict__ dAB, int B,
+                                                                int N) {
+  __builtin_amdgcn_s_setprio(SG_CHAIN_PRIO);      // see gemm_core.h: first kernel of the same chain
+  __shared__ float tT[32][33];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int i0 = blockIdx.y * 32, j0 = blockIdx.x * 32;
+  const float invB = 1.f / (float)B;
+  float own[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int r = ty + 8 * u;
+    const int gi = j0 + r, gj = i0 + tx;              // the partner tile: rows j0.., columns i0..
+    tT[r][tx] = (gi < N && gj < N) ? G[(size_t)gi * N + gj] : 0.f;
+    const int i = i0 + r, j = j0 + tx;
+    own[u] = (i < N && j < N) ? G[(size_t)i * N + j] : 0.f;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int r = ty + 8 * u;
+    const int i = i0 + r, j = j0 + tx;
+    if (i < N && j < N) dAB[(size_t)i * N + j] = (0.5f * (own[u] + tT[tx][r])) * invB;
   }
 }
 
@@ -727,12 +764,14 @@ extern "C" int stemgnn_attn_laplacian_fwd(const float* h, const float* wk, const
   return 0;
 }
 
-extern "C" int stemgnn_attn_laplacian_bwd(const float* dL, const float* h, const float* wk, const float* wq,
-                                          float alpha, float drop_p, int training, const uint64_t* seed, int B, int N,
-                                          const float* saved, float* scratch, int nchunk, float* dh, float* dwk,
-                                          float* dwq, int parts, void* stream) {
+// dL, dA_ext: at least one (checked by the two entries below).  dA_ext == NULL is the plain backward, dL == NULL the
+// attention-only one (seed kernel instead of the Laplacian backward); everything behind part 1 is the same chain.
+static int sg_attn_laplacian_bwd(const float* dL, const float* dA_ext, const float* h, const float* wk, const float* wq,
+                                 float alpha, float drop_p, int training, const uint64_t* seed, int B, int N,
+                                 const float* saved, float* scratch, int nchunk, float* dh, float* dwk, float* dwq,
+                                 int parts, void* stream) {
   const bool factored = (parts & 4) != 0;       // stop at dkey / dquery: no dh, dwk, dwq (-> stemgnn_keyquery_wgrad)
-  if (!dL || !h || !wk || !wq || !saved || !scratch || ((parts & 2) && !factored && (!dh || !dwk || !dwq)) || B <= 0 ||
+  if ((!dL && !dA_ext) || !h || !wk || !wq || !saved || !scratch || ((parts & 2) && !factored && (!dh || !dwk || !dwq)) || B <= 0 ||
       N <= 0 || nchunk <= 0 || (parts & 3) == 0)
     return SG_EINVAL;
   if (training && drop_p > 0.f && !seed) return SG_EINVAL;
@@ -748,8 +787,15 @@ extern "C" int stemgnn_attn_laplacian_bwd(const float* dL, const float* h, const
   float* dquery = dkey + (size_t)B * N;
   float* dqpart = dquery + (size_t)B * N;
   if (parts & 1) {      // Laplacian backward -> dA / B in scratch[0 .. N*N)  (a data-parallel caller may average it)
-    hipLaunchKernelGGL(sg_laplacian_bwd_kernel, dim3((N + 3) / 4), dim3(256), 0, st, dL, A, deg, dAB, B, N,
-                       (training && drop_p > 0.f) ? 1 : 0);
+    const int with_degree = (training && drop_p > 0.f) ? 1 : 0;
+    if (!dL)
+      hipLaunchKernelGGL(sg_attention_seed_kernel, dim3((N + 31) / 32, (N + 31) / 32), dim3(256), 0, st, dA_ext, dAB, B, N);
+    else if (dA_ext)
+      hipLaunchKernelGGL(sg_laplacian_bwd_kernel<true>, dim3((N + 3) / 4), dim3(256), 0, st, dL, A, deg, dAB, B, N, with_degree,
+                         dA_ext);
+    else
+      hipLaunchKernelGGL(sg_laplacian_bwd_kernel<false>, dim3((N + 3) / 4), dim3(256), 0, st, dL, A, deg, dAB, B, N, with_degree,
+                         dA_ext);
     SG_TRY(hipGetLastError());
   }
   if (!(parts & 2)) return 0;
@@ -769,6 +815,22 @@ extern "C" int stemgnn_attn_laplacian_bwd(const float* dL, const float* h, const
   hipLaunchKernelGGL(sg_keyquery_bwd_kernel, dim3(N), dim3(256), 0, st, h, wk, wq, dkey, dquery, dh, dwk, dwq, B, N);
   SG_TRY(hipGetLastError());
   return 0;
+}
+
+extern "C" int stemgnn_attn_laplacian_bwd(const float* dL, const float* h, const float* wk, const float* wq,
+                                          float alpha, float drop_p, int training, const uint64_t* seed, int B, int N,
+                                          const float* saved, float* scratch, int nchunk, float* dh, float* dwk,
+                                          float* dwq, int parts, void* stream) {
+  if (!dL) return SG_EINVAL;
+  return sg_attn_laplacian_bwd(dL, nullptr, h, wk, wq, alpha, drop_p, training, seed, B, N, saved, scratch, nchunk, dh, dwk,
+                               dwq, parts, stream);
+}
+extern "C" int stemgnn_attn_laplacian_bwd_ext(const float* dL, const float* dA_ext, const float* h, const float* wk,
+                                              const float* wq, float alpha, float drop_p, int training,
+                                              const uint64_t* seed, int B, int N, const float* saved, float* scratch,
+                                              int nchunk, float* dh, float* dwk, float* dwq, int parts, void* stream) {
+  return sg_attn_laplacian_bwd(dL, dA_ext, h, wk, wq, alpha, drop_p, training, seed, B, N, saved, scratch, nchunk, dh, dwk,
+                               dwq, parts, stream);
 }
 
 // The chunk sum of the attention backward's dquery partials as a call of its own (parts bit 3 of stemgnn_attn_laplacian_bwd left

@@ -135,7 +135,7 @@ def _time_replays(replay, n=10):
 class TrainStep:
     def __init__(self, model, optimizer, batch_size, window_size, horizon, units, series=None, world=1, graph=True,
                  exact=False, group=None, collective=None, one_graph=None, order_capacity=0, collective_fn=None,
-                 schedule_check=None):
+                 schedule_check=None, attention_penalty=None):
         """order_capacity > 0 (with a resident `series`): the step takes its windows from a device-side queue of window-end
         rows (`load_order` once per epoch, `run_next` per step; stemgnn_window_gather_queue advances the position on the
         device), so a hipGraph replay is the whole per-step host work -- no index copy ahead of it.
@@ -153,7 +153,17 @@ class TrainStep:
         N > 1 step with a collective that changes data (tests/test_hip_schedule.py).  Implies collective=True.
         schedule_check (default on, STEMGNN_SCHEDULE_CHECK=0 disables): after the capture, time the step against the
         same step with the side branch serialised and against the side branch's own kernel-time sum; a capture whose two
-        branches do not overlap is re-captured (up to 3 times, fresh side stream); the outcome is `self.schedule`."""
+        branches do not overlap is re-captured (up to 3 times, fresh side stream); the outcome is `self.schedule`.
+        attention_penalty: a callable ``attention [N,N] -> scalar float32 tensor on the device`` (a prior on the learned graph:
+        distance to a known adjacency, smoothness, a sparsity surrogate).  The step minimises loss + penalty: one backward
+        from both (``torch.autograd.backward([loss, penalty], [1, 1])``), so the hot path's backward runs once, with the
+        forecast's and the attention's gradient together, and the fused tail's unit-gradient promise holds.  The penalty's value
+        lands in the static scalar `self.penalty` (the MSE alone stays in `self.loss` / the epoch sum).  The callable's torch
+        operations are captured with the step's hipGraph, so it must be capture-safe: device tensors only, no host sync
+        (``.item()``, ``.cpu()``, printing a value), no allocation that depends on values, the same operations every call;
+        constants it uses (a prior matrix, a weight) must live on the device before the first step.  A penalty whose gradient
+        is constant along the rows of the symmetrised attention (``attention.sum()``) has no effect without dropout: the rows of the
+        softmax sum to 1.  None (default): the step is exactly what it is without the argument."""
         self.model, self.opt = model, optimizer
         self.collective_fn = collective_fn
         self.collective = (world > 1) if collective is None else bool(collective)
@@ -193,6 +203,8 @@ class TrainStep:
         self.loss = torch.zeros((), device=dev)
         self.loss_sum = torch.zeros((), device=dev, dtype=torch.float64)
         self._one = torch.ones((), device=dev)
+        self.attention_penalty = attention_penalty
+        self.penalty = torch.zeros((), device=dev) if attention_penalty is not None else None
         self.fuse_tail = hasattr(model, "loss")     # fc tail + MSE + both backwards as one node (2 launches instead of 5)
         self.want_graph = bool(graph) and self.fused
         self.group = group
@@ -252,12 +264,24 @@ class TrainStep:
         # :161-162 -- forward + loss; the loss lands in the static scalar and is added to the epoch sum inside the
         # reduction kernel (:166 without the per-step host sync or extra launches).  Model.loss fuses the fc tail, the
         # MSE and both their backwards (it is this step that promises the upstream gradient of 1 below)
-        if self.fuse_tail:
+        attention = None
+        if self.fuse_tail and self.attention_penalty is None:
             loss = self.model.loss(x, y, self.loss.detach(), self.loss_sum, unit_grad=True)
+        elif self.fuse_tail:
+            loss, attention = self.model.loss(x, y, self.loss.detach(), self.loss_sum, unit_grad=True, return_attention=True)
         else:
-            forecast, _ = self.model(x)
+            forecast, attention = self.model(x)
             loss = ops.mse_loss(forecast, y, self.loss.detach(), self.loss_sum)   # fresh alias: no history chaining
-        torch.autograd.backward(loss, grad_tensors=(self._one,))        # :164 (pre-allocated d(loss) = 1)
+        if self.attention_penalty is None:
+            torch.autograd.backward(loss, grad_tensors=(self._one,))    # :164 (pre-allocated d(loss) = 1)
+            return self.loss
+        pen = self.attention_penalty(attention)
+        if pen.shape != self._one.shape or pen.dtype != torch.float32 or pen.device != self._one.device:
+            raise ValueError("attention_penalty must return a float32 scalar tensor on the model's device, got "
+                             f"{pen.dtype} {tuple(pen.shape)} on {pen.device}")
+        self.penalty.copy_(pen.detach())
+        # one backward from both roots: SpectralHotPath.backward runs once with both gradients, each with d = 1
+        torch.autograd.backward([loss, pen], [self._one, self._one])
         return self.loss
 
     def _finish(self, loss):
@@ -561,6 +585,7 @@ class TrainStep:
         """Capture warm-ups execute real steps: keep parameters / optimizer state / dropout stream to put back."""
         st = dict(p=self.opt.flat_p.clone(), sq=self.opt.square_avg.clone(), g=self.opt.bucket.flat.clone(),
                   loss=self.loss.clone(), loss_sum=self.loss_sum.clone())
+        st["penalty"] = None if self.penalty is None else self.penalty.clone()
         seed = getattr(self.model, "_seed", None)
         st["seed"] = None if seed is None else seed.clone()
         st["queue"] = None if self.queue is None else self.queue.clone()
@@ -572,6 +597,8 @@ class TrainStep:
     def _restore(self, st):
         self.opt.flat_p.copy_(st["p"]); self.opt.square_avg.copy_(st["sq"]); self.opt.bucket.flat.copy_(st["g"])
         self.loss.copy_(st["loss"]); self.loss_sum.copy_(st["loss_sum"])
+        if st.get("penalty") is not None:
+            self.penalty.copy_(st["penalty"])
         if st["seed"] is not None:
             self.model._seed.copy_(st["seed"])
         if st.get("queue") is not None:

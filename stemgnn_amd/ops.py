@@ -723,6 +723,12 @@ class SpectralHotPath(torch.autograd.Function):
     (sum of the two block forecasts [B,N,W], attention [N,N], mul_L [4,N,N]).
 
     h is the GRU output [N_seq, B, N_hid] exactly as nn.GRU returns it; x is the model input [B,W,N].
+
+    Both the forecast sum and `attention` are differentiable (mul_L is not).  A gradient G for `attention` joins the backward
+    inside the Laplacian backward's launch (stemgnn_attn_laplacian_bwd_ext): dA / B gets (G + G^T) / 2 / B added, everything
+    behind it -- softmax backward, factored or materialised dh, GruFront.backward -- is the chain of the plain backward.
+    With G alone (nothing flows into the forecast sum) the blocks' backward is skipped altogether: a seed kernel writes
+    dA / B, no block tensor gets a gradient (None, not zeros) and x receives the GRU's share only.
     """
 
     @staticmethod
@@ -819,12 +825,14 @@ class SpectralHotPath(torch.autograd.Function):
         ctx.blocks = blocks
         ctx.aux = (h, x, wk, wq, seed, tables, mul_L, attn_saved, backcast, packed, saved)
         ctx.split = (splits, split)
-        ctx.mark_non_differentiable(attention, mul_L)
+        ctx.mark_non_differentiable(mul_L)
         ctx.set_materialize_grads(False)
         return fsum, attention, mul_L
 
     @staticmethod
-    def backward(ctx, dfsum, _datt, _dmulL):
+    def backward(ctx, dfsum, datt, _dmulL):
+        if dfsum is None and datt is None:
+            return (None,) * (10 + 2 * _lib.SG_BLOCK_NPARAMS)
         lib = _lib.load()
         B, N, W, multi, alpha, drop_p, training = ctx.dims
         h, x, wk, wq, seed, tables, mul_L, attn_saved, backcast, packed, saved = ctx.aux
@@ -833,20 +841,32 @@ class SpectralHotPath(torch.autograd.Function):
         splits, split = ctx.split
         dev, f32 = x.device, torch.float32
         st = _stream()
-        dfsum = dfsum.contiguous()
         tail_finish, state.tail_finish = state.tail_finish, None     # FcTailMse.forward's deferred partial-sum launch
+        if dfsum is None and tail_finish is not None:
+            # a gradient for the attention alone while the fused tail's deferred launch is pending (Model.loss whose loss was
+            # left out of this backward): no shortcut -- the whole backward with a zero forecast gradient queues the thunk
+            # where it always goes
+            dfsum = torch.zeros(B, N, W, device=dev, dtype=f32)
+        # attention-only: no gradient reaches the forecast sum, hence none reaches mul_L or any block tensor -- both blocks'
+        # heads / GLU / GFT backward, the d(mul_L) product and the Chebyshev backward are skipped and none of their buffers
+        # exists; the frozen-group machinery below (live -> no block gradient -> overlap off) does the rest
+        attn_only = dfsum is None
+        if not attn_only:
+            dfsum = dfsum.contiguous()
+        if datt is not None:
+            datt = datt.contiguous()        # (autograd has checked shape and dtype against the output)
         nsplit = _NSPLIT
         n_scratch = lib.stemgnn_scratch_floats(B, N, W, multi)
         off_dG = lib.stemgnn_scratch_offset_dG(B, N, W, multi)
         n_gradpart = lib.stemgnn_gradpart_floats(W, multi, nsplit)
-        dmul_L = torch.empty(4, N, N, device=dev, dtype=f32)
-        dbackcast = torch.empty(B, N, W, device=dev, dtype=f32)
+        dmul_L = None if attn_only else torch.empty(4, N, N, device=dev, dtype=f32)
+        dbackcast = None if attn_only else torch.empty(B, N, W, device=dev, dtype=f32)
         xviews = [(x, W * N, 1, N), (backcast, N * W, W, 1)]
         grads = [[None] * 33, [None] * 33]
         direct_idx = set()
         # frozen parameter groups (no tensor of the group needs a gradient) get no buffers and no weight-gradient launches
         nig = ctx.needs_input_grad
-        live = [any(nig[10 + 33 * s + i] for i, p in enumerate(blocks[s]) if p is not None) for s in (0, 1)]
+        live = [not attn_only and any(nig[10 + 33 * s + i] for i, p in enumerate(blocks[s]) if p is not None) for s in (0, 1)]
         kq_live = nig[2] or nig[3]
         for s in (1, 0):
             for i, p in enumerate(blocks[s]):
@@ -875,8 +895,8 @@ class SpectralHotPath(torch.autograd.Function):
         # (that kernel is latency-bound on half of the CUs and reserves its CUs' LDS, so the GEMMs land on the idle
         # CUs); block 1 therefore keeps its own scratch / partial buffers until the join.
         defer_b1 = overlap
-        scratch0 = torch.empty(n_scratch, device=dev, dtype=f32)
-        gradpart0 = torch.empty(n_gradpart, device=dev, dtype=f32)
+        scratch0 = None if attn_only else torch.empty(n_scratch, device=dev, dtype=f32)
+        gradpart0 = None if attn_only else torch.empty(n_gradpart, device=dev, dtype=f32)
         bufs = {0: (scratch0, gradpart0), 1: (scratch0, gradpart0)}
         if defer_b1:
             bufs[1] = (torch.empty(n_scratch, device=dev, dtype=f32), torch.empty(n_gradpart, device=dev, dtype=f32))
@@ -936,7 +956,7 @@ class SpectralHotPath(torch.autograd.Function):
         # product on the chain: the fork behind block 1's dX product and the join ahead of block 0's product were ~15 us of
         # cross-queue latency on the critical chain.
         dt1 = None
-        for s in (1, 0):
+        for s in (() if attn_only else (1, 0)):
             scratch = bufs[s][0]
             dG = scratch[off_dG:]
             X, sb, sn, stt = xviews[s]
@@ -982,7 +1002,7 @@ class SpectralHotPath(torch.autograd.Function):
                         state.block_grads_hook()         # data-parallel: reduce the finished range under the GRU recurrence
                 keep.append(bufs)                        # alive until the join
         dX0 = None
-        if nig[1]:
+        if nig[1] and not attn_only:
             # d(loss)/dx through block 0 (x is its input X, :169): the GFT adjoint sum_k T_k^T dG0_k (:63) minus the short-cut
             # head's direct term (:70-71), from block 0's heads data part still in scratch0 -- written [B,N,W], handed out as
             # x's [B,W,N] view.  The GRU's share comes from GruFront.backward; autograd adds the two.
@@ -994,10 +1014,12 @@ class SpectralHotPath(torch.autograd.Function):
                        "shortcut_dx")
         if overlap:
             state.pending = (side, (keep, packed, saved, split, backcast, dfsum, dbackcast))
-        dL = torch.empty(N, N, device=dev, dtype=f32)
-        cheb_scratch = torch.empty(2 * N * N, device=dev, dtype=f32)
-        _lib.check(lib.stemgnn_cheb_bwd(mul_L.data_ptr(), dmul_L.data_ptr(), dL.data_ptr(), cheb_scratch.data_ptr(),
-                                        N, st), "cheb_bwd")
+        dL = None
+        if not attn_only:
+            dL = torch.empty(N, N, device=dev, dtype=f32)
+            cheb_scratch = torch.empty(2 * N * N, device=dev, dtype=f32)
+            _lib.check(lib.stemgnn_cheb_bwd(mul_L.data_ptr(), dmul_L.data_ptr(), dL.data_ptr(), cheb_scratch.data_ptr(),
+                                            N, st), "cheb_bwd")
         # factored: dh[s,b,i] = dkey[b,i] wk[s] + dquery[b,i] wq[s] goes to the GRU backward as its two [B,N] factors
         # (stemgnn_gru_bwd_rank2); the kernel that would materialise the 6.6 MB tensor (and form dwk / dwq on the way) leaves
         # the critical chain, dwk / dwq come from a small kernel of their own on the side stream
@@ -1024,9 +1046,16 @@ class SpectralHotPath(torch.autograd.Function):
         dq_parts = bool(factored and overlap and kq_direct and not follower)      # (the follower's _begin call takes dquery reduced)
         if not kq_live:                 # frozen key / query: nothing else reads dquery -- the GRU backward's fill launch sums it
             dq_parts = bool(factored and not follower)
+        # a gradient for the returned attention: the _ext entry's Laplacian backward carries it in the same launch (dL None:
+        # its seed kernel).  Exact mode: G belongs to the rank-AVERAGED attention and is the same on every rank, so adding it in
+        # part 1, ahead of the rank mean, is right -- mean_r(dA_r + G) = mean_r(dA_r) + G
+        if datt is None:
+            bwd_entry, head = lib.stemgnn_attn_laplacian_bwd, (dL.data_ptr(),)
+        else:
+            bwd_entry, head = lib.stemgnn_attn_laplacian_bwd_ext, (_ptr(dL), datt.data_ptr())
         for part in ((3,) if exact is None else (1, 2)):
-            _lib.check(lib.stemgnn_attn_laplacian_bwd(
-                dL.data_ptr(), h.data_ptr(), wk.data_ptr(), wq.data_ptr(), alpha, drop_p, int(training),
+            _lib.check(bwd_entry(
+                *head, h.data_ptr(), wk.data_ptr(), wq.data_ptr(), alpha, drop_p, int(training),
                 seed.data_ptr() if use_drop else None, B, N, attn_saved.data_ptr(), attn_scratch.data_ptr(), _NCHUNK,
                 None if factored else dh.data_ptr(), _ptr(dwk), _ptr(dwq),
                 part | ((4 | (8 if dq_parts else 0)) if factored and part != 1 else 0), st), "attn_laplacian_bwd")
