@@ -492,6 +492,34 @@ int stemgnn_adam_step(float* params, float* grads, float* exp_avg, float* exp_av
                       float* step_dev, float beta1, float beta2, float eps, int zero_grad, float grad_scale,
                       void* stream);
 
+/* ---- opt-in controls of the two fused optimizers (csrc/optim.hip): gradient-norm clipping, weight decay, non-finite skip.
+ * The two entries above stay what the optimizers call when no control is enabled.
+ * Number of fp64 partial sums grad_sqsum writes for a bucket of n floats: one per fixed chunk of 8192 floats.  Host only; a
+ * function of n alone (never of the device), so the norm is the same bits on any device, eager or replayed. */
+size_t stemgnn_grad_norm_partials(size_t n);
+/* partials[c] = sum over chunk c of (grads[i] * grad_scale)^2, accumulated in fp64 in a fixed order (no atomics); one
+ * launch.  grads 16-byte aligned, any n > 0.  SG_EINVAL (nothing launched) on NULL, n == 0 or a misaligned pointer. */
+int stemgnn_grad_sqsum(const float* grads, size_t n, float grad_scale, double* partials, void* stream);
+/* rmsprop_step / adam_step with, per element,  g1 = (g * grad_scale) * coef ;  g2 = g1 + weight_decay * p  in front of
+ * the unchanged update (torch's order: clip_grad_norm_, then the optimizer adds the L2 term).  Every workgroup sums the
+ * stemgnn_grad_norm_partials(n) partials of a grad_sqsum call with the same grad_scale itself, in one fixed order:
+ * total = (float)sqrt(sum), coef = min(1, max_norm / (total + 1e-6f)) in fp32 (max_norm <= 0: no clipping, coef = 1).
+ * decoupled (Adam only; AdamW): p *= 1 - lr * weight_decay before the update and no decay term in the gradient.
+ * skip_nonfinite != 0 and total not finite: parameters, moments and Adam's step count are not written, gradients are
+ * still zeroed when zero_grad is set; otherwise NaN propagates as in torch.  partials may be NULL when max_norm <= 0 and
+ * skip_nonfinite == 0 (no norm is taken; stats[0] = NaN).  stats = 4 doubles on the device, written by one workgroup:
+ * [0] the pre-clip norm of this step, [1] the coefficient applied (1 not clipped, 0 skipped), [2] / [3] running counts of
+ * steps with coef < 1 / of skipped steps.  All flat buffers 16-byte aligned; SG_EINVAL (nothing launched) otherwise, on
+ * NULL, n == 0, a negative weight_decay, or missing partials.  1 - alpha / 1 - beta are formed as torch forms them (from
+ * the decimal the float argument stands for, in fp64, rounded once), so the moments track torch's to fp32 rounding. */
+int stemgnn_rmsprop_step_ext(float* params, float* grads, float* square_avg, size_t n, const float* lr_dev, float alpha,
+                             float eps, int zero_grad, float grad_scale, float weight_decay, float max_norm,
+                             int skip_nonfinite, const double* partials, double* stats, void* stream);
+int stemgnn_adam_step_ext(float* params, float* grads, float* exp_avg, float* exp_avg_sq, size_t n, const float* lr_dev,
+                          float* step_dev, float beta1, float beta2, float eps, int zero_grad, float grad_scale,
+                          float weight_decay, int decoupled, float max_norm, int skip_nonfinite, const double* partials,
+                          double* stats, void* stream);
+
 /* ---- data path either side of the hot path ---------------------------------------------
  * normalized() (data_loader/forecast_dataloader.py:7-22): out[t,n] = (float)clip01?((raw[t,n]-sub[n])/div[n]) in IEEE
  * fp64 (z_score: sub=mean, div=std with 0->1; min_max: sub=min, div=max-min+1e-5, clip01=1).  raw [T,N] fp64. */

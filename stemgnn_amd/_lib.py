@@ -96,6 +96,12 @@ SIGNATURES = {
     "stemgnn_fill_zero": (c_int, [_P, c_size_t, _P]),
     "stemgnn_rmsprop_step": (c_int, [_P, _P, _P, c_size_t, _P, c_float, c_float, c_int, c_float, _P]),
     "stemgnn_adam_step": (c_int, [_P, _P, _P, _P, c_size_t, _P, _P, c_float, c_float, c_float, c_int, c_float, _P]),
+    "stemgnn_grad_norm_partials": (c_size_t, [c_size_t]),
+    "stemgnn_grad_sqsum": (c_int, [_P, c_size_t, c_float, _P, _P]),
+    "stemgnn_rmsprop_step_ext": (c_int, [_P, _P, _P, c_size_t, _P, c_float, c_float, c_int, c_float, c_float, c_float, c_int,
+                                         _P, _P, _P]),
+    "stemgnn_adam_step_ext": (c_int, [_P, _P, _P, _P, c_size_t, _P, _P, c_float, c_float, c_float, c_int, c_float, c_float,
+                                      c_int, c_float, c_int, _P, _P, _P]),
     "stemgnn_normalize_series": (c_int, [_P, _P, _P, c_int, _P, c_long, c_int, _P]),
     "stemgnn_window_gather": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_long, _P, _P]),
     "stemgnn_window_gather_queue": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_long, _P, _P]),

@@ -589,7 +589,7 @@ class TrainStep:
         seed = getattr(self.model, "_seed", None)
         st["seed"] = None if seed is None else seed.clone()
         st["queue"] = None if self.queue is None else self.queue.clone()
-        for name in ("exp_avg", "_step_dev"):                      # FusedAdam's extra state
+        for name in ("exp_avg", "_step_dev", "stats"):             # FusedAdam's extra state; the controls' counters
             t = getattr(self.opt, name, None)
             st[name] = None if t is None else t.clone()
         return st
@@ -603,7 +603,7 @@ class TrainStep:
             self.model._seed.copy_(st["seed"])
         if st.get("queue") is not None:
             self.queue.copy_(st["queue"])
-        for name in ("exp_avg", "_step_dev"):
+        for name in ("exp_avg", "_step_dev", "stats"):
             if st.get(name) is not None:
                 getattr(self.opt, name).copy_(st[name])
         torch.cuda.synchronize()

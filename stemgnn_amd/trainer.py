@@ -131,7 +131,7 @@ class DeviceTrainer:
 
     def __init__(self, units, window, horizon, multi, *, batch_size=32, lr=1e-4, optimizer="RMSProp", decay_rate=0.5,
                  decay_every=5, norm_method="z_score", device="cuda", model_factory=None, hipgraph=True,
-                 dropout_seed=None):
+                 dropout_seed=None, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False):
         self.units, self.window, self.horizon, self.multi = units, window, horizon, multi
         self.batch_size, self.norm_method, self.device, self.hipgraph = batch_size, norm_method, device, hipgraph
         self.decay_every = decay_every
@@ -142,10 +142,12 @@ class DeviceTrainer:
             # the model's construction index in this process (two models never share a mask stream), so a run is only
             # reproducible if models are built in the same order; naming the key removes that dependence
             self.model.set_dropout_seed(int(dropout_seed), 0, torch.device(device))
+        # gradient-norm clipping / weight decay / non-finite skip inside the fused step (optim.py); defaults: the step as it was
+        controls = dict(weight_decay=weight_decay, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
         if optimizer == "RMSProp":
-            self.optimizer = FusedRMSprop(self.model.parameters(), lr=lr, eps=1e-8)
+            self.optimizer = FusedRMSprop(self.model.parameters(), lr=lr, eps=1e-8, **controls)
         else:                                   # the driver's other branch (models/handler.py:128-129), fused as well
-            self.optimizer = FusedAdam(self.model.parameters(), lr=lr, betas=(0.9, 0.999))
+            self.optimizer = FusedAdam(self.model.parameters(), lr=lr, betas=(0.9, 0.999), **controls)
         self.schedule = torch.optim.lr_scheduler.ExponentialLR(self.optimizer, gamma=decay_rate)
         self.statistic = None
         self.stepper = None
@@ -196,7 +198,11 @@ class DeviceTrainer:
             mean_loss = self.stepper.epoch_loss_sum() / max(n_steps, 1)       # one host sync per epoch
             ops.check_gather_status(train_set.device)                       # both raise if a device-side check tripped
             ops.check_gru_status(train_set.device)
-            log(f"epoch {epoch}: {time.time() - t0:.2f}s  mean train loss {mean_loss:.4f}  [{self.stepper.mode}]")
+            controls = ""
+            if self.optimizer.controls_enabled:                             # one more host sync per epoch, only then
+                rep = self.optimizer.grad_report(reset=True)
+                controls = f"  clipped {rep['clipped_steps']}/{n_steps}, skipped {rep['skipped_steps']}"
+            log(f"epoch {epoch}: {time.time() - t0:.2f}s  mean train loss {mean_loss:.4f}{controls}  [{self.stepper.mode}]")
             if out_dir is not None:
                 save_checkpoint(self.model, out_dir, epoch)
             if (epoch + 1) % self.decay_every == 0:
@@ -228,7 +234,9 @@ def train(train_data, valid_data, args, result_file, model_factory=None, on_step
     trainer = DeviceTrainer(train_data.shape[1], args.window_size, args.horizon, args.multi_layer,
                             batch_size=args.batch_size, lr=args.lr, optimizer=args.optimizer, decay_rate=args.decay_rate,
                             decay_every=args.exponential_decay_step, norm_method=args.norm_method, device=args.device,
-                            model_factory=model_factory, hipgraph=getattr(args, "hipgraph", True))
+                            model_factory=model_factory, hipgraph=getattr(args, "hipgraph", True),
+                            weight_decay=getattr(args, "weight_decay", 0.0), max_grad_norm=getattr(args, "max_grad_norm", None),
+                            skip_nonfinite=getattr(args, "skip_nonfinite", False))
     patience = getattr(args, "early_stop_step", 10) if getattr(args, "early_stop", False) else None
     return trainer.fit(train_data, valid_data, args.epoch, validate_every=args.validate_freq, patience=patience,
                        out_dir=result_file, on_step=on_step, on_validate=on_validate)
