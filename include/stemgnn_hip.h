@@ -474,6 +474,33 @@ int stemgnn_fc_tail_train_rows(const float* fsum, const float* target, const flo
                                void* stream);
 int stemgnn_fc_tail_train_finish(const float* scratch, int B, int N, int W, int H, float* loss, double* loss_accum,
                                  float* dw0, float* db0, float* dw2, float* db2, void* stream);
+/* The same tail with a choice of loss and with missing targets (csrc/tail.hip; one kernel template, the three entries above
+ * are its <MSE, unmasked> instantiation).  With d = forecast - target, `kind` picks the element loss:
+ *   SG_LOSS_MSE   d^2
+ *   SG_LOSS_MAE   |d|, derivative sign(d) with sign(0) = 0 (torch.nn.L1Loss)
+ *   SG_LOSS_HUBER torch.nn.HuberLoss(delta = param): d^2 / 2 for |d| <= param, else param (|d| - param / 2); derivative
+ *                 clamp(d, -param, param).  param must be finite and > 0 (ignored by the other kinds).
+ * norm == NULL: loss = sum / (B H N) and a NaN target propagates, as in the entries above.  norm != NULL: a NaN target is a
+ * MISSING target -- it is selected out (never multiplied by 0), so it reaches neither the loss nor any gradient whatever the
+ * forecast holds there, and loss = (sum over the valid targets) * norm[1], with norm = the two floats
+ * stemgnn_target_valid_count wrote for this target: norm[0] = (float)count of non-NaN values, norm[1] = (float)(1.0 / count),
+ * or 0 when count == 0 (loss and every gradient are then exactly 0).  +-inf is a value, not a missing one; a NaN forecast on a
+ * valid target still propagates.  `_rows_loss` and `_finish_loss` read norm[1] from device memory when they run; `_finish_loss`
+ * must get the norm (or NULL) its `_rows_loss` got.  stemgnn_target_valid_count is ONE launch of one workgroup with no
+ * host sync (capturable in a hipGraph); its count is an integer sum: exact, order-independent, independent of what norm held.
+ * Scratch: stemgnn_fc_tail_train_scratch_floats.  SG_EINVAL (nothing launched) on a NULL pointer other than norm / forecast /
+ * loss_accum, n == 0, an unknown kind, a Huber param that is not finite or <= 0, or a shape outside the fc tail's range. */
+enum { SG_LOSS_MSE = 0, SG_LOSS_MAE = 1, SG_LOSS_HUBER = 2 };
+int stemgnn_target_valid_count(const float* target, size_t n, float* norm, void* stream);
+int stemgnn_fc_tail_train_loss(const float* fsum, const float* target, const float* w0, const float* b0, const float* w2,
+                               const float* b2, int B, int N, int W, int H, int kind, float param, const float* norm,
+                               float* scratch, float* forecast, float* loss, double* loss_accum, float* dfsum, float* dw0,
+                               float* db0, float* dw2, float* db2, void* stream);
+int stemgnn_fc_tail_train_rows_loss(const float* fsum, const float* target, const float* w0, const float* b0, const float* w2,
+                                    const float* b2, int B, int N, int W, int H, int kind, float param, const float* norm,
+                                    float* scratch, float* forecast, float* dfsum, void* stream);
+int stemgnn_fc_tail_train_finish_loss(const float* scratch, int B, int N, int W, int H, const float* norm, float* loss,
+                                      double* loss_accum, float* dw0, float* db0, float* dw2, float* db2, void* stream);
 /* Zero `bytes` bytes at `ptr` in stream order, as a KERNEL launch (the reference's zero_grad, models/handler.py:160, when it is
  * not fused into the optimizer kernel; control words).  The step path never uses hipMemsetAsync: inside a captured hipGraph
  * a memset node was seen to run into the kernel node that follows it. */
@@ -537,6 +564,13 @@ int stemgnn_window_gather(const float* series, const long long* hi, float* x, fl
  * captured hipGraph step needs no per-step index copy.  Past the end: zeros + bit 1 of *status. */
 int stemgnn_window_gather_queue(const float* series, const long long* order, long long* queue, float* x, float* y, int B,
                                 int W, int H, int N, long T, int* status, void* stream);
+/* Both gathers with the y rows taken from a second series of the same shape (x from series_x, y from series_y): the
+ * targets of a data set that keeps its missing readings as NaN while the inputs stay imputed.  Same kernels -- the two
+ * entries above pass their series twice; for N % 4 == 0 both series must be 16-byte aligned. */
+int stemgnn_window_gather_pair(const float* series_x, const float* series_y, const long long* hi, float* x, float* y, int B,
+                               int W, int H, int N, long T, int* status, void* stream);
+int stemgnn_window_gather_queue_pair(const float* series_x, const float* series_y, const long long* order, long long* queue,
+                                     float* x, float* y, int B, int W, int H, int N, long T, int* status, void* stream);
 /* nn.MSELoss(reduction='mean') of the driver (models/handler.py:140,162): loss[0] = mean((forecast-target)^2) with
  * a fixed-order two-stage reduction; bwd: dforecast = grad_loss[0] * 2 (forecast-target)/n. */
 size_t stemgnn_mse_scratch_floats(void);
@@ -562,6 +596,12 @@ size_t stemgnn_eval_scratch_doubles(long count, int H, int N);
 size_t stemgnn_eval_out_doubles(int H, int N);
 int stemgnn_eval_metrics(const float* target, const float* forecast, const double* mul, const double* add,
                          long count, int H, int N, double* scratch, double* out, void* stream);
+/* The same metrics over the elements whose TARGET is not NaN (missing readings): same per-element formulas, output layout
+ * and fixed-order fp64 reduction, plus one plane that counts the elements kept; every mean divides by the valid count of its
+ * slice, and a slice with no valid element yields NaN.  Scratch: stemgnn_eval_scratch_doubles_masked (>= the unmasked size). */
+size_t stemgnn_eval_scratch_doubles_masked(long count, int H, int N);
+int stemgnn_eval_metrics_masked(const float* target, const float* forecast, const double* mul, const double* add,
+                                long count, int H, int N, double* scratch, double* out, void* stream);
 
 #ifdef __cplusplus
 }

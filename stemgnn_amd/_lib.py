@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STEMGNN_HIP_LIB", os.path.join(_HERE, "libstemgnn_hip.so"))   # override: A/B builds only
 SG_BLOCK_NPARAMS = 33
 SG_EINVAL = -10001
+SG_LOSS = {"mse": 0, "mae": 1, "huber": 2}    # SG_LOSS_* in include/stemgnn_hip.h
 # bits of stemgnn_block_paths (SG_PATH_* in include/stemgnn_hip.h)
 SG_PATH = {"glu_fwd_fused": 1, "glu_dgrad_fused": 2, "heads_fwd_fused": 4, "heads_bwd_fused": 8, "heads_bwd_16w": 16,
            "long_k": 32, "wgrad_fused": 64, "glu_wgrad_fused": 128}
@@ -105,6 +106,8 @@ SIGNATURES = {
     "stemgnn_normalize_series": (c_int, [_P, _P, _P, c_int, _P, c_long, c_int, _P]),
     "stemgnn_window_gather": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_long, _P, _P]),
     "stemgnn_window_gather_queue": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_long, _P, _P]),
+    "stemgnn_window_gather_pair": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_long, _P, _P]),
+    "stemgnn_window_gather_queue_pair": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_long, _P, _P]),
     "stemgnn_mse_scratch_floats": (c_size_t, []),
     "stemgnn_mse_fwd": (c_int, [_P, _P, c_size_t, _P, _P, _P, _P]),
     "stemgnn_mse_bwd": (c_int, [_P, _P, c_size_t, _P, _P, _P]),
@@ -113,6 +116,8 @@ SIGNATURES = {
     "stemgnn_eval_scratch_doubles": (c_size_t, [c_long, c_int, c_int]),
     "stemgnn_eval_out_doubles": (c_size_t, [c_int, c_int]),
     "stemgnn_eval_metrics": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, _P, _P, _P]),
+    "stemgnn_eval_scratch_doubles_masked": (c_size_t, [c_long, c_int, c_int]),
+    "stemgnn_eval_metrics_masked": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, _P, _P, _P]),
     "stemgnn_block_pack": (c_int, [_PP, _P, _P, c_int, c_int, _P]),
     "stemgnn_block_pack_panels": (c_int, [_PP, _P, _P, c_int, c_int, _P]),
     "stemgnn_block_unpack_grads": (c_int, [_P, c_int, _P, _PP, c_int, c_int, c_int, _P]),
@@ -138,6 +143,12 @@ SIGNATURES = {
                                       _P, _P]),
     "stemgnn_fc_tail_train_rows": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
     "stemgnn_fc_tail_train_finish": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "stemgnn_target_valid_count": (c_int, [_P, c_size_t, _P, _P]),
+    "stemgnn_fc_tail_train_loss": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, _P,
+                                           _P, _P, _P, _P, _P, _P, _P]),
+    "stemgnn_fc_tail_train_rows_loss": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P,
+                                                _P, _P]),
+    "stemgnn_fc_tail_train_finish_loss": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "stemgnn_infer_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
     "stemgnn_infer_workspace_split_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "stemgnn_gru_fwd_infer": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),

@@ -214,7 +214,8 @@ class Model(nn.Module):
         return SpectralHotPath.apply(h, x, self.weight_key, self.weight_query, self.multi_layer, self.alpha,
                                      self.dropout_rate, self.training, seed, hs, *params)
 
-    def loss(self, x, target, loss_out=None, accum=None, unit_grad=False, return_attention=False):
+    def loss(self, x, target, loss_out=None, accum=None, unit_grad=False, return_attention=False, *, kind="mse",
+             huber_delta=1.0, ignore_nan=False):
         """MSE training loss of one batch, ``nn.MSELoss()(self(x)[0], target)`` (models/handler.py:161-162), with the fc tail,
         the loss and both their backwards fused into one autograd node (two launches instead of five; forecast itself is
         not materialised).  `loss_out` / `accum`: optional static float32 scalar to write the loss into / float64 scalar
@@ -223,11 +224,20 @@ class Model(nn.Module):
         recording: a logging call under ``torch.no_grad()`` never touches ``p.grad``).  `return_attention`: return
         ``(loss, attention)`` from the same hot-path call -- attention [N,N] is differentiable, so a penalty on the learned
         graph rides on this fused node: ``torch.autograd.backward([loss, penalty], [one, one])`` (engine.TrainStep's
-        ``attention_penalty``) or ``(loss + penalty).backward()`` without `unit_grad`."""
+        ``attention_penalty``) or ``(loss + penalty).backward()`` without `unit_grad`.
+        `kind`: "mse" (default), "mae" (``nn.L1Loss``) or "huber" (``nn.HuberLoss(delta=huber_delta)``), all on the same fused
+        node.  `ignore_nan`: a NaN in `target` is a missing reading -- it contributes to neither the loss nor any gradient, and
+        the loss is the mean over the valid targets (0, with zero gradients, when there is none); one more launch
+        (``ops.target_valid_count``).  Only NaN means missing (+-inf does not), and a NaN *forecast* on a valid target still
+        propagates (the optimizers' ``skip_nonfinite`` is for that).  Data parallel: every rank normalises by its own count,
+        and the gradient all-reduce averages the ranks -- a mean of per-rank masked means."""
+        if kind not in _lib.SG_LOSS:
+            raise ValueError(f"unknown loss kind {kind!r}: one of {sorted(_lib.SG_LOSS)}")
         self._require_fc_tail()
         fsum, attention, _ = self.hot_path(x)
         loss = FcTailMse.apply(fsum, target, self.fc[0].weight, self.fc[0].bias, self.fc[2].weight, self.fc[2].bias,
-                               self.hot_state, loss_out, accum, bool(unit_grad) and torch.is_grad_enabled())
+                               self.hot_state, loss_out, accum, bool(unit_grad) and torch.is_grad_enabled(), kind,
+                               float(huber_delta) if kind == "huber" else 0.0, bool(ignore_nan))
         return (loss, attention) if return_attention else loss
 
     def _require_fc_tail(self):

@@ -46,8 +46,10 @@ extern "C" int stemgnn_normalize_series(const double* raw, const double* sub, co
 
 // ---------------------------------------------------------------------------------------------------------------
 // x[b,w,:] = series[hi[b]-W+w,:] (w<W), y[b,h,:] = series[hi[b]+h,:] (h<H).  One workgroup per (row of the slab, b).
-// Out-of-range rows (a bad index) set *status and write zeros instead of faulting.
-__global__ void sg_window_gather_kernel(const float* __restrict__ series, const long long* __restrict__ hi,
+// Out-of-range rows (a bad index) set *status and write zeros instead of faulting.  The y rows come from `series_y` (the same
+// shape; the series itself, or a copy of it that keeps its missing readings as NaN -- the _pair entries).
+__global__ void sg_window_gather_kernel(const float* __restrict__ series, const float* __restrict__ series_y,
+                                        const long long* __restrict__ hi,
                                         float* __restrict__ x, float* __restrict__ y, int W, int H, int N, long T,
                                         int* __restrict__ status) {
   const int r = blockIdx.x, b = blockIdx.y;
@@ -56,7 +58,7 @@ __global__ void sg_window_gather_kernel(const float* __restrict__ series, const 
   float* dst = r < W ? x + ((size_t)b * W + r) * N : y + ((size_t)b * H + (r - W)) * N;
   const bool ok = h0 - W >= 0 && h0 + H <= T;
   if (!ok && threadIdx.x == 0 && status) atomicOr(status, 1);
-  const float* src = series + (size_t)(ok ? t : 0) * N;
+  const float* src = (r < W ? series : series_y) + (size_t)(ok ? t : 0) * N;
   if ((N & 3) == 0) {
     const float4* s4 = reinterpret_cast<const float4*>(src);
     float4* d4 = reinterpret_cast<float4*>(dst);
@@ -66,15 +68,19 @@ __global__ void sg_window_gather_kernel(const float* __restrict__ series, const 
   }
 }
 
-extern "C" int stemgnn_window_gather(const float* series, const long long* hi, float* x, float* y, int B, int W, int H,
-                                     int N, long T, int* status, void* stream) {
-  if (!series || !hi || !x || !y || B <= 0 || W <= 0 || H < 0 || N <= 0 || T < (long)W + H) return SG_EINVAL;
-  if ((N & 3) == 0 && ((((uintptr_t)series | (uintptr_t)x | (uintptr_t)y) & 15) != 0)) return SG_EINVAL;
+extern "C" int stemgnn_window_gather_pair(const float* series_x, const float* series_y, const long long* hi, float* x,
+                                          float* y, int B, int W, int H, int N, long T, int* status, void* stream) {
+  if (!series_x || !series_y || !hi || !x || !y || B <= 0 || W <= 0 || H < 0 || N <= 0 || T < (long)W + H) return SG_EINVAL;
+  if ((N & 3) == 0 && ((((uintptr_t)series_x | (uintptr_t)series_y | (uintptr_t)x | (uintptr_t)y) & 15) != 0)) return SG_EINVAL;
   const int threads = N >= 1024 ? 256 : (N >= 256 ? 128 : 64);
-  hipLaunchKernelGGL(sg_window_gather_kernel, dim3(W + H, B), dim3(threads), 0, (hipStream_t)stream, series, hi, x, y,
-                     W, H, N, T, status);
+  hipLaunchKernelGGL(sg_window_gather_kernel, dim3(W + H, B), dim3(threads), 0, (hipStream_t)stream, series_x, series_y, hi,
+                     x, y, W, H, N, T, status);
   SG_TRY(hipGetLastError());
   return 0;
+}
+extern "C" int stemgnn_window_gather(const float* series, const long long* hi, float* x, float* y, int B, int W, int H,
+                                     int N, long T, int* status, void* stream) {
+  return stemgnn_window_gather_pair(series, series, hi, x, y, B, W, H, N, T, status, stream);
 }
 
 // Queue form of the gather (the DataLoader's iteration over one shuffled epoch, models/handler.py:136-138,157-159): the
@@ -84,7 +90,8 @@ extern "C" int stemgnn_window_gather(const float* series, const long long* hi, f
 // step).  A position past `count` writes zeros and sets bit 1 of *status.  q[3] != 0 selects WRAP mode: a position from
 // which no further full batch fits goes back to 0 (capture warm-ups and the schedule self-check of engine.TrainStep replay
 // the step many times over whatever the order buffer holds; training never sets it).
-__global__ void sg_window_gather_queue_kernel(const float* __restrict__ series, const long long* __restrict__ order,
+__global__ void sg_window_gather_queue_kernel(const float* __restrict__ series, const float* __restrict__ series_y,
+                                              const long long* __restrict__ order,
                                               long long* __restrict__ q, float* __restrict__ x, float* __restrict__ y,
                                               int W, int H, int N, long T, int rows_per_wg, int* __restrict__ status) {
   // few, larger workgroups (<= ~64: rows_per_wg slab rows of one batch element each), so that the arrival count costs
@@ -102,7 +109,7 @@ __global__ void sg_window_gather_queue_kernel(const float* __restrict__ series, 
   const int r0 = blockIdx.x * rows_per_wg, r1 = min(W + H, r0 + rows_per_wg);
   for (int r = r0; r < r1; ++r) {
     float* dst = r < W ? x + ((size_t)b * W + r) * N : y + ((size_t)b * H + (r - W)) * N;
-    const float* src = series + (size_t)(ok ? h0 - W + r : 0) * N;
+    const float* src = (r < W ? series : series_y) + (size_t)(ok ? h0 - W + r : 0) * N;
     if ((N & 3) == 0) {
       const float4* s4 = reinterpret_cast<const float4*>(src);
       float4* d4 = reinterpret_cast<float4*>(dst);
@@ -124,17 +131,23 @@ __global__ void sg_window_gather_queue_kernel(const float* __restrict__ series, 
   }
 }
 
-extern "C" int stemgnn_window_gather_queue(const float* series, const long long* order, long long* queue, float* x, float* y,
-                                           int B, int W, int H, int N, long T, int* status, void* stream) {
-  if (!series || !order || !queue || !x || !y || B <= 0 || W <= 0 || H < 0 || N <= 0 || T < (long)W + H) return SG_EINVAL;
-  if ((N & 3) == 0 && ((((uintptr_t)series | (uintptr_t)x | (uintptr_t)y) & 15) != 0)) return SG_EINVAL;
+extern "C" int stemgnn_window_gather_queue_pair(const float* series_x, const float* series_y, const long long* order,
+                                                long long* queue, float* x, float* y, int B, int W, int H, int N, long T,
+                                                int* status, void* stream) {
+  if (!series_x || !series_y || !order || !queue || !x || !y || B <= 0 || W <= 0 || H < 0 || N <= 0 || T < (long)W + H)
+    return SG_EINVAL;
+  if ((N & 3) == 0 && ((((uintptr_t)series_x | (uintptr_t)series_y | (uintptr_t)x | (uintptr_t)y) & 15) != 0)) return SG_EINVAL;
   const int threads = N >= 512 ? 256 : (N >= 128 ? 128 : 64);
   int rows_per_wg = ((W + H) * B + 63) / 64;
   if (rows_per_wg > W + H) rows_per_wg = W + H;
   hipLaunchKernelGGL(sg_window_gather_queue_kernel, dim3((W + H + rows_per_wg - 1) / rows_per_wg, B), dim3(threads), 0,
-                     (hipStream_t)stream, series, order, queue, x, y, W, H, N, T, rows_per_wg, status);
+                     (hipStream_t)stream, series_x, series_y, order, queue, x, y, W, H, N, T, rows_per_wg, status);
   SG_TRY(hipGetLastError());
   return 0;
+}
+extern "C" int stemgnn_window_gather_queue(const float* series, const long long* order, long long* queue, float* x, float* y,
+                                           int B, int W, int H, int N, long T, int* status, void* stream) {
+  return stemgnn_window_gather_queue_pair(series, series, order, queue, x, y, B, W, H, N, T, status, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -299,8 +312,11 @@ extern "C" int stemgnn_forecast_store(const float* forecast, const float* target
 // (numpy: `data * std + mean`).  Per element: ape = min?(|f-t|/|t| + 1e-5, 5) (NaN kept), ae = |f-t|, se = (f-t)^2.
 // Stage 1: column c = (h, n) sums over a chunk of `count`; stage 2: fixed-order chunk sum, then every axis variant:
 // out = overall[3] | by_node[3][N] | by_step[3][H] | by_step_node[3][H][N]   (each triple = mape, mae, rmse).
+// MASKED (stemgnn_eval_metrics_masked): an element whose target is NaN is skipped, a fourth plane of `part` / `colsum` counts
+// the elements kept per column, and every mean divides by its slice's count (a slice with none: 0 / 0 = NaN).
 constexpr int EVAL_CHUNK_ROWS = 64;
 
+template <bool MASKED>
 __global__ __launch_bounds__(256) void sg_eval_partial_kernel(const float* __restrict__ target,
                                                               const float* __restrict__ forecast,
                                                               const double* __restrict__ mul,
@@ -312,9 +328,13 @@ __global__ __launch_bounds__(256) void sg_eval_partial_kernel(const float* __res
   const long r1 = min(count, r0 + (long)EVAL_CHUNK_ROWS);
   const int n = c % N;
   const double mu = mul ? mul[n] : 1.0, ad = mul ? add[n] : 0.0;
-  double s_ape = 0.0, s_ae = 0.0, s_se = 0.0;
+  double s_ape = 0.0, s_ae = 0.0, s_se = 0.0, s_cnt = 0.0;
   for (long r = r0; r < r1; ++r) {
     double t = (double)target[(size_t)r * HN + c], f = (double)forecast[(size_t)r * HN + c];
+    if (MASKED) {
+      if (t != t) continue;
+      s_cnt += 1.0;                                               // a small integer: exact in fp64
+    }
     if (mul) {
       t = __dadd_rn(__dmul_rn(t, mu), ad);
       f = __dadd_rn(__dmul_rn(f, mu), ad);
@@ -331,16 +351,19 @@ __global__ __launch_bounds__(256) void sg_eval_partial_kernel(const float* __res
   part[((size_t)0 * nchunk + blockIdx.y) * HN + c] = s_ape;
   part[((size_t)1 * nchunk + blockIdx.y) * HN + c] = s_ae;
   part[((size_t)2 * nchunk + blockIdx.y) * HN + c] = s_se;
+  if (MASKED) part[((size_t)3 * nchunk + blockIdx.y) * HN + c] = s_cnt;
 }
 
 // one workgroup; thread-per-column chunk sums -> by_step_node sums in LDS-free global scratch (`colsum`), then the
 // coarser variants by fixed-order loops (H*N is a few thousand at most: this is a microsecond-scale epilogue)
+template <bool MASKED>
 __global__ __launch_bounds__(256) void sg_eval_final_kernel(const double* __restrict__ part, int nchunk, long count,
                                                             int H, int N, double* __restrict__ colsum,
                                                             double* __restrict__ out) {
   const int HN = H * N;
-  double* nodesum = colsum + (size_t)3 * HN;                      // [3][N]
-  for (int q = 0; q < 3; ++q)
+  constexpr int NQ = MASKED ? 4 : 3;                              // plane 3: the valid counts
+  double* nodesum = colsum + (size_t)NQ * HN;                     // [NQ][N]
+  for (int q = 0; q < NQ; ++q)
     for (int c = threadIdx.x; c < HN; c += blockDim.x) {
       double s = 0.0;
       for (int k = 0; k < nchunk; ++k) s += part[((size_t)q * nchunk + k) * HN + c];
@@ -352,31 +375,43 @@ __global__ __launch_bounds__(256) void sg_eval_final_kernel(const double* __rest
   double* by_step = by_node + 3 * (size_t)N;
   double* by_sn = by_step + 3 * (size_t)H;
   const double cnt = (double)count;
+  if (MASKED) {                                                   // the count plane's node sums, ahead of their readers
+    for (int n = threadIdx.x; n < N; n += blockDim.x) {
+      double s = 0.0;
+      for (int h = 0; h < H; ++h) s += colsum[(size_t)3 * HN + (size_t)h * N + n];
+      nodesum[(size_t)3 * N + n] = s;
+    }
+    __syncthreads();
+  }
   for (int q = 0; q < 3; ++q) {
     for (int c = threadIdx.x; c < HN; c += blockDim.x) {
-      const double m = colsum[(size_t)q * HN + c] / cnt;
+      const double m = colsum[(size_t)q * HN + c] / (MASKED ? colsum[(size_t)3 * HN + c] : cnt);
       by_sn[(size_t)q * HN + c] = q == 2 ? sqrt(m) : m;
     }
     for (int n = threadIdx.x; n < N; n += blockDim.x) {
       double s = 0.0;
       for (int h = 0; h < H; ++h) s += colsum[(size_t)q * HN + (size_t)h * N + n];
       nodesum[(size_t)q * N + n] = s;
-      const double m = s / (cnt * H);
+      const double m = s / (MASKED ? nodesum[(size_t)3 * N + n] : cnt * H);
       by_node[(size_t)q * N + n] = q == 2 ? sqrt(m) : m;
     }
     for (int h = threadIdx.x; h < H; h += blockDim.x) {
-      double s = 0.0;
+      double s = 0.0, k = 0.0;
       for (int n = 0; n < N; ++n) s += colsum[(size_t)q * HN + (size_t)h * N + n];
-      const double m = s / (cnt * N);
+      if (MASKED)
+        for (int n = 0; n < N; ++n) k += colsum[(size_t)3 * HN + (size_t)h * N + n];
+      const double m = s / (MASKED ? k : cnt * N);
       by_step[(size_t)q * H + h] = q == 2 ? sqrt(m) : m;
     }
   }
   __syncthreads();
   if (threadIdx.x < 3) {
     const int q = threadIdx.x;
-    double s = 0.0;
+    double s = 0.0, k = 0.0;
     for (int n = 0; n < N; ++n) s += nodesum[(size_t)q * N + n];
-    const double m = s / (cnt * HN);
+    if (MASKED)
+      for (int n = 0; n < N; ++n) k += nodesum[(size_t)3 * N + n];
+    const double m = s / (MASKED ? k : cnt * HN);
     overall[q] = q == 2 ? sqrt(m) : m;
   }
 }
@@ -392,19 +427,33 @@ extern "C" size_t stemgnn_eval_out_doubles(int H, int N) {
   return 3 + 3 * (size_t)N + 3 * (size_t)H + 3 * (size_t)H * N;
 }
 
-extern "C" int stemgnn_eval_metrics(const float* target, const float* forecast, const double* mul, const double* add,
-                                    long count, int H, int N, double* scratch, double* out, void* stream) {
+extern "C" size_t stemgnn_eval_scratch_doubles_masked(long count, int H, int N) {
+  if (count <= 0 || H <= 0 || N <= 0) return 0;
+  return (size_t)4 * H * N * ((size_t)eval_nchunk(count) + 1) + 4 * (size_t)N;
+}
+
+template <bool MASKED>
+static int eval_metrics_impl(const float* target, const float* forecast, const double* mul, const double* add, long count,
+                             int H, int N, double* scratch, double* out, void* stream) {
   if (!target || !forecast || !scratch || !out || count <= 0 || H <= 0 || N <= 0) return SG_EINVAL;
   if ((mul == nullptr) != (add == nullptr)) return SG_EINVAL;
   const int HN = H * N, nchunk = eval_nchunk(count);
   if (nchunk > 65535) return SG_EINVAL;
   double* part = scratch;
-  double* colsum = scratch + (size_t)3 * HN * nchunk;
-  hipLaunchKernelGGL(sg_eval_partial_kernel, dim3((HN + 255) / 256, nchunk), dim3(256), 0, (hipStream_t)stream, target,
-                     forecast, mul, add, count, HN, N, part);
+  double* colsum = scratch + (size_t)(MASKED ? 4 : 3) * HN * nchunk;
+  hipLaunchKernelGGL(sg_eval_partial_kernel<MASKED>, dim3((HN + 255) / 256, nchunk), dim3(256), 0, (hipStream_t)stream,
+                     target, forecast, mul, add, count, HN, N, part);
   SG_TRY(hipGetLastError());
-  hipLaunchKernelGGL(sg_eval_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, part, nchunk, count, H, N, colsum,
-                     out);
+  hipLaunchKernelGGL(sg_eval_final_kernel<MASKED>, dim3(1), dim3(256), 0, (hipStream_t)stream, part, nchunk, count, H, N,
+                     colsum, out);
   SG_TRY(hipGetLastError());
   return 0;
+}
+extern "C" int stemgnn_eval_metrics(const float* target, const float* forecast, const double* mul, const double* add,
+                                    long count, int H, int N, double* scratch, double* out, void* stream) {
+  return eval_metrics_impl<false>(target, forecast, mul, add, count, H, N, scratch, out, stream);
+}
+extern "C" int stemgnn_eval_metrics_masked(const float* target, const float* forecast, const double* mul, const double* add,
+                                           long count, int H, int N, double* scratch, double* out, void* stream) {
+  return eval_metrics_impl<true>(target, forecast, mul, add, count, H, N, scratch, out, stream);
 }

@@ -205,11 +205,20 @@ constexpr int TRAIN_RQ = 256 / TRAIN_RB;
 // gradient 2 (f - y) / n needs no global quantity, so nothing forces the five launches of the separate stages
 // (fc fwd, MSE, MSE bwd, fc bwd, reduce: 40 us at PEMS07).  Second launch: fixed-order sum of the per-block weight-gradient
 // and loss partials.  d(loss) upstream is taken as 1 (the driver calls loss.backward(), models/handler.py:164); the host
-// wrapper scales for any other value.  partial layout per block: dw0[W*W] | db0[W] | dw2[H*W] | db2[H] | sum (f - y)^2.
+// wrapper scales for any other value.  partial layout per block: dw0[W*W] | db0[W] | dw2[H*W] | db2[H] | sum of l(f - y).
+// KIND (SG_LOSS_*) picks the element loss l(d), d = f - y:  MSE d^2 | MAE |d| (derivative sign(d), 0 at 0) | Huber(param):
+// d^2 / 2 up to |d| = param, param (|d| - param / 2) beyond (derivative clamp(d, -param, param)).  MASKED: a NaN target is a
+// missing one -- its d is SELECTED to 0 (never multiplied), so it adds nothing to the loss or to any gradient whatever the
+// forecast holds there, and the normaliser is norm[1] = 1 / (valid targets) from stemgnn_target_valid_count (0 when there is
+// none: loss and gradients are then exactly 0).  <MSE, false> is the kernel as it was before the template, bit for bit.
+__device__ __forceinline__ bool sg_is_nan_bits(float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; }
+
+template <int KIND, bool MASKED>
 __global__ __launch_bounds__(256) void sg_fc_tail_train_kernel(const float* __restrict__ fsum, const float* __restrict__ target,
                                                                const float* __restrict__ w0, const float* __restrict__ b0,
                                                                const float* __restrict__ w2, const float* __restrict__ b2,
-                                                               int B, int N, int W, int H, float* __restrict__ forecast,
+                                                               int B, int N, int W, int H, float param,
+                                                               const float* __restrict__ norm, float* __restrict__ forecast,
                                                                float* __restrict__ dfsum, float* __restrict__ partial) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int nacc = W * W + W + H * W + H;
@@ -243,15 +252,32 @@ __global__ __launch_bounds__(256) void sg_fc_tail_train_kernel(const float* __re
   float sq = 0.f;
   {
     const int mc = m < M ? m : 0, b = mc / N, n = mc - b * N;
-    const float scale = 2.f / ((float)B * (float)H * (float)N);
+    float scale;                                         // d(loss)/d(l) of one element, times 2 for MSE (dl/dd = 2 d)
+    if constexpr (MASKED) scale = (KIND == SG_LOSS_MSE ? 2.f : 1.f) * norm[1];
+    else scale = (KIND == SG_LOSS_MSE ? 2.f : 1.f) / ((float)B * (float)H * (float)N);
     for (int h = q; h < H; h += TRAIN_RQ) {
       float y = sb2[h];
       for (int t = 0; t < W; ++t) y = fmaf(sa[r * (W + 1) + t], sw2[h * W + t], y);
       const size_t o = ((size_t)b * H + h) * N + n;
-      const float d = m < M ? y - target[o] : 0.f;
+      float d;
+      if constexpr (MASKED) {
+        const float tv = m < M ? target[o] : 0.f;
+        d = (m < M && !sg_is_nan_bits(tv)) ? y - tv : 0.f;
+      } else {
+        d = m < M ? y - target[o] : 0.f;
+      }
       if (m < M && forecast) forecast[o] = y;
-      sq = fmaf(d, d, sq);
-      sdy[r * (H + 1) + h] = d * scale;
+      if constexpr (KIND == SG_LOSS_MSE) {
+        sq = fmaf(d, d, sq);
+        sdy[r * (H + 1) + h] = d * scale;
+      } else if constexpr (KIND == SG_LOSS_MAE) {            // a NaN d (NaN forecast on a valid target) stays NaN in both
+        sq += fabsf(d);
+        sdy[r * (H + 1) + h] = d > 0.f ? scale : (d < 0.f ? -scale : d * scale);
+      } else {
+        const float a = fabsf(d);
+        sq += a > param ? param * (a - 0.5f * param) : 0.5f * d * d;
+        sdy[r * (H + 1) + h] = (a > param ? copysignf(param, d) : d) * scale;
+      }
     }
   }
   sred[tid] = sq;
@@ -291,7 +317,8 @@ __global__ __launch_bounds__(256) void sg_fc_tail_train_kernel(const float* __re
 }
 
 __global__ __launch_bounds__(256) void sg_fc_tail_train_reduce_kernel(const float* __restrict__ partial, int nblocks, int W,
-                                                                      int H, float inv_n, float* __restrict__ dw0,
+                                                                      int H, float inv_n, const float* __restrict__ norm,
+                                                                      float* __restrict__ dw0,
                                                                       float* __restrict__ db0, float* __restrict__ dw2,
                                                                       float* __restrict__ db2, float* __restrict__ loss,
                                                                       double* __restrict__ accum) {
@@ -320,7 +347,7 @@ __global__ __launch_bounds__(256) void sg_fc_tail_train_reduce_kernel(const floa
   else if (i < W * W + W + H * W) dw2[i - W * W - W] = s;
   else if (i < nacc) db2[i - W * W - W - H * W] = s;
   else {
-    const float l = s * inv_n;
+    const float l = s * (norm ? norm[1] : inv_n);          // masked: 1 / (valid targets), 0 when there is none
     loss[0] = l;
     if (accum) accum[0] += (double)l;
   }
@@ -332,27 +359,46 @@ static size_t fc_tail_train_lds(int W, int H) {
 extern "C" size_t stemgnn_fc_tail_train_scratch_floats(int B, int N, int W, int H) {
   return (size_t)((B * N + TRAIN_RB - 1) / TRAIN_RB) * (W * W + W + H * W + H + 1);
 }
+template <int KIND, bool MASKED>
+static int fc_tail_train_rows_launch(const float* fsum, const float* target, const float* w0, const float* b0, const float* w2,
+                                     const float* b2, int B, int N, int W, int H, float param, const float* norm,
+                                     float* scratch, float* forecast, float* dfsum, hipStream_t st) {
+  const size_t lds = fc_tail_train_lds(W, H);
+  static SgDynLds lds_guard;
+  SG_TRY(sg_ensure_dyn_lds((const void*)sg_fc_tail_train_kernel<KIND, MASKED>, lds, lds_guard));
+  hipLaunchKernelGGL((sg_fc_tail_train_kernel<KIND, MASKED>), dim3((B * N + TRAIN_RB - 1) / TRAIN_RB), dim3(256), lds, st, fsum,
+                     target, w0, b0, w2, b2, B, N, W, H, param, norm, forecast, dfsum, scratch);
+  SG_TRY(hipGetLastError());
+  return 0;
+}
+// parts: 1 = the per-row launch, 2 = the partial-sum launch.  norm == NULL: unmasked, normaliser B * H * N.
 static int fc_tail_train_impl(const float* fsum, const float* target, const float* w0, const float* b0, const float* w2,
-                              const float* b2, int B, int N, int W, int H, float* scratch, float* forecast, float* loss,
-                              double* loss_accum, float* dfsum, float* dw0, float* db0, float* dw2, float* db2, void* stream,
-                              int parts) {
+                              const float* b2, int B, int N, int W, int H, int kind, float param, const float* norm,
+                              float* scratch, float* forecast, float* loss, double* loss_accum, float* dfsum, float* dw0,
+                              float* db0, float* dw2, float* db2, void* stream, int parts) {
   if (!scratch || B <= 0 || N <= 0 || !stemgnn_fc_tail_supported(W, H) || fc_tail_train_lds(W, H) > 150 * 1024) return SG_EINVAL;
   if ((parts & 1) && (!fsum || !target || !w0 || !b0 || !w2 || !b2 || !dfsum)) return SG_EINVAL;
   if ((parts & 2) && (!loss || !dw0 || !db0 || !dw2 || !db2)) return SG_EINVAL;
+  if (parts & 1) {
+    if (kind != SG_LOSS_MSE && kind != SG_LOSS_MAE && kind != SG_LOSS_HUBER) return SG_EINVAL;
+    if (kind == SG_LOSS_HUBER && !(param > 0.f && param <= 3.402823466e+38f)) return SG_EINVAL;       // NaN fails both
+  }
   hipStream_t st = (hipStream_t)stream;
   const int nacc = W * W + W + H * W + H;
   const int nblocks = (B * N + TRAIN_RB - 1) / TRAIN_RB;
   if (parts & 1) {
-    const size_t lds = fc_tail_train_lds(W, H);
-    static SgDynLds lds_guard;
-    SG_TRY(sg_ensure_dyn_lds((const void*)sg_fc_tail_train_kernel, lds, lds_guard));
-    hipLaunchKernelGGL(sg_fc_tail_train_kernel, dim3(nblocks), dim3(256), lds, st, fsum, target, w0, b0, w2, b2, B, N, W, H,
-                       forecast, dfsum, scratch);
-    SG_TRY(hipGetLastError());
+    int rc;
+#define SG_TAIL_ROWS(K, MSK) \
+  rc = fc_tail_train_rows_launch<K, MSK>(fsum, target, w0, b0, w2, b2, B, N, W, H, param, norm, scratch, forecast, dfsum, st)
+    if (kind == SG_LOSS_MSE) { if (norm) SG_TAIL_ROWS(SG_LOSS_MSE, true); else SG_TAIL_ROWS(SG_LOSS_MSE, false); }
+    else if (kind == SG_LOSS_MAE) { if (norm) SG_TAIL_ROWS(SG_LOSS_MAE, true); else SG_TAIL_ROWS(SG_LOSS_MAE, false); }
+    else { if (norm) SG_TAIL_ROWS(SG_LOSS_HUBER, true); else SG_TAIL_ROWS(SG_LOSS_HUBER, false); }
+#undef SG_TAIL_ROWS
+    if (rc != 0) return rc;
   }
   if (parts & 2) {
     hipLaunchKernelGGL(sg_fc_tail_train_reduce_kernel, dim3((nacc + 1 + 63) / 64), dim3(256), 0, st, scratch, nblocks, W, H,
-                       1.f / ((float)B * (float)H * (float)N), dw0, db0, dw2, db2, loss, loss_accum);
+                       1.f / ((float)B * (float)H * (float)N), norm, dw0, db0, dw2, db2, loss, loss_accum);
     SG_TRY(hipGetLastError());
   }
   return 0;
@@ -361,8 +407,8 @@ extern "C" int stemgnn_fc_tail_train(const float* fsum, const float* target, con
                                      const float* b2, int B, int N, int W, int H, float* scratch, float* forecast,
                                      float* loss, double* loss_accum, float* dfsum, float* dw0, float* db0, float* dw2,
                                      float* db2, void* stream) {
-  return fc_tail_train_impl(fsum, target, w0, b0, w2, b2, B, N, W, H, scratch, forecast, loss, loss_accum, dfsum, dw0, db0, dw2,
-                            db2, stream, 3);
+  return fc_tail_train_impl(fsum, target, w0, b0, w2, b2, B, N, W, H, SG_LOSS_MSE, 0.f, nullptr, scratch, forecast, loss,
+                            loss_accum, dfsum, dw0, db0, dw2, db2, stream, 3);
 }
 // The two launches of stemgnn_fc_tail_train as separate calls (round 6): `_rows` is all the backward's chain needs (d(fsum));
 // `_finish` -- the fixed-order sum of the row blocks' partials into the loss and the fc gradients -- has no consumer before
@@ -371,13 +417,59 @@ extern "C" int stemgnn_fc_tail_train(const float* fsum, const float* target, con
 extern "C" int stemgnn_fc_tail_train_rows(const float* fsum, const float* target, const float* w0, const float* b0,
                                           const float* w2, const float* b2, int B, int N, int W, int H, float* scratch,
                                           float* forecast, float* dfsum, void* stream) {
-  return fc_tail_train_impl(fsum, target, w0, b0, w2, b2, B, N, W, H, scratch, forecast, nullptr, nullptr, dfsum, nullptr,
-                            nullptr, nullptr, nullptr, stream, 1);
+  return fc_tail_train_impl(fsum, target, w0, b0, w2, b2, B, N, W, H, SG_LOSS_MSE, 0.f, nullptr, scratch, forecast, nullptr,
+                            nullptr, dfsum, nullptr, nullptr, nullptr, nullptr, stream, 1);
 }
 extern "C" int stemgnn_fc_tail_train_finish(const float* scratch, int B, int N, int W, int H, float* loss, double* loss_accum,
                                             float* dw0, float* db0, float* dw2, float* db2, void* stream) {
-  return fc_tail_train_impl(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, N, W, H, const_cast<float*>(scratch),
-                            nullptr, loss, loss_accum, nullptr, dw0, db0, dw2, db2, stream, 2);
+  return fc_tail_train_impl(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, N, W, H, SG_LOSS_MSE, 0.f, nullptr,
+                            const_cast<float*>(scratch), nullptr, loss, loss_accum, nullptr, dw0, db0, dw2, db2, stream, 2);
+}
+
+// ---- the same tail with a choice of loss and missing-value masking --------------------------------------------------
+// norm = {count, 1 / count} of the valid (non-NaN) targets, written by ONE workgroup in one launch: an integer count per
+// thread, summed over the workgroup in a fixed tree -- exact and order-independent whatever the buffer held before.
+constexpr int COUNT_THREADS = 1024;
+__global__ __launch_bounds__(COUNT_THREADS) void sg_target_valid_count_kernel(const float* __restrict__ target, size_t n,
+                                                                             float* __restrict__ norm) {
+  __shared__ unsigned long long sm[COUNT_THREADS / 64];
+  unsigned long long c = 0;
+  for (size_t i = threadIdx.x; i < n; i += COUNT_THREADS) c += sg_is_nan_bits(target[i]) ? 0u : 1u;
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t = 0;
+    for (int i = 0; i < COUNT_THREADS / 64; ++i) t += sm[i];
+    norm[0] = (float)t;
+    norm[1] = t ? (float)(1.0 / (double)t) : 0.f;
+  }
+}
+extern "C" int stemgnn_target_valid_count(const float* target, size_t n, float* norm, void* stream) {
+  if (!target || !norm || n == 0) return SG_EINVAL;
+  hipLaunchKernelGGL(sg_target_valid_count_kernel, dim3(1), dim3(COUNT_THREADS), 0, (hipStream_t)stream, target, n, norm);
+  SG_TRY(hipGetLastError());
+  return 0;
+}
+extern "C" int stemgnn_fc_tail_train_loss(const float* fsum, const float* target, const float* w0, const float* b0,
+                                          const float* w2, const float* b2, int B, int N, int W, int H, int kind, float param,
+                                          const float* norm, float* scratch, float* forecast, float* loss, double* loss_accum,
+                                          float* dfsum, float* dw0, float* db0, float* dw2, float* db2, void* stream) {
+  return fc_tail_train_impl(fsum, target, w0, b0, w2, b2, B, N, W, H, kind, param, norm, scratch, forecast, loss, loss_accum,
+                            dfsum, dw0, db0, dw2, db2, stream, 3);
+}
+extern "C" int stemgnn_fc_tail_train_rows_loss(const float* fsum, const float* target, const float* w0, const float* b0,
+                                               const float* w2, const float* b2, int B, int N, int W, int H, int kind,
+                                               float param, const float* norm, float* scratch, float* forecast, float* dfsum,
+                                               void* stream) {
+  return fc_tail_train_impl(fsum, target, w0, b0, w2, b2, B, N, W, H, kind, param, norm, scratch, forecast, nullptr, nullptr,
+                            dfsum, nullptr, nullptr, nullptr, nullptr, stream, 1);
+}
+extern "C" int stemgnn_fc_tail_train_finish_loss(const float* scratch, int B, int N, int W, int H, const float* norm,
+                                                 float* loss, double* loss_accum, float* dw0, float* db0, float* dw2,
+                                                 float* db2, void* stream) {
+  return fc_tail_train_impl(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, N, W, H, SG_LOSS_MSE, 0.f, norm,
+                            const_cast<float*>(scratch), nullptr, loss, loss_accum, nullptr, dw0, db0, dw2, db2, stream, 2);
 }
 
 // ---- fused RMSprop over flat buffers ------------------------------------------------------------------------------

@@ -14,7 +14,7 @@ import time
 
 import torch
 
-from . import ops
+from . import _lib, ops
 from .distributed import FlatGradBucket
 
 
@@ -135,7 +135,8 @@ def _time_replays(replay, n=10):
 class TrainStep:
     def __init__(self, model, optimizer, batch_size, window_size, horizon, units, series=None, world=1, graph=True,
                  exact=False, group=None, collective=None, one_graph=None, order_capacity=0, collective_fn=None,
-                 schedule_check=None, attention_penalty=None):
+                 schedule_check=None, attention_penalty=None, loss="mse", huber_delta=1.0, ignore_nan=False,
+                 target_series=None):
         """order_capacity > 0 (with a resident `series`): the step takes its windows from a device-side queue of window-end
         rows (`load_order` once per epoch, `run_next` per step; stemgnn_window_gather_queue advances the position on the
         device), so a hipGraph replay is the whole per-step host work -- no index copy ahead of it.
@@ -163,7 +164,20 @@ class TrainStep:
         (``.item()``, ``.cpu()``, printing a value), no allocation that depends on values, the same operations every call;
         constants it uses (a prior matrix, a weight) must live on the device before the first step.  A penalty whose gradient
         is constant along the rows of the symmetrised attention (``attention.sum()``) has no effect without dropout: the rows of the
-        softmax sum to 1.  None (default): the step is exactly what it is without the argument."""
+        softmax sum to 1.  None (default): the step is exactly what it is without the argument.
+        loss / huber_delta / ignore_nan: Model.loss's `kind`, `huber_delta`, `ignore_nan` (needs a model with the fused
+        ``loss``).  target_series: [T,N] fp32 of the series' shape and device; the targets `y` are gathered from it instead of
+        from `series` (a copy that keeps missing readings as NaN while the inputs stay imputed).  Defaults: the step as it was."""
+        if loss not in _lib.SG_LOSS:
+            raise ValueError(f"unknown loss {loss!r}: one of {sorted(_lib.SG_LOSS)}")
+        self.loss_kw = {} if (loss == "mse" and not ignore_nan) else \
+            dict(kind=loss, huber_delta=float(huber_delta), ignore_nan=bool(ignore_nan))
+        if self.loss_kw and not hasattr(model, "loss"):
+            raise ValueError("loss / ignore_nan need a model with the fused Model.loss")
+        if target_series is not None and (series is None or target_series.shape != series.shape or
+                                          target_series.device != series.device):
+            raise ValueError("target_series must have the shape and device of `series`")
+        self.target_series = target_series
         self.model, self.opt = model, optimizer
         self.collective_fn = collective_fn
         self.collective = (world > 1) if collective is None else bool(collective)
@@ -251,9 +265,9 @@ class TrainStep:
             self.state.fork_event.record()
         if self.series is not None:
             if hi is None:
-                ops.window_gather_queue(self.series, self.order, self.queue, self.B, self.W, self.H, x, y)
+                ops.window_gather_queue(self.series, self.order, self.queue, self.B, self.W, self.H, x, y, self.target_series)
             else:
-                ops.window_gather(self.series, hi, self.W, self.H, x, y)
+                ops.window_gather(self.series, hi, self.W, self.H, x, y, self.target_series)
         if early:
             self.model.prefetch_side(self.device, batch=x.shape[0])
         if not self.fuse_zero:
@@ -266,9 +280,10 @@ class TrainStep:
         # MSE and both their backwards (it is this step that promises the upstream gradient of 1 below)
         attention = None
         if self.fuse_tail and self.attention_penalty is None:
-            loss = self.model.loss(x, y, self.loss.detach(), self.loss_sum, unit_grad=True)
+            loss = self.model.loss(x, y, self.loss.detach(), self.loss_sum, unit_grad=True, **self.loss_kw)
         elif self.fuse_tail:
-            loss, attention = self.model.loss(x, y, self.loss.detach(), self.loss_sum, unit_grad=True, return_attention=True)
+            loss, attention = self.model.loss(x, y, self.loss.detach(), self.loss_sum, unit_grad=True, return_attention=True,
+                                              **self.loss_kw)
         else:
             forecast, attention = self.model(x)
             loss = ops.mse_loss(forecast, y, self.loss.detach(), self.loss_sum)   # fresh alias: no history chaining
@@ -710,12 +725,17 @@ class ForecastStep:
         forecast, target = fs.result()     # rolling_forecast's format: [count, horizon, N] each
     """
 
-    def __init__(self, model, batch_size, window, horizon, series, order_capacity, graph=True):
+    def __init__(self, model, batch_size, window, horizon, series, order_capacity, graph=True, target_series=None):
+        """target_series: [T,N] fp32 of the series' shape and device; the result's targets come from it (missing readings kept
+        as NaN for the masked metrics) while the model's inputs come from `series`."""
         self.model = model
         self.B, self.W, self.horizon = int(batch_size), int(window), int(horizon)
         if series is None or series.dim() != 2:
             raise ValueError("ForecastStep needs the resident series [T, N]")
         self.series = series
+        if target_series is not None and (target_series.shape != series.shape or target_series.device != series.device):
+            raise ValueError("target_series must have the shape and device of `series`")
+        self.target_series = target_series
         self.N = int(series.shape[1])
         dev = series.device
         self.device = dev
@@ -750,7 +770,8 @@ class ForecastStep:
 
     def _body(self):
         self.pos.copy_(self.queue[:1])                  # device-side position before the gather advances it
-        ops.window_gather_queue(self.series, self.order, self.queue, self.B, self.W, self.horizon, self.x, self.y)
+        ops.window_gather_queue(self.series, self.order, self.queue, self.B, self.W, self.horizon, self.x, self.y,
+                                self.target_series)
         self._roll(self.x, self.steps)
         ops.forecast_store(self.steps, self.y, self.pos, self.out_forecast, self.out_target)
 
@@ -789,7 +810,7 @@ class ForecastStep:
         if left < self.B:
             p = self._done
             hi = self.order[p:p + left]
-            x, y = ops.window_gather(self.series, hi, self.W, self.horizon)
+            x, y = ops.window_gather(self.series, hi, self.W, self.horizon, target_series=self.target_series)
             steps = torch.empty(left, self.horizon, self.N, device=self.device)
             self._roll(x, steps)
             self.out_forecast[p:p + left].copy_(steps)

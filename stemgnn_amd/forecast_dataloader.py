@@ -35,6 +35,20 @@ def _fill_na(data):
     return out
 
 
+def mark_missing(data, missing=None):
+    """(data with its missing readings as NaN, their boolean mask) -- host.  missing=None: nothing is marked (data as a 2-D
+    float64 array, mask None).  Otherwise an entry is missing when it is NaN or equals `missing` (a float, e.g. 0.0: what
+    PEMS-type sets write for a dead sensor); `_fill_na` then imputes exactly those."""
+    data = np.array(data, dtype=np.float64, copy=True)
+    if data.ndim == 1:
+        data = data[:, None]
+    if missing is None:
+        return data, None
+    mask = np.isnan(data) | (data == float(missing))
+    data[mask] = np.nan
+    return data, mask
+
+
 def _stat_arrays(data, normalize_method, norm_statistic):
     """(sub, div, clip01, statistic) of normalized() (forecast_dataloader.py:7-22), float64 host arrays.
 
@@ -105,18 +119,27 @@ class ForecastDataset(torch.utils.data.Dataset):
     `.type(torch.float)` would produce row by row)."""
 
     def __init__(self, df, window_size, horizon, normalize_method=None, norm_statistic=None, interval=1,
-                 device="cuda"):
+                 device="cuda", missing=None):
+        """missing (a float, e.g. 0.0): raw NaN entries and entries equal to it are missing readings.  The inputs stay imputed
+        as without the argument (`_fill_na` over the marked array); `self.target` is the normalised series with NaN written
+        back at those positions (after normalisation: min_max clips), and `gather` takes `y` from it -- for the masked
+        losses and metrics.  None: `self.target` is None and nothing changes."""
         self.window_size = window_size
         self.interval = interval
         self.horizon = horizon
         self.normalize_method = normalize_method
         self.norm_statistic = norm_statistic
         self.device = _device(device)
-        host = _fill_na(np.asarray(df, dtype=np.float64))
+        marked, mask = mark_missing(np.asarray(df, dtype=np.float64), missing)
+        host = _fill_na(marked)
         self.df_length = len(host)
         self.x_end_idx = self.get_x_end_idx()
         self.data, _ = normalized(host, normalize_method, norm_statistic, device=self.device)
         self.hi_all = torch.tensor(self.x_end_idx, dtype=torch.int64, device=self.device)
+        self.target = None
+        if mask is not None:
+            self.target = self.data.clone()
+            self.target[torch.from_numpy(mask).to(self.device)] = float("nan")
 
     def get_x_end_idx(self):
         x_index_set = range(self.window_size, self.df_length - self.horizon + 1)
@@ -130,7 +153,7 @@ class ForecastDataset(torch.utils.data.Dataset):
         if not torch.is_tensor(indices):
             indices = torch.tensor(list(indices), dtype=torch.int64, device=self.device)
         hi = self.hi_all.index_select(0, indices)
-        return ops.window_gather(self.data, hi, self.window_size, self.horizon, x, y)
+        return ops.window_gather(self.data, hi, self.window_size, self.horizon, x, y, target_series=self.target)
 
     def __getitem__(self, index):
         if not -len(self) <= index < len(self):

@@ -19,13 +19,14 @@ def _as_f32(t, like=None):
 
 
 class Scores:
-    """All axis variants of (MAPE, MAE, RMSE) from one kernel pass."""
+    """All axis variants of (MAPE, MAE, RMSE) from one kernel pass.  ignore_nan: elements whose ground truth is NaN (missing
+    readings) are left out of every mean (`stemgnn_eval_metrics_masked`); a slice with none left is NaN."""
 
-    def __init__(self, y, y_hat, mul=None, add=None):
+    def __init__(self, y, y_hat, mul=None, add=None, ignore_nan=False):
         y_hat = _as_f32(y_hat)
         y = _as_f32(y, like=y_hat)
         C, H, N = y.shape
-        v = ops.eval_metrics(y, y_hat, mul, add).cpu().numpy()
+        v = ops.eval_metrics(y, y_hat, mul, add, ignore_nan=bool(ignore_nan)).cpu().numpy()
         self.overall = v[:3]
         o = 3
         self.by_node = v[o:o + 3 * N].reshape(3, N); o += 3 * N
@@ -44,9 +45,10 @@ class Scores:
         return m[0].copy(), m[1].copy(), m[2].copy()
 
 
-def evaluate(y, y_hat, by_step=False, by_node=False):
-    """utils/math_utils.py:59-74.  y: ground truth, y_hat: prediction, both [count, time_step, node] on the GPU."""
-    return Scores(y, y_hat).get(by_step, by_node)
+def evaluate(y, y_hat, by_step=False, by_node=False, ignore_nan=False):
+    """utils/math_utils.py:59-74.  y: ground truth, y_hat: prediction, both [count, time_step, node] on the GPU.
+    ignore_nan: leave the elements whose ground truth is NaN out of every mean."""
+    return Scores(y, y_hat, ignore_nan=ignore_nan).get(by_step, by_node)
 
 
 _AXES = {None: (False, False), 0: (True, True), (0, 2): (True, False), (0, 1): (False, True)}

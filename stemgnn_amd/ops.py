@@ -440,11 +440,18 @@ class FcTailMse(torch.autograd.Function):
     (models/handler.py:140,162) + both backwards, two launches (``stemgnn_fc_tail_train``).  forward returns the loss
     and already holds d(loss)/d(fsum) and the fc parameter gradients for an upstream gradient of 1 (``loss.backward()``,
     handler.py:164); backward hands them out (scaled by the upstream gradient unless ``unit_grad``).
-    (fsum [B,N,W], target [B,H,N], fc.0.weight, fc.0.bias, fc.2.weight, fc.2.bias) -> loss []."""
+    (fsum [B,N,W], target [B,H,N], fc.0.weight, fc.0.bias, fc.2.weight, fc.2.bias) -> loss [].
+    kind "mse" | "mae" | "huber" (param: Huber's delta) and ignore_nan (a NaN target is a missing one; the loss is the mean
+    over the valid targets, ``target_valid_count`` being one more launch ahead of the tail) go through the ``_loss`` entries
+    of the same kernels; with all three at their defaults the calls are the ones named above."""
 
     @staticmethod
-    def forward(ctx, fsum, target, w0, b0, w2, b2, state=None, loss_out=None, accum=None, unit_grad=False):
+    def forward(ctx, fsum, target, w0, b0, w2, b2, state=None, loss_out=None, accum=None, unit_grad=False, kind="mse",
+                param=0.0, ignore_nan=False):
         lib = _lib.load()
+        if kind not in _lib.SG_LOSS:
+            raise ValueError(f"unknown loss kind {kind!r}: one of {sorted(_lib.SG_LOSS)}")
+        plain = kind == "mse" and not ignore_nan           # today's entries
         ctx.state = _state(state)
         _require_gpu(fsum, "fsum")
         _require_gpu(target, "target")
@@ -470,25 +477,36 @@ class FcTailMse(torch.autograd.Function):
         scratch = torch.empty(lib.stemgnn_fc_tail_train_scratch_floats(B, N, W, H), device=dev, dtype=f32)
 
         acc_ptr = accum.data_ptr() if accum is not None else None
+        norm = target_valid_count(target) if ignore_nan else None
+        # one shared direct / deferred logic; only the three library calls differ between the plain and the `_loss` form
+        if plain:
+            rows_call, finish_call, both_call = (lib.stemgnn_fc_tail_train_rows, lib.stemgnn_fc_tail_train_finish,
+                                                 lib.stemgnn_fc_tail_train)
+            sel = fin_sel = ()
+        else:
+            rows_call, finish_call, both_call = (lib.stemgnn_fc_tail_train_rows_loss, lib.stemgnn_fc_tail_train_finish_loss,
+                                                 lib.stemgnn_fc_tail_train_loss)
+            norm_ptr = norm.data_ptr() if norm is not None else None
+            sel, fin_sel = (_lib.SG_LOSS[kind], float(param), norm_ptr), (norm_ptr,)
         # direct + unit_grad + side-stream mode: the step driver promises an immediate backward with an upstream gradient of 1
         # (engine.TrainStep) -> only the per-row launch runs here; the partial-sum launch (loss, fc gradients: no consumer
         # before the optimizer) is left for SpectralHotPath.backward to queue on the side branch (-10 us on the chain)
         defer = direct and ctx.state.overlap and ctx.state.tail_finish is None
         if defer:
-            _lib.check(lib.stemgnn_fc_tail_train_rows(
+            _lib.check(rows_call(
                 fsum.data_ptr(), target.data_ptr(), w0c.data_ptr(), b0c.data_ptr(), w2c.data_ptr(), b2c.data_ptr(), B, N, W, H,
-                scratch.data_ptr(), None, dfsum.data_ptr(), _stream()), "fc_tail_train_rows")
+                *sel, scratch.data_ptr(), None, dfsum.data_ptr(), _stream()), "fc_tail_train_rows")
             g0, g1, g2, g3 = grads
 
-            def finish(stream, scratch=scratch, loss=loss, g0=g0, g1=g1, g2=g2, g3=g3):
-                _lib.check(lib.stemgnn_fc_tail_train_finish(scratch.data_ptr(), B, N, W, H, loss.data_ptr(), acc_ptr, g0.data_ptr(),
-                                                            g1.data_ptr(), g2.data_ptr(), g3.data_ptr(), stream),
+            def finish(stream, scratch=scratch, loss=loss, g0=g0, g1=g1, g2=g2, g3=g3, norm=norm):   # norm: kept alive
+                _lib.check(finish_call(scratch.data_ptr(), B, N, W, H, *fin_sel, loss.data_ptr(), acc_ptr, g0.data_ptr(),
+                                       g1.data_ptr(), g2.data_ptr(), g3.data_ptr(), stream),
                            "fc_tail_train_finish")
             ctx.state.tail_finish = finish
         else:
-            _lib.check(lib.stemgnn_fc_tail_train(
+            _lib.check(both_call(
                 fsum.data_ptr(), target.data_ptr(), w0c.data_ptr(), b0c.data_ptr(), w2c.data_ptr(), b2c.data_ptr(), B, N, W, H,
-                scratch.data_ptr(), None, loss.data_ptr(), acc_ptr, dfsum.data_ptr(),
+                *sel, scratch.data_ptr(), None, loss.data_ptr(), acc_ptr, dfsum.data_ptr(),
                 grads[0].data_ptr(), grads[1].data_ptr(), grads[2].data_ptr(), grads[3].data_ptr(), _stream()), "fc_tail_train")
         # (the reduction of the per-block partials -- loss, fc gradients -- stays a launch of its own on this stream.  Measured
         # in round 4: on the side stream no gain (the cross-queue edge costs what the 9 us launch returns); as the job of the
@@ -513,8 +531,19 @@ class FcTailMse(torch.autograd.Function):
             if grads is not None:
                 grads = [g * grad_loss for g in grads]
         if grads is None:
-            return dfsum, None, None, None, None, None, None, None, None, None
-        return dfsum, None, grads[0], grads[1], grads[2], grads[3], None, None, None, None
+            return (dfsum,) + (None,) * 12
+        return (dfsum, None, grads[0], grads[1], grads[2], grads[3]) + (None,) * 7
+
+
+def target_valid_count(y):
+    """``stemgnn_target_valid_count``: float32[2] = {count, 1 / count (0 when count is 0)} of the non-NaN values of `y`, one
+    launch on the current stream, no host sync -- the normaliser the masked ``_loss`` entries read on the device."""
+    lib = _lib.load()
+    _require_gpu(y, "target")
+    y = y.contiguous()
+    norm = torch.empty(2, device=y.device, dtype=torch.float32)
+    _lib.check(lib.stemgnn_target_valid_count(y.data_ptr(), y.numel(), norm.data_ptr(), _stream()), "target_valid_count")
+    return norm
 
 
 class GluFn(torch.autograd.Function):
@@ -1263,8 +1292,15 @@ def normalize_series(raw, sub, div, clip01):
 _gather_status = {}
 
 
-def window_gather(series, hi, W, H, x=None, y=None):
-    """series [T,N] fp32 resident, hi [B] int64 (device): x[b] = series[hi-W:hi], y[b] = series[hi:hi+H]."""
+def _check_target_series(series, target_series, what):
+    _require_gpu(target_series, "target_series")
+    if target_series.shape != series.shape or target_series.device != series.device or not target_series.is_contiguous():
+        raise _lib.StemGNNHipError(f"{what}: target_series must be a contiguous [T,N] tensor of the series' shape and device")
+
+
+def window_gather(series, hi, W, H, x=None, y=None, target_series=None):
+    """series [T,N] fp32 resident, hi [B] int64 (device): x[b] = series[hi-W:hi], y[b] = series[hi:hi+H]; with
+    `target_series` (same shape) y[b] = target_series[hi:hi+H] instead (stemgnn_window_gather_pair)."""
     lib = _lib.load()
     _require_gpu(series, "series")
     if hi.dtype != torch.int64 or hi.device != series.device:
@@ -1279,14 +1315,20 @@ def window_gather(series, hi, W, H, x=None, y=None):
     st = _gather_status.get(key)
     if st is None:
         st = _gather_status[key] = torch.zeros(1, dtype=torch.int32, device=series.device)
+    if target_series is not None:
+        _check_target_series(series, target_series, "window_gather")
+        _lib.check(lib.stemgnn_window_gather_pair(series.data_ptr(), target_series.data_ptr(), hi.data_ptr(), x.data_ptr(),
+                                                  y.data_ptr(), B, W, H, N, T, st.data_ptr(), _stream()), "window_gather")
+        return x, y
     _lib.check(lib.stemgnn_window_gather(series.data_ptr(), hi.data_ptr(), x.data_ptr(), y.data_ptr(), B, W, H, N, T,
                                          st.data_ptr(), _stream()), "window_gather")
     return x, y
 
 
-def window_gather_queue(series, order, queue, B, W, H, x, y):
+def window_gather_queue(series, order, queue, B, W, H, x, y, target_series=None):
     """Iterator form (stemgnn_window_gather_queue): the next B windows of `order` (int64, device) at the device-side
-    position queue[0]; the kernel advances the position itself.  queue: int64[4] = {position, 0, count, -}."""
+    position queue[0]; the kernel advances the position itself.  queue: int64[4] = {position, 0, count, -}.
+    `target_series`: as in window_gather (stemgnn_window_gather_queue_pair)."""
     lib = _lib.load()
     _require_gpu(series, "series")
     for t, n in ((order, "order"), (queue, "queue")):
@@ -1297,6 +1339,12 @@ def window_gather_queue(series, order, queue, B, W, H, x, y):
     st = _gather_status.get(key)
     if st is None:
         st = _gather_status[key] = torch.zeros(1, dtype=torch.int32, device=series.device)
+    if target_series is not None:
+        _check_target_series(series, target_series, "window_gather_queue")
+        _lib.check(lib.stemgnn_window_gather_queue_pair(series.data_ptr(), target_series.data_ptr(), order.data_ptr(),
+                                                        queue.data_ptr(), x.data_ptr(), y.data_ptr(), B, W, H, N, T,
+                                                        st.data_ptr(), _stream()), "window_gather_queue")
+        return x, y
     _lib.check(lib.stemgnn_window_gather_queue(series.data_ptr(), order.data_ptr(), queue.data_ptr(), x.data_ptr(),
                                                y.data_ptr(), B, W, H, N, T, st.data_ptr(), _stream()), "window_gather_queue")
     return x, y
@@ -1330,9 +1378,11 @@ def roll_window(inputs, forecast, forecast_steps, step, horizon):
     return nxt
 
 
-def eval_metrics(target, forecast, mul=None, add=None):
+def eval_metrics(target, forecast, mul=None, add=None, ignore_nan=False):
     """target / forecast [count,H,N] fp32 -> float64 device vector
-    overall[3] | by_node[3][N] | by_step[3][H] | by_step_node[3][H][N]  (MAPE, MAE, RMSE each)."""
+    overall[3] | by_node[3][N] | by_step[3][H] | by_step_node[3][H][N]  (MAPE, MAE, RMSE each).
+    ignore_nan: elements whose target is NaN are left out and every mean divides by its slice's valid count
+    (stemgnn_eval_metrics_masked; a slice with no valid element is NaN)."""
     lib = _lib.load()
     _require_gpu(target, "target")
     _require_gpu(forecast, "forecast")
@@ -1341,13 +1391,14 @@ def eval_metrics(target, forecast, mul=None, add=None):
     target, forecast = target.contiguous(), forecast.contiguous()
     C, H, N = target.shape
     dev = target.device
-    scratch = torch.empty(lib.stemgnn_eval_scratch_doubles(C, H, N), device=dev, dtype=torch.float64)
+    sizer, entry = (lib.stemgnn_eval_scratch_doubles_masked, lib.stemgnn_eval_metrics_masked) if ignore_nan else \
+        (lib.stemgnn_eval_scratch_doubles, lib.stemgnn_eval_metrics)
+    scratch = torch.empty(sizer(C, H, N), device=dev, dtype=torch.float64)
     out = torch.empty(lib.stemgnn_eval_out_doubles(H, N), device=dev, dtype=torch.float64)
     if mul is not None:
         mul = mul.to(device=dev, dtype=torch.float64).contiguous()
         add = add.to(device=dev, dtype=torch.float64).contiguous()
-    _lib.check(lib.stemgnn_eval_metrics(target.data_ptr(), forecast.data_ptr(),
-                                        mul.data_ptr() if mul is not None else None,
-                                        add.data_ptr() if add is not None else None,
-                                        C, H, N, scratch.data_ptr(), out.data_ptr(), _stream()), "eval_metrics")
+    _lib.check(entry(target.data_ptr(), forecast.data_ptr(), mul.data_ptr() if mul is not None else None,
+                     add.data_ptr() if add is not None else None, C, H, N, scratch.data_ptr(), out.data_ptr(), _stream()),
+               "eval_metrics")
     return out

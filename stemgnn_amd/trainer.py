@@ -27,7 +27,7 @@ import torch
 from . import ops
 from .base_model import Model
 from .engine import ForecastStep, TrainStep
-from .forecast_dataloader import ForecastDataset, WindowLoader, denorm_coefficients
+from .forecast_dataloader import ForecastDataset, WindowLoader, denorm_coefficients, mark_missing
 from .math_utils import Scores
 from .optim import FusedAdam, FusedRMSprop
 
@@ -91,16 +91,17 @@ def rolling_forecast_graph(model, dataset, horizon, batch_size):
     return step.result()
 
 
-def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=None):
+def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=None, ignore_nan=False):
     """Metrics of a rolling forecast in raw units (and normalised units under ``*_norm``).  With `dump_dir`, the first
-    forecast step of every window is written as CSV (target / predict / absolute error / absolute percentage error)."""
+    forecast step of every window is written as CSV (target / predict / absolute error / absolute percentage error).
+    ignore_nan: NaN targets (missing readings) are left out of every metric; the CSV files keep them as NaN."""
     mul = add = None
     if norm_method and statistic:
         mul, add = denorm_coefficients(norm_method, statistic, forecast.device)
-    raw = Scores(target, forecast, mul, add)
+    raw = Scores(target, forecast, mul, add, ignore_nan=ignore_nan)
     (mape, mae, rmse), (mape_n, mae_n, rmse_n) = raw.get(), raw.get(by_node=True)
     out = dict(mae=mae, mape=mape, rmse=rmse, mae_node=mae_n, mape_node=mape_n, rmse_node=rmse_n)
-    normed = Scores(target, forecast).get() if mul is not None else (mape, mae, rmse)
+    normed = Scores(target, forecast, ignore_nan=ignore_nan).get() if mul is not None else (mape, mae, rmse)
     out.update(mape_norm=normed[0], mae_norm=normed[1], rmse_norm=normed[2])
     if dump_dir is not None:
         d = pathlib.Path(dump_dir)
@@ -117,12 +118,17 @@ def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=
     return out
 
 
-def column_statistics(series, norm_method):
+def column_statistics(series, norm_method, missing=None):
+    """missing (see ForecastDataset): the statistics are taken over the valid entries of every column only."""
     series = np.asarray(series)
+    mean, std, lo, hi = np.mean, np.std, np.min, np.max
+    if missing is not None:
+        series, _ = mark_missing(series, missing)
+        mean, std, lo, hi = np.nanmean, np.nanstd, np.nanmin, np.nanmax
     if norm_method == "z_score":
-        return {"mean": series.mean(axis=0).tolist(), "std": series.std(axis=0).tolist()}
+        return {"mean": mean(series, axis=0).tolist(), "std": std(series, axis=0).tolist()}
     if norm_method == "min_max":
-        return {"min": series.min(axis=0).tolist(), "max": series.max(axis=0).tolist()}
+        return {"min": lo(series, axis=0).tolist(), "max": hi(series, axis=0).tolist()}
     return None
 
 
@@ -131,10 +137,15 @@ class DeviceTrainer:
 
     def __init__(self, units, window, horizon, multi, *, batch_size=32, lr=1e-4, optimizer="RMSProp", decay_rate=0.5,
                  decay_every=5, norm_method="z_score", device="cuda", model_factory=None, hipgraph=True,
-                 dropout_seed=None, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False):
+                 dropout_seed=None, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False, loss="mse", huber_delta=1.0,
+                 missing=None):
+        """loss / huber_delta: the training loss of engine.TrainStep ("mse" | "mae" | "huber").  missing (a float, e.g. 0.0):
+        raw NaN entries and entries equal to it are missing readings -- left out of the column statistics, the training loss
+        and the validation metrics, while the model's inputs stay imputed (ForecastDataset)."""
         self.units, self.window, self.horizon, self.multi = units, window, horizon, multi
         self.batch_size, self.norm_method, self.device, self.hipgraph = batch_size, norm_method, device, hipgraph
         self.decay_every = decay_every
+        self.loss, self.huber_delta, self.missing = loss, huber_delta, missing
         self.model = (model_factory or Model)(units, 2, window, multi, horizon=horizon)
         self.model.to(device)
         if dropout_seed is not None and hasattr(self.model, "set_dropout_seed"):
@@ -154,11 +165,12 @@ class DeviceTrainer:
 
     def _dataset(self, series):
         return ForecastDataset(series, window_size=self.window, horizon=self.horizon, normalize_method=self.norm_method,
-                               norm_statistic=self.statistic, device=self.device)
+                               norm_statistic=self.statistic, device=self.device, missing=self.missing)
 
     def validate(self, loader, dump_dir=None):
         forecast, target = rolling_forecast(self.model, loader, self.horizon)
-        return score_forecast(forecast, target, self.norm_method, self.statistic, dump_dir)
+        return score_forecast(forecast, target, self.norm_method, self.statistic, dump_dir,
+                              ignore_nan=self.missing is not None)
 
     def fit(self, train_series, valid_series, epochs, *, validate_every=1, patience=None, out_dir=None, on_step=None,
             on_validate=None, log=print):
@@ -166,7 +178,7 @@ class DeviceTrainer:
             raise Exception("Cannot organize enough training data")
         if len(valid_series) == 0:
             raise Exception("Cannot organize enough validation data")
-        self.statistic = column_statistics(train_series, self.norm_method)
+        self.statistic = column_statistics(train_series, self.norm_method, self.missing)
         if out_dir is not None and self.statistic is not None:
             pathlib.Path(out_dir).mkdir(parents=True, exist_ok=True)
             (pathlib.Path(out_dir) / "norm_stat.json").write_text(json.dumps(self.statistic))
@@ -175,7 +187,9 @@ class DeviceTrainer:
         valid_loader = WindowLoader(valid_set, batch_size=self.batch_size, shuffle=False)
         log(f"trainable parameters: {sum(p.numel() for p in self.model.parameters() if p.requires_grad)}")
         self.stepper = TrainStep(self.model, self.optimizer, self.batch_size, self.window, self.horizon, self.units,
-                                 series=train_set.data, graph=self.hipgraph, order_capacity=len(train_set))
+                                 series=train_set.data, graph=self.hipgraph, order_capacity=len(train_set), loss=self.loss,
+                                 huber_delta=self.huber_delta, ignore_nan=self.missing is not None,
+                                 target_series=train_set.target)
         best, stale, metrics = float("inf"), 0, {}
         for epoch in range(epochs):
             t0 = time.time()
@@ -236,7 +250,8 @@ def train(train_data, valid_data, args, result_file, model_factory=None, on_step
                             decay_every=args.exponential_decay_step, norm_method=args.norm_method, device=args.device,
                             model_factory=model_factory, hipgraph=getattr(args, "hipgraph", True),
                             weight_decay=getattr(args, "weight_decay", 0.0), max_grad_norm=getattr(args, "max_grad_norm", None),
-                            skip_nonfinite=getattr(args, "skip_nonfinite", False))
+                            skip_nonfinite=getattr(args, "skip_nonfinite", False), loss=getattr(args, "loss", "mse"),
+                            huber_delta=getattr(args, "huber_delta", 1.0), missing=getattr(args, "missing", None))
     patience = getattr(args, "early_stop_step", 10) if getattr(args, "early_stop", False) else None
     return trainer.fit(train_data, valid_data, args.epoch, validate_every=args.validate_freq, patience=patience,
                        out_dir=result_file, on_step=on_step, on_validate=on_validate)
