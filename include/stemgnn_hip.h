@@ -105,6 +105,32 @@ int stemgnn_cheb_fwd(float* mul_L, int N, void* stream);
 /* dmul_L [4,N,N] gradient of all four slots (slot 0 ignored) -> dL [N,N]; scratch 2*N*N floats. */
 int stemgnn_cheb_bwd(const float* mul_L, const float* dmul_L, float* dL, float* scratch, int N, void* stream);
 
+/* ---- frozen / user-supplied graphs: the spectral basis from a given adjacency, without the GRU + attention front --------
+ * A        [N,N]  un-symmetrised adjacency (what the model has after the batch mean, models/base_model.py:140), fp32 row-major
+ * deg      [N]    its degrees (:141).  A graph taken from the model carries the degrees the model computed (the fused front sums
+ *                 them in another order than a row sum of A); a free adjacency gets them from stemgnn_graph_degree.
+ * All entries: one launch each (stemgnn_graph_basis_bwd: one), no memset node, no host sync -- graph-capturable; SG_EINVAL
+ * before anything is launched for a NULL pointer or N <= 0 (n == 0, w <= 0, wsum <= 0).
+ *
+ * stemgnn_graph_degree: deg[i] = sum_j A[i][j], one wave per row, fixed order (independent of the launch geometry). */
+int stemgnn_graph_degree(const float* A, int N, float* deg, void* stream);
+/* (A, deg) -> attention_out [N,N] = 0.5 (A + A^T) and mul_L slots 0 (zeros) and 1 (L, :144-147): part 2 of
+ * stemgnn_attn_laplacian_fwd as a call of its own (the same kernel, the same bits).  The caller runs stemgnn_cheb_fwd or
+ * stemgnn_eigh_fwd on mul_L afterwards, as behind stemgnn_attn_laplacian_fwd. */
+int stemgnn_graph_basis_fwd(const float* A, const float* deg, float* attention_out, float* mul_L, int N, void* stream);
+/* Adjoint of the above w.r.t. A for deg = row sums of A: dL [N,N] = gradient of mul_L slot 1 (total, from stemgnn_cheb_bwd),
+ * dA_ext [N,N] = gradient of attention_out; dA [N,N] out.  The degree term is always on (a free adjacency has no softmax behind
+ * it to annihilate a row-constant gradient).  dL == NULL: dA = (dA_ext + dA_ext^T) / 2; dA_ext == NULL: the Laplacian's share
+ * alone; both NULL: SG_EINVAL (the semantics of stemgnn_attn_laplacian_bwd_ext with B = 1).  For a STORED degree (a constant
+ * of the graph) this is not the gradient: the caller decides. */
+int stemgnn_graph_basis_bwd(const float* dL, const float* dA_ext, const float* A, const float* deg, float* dA, int N,
+                            void* stream);
+/* Running weighted mean of n floats (A | deg of one batch's graph) in fp64: acc[e] += w * v[e] (init != 0: acc[e] = w * v[e],
+ * acc need not be cleared), then out[e] = (float)(acc[e] / wsum).  One thread per element and no atomics: the result depends
+ * on the order of the calls alone. */
+int stemgnn_graph_accumulate(const float* v, double w, double* acc, size_t n, int init, void* stream);
+int stemgnn_graph_finish(const double* acc, double wsum, float* out, size_t n, void* stream);
+
 /* ---- Laplacian eigendecomposition route (north-star; same function of L as stemgnn_cheb_fwd) --------
  * Symmetric N x N eigensolver L = U^T diag(lam) U, then slot k := sum_e p_k(lam_e) u_e u_e^T for k = 2,3 with
  * p = (2 l^2, 4 l^3 - l) (slot 0 = zeros and slot 1 = L are left as attn_laplacian_fwd wrote them).

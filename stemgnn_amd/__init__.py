@@ -6,6 +6,7 @@ The product path is hand-written HIP behind a C ABI (``include/stemgnn_hip.h`` -
 fallback: calling the model without the HIP library or on a non-GPU tensor raises.
 """
 from .base_model import GLU, Model, StockBlockLayer  # noqa: F401
+from .graph import LatentGraph  # noqa: F401
 
-__all__ = ["Model", "StockBlockLayer", "GLU"]
+__all__ = ["Model", "StockBlockLayer", "GLU", "LatentGraph"]
 __version__ = "0.1.0"

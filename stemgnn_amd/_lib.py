@@ -4,7 +4,7 @@ Fails loudly: a missing / unloadable library raises at first use -- there is no 
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_long, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STEMGNN_HIP_LIB", os.path.join(_HERE, "libstemgnn_hip.so"))   # override: A/B builds only
@@ -55,6 +55,11 @@ SIGNATURES = {
     "stemgnn_dropout_seed_next": (c_int, [_P, _P, _P]),
     "stemgnn_cheb_fwd": (c_int, [_P, c_int, _P]),
     "stemgnn_cheb_bwd": (c_int, [_P, _P, _P, _P, c_int, _P]),
+    "stemgnn_graph_degree": (c_int, [_P, c_int, _P, _P]),
+    "stemgnn_graph_basis_fwd": (c_int, [_P, _P, _P, _P, c_int, _P]),
+    "stemgnn_graph_basis_bwd": (c_int, [_P, _P, _P, _P, _P, c_int, _P]),
+    "stemgnn_graph_accumulate": (c_int, [_P, c_double, _P, c_size_t, c_int, _P]),
+    "stemgnn_graph_finish": (c_int, [_P, c_double, _P, c_size_t, _P]),
     "stemgnn_eigh_scratch_floats": (c_size_t, [c_int]),
     "stemgnn_eigh_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, _P]),
     "stemgnn_eigh_batched": (c_int, [_P, _P, _P, _P, c_int, c_int, _P]),

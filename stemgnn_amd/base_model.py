@@ -214,8 +214,77 @@ class Model(nn.Module):
         return SpectralHotPath.apply(h, x, self.weight_key, self.weight_query, self.multi_layer, self.alpha,
                                      self.dropout_rate, self.training, seed, hs, *params)
 
+    def _check_input(self, x):
+        if not x.is_cuda:
+            raise _lib.StemGNNHipError(
+                f"input is on {x.device}: stemgnn_amd.Model runs only on a HIP device (no CPU fallback)")
+        if self.stack_cnt > 2:        # the reference's failures for other stack counts, as in hot_path
+            raise AttributeError("'NoneType' object has no attribute 'unsqueeze'")
+        if self.stack_cnt < 2:
+            raise IndexError("list index out of range")
+
+    def graph_path(self, x, adjacency):
+        """The model from a GIVEN graph (`adjacency`: a graph.LatentGraph, or a raw [N,N] float32 tensor = a free adjacency
+        whose degrees are its row sums, differentiable): no GRU, no attention.  mul_L comes from the graph (graph.resolve_basis),
+        block 0 runs as ops.StockBlockFn on x [B,N,W], block 1 on block 0's backcast (:169-174).  Returns (block forecast sum
+        [B,N,W], attention [N,N] = 0.5 (A + A^T)).  GRU.*, weight_key and weight_query take no part and get no gradient (None);
+        there is no dropout (the reference's only dropout is on the computed attention), so train and eval coincide; x gets its
+        gradient through block 0.  The GLU layers run in exact fp32 whatever STEMGNN_DTYPE says (StockBlockFn has no
+        split-bf16 form; Model.predict(x, adjacency=) does honour it)."""
+        from .graph import resolve_basis
+        self._check_input(x)
+        attention, mul_L = resolve_basis(adjacency, x.device)
+        if mul_L.shape[1] != x.shape[2]:
+            raise _lib.StemGNNHipError(f"adjacency is [{mul_L.shape[1]},{mul_L.shape[1]}] but x has {x.shape[2]} nodes")
+        X0 = x.permute(0, 2, 1).contiguous()                  # :169  [B,N,W]
+        f0, backcast = StockBlockFn.apply(X0, mul_L, self.multi_layer, True, *self.stock_block[0].hip_params())
+        f1, _ = StockBlockFn.apply(backcast, mul_L, self.multi_layer, False, *self.stock_block[1].hip_params())
+        return f0 + f1, attention                             # :174
+
+    def latent_graph(self, x):
+        """The graph the model itself computes for the batch x [B,W,N] in eval mode, as a graph.LatentGraph: A (the batch-mean
+        attention ahead of the symmetrisation) and the degrees of the fused front, copied out of the attention kernels' saved
+        buffer.  ``self.predict(x, adjacency=self.latent_graph(x))`` returns exactly the bits of ``self.predict(x)``, forecast and
+        attention.  Like predict it neither reads nor changes the training state."""
+        from .graph import LatentGraph
+        N = self.unit
+        buf = self._latent_adjacency(x).clone()
+        return LatentGraph(buf[:N * N].view(N, N), buf[N * N:])
+
+    def _latent_adjacency(self, x):
+        self._check_input(x)
+        g = self.GRU
+        with torch.no_grad():
+            return ops.latent_adjacency(x, (g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0), self.weight_key,
+                                        self.weight_query, self.alpha, self.dropout_rate)
+
+    def average_graph(self, batches):
+        """The batch-size-weighted mean of latent_graph over a data set: `batches` yields x [B,W,N] (or (x, ...) tuples, as a
+        loader does).  A | deg of every batch is added into an fp64 accumulator on the device (``stemgnn_graph_accumulate``,
+        weight B) and divided once at the end (``stemgnn_graph_finish``): no host sync per batch, no atomics, the same bits
+        on every run."""
+        from .graph import LatentGraph
+        lib = _lib.load()
+        N, n = self.unit, self.unit * self.unit + self.unit
+        acc, wsum = None, 0
+        for item in batches:
+            x = item[0] if isinstance(item, (tuple, list)) else item
+            v = self._latent_adjacency(x)
+            st = torch.cuda.current_stream(x.device).cuda_stream
+            if acc is None:
+                acc = torch.empty(n, device=x.device, dtype=torch.float64)
+            _lib.check(lib.stemgnn_graph_accumulate(v.data_ptr(), float(x.shape[0]), acc.data_ptr(), n, int(wsum == 0), st),
+                       "graph_accumulate")
+            wsum += int(x.shape[0])
+        if acc is None:
+            raise ValueError("average_graph: no batch")
+        out = torch.empty(n, device=acc.device, dtype=torch.float32)
+        _lib.check(lib.stemgnn_graph_finish(acc.data_ptr(), float(wsum), out.data_ptr(), n,
+                                            torch.cuda.current_stream(acc.device).cuda_stream), "graph_finish")
+        return LatentGraph(out[:N * N].view(N, N), out[N * N:])
+
     def loss(self, x, target, loss_out=None, accum=None, unit_grad=False, return_attention=False, *, kind="mse",
-             huber_delta=1.0, ignore_nan=False):
+             huber_delta=1.0, ignore_nan=False, adjacency=None):
         """MSE training loss of one batch, ``nn.MSELoss()(self(x)[0], target)`` (models/handler.py:161-162), with the fc tail,
         the loss and both their backwards fused into one autograd node (two launches instead of five; forecast itself is
         not materialised).  `loss_out` / `accum`: optional static float32 scalar to write the loss into / float64 scalar
@@ -230,14 +299,23 @@ class Model(nn.Module):
         the loss is the mean over the valid targets (0, with zero gradients, when there is none); one more launch
         (``ops.target_valid_count``).  Only NaN means missing (+-inf does not), and a NaN *forecast* on a valid target still
         propagates (the optimizers' ``skip_nonfinite`` is for that).  Data parallel: every rank normalises by its own count,
-        and the gradient all-reduce averages the ranks -- a mean of per-rank masked means."""
+        and the gradient all-reduce averages the ranks -- a mean of per-rank masked means.
+        `adjacency`: run from a given graph instead of the GRU + attention front (graph_path: no gradient for GRU / key / query,
+        exact-fp32 GLU layers); the fused tail then runs both its launches in place -- nothing is left for a later backward."""
         if kind not in _lib.SG_LOSS:
             raise ValueError(f"unknown loss kind {kind!r}: one of {sorted(_lib.SG_LOSS)}")
         self._require_fc_tail()
-        fsum, attention, _ = self.hot_path(x)
-        loss = FcTailMse.apply(fsum, target, self.fc[0].weight, self.fc[0].bias, self.fc[2].weight, self.fc[2].bias,
-                               self.hot_state, loss_out, accum, bool(unit_grad) and torch.is_grad_enabled(), kind,
-                               float(huber_delta) if kind == "huber" else 0.0, bool(ignore_nan))
+        if adjacency is None:
+            fsum, attention, _ = self.hot_path(x)
+        else:
+            fsum, attention = self.graph_path(x, adjacency)
+        self.hot_state.tail_may_defer = adjacency is None
+        try:
+            loss = FcTailMse.apply(fsum, target, self.fc[0].weight, self.fc[0].bias, self.fc[2].weight, self.fc[2].bias,
+                                   self.hot_state, loss_out, accum, bool(unit_grad) and torch.is_grad_enabled(), kind,
+                                   float(huber_delta) if kind == "huber" else 0.0, bool(ignore_nan))
+        finally:
+            self.hot_state.tail_may_defer = True
         return (loss, attention) if return_attention else loss
 
     def _require_fc_tail(self):
@@ -247,31 +325,33 @@ class Model(nn.Module):
             raise _lib.StemGNNHipError(f"fc tail: time_step={self.time_step}, horizon={self.horizon} outside the HIP kernels' "
                                        "range (time_step <= 64, horizon <= 32); stemgnn_amd has no torch fallback")
 
-    def predict(self, x):
+    def predict(self, x, adjacency=None):
         """Inference forward: ``(forecast [B,H,N], attention [N,N])``, bit-identical to ``self.eval(); self(x)`` under
         ``torch.no_grad()``, with nothing stored for a backward pass (ops.forecast_forward: the _infer kernels of
         include/stemgnn_hip.h).  Eval semantics whatever ``self.training`` is (no dropout); ``self.training``, the dropout
         stream and ``self.hot_state`` are neither read nor changed, so a call between two training steps leaves training
         bit for bit as it was.  The weights are packed on every call (FusedRMSprop writes parameters through raw pointers:
-        a cache keyed on torch's version counters would not see it)."""
+        a cache keyed on torch's version counters would not see it).
+        `adjacency` (a graph.LatentGraph or an [N,N] tensor): the GRU and the attention are skipped, mul_L comes from the graph
+        (cached inside a LatentGraph); the forecast of a window then no longer depends on the other windows of its batch.
+        STEMGNN_DTYPE applies as without it.  Returns (forecast, 0.5 (A + A^T))."""
         self._require_fc_tail()
-        if not x.is_cuda:
-            raise _lib.StemGNNHipError(
-                f"input is on {x.device}: stemgnn_amd.Model runs only on a HIP device (no CPU fallback)")
-        if self.stack_cnt > 2:        # the reference's failures for other stack counts, as in hot_path
-            raise AttributeError("'NoneType' object has no attribute 'unsqueeze'")
-        if self.stack_cnt < 2:
-            raise IndexError("list index out of range")
+        self._check_input(x)
         g = self.GRU
         blocks = self.stock_block[0].hip_params() + self.stock_block[1].hip_params()
         with torch.no_grad():
             return ops.forecast_forward(x, (g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0), self.weight_key,
                                         self.weight_query, self.multi_layer, self.alpha, self.dropout_rate, blocks,
-                                        (self.fc[0].weight, self.fc[0].bias, self.fc[2].weight, self.fc[2].bias))
+                                        (self.fc[0].weight, self.fc[0].bias, self.fc[2].weight, self.fc[2].bias),
+                                        adjacency=adjacency)
 
-    def forward(self, x):
+    def forward(self, x, adjacency=None):
+        """(forecast [B,H,N], attention [N,N]).  `adjacency`: see graph_path."""
         self._require_fc_tail()
-        fsum, attention, _ = self.hot_path(x)
+        if adjacency is None:
+            fsum, attention, _ = self.hot_path(x)
+        else:
+            fsum, attention = self.graph_path(x, adjacency)
         # fused fc tail (csrc/tail.hip, models/base_model.py:175-179): Linear - LeakyReLU - Linear and the permute to [B,H,N]
         # in one kernel; for H == 1 the reference's unsqueeze/squeeze (:176-177) yields the same [B,1,N] tensor
         return FcTail.apply(fsum, self.fc[0].weight, self.fc[0].bias, self.fc[2].weight, self.fc[2].bias,

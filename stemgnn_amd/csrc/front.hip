@@ -864,6 +864,97 @@ extern "C" int stemgnn_keyquery_wgrad(const float* h, const float* attn_scratch,
   return 0;
 }
 
+// ---- frozen / user-supplied graphs --------------------------------------------------------------------------------
+// The model run from a given adjacency (A, deg) instead of the GRU + attention front: the Laplacian kernels above are
+// launched as they are (B = 1, degree term on), the kernels below only supply what a free adjacency lacks -- its row sums --
+// and the fp64 running mean of A | deg over a data set.
+//
+// deg[i] = sum_j A[i][j] (:141, before the symmetrisation).  One wave per row, as sg_attention_reduce_kernel: lane l adds the
+// columns l, l + 64, ... in ascending order, then the wave's butterfly -- a fixed order whatever the grid.  N <= 256: the
+// lane's four loads are issued before the first add (the kernel is one L2 round trip long).
+__global__ __launch_bounds__(256) void sg_graph_degree_kernel(const float* __restrict__ A, int N, float* __restrict__ deg) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = blockIdx.x * 4 + wave;
+  if (i >= N) return;
+  const float* row = A + (size_t)i * N;
+  float d = 0.f;
+  if (N <= 256) {
+    float v[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int j = lane + 64 * t;
+      v[t] = row[j < N ? j : N - 1];
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+      if (lane + 64 * t < N) d += v[t];
+  } else {
+    for (int j = lane; j < N; j += 64) d += row[j];
+  }
+  d = sg_wave_sum(d);
+  if (lane == 0) deg[i] = d;
+}
+
+// acc[e] (+)= w * v[e] in fp64, one thread per element, no atomics: the sum's order is the order of the calls.
+__global__ void sg_graph_accumulate_kernel(const float* __restrict__ v, double w, double* __restrict__ acc, size_t n, int init) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  const double t = w * (double)v[e];
+  acc[e] = init ? t : acc[e] + t;
+}
+// out[e] = (float)(acc[e] / wsum): the one rounding to fp32 of the mean.
+__global__ void sg_graph_finish_kernel(const double* __restrict__ acc, double wsum, float* __restrict__ out, size_t n) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  out[e] = (float)(acc[e] / wsum);
+}
+
+extern "C" int stemgnn_graph_degree(const float* A, int N, float* deg, void* stream) {
+  if (!A || !deg || N <= 0) return SG_EINVAL;
+  hipLaunchKernelGGL(sg_graph_degree_kernel, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, A, N, deg);
+  SG_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int stemgnn_graph_basis_fwd(const float* A, const float* deg, float* attention_out, float* mul_L, int N,
+                                       void* stream) {
+  if (!A || !deg || !attention_out || !mul_L || N <= 0) return SG_EINVAL;
+  hipLaunchKernelGGL(sg_laplacian_fwd_kernel, dim3((N + 31) / 32, (N + 31) / 32), dim3(256), 0, (hipStream_t)stream, A, deg,
+                     attention_out, mul_L, N);
+  SG_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int stemgnn_graph_basis_bwd(const float* dL, const float* dA_ext, const float* A, const float* deg, float* dA, int N,
+                                       void* stream) {
+  if ((!dL && !dA_ext) || !A || !deg || !dA || N <= 0) return SG_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (!dL)
+    hipLaunchKernelGGL(sg_attention_seed_kernel, dim3((N + 31) / 32, (N + 31) / 32), dim3(256), 0, st, dA_ext, dA, 1, N);
+  else if (dA_ext)
+    hipLaunchKernelGGL(sg_laplacian_bwd_kernel<true>, dim3((N + 3) / 4), dim3(256), 0, st, dL, A, deg, dA, 1, N, 1, dA_ext);
+  else
+    hipLaunchKernelGGL(sg_laplacian_bwd_kernel<false>, dim3((N + 3) / 4), dim3(256), 0, st, dL, A, deg, dA, 1, N, 1, dA_ext);
+  SG_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int stemgnn_graph_accumulate(const float* v, double w, double* acc, size_t n, int init, void* stream) {
+  if (!v || !acc || n == 0 || !(w > 0.0) || (n + 255) / 256 > 0x7fffffffu) return SG_EINVAL;
+  hipLaunchKernelGGL(sg_graph_accumulate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, v, w, acc,
+                     n, init);
+  SG_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int stemgnn_graph_finish(const double* acc, double wsum, float* out, size_t n, void* stream) {
+  if (!acc || !out || n == 0 || !(wsum > 0.0) || (n + 255) / 256 > 0x7fffffffu) return SG_EINVAL;
+  hipLaunchKernelGGL(sg_graph_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, acc, wsum, out,
+                     n);
+  SG_TRY(hipGetLastError());
+  return 0;
+}
+
 // used := seed; seed.offset += 1 -- the per-forward step of the model's Philox stream as ONE launch (a clone + an in-place
 // add were two dispatches of the step)
 __global__ void sg_dropout_seed_next_kernel(uint64_t* __restrict__ seed, uint64_t* __restrict__ used) {

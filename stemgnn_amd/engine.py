@@ -136,7 +136,7 @@ class TrainStep:
     def __init__(self, model, optimizer, batch_size, window_size, horizon, units, series=None, world=1, graph=True,
                  exact=False, group=None, collective=None, one_graph=None, order_capacity=0, collective_fn=None,
                  schedule_check=None, attention_penalty=None, loss="mse", huber_delta=1.0, ignore_nan=False,
-                 target_series=None):
+                 target_series=None, adjacency=None):
         """order_capacity > 0 (with a resident `series`): the step takes its windows from a device-side queue of window-end
         rows (`load_order` once per epoch, `run_next` per step; stemgnn_window_gather_queue advances the position on the
         device), so a hipGraph replay is the whole per-step host work -- no index copy ahead of it.
@@ -167,7 +167,18 @@ class TrainStep:
         softmax sum to 1.  None (default): the step is exactly what it is without the argument.
         loss / huber_delta / ignore_nan: Model.loss's `kind`, `huber_delta`, `ignore_nan` (needs a model with the fused
         ``loss``).  target_series: [T,N] fp32 of the series' shape and device; the targets `y` are gathered from it instead of
-        from `series` (a copy that keeps missing readings as NaN while the inputs stay imputed).  Defaults: the step as it was."""
+        from `series` (a copy that keeps missing readings as NaN while the inputs stay imputed).  Defaults: the step as it was.
+        adjacency (a graph.LatentGraph or an [N,N] tensor): train from a fixed graph -- passed to Model.loss / Model.forward inside
+        the (captured) step: no GRU, no attention, no gradient for GRU / key / query, exact-fp32 GLU layers.  Nothing of such a
+        step runs on the side stream (the schedule self-check is skipped), and a data-parallel step has no cross-sample reduction
+        left: `exact` has nothing to do and is not entered.  Not combinable with attention_penalty (the graph is not learned)."""
+        if adjacency is not None and attention_penalty is not None:
+            raise ValueError("attention_penalty acts on the learned graph; with adjacency= there is none")
+        if adjacency is not None:
+            from .graph import prepare
+            adjacency = prepare(adjacency, next(model.parameters()).device)
+        self.adjacency = adjacency
+        self.graph_kw = {} if adjacency is None else dict(adjacency=adjacency)
         if loss not in _lib.SG_LOSS:
             raise ValueError(f"unknown loss {loss!r}: one of {sorted(_lib.SG_LOSS)}")
         self.loss_kw = {} if (loss == "mse" and not ignore_nan) else \
@@ -186,6 +197,8 @@ class TrainStep:
         self.one_graph = (os.environ.get("STEMGNN_DDP_ONE_GRAPH", "1") == "1") if one_graph is None else bool(one_graph)
         self.schedule_check = (os.environ.get("STEMGNN_SCHEDULE_CHECK", "1") != "0") if schedule_check is None \
             else bool(schedule_check)
+        if adjacency is not None:
+            self.schedule_check = False
         self.schedule = {"checked": False}
         if self.collective and self.one_graph and collective_fn is None:
             # only RCCL collectives can be captured into a hipGraph; a gloo group (CPU transport, tests) copies through the
@@ -226,7 +239,7 @@ class TrainStep:
             # the all-reduce SUMs; the optimizer kernel applies 1 / world.  Passed per step (see _finish): the optimizer
             # object itself is left as it was, so using it elsewhere with all_reduce_mean does not double-scale
             self._grad_scale = 1.0 / world if self.collective else 1.0
-        if exact and (world > 1 or self.collective):
+        if exact and (world > 1 or self.collective) and adjacency is None:
             # exact data-parallel mode: A and dA are averaged over the ranks inside forward / backward
             # (two [N,N] collectives).  Host-launched collectives cannot sit between the kernels of a captured graph, so the
             # step runs eagerly -- unless one_graph asks for the collectives to be captured WITH the step (RCCL capture
@@ -244,7 +257,8 @@ class TrainStep:
         # [0, split) = weight_key / weight_query / GRU behind the GRU weight gradients
         self._split = None
         self._tail_reduced = False
-        if self.collective and self.fused and self.one_graph and self.state.overlap and hasattr(model, "stock_block"):
+        if self.collective and self.fused and self.one_graph and self.state.overlap and hasattr(model, "stock_block") \
+                and adjacency is None:         # (the hook that reduces the tail range belongs to SpectralHotPath.backward)
             self._split = self.bucket.offset_of(next(model.stock_block[0].parameters()))
             self.state.block_grads_hook = self._reduce_tail_range
         self._q_header = None
@@ -259,7 +273,8 @@ class TrainStep:
         # after the gather so that the gather stays the first node the graph launches (queued ahead of the gather, the
         # gather starts 10 us late -- measured in round 3).
         self._tail_reduced = False
-        early = self.state.overlap and hasattr(self.model, "prefetch_side")
+        # (a step from a given adjacency has no SpectralHotPath node to pick the pre-packed panels up: nothing is queued for it)
+        early = self.state.overlap and hasattr(self.model, "prefetch_side") and self.adjacency is None
         if early:
             self.state.fork_event = torch.cuda.Event()
             self.state.fork_event.record()
@@ -280,12 +295,12 @@ class TrainStep:
         # MSE and both their backwards (it is this step that promises the upstream gradient of 1 below)
         attention = None
         if self.fuse_tail and self.attention_penalty is None:
-            loss = self.model.loss(x, y, self.loss.detach(), self.loss_sum, unit_grad=True, **self.loss_kw)
+            loss = self.model.loss(x, y, self.loss.detach(), self.loss_sum, unit_grad=True, **self.loss_kw, **self.graph_kw)
         elif self.fuse_tail:
             loss, attention = self.model.loss(x, y, self.loss.detach(), self.loss_sum, unit_grad=True, return_attention=True,
                                               **self.loss_kw)
         else:
-            forecast, attention = self.model(x)
+            forecast, attention = self.model(x, **self.graph_kw)
             loss = ops.mse_loss(forecast, y, self.loss.detach(), self.loss_sum)   # fresh alias: no history chaining
         if self.attention_penalty is None:
             torch.autograd.backward(loss, grad_tensors=(self._one,))    # :164 (pre-allocated d(loss) = 1)
@@ -725,9 +740,12 @@ class ForecastStep:
         forecast, target = fs.result()     # rolling_forecast's format: [count, horizon, N] each
     """
 
-    def __init__(self, model, batch_size, window, horizon, series, order_capacity, graph=True, target_series=None):
+    def __init__(self, model, batch_size, window, horizon, series, order_capacity, graph=True, target_series=None,
+                 adjacency=None):
         """target_series: [T,N] fp32 of the series' shape and device; the result's targets come from it (missing readings kept
-        as NaN for the masked metrics) while the model's inputs come from `series`."""
+        as NaN for the masked metrics) while the model's inputs come from `series`.
+        adjacency (a graph.LatentGraph or an [N,N] tensor): every Model.predict of the pass runs from this graph (no GRU, no
+        attention; a window's forecast no longer depends on its batch)."""
         self.model = model
         self.B, self.W, self.horizon = int(batch_size), int(window), int(horizon)
         if series is None or series.dim() != 2:
@@ -739,6 +757,10 @@ class ForecastStep:
         self.N = int(series.shape[1])
         dev = series.device
         self.device = dev
+        if adjacency is not None:
+            from .graph import prepare
+            adjacency = prepare(adjacency, dev)
+        self.graph_kw = {} if adjacency is None else dict(adjacency=adjacency)
         cap = max(int(order_capacity), self.B)
         self.order = torch.full((cap,), self.W, dtype=torch.int64, device=dev)   # every slot a valid window end
         self.queue = torch.zeros(4, dtype=torch.int64, device=dev)              # {position, arrival ticket, count, wrap}
@@ -764,7 +786,7 @@ class ForecastStep:
         """Rolling inference of one batch (trainer.rolling_forecast's inner loop) into `steps`."""
         done = 0
         while done < self.horizon:
-            out, _ = self.model.predict(window)
+            out, _ = self.model.predict(window, **self.graph_kw)
             window = ops.roll_window(window, out, steps, done, self.horizon)
             done += min(self.horizon - done, out.shape[1])
 

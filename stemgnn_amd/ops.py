@@ -66,6 +66,8 @@ class HotPathState:
         self.warm_saved = None       # dummy saved-activation buffer of the fused forward's warm-up launch (prepack_blocks)
         self.tail_finish = None      # thunk(stream): the fc tail's partial-sum launch (loss, fc gradients) FcTailMse.forward left for
                                      # SpectralHotPath.backward to queue on the side branch (nothing on the chain reads its output)
+        self.tail_may_defer = True   # False while Model.loss runs from a given adjacency: no SpectralHotPath.backward will come
+                                     # for the thunk, FcTailMse.forward runs both launches itself
         self.side_probe = None       # a list: every kernel the step would put on the SIDE branch is also appended as a
                                      # re-issuable thunk(stream) -- engine.TrainStep's schedule self-check replays them alone to
                                      # measure the side branch's kernel-time sum (collectives and the dropout key step excluded)
@@ -491,7 +493,9 @@ class FcTailMse(torch.autograd.Function):
         # direct + unit_grad + side-stream mode: the step driver promises an immediate backward with an upstream gradient of 1
         # (engine.TrainStep) -> only the per-row launch runs here; the partial-sum launch (loss, fc gradients: no consumer
         # before the optimizer) is left for SpectralHotPath.backward to queue on the side branch (-10 us on the chain)
-        defer = direct and ctx.state.overlap and ctx.state.tail_finish is None
+        # (state.tail_may_defer False: a caller whose backward has no SpectralHotPath node -- Model.loss with an adjacency --
+        # nobody would run the thunk, so both launches run here)
+        defer = direct and ctx.state.overlap and ctx.state.tail_finish is None and ctx.state.tail_may_defer
         if defer:
             _lib.check(rows_call(
                 fsum.data_ptr(), target.data_ptr(), w0c.data_ptr(), b0c.data_ptr(), w2c.data_ptr(), b2c.data_ptr(), B, N, W, H,
@@ -596,7 +600,10 @@ class GluFn(torch.autograd.Function):
 class StockBlockFn(torch.autograd.Function):
     """One StockBlockLayer (reference models/base_model.py:61-75) as a stand-alone autograd node:
     (X [B,N,W] contiguous, mul_L [4,N,N], multi, has_backcast, 33 block params) -> (forecast [B,N,W], backcast [B,N,W]).
-    Model.forward uses the fused two-block node (SpectralHotPath); this one backs StockBlockLayer.forward."""
+    Model.forward uses the fused two-block node (SpectralHotPath); this one backs StockBlockLayer.forward and the model run
+    from a given adjacency (Model.forward(x, adjacency=...)).  The GLU layers run in exact fp32 here whatever STEMGNN_DTYPE
+    says (no split-bf16 form of this node).  A mul_L that needs no gradient (a frozen graph) gets none: the d(mul_L) product
+    of stemgnn_gft_bwd is not launched."""
 
     @staticmethod
     def forward(ctx, X, mul_L, multi, has_bc, *params):
@@ -648,7 +655,7 @@ class StockBlockFn(torch.autograd.Function):
         scratch = torch.empty(lib.stemgnn_scratch_floats(B, N, W, multi), device=dev, dtype=f32)
         dG = scratch[lib.stemgnn_scratch_offset_dG(B, N, W, multi):]
         gradpart = torch.empty(lib.stemgnn_gradpart_floats(W, multi, nsplit), device=dev, dtype=f32)
-        dmul_L = torch.zeros(4, N, N, device=dev, dtype=f32)
+        dmul_L = torch.zeros(4, N, N, device=dev, dtype=f32) if ctx.needs_input_grad[1] else None
         dX = torch.empty(B, N, W, device=dev, dtype=f32)
         parr = _lib.ptr_array(params)
         sb, sn, stt = N * W, W, 1
@@ -662,7 +669,7 @@ class StockBlockFn(torch.autograd.Function):
                                            dforecast.data_ptr(), int(use_bc), scratch.data_ptr(), gradpart.data_ptr(),
                                            nsplit, 100, B, N, W, multi, st), "block_wgrad")
         _lib.check(lib.stemgnn_gft_bwd(mul_L.data_ptr(), X.data_ptr(), sb, sn, stt, dG.data_ptr(), dX.data_ptr(),
-                                       dmul_L.data_ptr(), 0, B, N, W, st), "gft_bwd")
+                                       dmul_L.data_ptr() if dmul_L is not None else None, 0, B, N, W, st), "gft_bwd")
         grads = [None] * 33
         for i, p in enumerate(params):
             if p is None or (not has_bc and i in (7, 8)):
@@ -676,6 +683,92 @@ class StockBlockFn(torch.autograd.Function):
             _lib.check(lib.stemgnn_shortcut_dx(scratch.data_ptr(), params[7].data_ptr(), dX.data_ptr(), B, N, W, multi, st),
                        "shortcut_dx")
         return (dX, dmul_L, None, None, *grads)
+
+
+def graph_degree(A):
+    """``stemgnn_graph_degree``: deg [N] = row sums of the adjacency A [N,N] (reference models/base_model.py:141, before the
+    symmetrisation), one wave per row in a fixed order."""
+    lib = _lib.load()
+    _require_gpu(A, "adjacency")
+    A = A.contiguous()
+    N = A.shape[0]
+    deg = torch.empty(N, device=A.device, dtype=torch.float32)
+    _lib.check(lib.stemgnn_graph_degree(A.data_ptr(), N, deg.data_ptr(), _stream()), "graph_degree")
+    return deg
+
+
+def spectral_route():
+    """STEMGNN_SPECTRAL: "cheb" (default) or "eig", read per call."""
+    return "eig" if os.environ.get("STEMGNN_SPECTRAL", "cheb") == "eig" else "cheb"
+
+
+def graph_basis(A, deg):
+    """(A [N,N], deg [N]) -> (attention [N,N] = 0.5 (A + A^T), mul_L [4,N,N]): the Laplacian kernel of the model's own front
+    (``stemgnn_graph_basis_fwd``) and then the Chebyshev products, or the eigen route under STEMGNN_SPECTRAL=eig -- the launches
+    SpectralHotPath.forward makes behind its attention, on the same values: the same bits."""
+    lib = _lib.load()
+    _require_gpu(A, "adjacency")
+    _require_gpu(deg, "degree")
+    A, deg = A.contiguous(), deg.contiguous()
+    N = A.shape[0]
+    if A.dim() != 2 or A.shape[1] != N or deg.numel() != N:
+        raise _lib.StemGNNHipError(f"adjacency must be [N,N] with a degree of N entries, got {tuple(A.shape)} / {tuple(deg.shape)}")
+    dev, f32, st = A.device, torch.float32, _stream()
+    mul_L = torch.empty(4, N, N, device=dev, dtype=f32)
+    attention = torch.empty(N, N, device=dev, dtype=f32)
+    _lib.check(lib.stemgnn_graph_basis_fwd(A.data_ptr(), deg.data_ptr(), attention.data_ptr(), mul_L.data_ptr(), N, st),
+               "graph_basis_fwd")
+    if spectral_route() == "eig":
+        lam = torch.empty(N, device=dev, dtype=f32)
+        U = torch.empty(N, N, device=dev, dtype=f32)
+        escr = torch.empty(lib.stemgnn_eigh_scratch_floats(N), device=dev, dtype=f32)
+        _lib.check(lib.stemgnn_eigh_fwd(mul_L.data_ptr(), lam.data_ptr(), U.data_ptr(), escr.data_ptr(), N, 0, st), "eigh_fwd")
+    else:
+        _lib.check(lib.stemgnn_cheb_fwd(mul_L.data_ptr(), N, st), "cheb_fwd")
+    return attention, mul_L
+
+
+class GraphBasisFn(torch.autograd.Function):
+    """(A [N,N], degree [N] | None) -> (attention [N,N] = 0.5 (A + A^T), mul_L [4,N,N]): the spectral basis of a GIVEN adjacency
+    (reference models/base_model.py:141-148 from the point behind the batch mean of :140).  degree None: the row sums of A
+    (``stemgnn_graph_degree``), and A is differentiable -- both outputs are, mul_L too (unlike SpectralHotPath's): backward is
+    d(mul_L) -> ``stemgnn_cheb_bwd`` -> ``stemgnn_graph_basis_bwd`` (degree term on), a gradient of the attention joining in
+    that launch; with a gradient for the attention alone a seed kernel writes (G + G^T) / 2.  A stored degree is a constant of
+    the graph and A then gets no gradient (None)."""
+
+    @staticmethod
+    def forward(ctx, A, degree=None):
+        _require_gpu(A, "adjacency")
+        A = A.contiguous()
+        ctx.derived = degree is None
+        deg = graph_degree(A) if degree is None else degree.contiguous()
+        attention, mul_L = graph_basis(A, deg)
+        ctx.save_for_backward(A, deg)
+        ctx.mul_L = mul_L.detach() if ctx.derived and ctx.needs_input_grad[0] else None
+        ctx.set_materialize_grads(False)
+        return attention, mul_L
+
+    @staticmethod
+    def backward(ctx, datt, dmul_L):
+        if not (ctx.derived and ctx.needs_input_grad[0]) or (datt is None and dmul_L is None):
+            return None, None
+        lib = _lib.load()
+        A, deg = ctx.saved_tensors
+        N = A.shape[0]
+        dev, f32, st = A.device, torch.float32, _stream()
+        dL = None
+        if dmul_L is not None:
+            dL = torch.empty(N, N, device=dev, dtype=f32)
+            scratch = torch.empty(2 * N * N, device=dev, dtype=f32)
+            _lib.check(lib.stemgnn_cheb_bwd(ctx.mul_L.data_ptr(), dmul_L.contiguous().data_ptr(), dL.data_ptr(),
+                                            scratch.data_ptr(), N, st), "cheb_bwd")
+        if datt is not None:
+            datt = datt.contiguous()
+        dA = torch.empty(N, N, device=dev, dtype=f32)
+        _lib.check(lib.stemgnn_graph_basis_bwd(dL.data_ptr() if dL is not None else None,
+                                               datt.data_ptr() if datt is not None else None, A.data_ptr(), deg.data_ptr(),
+                                               dA.data_ptr(), N, st), "graph_basis_bwd")
+        return dA, None
 
 
 _keep_attention_state = False
@@ -1130,7 +1223,38 @@ class SpectralHotPath(torch.autograd.Function):
 # ---------------------------------------------------------------------------------------------------------------
 # data path either side of the hot path: thin wrappers over csrc/data.hip
 
-def forecast_forward(x, gru_params, wk, wq, multi, alpha, drop_p, block_params, fc_params):
+def latent_adjacency(x, gru_params, wk, wq, alpha, drop_p):
+    """The model's own graph for the batch x [B,W,N] in eval mode: the GRU recurrence (stemgnn_gru_fwd_infer) and the attention /
+    Laplacian launches of forecast_forward, of which A [N,N] | deg [N] -- the batch-mean attention ahead of the symmetrisation
+    and the degrees the fused front summed for it -- are returned as one contiguous view of N*N + N floats."""
+    lib = _lib.load()
+    w_ih, w_hh, b_ih, b_hh = (t.contiguous() for t in gru_params)
+    for name, t in (("x", x), ("GRU.weight_ih_l0", w_ih), ("GRU.weight_hh_l0", w_hh), ("weight_key", wk),
+                    ("weight_query", wq)):
+        _require_gpu(t, name)
+    x = x.contiguous()
+    B, W, N = x.shape
+    Hd = w_hh.shape[1]
+    if Hd != N:
+        raise _lib.StemGNNHipError(f"GRU hidden size {Hd} != units {N}")
+    dev, f32, st = x.device, torch.float32, _stream()
+    h_ext = torch.empty(N + 1, B, Hd, device=dev, dtype=f32)
+    gscr = torch.empty(lib.stemgnn_gru_fwd_scratch_floats(B, N, Hd), device=dev, dtype=f32)
+    _lib.check(lib.stemgnn_gru_fwd_infer(x.data_ptr(), w_ih.data_ptr(), w_hh.data_ptr(), b_ih.data_ptr(), b_hh.data_ptr(),
+                                         B, N, Hd, W, gscr.data_ptr(), h_ext.data_ptr(), gru_status(dev).data_ptr(), st),
+               "gru_fwd_infer")
+    mul_L = torch.empty(4, N, N, device=dev, dtype=f32)
+    attention = torch.empty(N, N, device=dev, dtype=f32)
+    attn_saved = torch.empty(lib.stemgnn_attn_saved_floats(B, N), device=dev, dtype=f32)
+    # parts = 3, the call forecast_forward makes: its fused kernel takes the degrees from the per-chunk row sums (another order
+    # than the separate reduction of parts = 1), and those are the degrees a frozen graph must carry to reproduce its bits
+    _lib.check(lib.stemgnn_attn_laplacian_fwd(h_ext[1:].data_ptr(), wk.data_ptr(), wq.data_ptr(), float(alpha), float(drop_p),
+                                              0, None, B, N, attn_saved.data_ptr(), attention.data_ptr(), mul_L.data_ptr(), 3,
+                                              st), "attn_laplacian_fwd")
+    return attn_saved[3 * B * N:3 * B * N + N * N + N]
+
+
+def forecast_forward(x, gru_params, wk, wq, multi, alpha, drop_p, block_params, fc_params, adjacency=None):
     """Inference forward of Model (reference models/base_model.py:136-179 in eval mode) without autograd and without the
     tensors only a backward pass reads: the GRU recurrence without its gate reserve (stemgnn_gru_fwd_infer), attention /
     Laplacian with training = 0, Chebyshev basis (eigen route under STEMGNN_SPECTRAL=eig), both StockBlocks on the _infer
@@ -1138,8 +1262,12 @@ def forecast_forward(x, gru_params, wk, wq, multi, alpha, drop_p, block_params, 
     Same kernels and arithmetic as SpectralHotPath.forward in eval mode: bit-identical outputs.  The weights are packed
     on every call, as in training.  x [B,W,N]; gru_params = (weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0);
     block_params = 2 x 33 block tensors; fc_params = (fc.0.weight, fc.0.bias, fc.2.weight, fc.2.bias).
+    adjacency (a graph.LatentGraph or an [N,N] tensor): the GRU and the attention are skipped, mul_L and the symmetrised
+    attention come from the graph (a LatentGraph caches them); everything from the blocks on is unchanged.
     Returns (forecast [B,H,N], attention [N,N])."""
     lib = _lib.load()
+    if adjacency is not None:
+        return _forecast_forward_graph(x, adjacency, multi, block_params, fc_params)
     w_ih, w_hh, b_ih, b_hh = (t.contiguous() for t in gru_params)
     for name, t in (("x", x), ("GRU.weight_ih_l0", w_ih), ("GRU.weight_hh_l0", w_hh), ("weight_key", wk),
                     ("weight_query", wq)):
@@ -1174,6 +1302,26 @@ def forecast_forward(x, gru_params, wk, wq, multi, alpha, drop_p, block_params, 
     else:
         _lib.check(lib.stemgnn_cheb_fwd(mul_L.data_ptr(), N, st), "cheb_fwd")
     del attn_saved
+    return _forecast_blocks(x, mul_L, multi, block_params, fc_params), attention
+
+
+def _forecast_forward_graph(x, adjacency, multi, block_params, fc_params):
+    from .graph import resolve_basis
+    _require_gpu(x, "x")
+    assert len(block_params) == 2 * _lib.SG_BLOCK_NPARAMS
+    x = x.contiguous()
+    attention, mul_L = resolve_basis(adjacency, x.device)
+    if mul_L.shape[1] != x.shape[2]:
+        raise _lib.StemGNNHipError(f"adjacency is [{mul_L.shape[1]},{mul_L.shape[1]}] but x has {x.shape[2]} nodes")
+    return _forecast_blocks(x, mul_L.detach(), multi, block_params, fc_params), attention.detach()
+
+
+def _forecast_blocks(x, mul_L, multi, block_params, fc_params):
+    """Both StockBlocks on the _infer entries and the fc tail: x [B,W,N] contiguous, mul_L [4,N,N] -> forecast [B,H,N]."""
+    lib = _lib.load()
+    B, W, N = x.shape
+    dev, f32 = x.device, torch.float32
+    st = _stream()
     # both StockBlocks through one inference workspace (G | layer-2 GLU outputs | ping-pong slabs where needed)
     splits = glu_splits()
     tables = dft_tables(W, multi, dev)
@@ -1207,7 +1355,7 @@ def forecast_forward(x, gru_params, wk, wq, multi, alpha, drop_p, block_params, 
     forecast = torch.empty(B, H, N, device=dev, dtype=f32)
     _lib.check(lib.stemgnn_fc_tail_fwd(fsum.data_ptr(), w0.data_ptr(), b0.data_ptr(), w2.data_ptr(), b2.data_ptr(),
                                        B, N, W, H, forecast.data_ptr(), st), "fc_tail_fwd")
-    return forecast, attention
+    return forecast
 
 
 def forecast_store(forecast, target, pos, out_forecast, out_target):

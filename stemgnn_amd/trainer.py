@@ -53,9 +53,11 @@ def load_checkpoint(directory, tag=None):
     return torch.load(path, weights_only=False) if path.is_file() else None
 
 
-def rolling_forecast(model, loader, horizon):
+def rolling_forecast(model, loader, horizon, adjacency=None):
     """Multi-step forecast of every window the loader yields: the model's first outputs are fed back as inputs until
     `horizon` steps exist (what the reference's validation does, models/handler.py:41-65), all on the device.
+    adjacency (a graph.LatentGraph or an [N,N] tensor): every round is ``model.predict(window, adjacency=adjacency)`` -- the
+    forecast from a fixed graph, independent of how the loader batches the windows.
     Returns (forecast [count, horizon, N], target [count, horizon, N]) float32 device tensors."""
     was_training = model.training
     model.eval()
@@ -65,7 +67,7 @@ def rolling_forecast(model, loader, horizon):
             steps = torch.zeros(window.shape[0], horizon, window.shape[2], device=window.device)
             done = 0
             while done < horizon:
-                out, _ = model(window)
+                out, _ = model(window) if adjacency is None else model.predict(window, adjacency=adjacency)
                 if out.shape[1] == 0:
                     raise Exception("Get blank inference result")
                 window = ops.roll_window(window, out, steps, done, horizon)
@@ -76,15 +78,15 @@ def rolling_forecast(model, loader, horizon):
     return torch.cat(forecasts), torch.cat(targets)
 
 
-def rolling_forecast_graph(model, dataset, horizon, batch_size):
+def rolling_forecast_graph(model, dataset, horizon, batch_size, adjacency=None):
     """rolling_forecast(model, WindowLoader(dataset, batch_size), horizon) on engine.ForecastStep: each full batch is one
     hipGraph replay of window gather -> Model.predict -> roll_window rounds -> result slabs; the ragged last batch runs
     eagerly.  Same (forecast, target) [count, horizon, N], bit for bit; the model's training state is left untouched.
-    The dataset's horizon (its target length) must equal `horizon`."""
+    The dataset's horizon (its target length) must equal `horizon`.  adjacency: as in rolling_forecast."""
     if int(dataset.horizon) != int(horizon):
         raise ValueError(f"rolling_forecast_graph: dataset horizon {dataset.horizon} != horizon {horizon}")
     n = len(dataset)
-    step = ForecastStep(model, batch_size, dataset.window_size, horizon, dataset.data, order_capacity=n)
+    step = ForecastStep(model, batch_size, dataset.window_size, horizon, dataset.data, order_capacity=n, adjacency=adjacency)
     step.load_order(dataset.hi_all)
     while step.remaining > 0:
         step.run_next()
