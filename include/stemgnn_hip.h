@@ -7,6 +7,9 @@
  *   - all buffers (inputs, outputs, saved activations, workspaces) are owned by the caller; the
  *     library never allocates, frees or synchronises; every launch goes to `stream` (a hipStream_t
  *     passed as void*), so the calls are stream-ordered and graph-capturable;
+ *   - a block's `packed`, `split`, `saved`, `scratch`, `gradpart` and the inference workspace need no initialisation by the caller:
+ *     the library writes every float of them it later reads, padding columns and ragged row blocks included, and writes nothing
+ *     beyond the size its stemgnn_*_floats function returns (tests/test_hip_block.py runs every entry on NaN-filled, guarded buffers);
  *   - return value: 0 on success, a negative hipError_t (-(int)err) on a launch failure, or
  *     SG_EINVAL (-10001) for a bad argument.  No exception crosses this boundary.
  *   - shapes: B batch, N nodes (units), W window (time_step), multi, H horizon, Wm = W*multi,
@@ -328,7 +331,8 @@ int stemgnn_block_pack_panels(const float* const* params_host, const float* tabl
 int stemgnn_glu_fused_repack(float* packed, int W, int multi, void* stream);
 /* adjoint of the above: scatter the weight gradients (slab 0 of every gradpart region, left complete by
  * stemgnn_block_wgrad or by the parts & 2 calls of stemgnn_igft_heads_bwd / stemgnn_spectral_glu_bwd) into the parameter
- * gradients grads_host[SG_BLOCK_NPARAMS] (entries may be NULL to skip).  nsplit = the value gradpart was sized with. */
+ * gradients grads_host[SG_BLOCK_NPARAMS] (entries may be NULL to skip).  nsplit = the value gradpart was sized with.
+ * has_backcast == 0: entries 5..8 (the backcast head and the short-cut the block then never evaluates, :73-74) are not written. */
 int stemgnn_block_unpack_grads(const float* gradpart, int nsplit, const float* tables,
                                float* const* grads_host, int W, int multi, int has_backcast, void* stream);
 
@@ -393,7 +397,8 @@ int stemgnn_spectral_glu_dgrad_split(const float* packed, const float* split, co
 int stemgnn_glu_fused_bf16_ok(int W, int multi, int splits);
 
 /* ---- C2R iDFT + graph-conv weight + forecast / backcast heads (models/base_model.py:55-58, 65-74)
- * forecast [M,W]: written (accumulate=0) or added to (accumulate=1: result[0]+result[1], :174).
+ * forecast [M,W]: written (accumulate=0) or added to (accumulate=1: result[0]+result[1], :174 -- old + the finished forecast, one
+ * rounding away from the sum of the two).
  * backcast [M,W] (block 0 only, else NULL); X as in gft_fwd (short-cut input, :71). */
 int stemgnn_igft_heads_fwd(const float* const* params_host, const float* packed, float* saved,
                            const float* X, long xs_b, long xs_n, long xs_t,

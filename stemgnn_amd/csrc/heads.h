@@ -242,9 +242,10 @@ __global__ __launch_bounds__(NW * 64) void sg_heads_fwd_kernel(const HeadsFwdArg
       for (int reg = 0; reg < 4; ++reg) {
         const int r0 = rh3 * 16 + kq * 4 + reg, r1 = 16 + r0;
         if (col < W) {
-          if (m0 + r0 < M) { float* o = g.forecast + (size_t)(m0 + r0) * W + col; *o = (g.accumulate ? *o : 0.f) + c0[reg] + bias; }
+          // accumulate: old + (product + bias) -- result[0] + result[1] (:174) adds the FINISHED forecast, as Head2Op does
+          if (m0 + r0 < M) { float* o = g.forecast + (size_t)(m0 + r0) * W + col; const float v = c0[reg] + bias; *o = g.accumulate ? *o + v : v; }
           if constexpr (!SPLIT) {
-            if (m0 + r1 < M) { float* o = g.forecast + (size_t)(m0 + r1) * W + col; *o = (g.accumulate ? *o : 0.f) + c1[reg] + bias; }
+            if (m0 + r1 < M) { float* o = g.forecast + (size_t)(m0 + r1) * W + col; const float v = c1[reg] + bias; *o = g.accumulate ? *o + v : v; }
           }
         }
       }

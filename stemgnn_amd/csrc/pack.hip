@@ -246,7 +246,7 @@ __global__ void sg_unpack_kernel(const float* __restrict__ part, const float* __
   } else if (pi <= 8) {
     const int isb = (pi - 1) & 1;             // 1,3,5,7 weights; 2,4,6,8 biases
     const int which = (pi - 1) >> 1;          // 0 forecast, 1 forecast_result, 2 backcast, 3 short-cut
-    if (which >= 2 && !has_bc) { out[e] = 0.f; return; }
+    if (which >= 2 && !has_bc) return;        // no backcast heads: their buffers (the unused short-cut's too) are left alone
     const float* p; int in;
     switch (which) {
       case 0: p = part + G.fc; in = Wm; break;

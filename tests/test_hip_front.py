@@ -72,7 +72,7 @@ import pytest
 import torch
 
 from tests.helpers import philox_ref
-from tests.util import kink_audit
+from tests.util import DEV, GUARD, SENTINEL, _all_nan, _bits, _Buf, _relerr, kink_audit      # noqa: F401 (GUARD, SENTINEL: the guard band of _Buf)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -81,9 +81,6 @@ K = 8
 K_CHEB = 2
 FLOOR = 2.0 ** -22
 ALPHA = 0.2
-GUARD = 256                      # floats behind every buffer
-SENTINEL = -7777.25
-DEV = "cuda:0"
 SG_EINVAL = -10001
 SEED, OFFSET = 0x9E3779B97F4A7C15, (1 << 32) + 0xFFFFFFF0      # high words set; the offset above 2^32
 
@@ -111,39 +108,6 @@ MASK_PS = [0.0, 0.2, 0.5, 0.9]
 MASK_SEEDS = [(SEED, OFFSET), (0xFFFFFFFF00000001, 1 << 32), ((1 << 63) + 12345, (1 << 40) + 7)]
 CHEB_NS = [1, 2, 3, 31, 32, 33, 127, 128, 129, 511, 512, 513, 640]
 CHEB_GENERIC_N = 129             # also with STEMGNN_GRAPH_PHASED=0 (the generic launch of the first backward product)
-
-
-def _relerr(got, ref):
-    """tests/util.relerr on the device: max|got - ref| / max|ref| (absolute where the reference is all zero; NaN if got holds one)."""
-    ref = ref.double()
-    d = (got.double() - ref).abs().max().item()
-    den = ref.abs().max().item()
-    return d / den if den > 0 else d
-
-
-def _bits(a, b):
-    """same bits, NaN included"""
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def _all_nan(t):
-    return bool(torch.isnan(t).all())
-
-
-class _Buf:
-    """n floats of NaN with a guard band behind them"""
-
-    def __init__(self, n, fill=float("nan")):
-        self.n = int(n)
-        self.full = torch.full((self.n + GUARD,), fill, device=DEV)
-        self.full[self.n:] = SENTINEL
-        self.t = self.full[: self.n]
-
-    def ptr(self):
-        return self.full.data_ptr()
-
-    def intact(self):
-        return bool((self.full[self.n:] == SENTINEL).all())
 
 
 def _seed_tensor(seed, offset):

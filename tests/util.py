@@ -1,6 +1,7 @@
 """Shared helpers for the test-suite (test infrastructure)."""
 import glob
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -69,3 +70,90 @@ def kink_audit(pos_impl, ref64, err, what):
     assert n_near <= max(16, int(2e-5 * ref64.numel())), n_near
     assert n_flip <= max(8, int(5e-7 * ref64.numel())) and bool((flips & ~near).sum() == 0), (n_flip, int((flips & ~near).sum()))
     return flips
+
+
+# ---- stage suites through the C ABI (tests/test_hip_front.py, tests/test_hip_block.py): NaN-filled, guarded buffers --------------
+GUARD = 256                      # floats behind every buffer
+SENTINEL = -7777.25
+DEV = "cuda:0"
+
+
+def _relerr(got, ref):
+    """tests/util.relerr on the device: max|got - ref| / max|ref| (absolute where the reference is all zero; NaN if got holds one)."""
+    ref = ref.double()
+    d = (got.double() - ref).abs().max().item()
+    den = ref.abs().max().item()
+    return d / den if den > 0 else d
+
+
+def _bits(a, b):
+    """same bits, NaN included"""
+    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+def _all_nan(t):
+    return bool(torch.isnan(t).all())
+
+
+class _Buf:
+    """n floats of NaN with a guard band behind them"""
+
+    def __init__(self, n, fill=float("nan")):
+        self.n = int(n)
+        self.full = torch.full((self.n + GUARD,), fill, device=DEV)
+        self.full[self.n:] = SENTINEL
+        self.t = self.full[: self.n]
+
+    def ptr(self):
+        return self.full.data_ptr()
+
+    def intact(self):
+        return bool((self.full[self.n:] == SENTINEL).all())
+
+
+# ---- csrc/layout.h in Python (tests/test_block_cases.py checks it against the stemgnn_*_floats functions) ----
+def dims(B, N, W, multi):
+    c16 = lambda v: (v + 15) & ~15
+    Wm = W * multi
+    nf = (Wm // 2 + 1, (Wm + 1) // 2 - 1)
+    U = (4 * nf[0], 4 * nf[1])
+    CP2 = tuple(c16(u if u > 0 else 1) for u in U)
+    return SimpleNamespace(B=B, N=N, W=W, multi=multi, Wm=Wm, WmP=c16(Wm), C=4 * Wm, CP=c16(4 * Wm), KG=3 * W, M=B * N, nf=nf, U=U,
+                           CP2=CP2, KF=CP2[0] + CP2[1])
+
+
+def saved_layout(d):
+    """name -> (offset, rows, row stride, useful columns); the order of SgSavedLayout"""
+    L, off = {}, 0
+
+    def add(name, ld, useful):
+        nonlocal off
+        L[name] = (off, d.M, ld, useful)
+        off += d.M * ld
+
+    add("G", d.KG, d.KG)
+    for r in range(2):
+        for l in range(3):
+            cp, cu = (d.CP, d.C) if l < 2 else (d.CP2[r], d.U[r])
+            add(f"out{r}{l}", cp, cu)
+            add(f"gate{r}{l}", cp, cu)
+    add("ig", d.Wm, d.Wm)
+    add("fs", d.Wm, d.Wm)
+    L["total"] = off
+    return L
+
+
+def scratch_layout(d):
+    L, off = {}, 0
+    for name, ld in (("dpF", d.Wm), ("dpB", d.W), ("dig", d.Wm)):
+        L[name] = (off, d.M, ld, ld)
+        off += d.M * ld
+    off += 6 * d.M * 2 * d.CP                                   # d(pre-activation) of the six GLU layers, pair order
+    L["dG"] = (off, 2 * d.M, d.KG, d.KG)
+    L["total"] = off + 2 * d.M * d.KG
+    return L
+
+
+def l2_channels(d, r):
+    """useful channel c of the last GLU layer -> channel kq * Wm + f of GLUs[4 + r] (sg_l2_orig_channel)"""
+    return [(c // d.nf[r]) * d.Wm + c % d.nf[r] + (1 if r == 1 else 0) for c in range(d.U[r])]
