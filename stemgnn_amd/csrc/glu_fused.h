@@ -11,8 +11,9 @@
 //     registers; the whole layer output lives in the accumulators of the four waves;
 //   * the weights of the three layers are ONE contiguous stream of 16 KB stages (pre-packed by sg_pack_fused_kernel in
 //     exactly the LDS image the fragment reads want), moved L2 -> LDS by `global_load_lds_dwordx4` into a 5-stage ring
-//     that never drains: the first stages of layer l+1 land while layer l's epilogue runs; one raw s_barrier and one
-//     counted `s_waitcnt vmcnt` per stage (the csrc/wgrad.h ring, here with the A operand resident);
+//     that never drains: the first stages of layer l+1 land while layer l's epilogue runs; one counted `s_waitcnt vmcnt`
+//     per stage and -- a stage being stored wave-major, every wave requesting exactly the slice it reads (GF_PRIVATE_RING)
+//     -- no barrier inside a layer's K loop (the csrc/wgrad.h ring, here with the A operand resident);
 //   * per k-step one 8-byte A fragment read + HP 8-byte B fragment reads feed 4 HP MFMAs (v_mfma_f32_32x32x2_f32, exact
 //     fp32: every accumulator sums k = 0, 1, 2, .. in order, as the per-layer kernels do -- same bits);
 //   * the epilogue adds the bias, forms out = u * sigmoid(v), stores `out` and `gate` for the backward pass (128
@@ -36,6 +37,28 @@ constexpr int GF_NI = 4;             // DMA pieces (1 KB each) per wave and stag
 #ifndef GF_ABL
 #define GF_ABL 0                     // timing-probe ablation bits (tools/probe/glu_fused_probe): 1 no epilogue stores,
 #endif                               // 2 no MFMA, 4 no DMA in the K loop, 8 no sigmoid.  Results wrong by design.
+// Wave-private weight ring.  A wave owns all rows of the block times its own channel slice, so of a weight stage it reads
+// only its own CW = NC / 4 columns.  With the stage stored wave-major ([wave][RS rows][CW columns]: a wave's slice is 4 KB =
+// exactly its GF_NI pieces of 1 KB) every wave requests precisely the bytes it will read: its own counted `s_waitcnt vmcnt`
+// orders its fragment reads behind its own DMA and no barrier is needed inside a K loop.  The first fragments of stage s + 1
+// are then read under the last MFMAs of stage s (GF_XPF) -- the K loop of a layer is one uninterrupted MFMA stream.  The
+// pack kernels emit the wave-major order (route "repack": the DMA source stays one contiguous run and the producer side of
+// the ring does not change at all; nothing outside this file knows the element order inside a stage).
+// -DGF_PRIVATE_RING=0 restores the shared ring (pieces dealt by position, one s_barrier per stage); -DGF_XPF=0 keeps the
+// private ring but starts every stage with its own fragment reads (A/B: tools/build_variant.sh, STEMGNN_HIP_LIB).
+#ifndef GF_PRIVATE_RING
+#define GF_PRIVATE_RING 1
+#endif
+#ifndef GF_XPF
+#define GF_XPF 1
+#endif
+#define GF_CARRY (GF_PRIVATE_RING && GF_XPF)
+// prologue copies (G -> LDS in the forward, d(pre-activation) of layer 2 -> LDS in the chain): loads in flight per thread
+// before the first LDS write; 0 = the one-load-one-write loops
+#ifndef GF_G_BATCH
+#define GF_G_BATCH 8
+#endif
+constexpr int GF_WSLICE = 1024;      // floats of a wave's slice of a stage (GF_STAGE / 4 = GF_NI pieces of 256)
 
 __device__ __forceinline__ float gf_sigmoid(float v) { return __frcp_rn(1.f + __expf(-v)); }
 // saved out / gate and d(pre-activation) stores: 82 / 148 MB per launch that nobody reads before the backward pass -- as
@@ -54,6 +77,8 @@ __device__ __forceinline__ float gf_sigmoid(float v) { return __frcp_rn(1.f + __
 // stage s of layer l, element (kk, p): kk < rs weight rows, p < 256 hp columns; column p = wave * 64 hp + h * 64 + 2 fi + t
 // holds linear_left (t = 0) / linear_right (t = 1) of channel c = wave * 32 hp + h * 32 + fi, input k = s * rs + kk.
 // Source: the K-major "pair" panel Wp[k][q], q = (c / 16) * 32 + c % 16 + 16 t (layout.h).  Padding rows / channels = 0.
+// Position inside the stage: private ring  wave * 1024 + kk * 64 hp + (p - wave * 64 hp)   (wave-major, a wave's columns
+// contiguous per row);  shared ring  kk * 256 hp + p.
 struct GfPackArgs {
   const float* wp[2][3];
   float* wf[2];
@@ -68,8 +93,15 @@ static __global__ __launch_bounds__(256) void sg_pack_fused_kernel(const GfPackA
   while (l < 2 && s >= a.g.nst[l]) { s -= a.g.nst[l]; ++l; }
   const int hp = 16 / a.g.rs[l], nc = 256 * hp;
   const int w = (int)(e % GF_STAGE);
+#if GF_PRIVATE_RING
+  // wave-major stage image: [wave][rs rows][64 hp columns]; the column inside the wave's slice as before
+  const int wave = w / GF_WSLICE, kk = (w % GF_WSLICE) / (64 * hp), rem = w % (64 * hp);
+  (void)nc;
+#else
   const int kk = w / nc, p = w % nc;
-  const int wave = p / (64 * hp), rem = p % (64 * hp), h = rem >> 6, fi = (rem & 63) >> 1, t = rem & 1;
+  const int wave = p / (64 * hp), rem = p % (64 * hp);
+#endif
+  const int h = rem >> 6, fi = (rem & 63) >> 1, t = rem & 1;
   const int c = wave * 32 * hp + h * 32 + fi, k = s * a.g.rs[l] + kk;
   float v = 0.f;
   if (k < a.K[l] && c < a.cp[r][l]) v = a.wp[r][l][(size_t)k * a.np[r][l] + ((c >> 4) << 5) + (c & 15) + 16 * t];
@@ -125,10 +157,32 @@ struct GfTile {
 // inside it.  The fragment reads go through __restrict__ pointers: that gives them alias-scope metadata, without which
 // hipcc's waitcnt pass assumes every LDS read may alias the LDS-DMA in flight and drains the ring (vmcnt(0)) per k-step.
 // Aq points at (row k0 + fk, column 2 fi) of the operand buffer; A2 at (row k0 + fk, column 64 + fi) (MT = 3 only).
-template <int MT, int HP>
+// Row stride of a weight stage as a wave's fragment reads see it: the wave's own CW columns (private ring) or all NC.
+#if GF_PRIVATE_RING
+#define GF_BSTRIDE(NC_) ((NC_) / 4)
+#else
+#define GF_BSTRIDE(NC_) (NC_)
+#endif
+// The first fragments of a stage (k-steps 0 .. PF - 1), carried from the stage before it (GF_XPF)
+template <int HP>
+struct GfFrag {
+  float2 a[GF_PF], b[GF_PF][HP];
+  float c[GF_PF];
+};
+// NEXT (GF_XPF): this stage is not the K loop's last -- behind the request of its last DMA piece it waits for this wave's
+// pieces of the next stage (same counted constant: STAGES - 2 newer stages may still be in flight) and reads that stage's
+// first fragments (operand rows + RS, weights at Bn) into pf, under the MFMAs that are left.  Those reads touch the buffer of
+// stage s + 1 only; the pieces requested from inside this stage go to the buffer of stage s - 1, whose fragment reads -- this
+// wave's own, nobody else reads its slice -- had all returned before its last MFMA issued (per-wave write-after-read).
+// FIRST: the K loop's first stage reads its own first fragments (nothing was carried to it).  All fragment reads, the
+// carried ones too, are on this function's __restrict__ parameters and land in locals first: they must keep the alias
+// scopes that the DMA requests issued from here are marked not to alias, or hipcc puts a `vmcnt(0)` ahead of them
+// (compiler facts (i) and (iii) of DESIGN 4).
+template <int MT, int HP, bool FIRST, bool NEXT>
 __device__ __forceinline__ void gf_stage(const float* __restrict__ Aq, const float* __restrict__ A2,
-                                         const float* __restrict__ Bs, sg_f32x16 (&acc)[MT][HP][2], GfRing& rg) {
-  constexpr int NC = 256 * HP, RS = 16 / HP, STEPS = RS / 2, LDA = GfTile<MT>::LDA;
+                                         const float* __restrict__ Bs, const float* __restrict__ Bn,
+                                         sg_f32x16 (&acc)[MT][HP][2], GfRing& rg, GfFrag<HP>& pf) {
+  constexpr int NC = 256 * HP, RS = 16 / HP, STEPS = RS / 2, LDA = GfTile<MT>::LDA, BST = GF_BSTRIDE(NC);
   constexpr int EVERY = STEPS / GF_NI;                 // one DMA piece every EVERY k-steps (1 or 2)
   float2 fa[STEPS], fb[STEPS][HP];
   float fc[STEPS];
@@ -136,10 +190,18 @@ __device__ __forceinline__ void gf_stage(const float* __restrict__ Aq, const flo
     fa[st] = *reinterpret_cast<const float2*>(Aq + 2 * st * LDA);
     if constexpr (MT == 3) fc[st] = A2[2 * st * LDA];
 #pragma unroll
-    for (int h = 0; h < HP; ++h) fb[st][h] = *reinterpret_cast<const float2*>(Bs + 2 * st * NC + h * 64);
+    for (int h = 0; h < HP; ++h) fb[st][h] = *reinterpret_cast<const float2*>(Bs + 2 * st * BST + h * 64);
   };
 #pragma unroll
-  for (int st = 0; st < GF_PF && st < STEPS; ++st) rd(st);
+  for (int st = 0; st < GF_PF && st < STEPS; ++st) {
+    if constexpr (GF_CARRY && !FIRST) {
+      fa[st] = pf.a[st]; fc[st] = MT == 3 ? pf.c[st] : 0.f;
+#pragma unroll
+      for (int h = 0; h < HP; ++h) fb[st][h] = pf.b[st][h];
+    } else {
+      rd(st);
+    }
+  }
 #pragma unroll
   for (int st = 0; st < STEPS; ++st) {
     float a[3];
@@ -150,6 +212,27 @@ __device__ __forceinline__ void gf_stage(const float* __restrict__ Aq, const flo
     __builtin_amdgcn_sched_barrier(0);
     if (!(GF_ABL & 2)) acc[0][0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[0], fb[st][0].y, acc[0][0][1], 0, 0, 0);
     if (!(GF_ABL & 4) && st % EVERY == 0 && st / EVERY < GF_NI) rg.issue(st / EVERY);
+#if GF_CARRY
+    if constexpr (NEXT) {
+      if (st == (GF_NI - 1) * EVERY) {                 // the stage's last piece is out
+        gf_wait_vm<(GfTile<MT>::STAGES - 2) * GF_NI>();
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int pn = 0; pn < GF_PF && pn < STEPS; ++pn) {
+          // (through locals: a float2 copied straight into pf is a memcpy at the time the alias scopes are handed out,
+          // and the load it becomes later has none)
+          const float2 va = *reinterpret_cast<const float2*>(Aq + (RS + 2 * pn) * LDA);
+          pf.a[pn].x = va.x; pf.a[pn].y = va.y;
+          if constexpr (MT == 3) pf.c[pn] = A2[(RS + 2 * pn) * LDA];
+#pragma unroll
+          for (int h = 0; h < HP; ++h) {
+            const float2 vb = *reinterpret_cast<const float2*>(Bn + 2 * pn * BST + h * 64);
+            pf.b[pn][h].x = vb.x; pf.b[pn][h].y = vb.y;
+          }
+        }
+      }
+    }
+#endif
     __builtin_amdgcn_sched_barrier(0);
     if (!(GF_ABL & 2)) {
 #pragma unroll
@@ -184,14 +267,56 @@ __device__ __forceinline__ void gf_layer(float* As, GfRing& rg, int& rbuf, int n
         for (int e = 0; e < 16; ++e) acc[i][h][t][e] = 0.f;
   const float* Ap = As + fk * LDA + 2 * fi;
   const float* Ap2 = As + fk * LDA + 64 + fi;
+  GfFrag<HP> pf;
+#if GF_PRIVATE_RING
+  // Private ring: NO barrier inside the K loop.  What orders the LDS traffic instead:
+  //   * weights, read-after-write: a wave reads only the slice its own pieces filled, behind its own counted vmcnt wait
+  //     (in-order retirement: with STAGES - 2 stages' pieces allowed in flight the oldest requested stage has landed);
+  //   * weights, write-after-read, per wave: the pieces requested from inside stage s go to the buffer of stage s - 1; this
+  //     wave's fragment reads of that buffer have returned (its MFMAs consumed them), and no other wave reads the slice;
+  //   * activation buffer: ONE barrier here, after the prologue copy's / the previous layer's epilogue LDS writes (each
+  //     wave has waited lgkmcnt(0) behind its own) and before the K loop's first read of it.  It does not change during
+  //     the K loop; the barrier ahead of the epilogue (below) keeps the epilogue from overwriting it under a reader.
+  const int boff = wave * GF_WSLICE + fk * (NC / 4) + 2 * fi;
+  const float* Bw = rg.ring + boff;
+  gf_wait_vm<(T::STAGES - 2) * GF_NI>();               // my pieces of the layer's first stage have landed
+  __builtin_amdgcn_s_barrier();                        // the layer input in LDS is complete
+  // every stage but the last waits for and reads the start of the next one from inside (gf_stage<.., NEXT>); the first and
+  // the last stage are peeled off the loop (straight-line code: no join at which hipcc would wait for the ring)
+  auto stage = [&](int s, auto first, auto next) __attribute__((always_inline)) {
+    const int nbuf = rbuf + 1 == T::STAGES ? 0 : rbuf + 1;
+    gf_stage<MT, HP, decltype(first)::value, decltype(next)::value>(Ap + (size_t)s * RS * LDA, Ap2 + (size_t)s * RS * LDA,
+                                            Bw + rbuf * GF_STAGE, Bw + nbuf * GF_STAGE, acc, rg, pf);
+    rg.advance();
+    rbuf = nbuf;
+  };
+#if GF_XPF
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  if (nst == 1) {
+    stage(0, yes, no);
+  } else {
+    stage(0, yes, yes);
+    for (int s = 1; s + 1 < nst; ++s) stage(s, no, yes);
+    stage(nst - 1, no, no);
+  }
+#else
+  for (int s = 0; s < nst; ++s) {
+    if (s) gf_wait_vm<(T::STAGES - 2) * GF_NI>();      // my pieces of this stage have landed
+    stage(s, std::true_type{}, std::false_type{});
+  }
+#endif
+#else
   const int boff = fk * NC + wave * (64 * HP) + 2 * fi;
   for (int s = 0; s < nst; ++s) {
     gf_wait_vm<(T::STAGES - 2) * GF_NI>();             // my pieces of this stage have landed
     __builtin_amdgcn_s_barrier();                      // everybody's have; the buffer read last stage is free
-    gf_stage<MT, HP>(Ap + (size_t)s * RS * LDA, Ap2 + (size_t)s * RS * LDA, rg.ring + rbuf * GF_STAGE + boff, acc, rg);
+    const float* Bs = rg.ring + rbuf * GF_STAGE + boff;
+    gf_stage<MT, HP, true, false>(Ap + (size_t)s * RS * LDA, Ap2 + (size_t)s * RS * LDA, Bs, Bs, acc, rg, pf);
     rg.advance();
     rbuf = rbuf + 1 == T::STAGES ? 0 : rbuf + 1;
   }
+#endif
   // ---- epilogue: bias, GLU gating, saved tensors, next layer's input ----------------------------------------------------
   if constexpr (!LAST) __builtin_amdgcn_s_barrier();     // every wave is done reading the activation buffer
   const bool full = m0 + T::BM <= M;                     // wave-uniform: only the last row block of a launch is ragged
@@ -243,7 +368,7 @@ __device__ __forceinline__ void gf_layer(float* As, GfRing& rg, int& rbuf, int n
       }
     }
   }
-  if constexpr (!LAST) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // published by the next layer's first barrier
+  if constexpr (!LAST) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // published by the barrier at the next K loop's entry
   if (GF_ABL & 1) {
     if (acc[0][0][0][0] + acc[MT - 1][HP - 1][1][7] == 1.2345e-30f) As[0] = 1.f;   // keep the accumulators alive
   }
@@ -296,11 +421,30 @@ static __global__ __launch_bounds__(256, 1) void sg_glu_fused_fwd_kernel(const G
     const int KG = g.KG;
     const float* Gp = g.G + (size_t)m0 * KG;
     const int nlive = (M - m0 < T::BM ? M - m0 : T::BM) * KG;
+#if GF_G_BATCH
+    // a thread's elements GF_G_BATCH at a time: all of a batch's loads requested before the first LDS write waits for one
+    // (the one-load-one-write loop paid an L2 round trip per iteration, 9 of them at 64 rows x 36 columns)
+    for (int base = tid; base < T::BM * KG; base += 256 * GF_G_BATCH) {
+      float v[GF_G_BATCH];
+#pragma unroll
+      for (int j = 0; j < GF_G_BATCH; ++j) {
+        const int idx = base + 256 * j;
+        v[j] = Gp[idx < nlive ? idx : 0];
+      }
+#pragma unroll
+      for (int j = 0; j < GF_G_BATCH; ++j) {
+        const int idx = base + 256 * j;
+        const int i = idx / KG, k = idx - i * KG;
+        if (idx < T::BM * KG) As[k * T::LDA + i] = idx < nlive ? v[j] : 0.f;
+      }
+    }
+#else
     for (int idx = tid; idx < T::BM * KG; idx += 256) {
       const int i = idx / KG, k = idx - i * KG;
       const float v = Gp[idx < nlive ? idx : 0];
       As[k * T::LDA + i] = idx < nlive ? v : 0.f;
     }
+#endif
     for (int idx = tid; idx < (g.KP0 - KG) * T::BM; idx += 256) As[(KG + idx / T::BM) * T::LDA + (idx % T::BM)] = 0.f;
   }
   // materialise the biases HERE (the copy loop above has drained the loads anyway): left to the compiler their selects
@@ -309,7 +453,7 @@ static __global__ __launch_bounds__(256, 1) void sg_glu_fused_fwd_kernel(const G
   for (int l = 0; l < 3; ++l)
 #pragma unroll
     for (int h = 0; h < 2; ++h) asm volatile("" : "+v"(bl[l][h]), "+v"(br[l][h]));
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // (the first stage's barrier publishes the buffer)
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // (the barrier at the K loop's entry publishes the buffer)
   int rbuf = 0;
   gf_layer<MT, HP01, false, INF>(As, rg, rbuf, g.nst[0], lane, wave, bl[0], br[0], g.out[r][0], g.gate[r][0], g.cp[r][0], M, m0, g.KA);
   gf_layer<MT, HP01, false, INF>(As, rg, rbuf, g.nst[1], lane, wave, bl[1], br[1], g.out[r][1], g.gate[r][1], g.cp[r][1], M, m0, g.KA);
@@ -364,7 +508,16 @@ static __global__ __launch_bounds__(256) void sg_pack_dgrad_kernel(const GdPackA
     a.wd[r][e] = v;
     return;
   }
+  // first / second product: a wave's 32 nt columns of a weight row are  wave * 32 nt + (nt == 2 ? 2 fi + j : fi).
+  // Position inside the stage: private ring  wave * 1024 + kk * 32 nt + column in the slice  (wave-major, as the forward's
+  // stream);  shared ring  kk * 128 nt + column.  The third product's stages (above) are shared by wave pairs and keep
+  // their order in both forms.
+#if GF_PRIVATE_RING
+  const int kk = (wi % GF_WSLICE) / (32 * nt), p = (wi / GF_WSLICE) * (32 * nt) + wi % (32 * nt);
+  (void)nc;
+#else
   const int kk = wi / nc, p = wi % nc;
+#endif
   int wave, fi, j;
   if (nt == 2) { wave = p >> 6; fi = (p & 63) >> 1; j = p & 1; }
   else { wave = p >> 5; fi = p & 31; j = 0; }
@@ -408,10 +561,36 @@ struct GdTile {
   static constexpr int STAGES = MT == 3 ? 3 : 5;
 };
 
+// first fragments of a stage of the first / second product, carried from the stage before it (GF_XPF; as GfFrag)
+struct GdFrag {
+  float2 a[GF_PF];
+  float c[GF_PF], b[GF_PF][2];
+};
 template <int MT, int NT>
+__device__ __forceinline__ void gd_frag_load(const float* __restrict__ Aq, const float* __restrict__ A2,
+                                             const float* __restrict__ Bs, GdFrag& pf) {
+  constexpr int RS = 32 / NT, STEPS = RS / 2, LDA = GdTile<MT>::LDA, BST = GF_BSTRIDE(128 * NT);
+#pragma unroll
+  for (int st = 0; st < GF_PF && st < STEPS; ++st) {
+    const float2 va = *reinterpret_cast<const float2*>(Aq + 2 * st * LDA);   // (through locals: see gf_stage)
+    pf.a[st].x = va.x; pf.a[st].y = va.y;
+    if constexpr (MT == 3) pf.c[st] = A2[2 * st * LDA];
+    if constexpr (NT == 2) {
+      const float2 b = *reinterpret_cast<const float2*>(Bs + 2 * st * BST);
+      pf.b[st][0] = b.x; pf.b[st][1] = b.y;
+    } else {
+      pf.b[st][0] = Bs[2 * st * BST]; pf.b[st][1] = 0.f;
+    }
+  }
+}
+// NEXT: as in gf_stage -- behind the stage's last DMA piece, wait for this wave's pieces of the next stage and read its
+// first fragments (operand rows + RS, weights at Bn) into pf under the MFMAs that are left.  The saved out / gate loads of
+// the loop's tail (gd_load_batch) are ordinary loads on the same counter: they only make the counted wait cover more.
+template <int MT, int NT, bool NEXT>
 __device__ __forceinline__ void gd_stage(const float* __restrict__ Aq, const float* __restrict__ A2,
-                                         const float* __restrict__ Bs, sg_f32x16 (&acc)[MT][NT], GfRing& rg) {
-  constexpr int NC = 128 * NT, RS = 32 / NT, STEPS = RS / 2, LDA = GdTile<MT>::LDA;
+                                         const float* __restrict__ Bs, const float* __restrict__ Bn,
+                                         sg_f32x16 (&acc)[MT][NT], GfRing& rg, GdFrag& pf) {
+  constexpr int NC = 128 * NT, RS = 32 / NT, STEPS = RS / 2, LDA = GdTile<MT>::LDA, BST = GF_BSTRIDE(NC);
   constexpr int EVERY = STEPS / GF_NI;                 // one DMA piece every EVERY k-steps (2 or 4)
   float2 fa[STEPS];
   float fc[STEPS];
@@ -420,14 +599,21 @@ __device__ __forceinline__ void gd_stage(const float* __restrict__ Aq, const flo
     fa[st] = *reinterpret_cast<const float2*>(Aq + 2 * st * LDA);
     if constexpr (MT == 3) fc[st] = A2[2 * st * LDA];
     if constexpr (NT == 2) {
-      const float2 b = *reinterpret_cast<const float2*>(Bs + 2 * st * NC);
+      const float2 b = *reinterpret_cast<const float2*>(Bs + 2 * st * BST);
       fb[st][0] = b.x; fb[st][1] = b.y;
     } else {
-      fb[st][0] = Bs[2 * st * NC]; fb[st][1] = 0.f;
+      fb[st][0] = Bs[2 * st * BST]; fb[st][1] = 0.f;
     }
   };
 #pragma unroll
-  for (int st = 0; st < GF_PF && st < STEPS; ++st) rd(st);
+  for (int st = 0; st < GF_PF && st < STEPS; ++st) {
+#if GF_CARRY
+    fa[st] = pf.a[st]; fc[st] = MT == 3 ? pf.c[st] : 0.f;
+    fb[st][0] = pf.b[st][0]; fb[st][1] = pf.b[st][1];
+#else
+    rd(st);
+#endif
+  }
 #pragma unroll
   for (int st = 0; st < STEPS; ++st) {
     float a[3];
@@ -438,6 +624,15 @@ __device__ __forceinline__ void gd_stage(const float* __restrict__ Aq, const flo
     __builtin_amdgcn_sched_barrier(0);
     if (!(GF_ABL & 2)) acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[1], fb[st][0], acc[1][0], 0, 0, 0);
     if (!(GF_ABL & 4) && st % EVERY == 0 && st / EVERY < GF_NI) rg.issue(st / EVERY);
+#if GF_CARRY
+    if constexpr (NEXT) {
+      if (st == (GF_NI - 1) * EVERY) {                 // the stage's last piece is out
+        gf_wait_vm<(GdTile<MT>::STAGES - 2) * GF_NI>();
+        __builtin_amdgcn_sched_barrier(0);
+        gd_frag_load<MT, NT>(Aq + RS * LDA, A2 + RS * LDA, Bn, pf);
+      }
+    }
+#endif
     __builtin_amdgcn_sched_barrier(0);
     if (!(GF_ABL & 2)) {
       if constexpr (MT == 3) acc[2][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2], fb[st][0], acc[2][0], 0, 0, 0);
@@ -541,13 +736,62 @@ __device__ __forceinline__ void gd_kloop(const float* As, GfRing& rg, int& rbuf,
   const int fi = lane & 31, fk = lane >> 5;
   const float* Ap = As + fk * T::LDA + 2 * fi;
   const float* Ap2 = As + fk * T::LDA + 64 + fi;
-  const int boff = fk * NC + (NT == 2 ? wave * 64 + 2 * fi : wave * 32 + fi);
   const int nhead = (PJ >= 0 && nst > GD_NB) ? nst - GD_NB : (PJ >= 0 ? 0 : nst);
   int s = 0;
+  GdFrag pf;
+#if GF_PRIVATE_RING
+  // Private ring: NO barrier inside the K loop (gf_layer has the argument in full).  A wave reads only the weight slice its
+  // own pieces filled, behind its own counted vmcnt wait; it re-requests into the buffer of stage s - 1 only from inside
+  // stage s, when its own fragment reads of that buffer have returned (per-wave write-after-read).  ONE barrier at the
+  // entry: the operand buffer (the prologue copy / the LDS rows of the epilogue before this loop, each wave behind its own
+  // lgkmcnt(0)) is complete before the loop's first read of it; the barrier ahead of every epilogue (in the kernel body)
+  // keeps the epilogue from overwriting it under a reader.  The third product (gd_kloop_c) stays on the barrier form: two
+  // waves share a column tile of its weights; its first stage barrier also covers the hand-over from this form.
+  const int boff = wave * GF_WSLICE + fk * (NC / 4) + (NT == 2 ? 2 * fi : fi);
+  gf_wait_vm<(T::STAGES - 2) * GF_NI>();               // my pieces of the loop's first stage have landed
+  __builtin_amdgcn_s_barrier();                        // the operand in LDS is complete
+#if GF_XPF
+  gd_frag_load<MT, NT>(Ap, Ap2, rg.ring + rbuf * GF_STAGE + boff, pf);
+#endif
+  // every stage but the loop's last waits for and reads the start of the next one from inside (gd_stage<.., NEXT>)
+  auto top = [&]() __attribute__((always_inline)) {    // GF_XPF=0: a stage's own wait, where the shared form has it
+#if !GF_XPF
+    if (s) gf_wait_vm<(T::STAGES - 2) * GF_NI>();
+#endif
+  };
+  auto stage = [&](auto next) __attribute__((always_inline)) {
+    const int nbuf = rbuf + 1 == T::STAGES ? 0 : rbuf + 1;
+    gd_stage<MT, NT, decltype(next)::value>(Ap + (size_t)s * RS * T::LDA, Ap2 + (size_t)s * RS * T::LDA,
+                                            rg.ring + rbuf * GF_STAGE + boff, rg.ring + nbuf * GF_STAGE + boff, acc, rg, pf);
+    rg.advance();
+    rbuf = nbuf;
+    ++s;
+  };
+  if constexpr (PJ >= 0) {
+    while (s < nhead) { top(); stage(std::true_type{}); }   // (nhead > 0 only with the full tail behind it)
+    // tail: stage s of the last min(nst, GD_NB) carries batch (GD_NB - (nst - s)); batches a short loop has no stage
+    // for go out ahead of it.  The last batch's stage is the loop's last (peeled: NEXT is a compile-time property)
+    const int first = nst < GD_NB ? GD_NB - nst : 0;
+    auto tail = [&](int b, auto next) __attribute__((always_inline)) {
+      if (b >= first) top();
+      gd_load_batch<MT, NT, PJ>(sv, b, y, gt, CP, M, m0, lane, wave);
+      if constexpr (P2 >= 0) gd_load_batch<MT, NT, P2>(sv2, b, y, gt, CP, M, m0, lane, wave);
+      if (b >= first) stage(next);
+    };
+#pragma unroll
+    for (int b = 0; b < GD_NB - 1; ++b) tail(b, std::true_type{});
+    tail(GD_NB - 1, std::false_type{});
+  } else {
+    while (s + 1 < nhead) { top(); stage(std::true_type{}); }
+    if (s < nhead) { top(); stage(std::false_type{}); }
+  }
+#else
+  const int boff = fk * NC + (NT == 2 ? wave * 64 + 2 * fi : wave * 32 + fi);
   for (; s < nhead; ++s) {
     gf_wait_vm<(T::STAGES - 2) * GF_NI>();
     __builtin_amdgcn_s_barrier();
-    gd_stage<MT, NT>(Ap + (size_t)s * RS * T::LDA, Ap2 + (size_t)s * RS * T::LDA, rg.ring + rbuf * GF_STAGE + boff, acc, rg);
+    const float* Bs = rg.ring + rbuf * GF_STAGE + boff;
+    gd_stage<MT, NT, false>(Ap + (size_t)s * RS * T::LDA, Ap2 + (size_t)s * RS * T::LDA, Bs, Bs, acc, rg, pf);
     rg.advance();
     rbuf = rbuf + 1 == T::STAGES ? 0 : rbuf + 1;
   }
@@ -564,13 +808,15 @@ __device__ __forceinline__ void gd_kloop(const float* As, GfRing& rg, int& rbuf,
       gd_load_batch<MT, NT, PJ>(sv, b, y, gt, CP, M, m0, lane, wave);
       if constexpr (P2 >= 0) gd_load_batch<MT, NT, P2>(sv2, b, y, gt, CP, M, m0, lane, wave);
       if (b >= first) {
-        gd_stage<MT, NT>(Ap + (size_t)s * RS * T::LDA, Ap2 + (size_t)s * RS * T::LDA, rg.ring + rbuf * GF_STAGE + boff, acc, rg);
+        const float* Bs = rg.ring + rbuf * GF_STAGE + boff;
+        gd_stage<MT, NT, false>(Ap + (size_t)s * RS * T::LDA, Ap2 + (size_t)s * RS * T::LDA, Bs, Bs, acc, rg, pf);
         rg.advance();
         rbuf = rbuf + 1 == T::STAGES ? 0 : rbuf + 1;
         ++s;
       }
     }
   }
+#endif
 }
 
 // GLU backward of column tile J of the accumulators: -> d(pre-activation) of the layer below in HBM (pair order) and, when
@@ -673,7 +919,36 @@ static __global__ __launch_bounds__(256, 1) void sg_glu_fused_dgrad_kernel(const
     const int rows = M - m0 < T::BM ? M - m0 : T::BM;
     const int r16 = lane & 15, a4 = lane >> 4;
     const int nkc = (nq + 7) >> 3;                      // chunks of 8 k-quads
-    for (int item = wave; item < (T::BM / 16) * nkc * 2; item += 4) {
+    const int nitem = (T::BM / 16) * nkc * 2;
+#if GF_G_BATCH
+    // as the forward's G copy: a wave's float4 loads GF_G_BATCH at a time, all requested before the first LDS write
+    for (int base = wave; base < nitem; base += 4 * GF_G_BATCH) {
+      float4 v[GF_G_BATCH];
+#pragma unroll
+      for (int j = 0; j < GF_G_BATCH; ++j) {
+        const int item = base + 4 * j;
+        const int par = item & 1, kc = (item >> 1) % nkc, rblk = (item >> 1) / nkc;
+        const int i = 16 * rblk + r16, kq = kc * 8 + 2 * a4 + par;
+        const bool ok = item < nitem && i < rows && kq < nq;
+        v[j] = *reinterpret_cast<const float4*>(src + (ok ? (size_t)i * np2 + 4 * kq : 0));
+      }
+#pragma unroll
+      for (int j = 0; j < GF_G_BATCH; ++j) {
+        const int item = base + 4 * j;
+        const int par = item & 1, kc = (item >> 1) % nkc, rblk = (item >> 1) / nkc;
+        const int i = 16 * rblk + r16, kq = kc * 8 + 2 * a4 + par;
+        const bool ok = i < rows && kq < nq;
+        if (item < nitem && kq < nq) {
+          float* d = As + (4 * kq) * T::LDA + i;
+          d[0] = ok ? v[j].x : 0.f;
+          d[T::LDA] = ok ? v[j].y : 0.f;
+          d[2 * T::LDA] = ok ? v[j].z : 0.f;
+          d[3 * T::LDA] = ok ? v[j].w : 0.f;
+        }
+      }
+    }
+#else
+    for (int item = wave; item < nitem; item += 4) {
       const int par = item & 1, kc = (item >> 1) % nkc, rblk = (item >> 1) / nkc;
       const int i = 16 * rblk + r16, kq = kc * 8 + 2 * a4 + par;
       const bool ok = i < rows && kq < nq;
@@ -686,6 +961,7 @@ static __global__ __launch_bounds__(256, 1) void sg_glu_fused_dgrad_kernel(const
         d[3 * T::LDA] = ok ? v.w : 0.f;
       }
     }
+#endif
     const int kend = g.nstA[r] * RS;
     for (int idx = tid; idx < (kend - np2) * T::BM; idx += 256) As[(np2 + idx / T::BM) * T::LDA + (idx % T::BM)] = 0.f;
   }
