@@ -521,7 +521,7 @@ int stemgnn_fc_tail_train_finish(const float* scratch, int B, int N, int W, int 
  * host sync (capturable in a hipGraph); its count is an integer sum: exact, order-independent, independent of what norm held.
  * Scratch: stemgnn_fc_tail_train_scratch_floats.  SG_EINVAL (nothing launched) on a NULL pointer other than norm / forecast /
  * loss_accum, n == 0, an unknown kind, a Huber param that is not finite or <= 0, or a shape outside the fc tail's range. */
-enum { SG_LOSS_MSE = 0, SG_LOSS_MAE = 1, SG_LOSS_HUBER = 2 };
+enum { SG_LOSS_MSE = 0, SG_LOSS_MAE = 1, SG_LOSS_HUBER = 2, SG_LOSS_PINBALL = 3 };
 int stemgnn_target_valid_count(const float* target, size_t n, float* norm, void* stream);
 int stemgnn_fc_tail_train_loss(const float* fsum, const float* target, const float* w0, const float* b0, const float* w2,
                                const float* b2, int B, int N, int W, int H, int kind, float param, const float* norm,
@@ -532,6 +532,29 @@ int stemgnn_fc_tail_train_rows_loss(const float* fsum, const float* target, cons
                                     float* scratch, float* forecast, float* dfsum, void* stream);
 int stemgnn_fc_tail_train_finish_loss(const float* scratch, int B, int N, int W, int H, const float* norm, float* loss,
                                       double* loss_accum, float* dw0, float* db0, float* dw2, float* db2, void* stream);
+/* The same tail for a QUANTILE head trained by the pinball loss (SG_LOSS_PINBALL: one more instantiation of the same kernel
+ * template; the `_loss` entries above keep refusing kind 3 -- this loss needs Q and the levels).  fc.2 has Q * H output rows, row
+ * j = q * H + h being quantile level taus[q] of horizon step h; forecast (optional) and the fc.2 gradients are [B, Q * H, N] /
+ * [Q * H, W] / [Q * H].  The target stays [B, H, N]: row j reads target[b, j % H, n], nobody replicates it Q times.  With
+ * d = forecast - target and t = taus[j / H]:   l = d >= 0 ? (1 - t) d : -t d ;   dl/dd = 1 - t (d > 0), -t (d < 0), 0 (d == 0);
+ * a NaN d on a valid target stays NaN in both.  loss = sum / (B Q H N) = torch.maximum(t (y - f), (t - 1) (y - f)).mean() with y
+ * broadcast over q.  norm != NULL (stemgnn_target_valid_count of the [B, H, N] target): a NaN target is missing for all Q of its
+ * rows (selected out, never multiplied) and the normaliser is norm[1] / Q; with no valid target the loss and every gradient are
+ * exactly 0.  taus: Q floats in HOST memory, read by the call itself and handed to the kernel by value (nothing to allocate or
+ * keep alive; a captured step carries them in its kernel node).  Same launch count as the `_loss` entries (rows + finish), the
+ * partial-sum kernel is theirs; scratch: stemgnn_fc_tail_train_scratch_floats(B, N, W, Q * H).  `_finish_quantile` needs Q for the
+ * loss scale only.  SG_EINVAL (nothing launched) on a NULL pointer other than norm / forecast / loss_accum, B, N, W, H or Q <= 0,
+ * Q * H or W outside the fc tail's range (stemgnn_fc_tail_supported(W, Q * H)), or a level that is NaN, <= 0 or >= 1. */
+int stemgnn_fc_tail_train_quantile(const float* fsum, const float* target, const float* w0, const float* b0, const float* w2,
+                                   const float* b2, int B, int N, int W, int H, int Q, const float* taus, const float* norm,
+                                   float* scratch, float* forecast, float* loss, double* loss_accum, float* dfsum, float* dw0,
+                                   float* db0, float* dw2, float* db2, void* stream);
+int stemgnn_fc_tail_train_rows_quantile(const float* fsum, const float* target, const float* w0, const float* b0,
+                                        const float* w2, const float* b2, int B, int N, int W, int H, int Q, const float* taus,
+                                        const float* norm, float* scratch, float* forecast, float* dfsum, void* stream);
+int stemgnn_fc_tail_train_finish_quantile(const float* scratch, int B, int N, int W, int H, int Q, const float* norm,
+                                          float* loss, double* loss_accum, float* dw0, float* db0, float* dw2, float* db2,
+                                          void* stream);
 /* Zero `bytes` bytes at `ptr` in stream order, as a KERNEL launch (the reference's zero_grad, models/handler.py:160, when it is
  * not fused into the optimizer kernel; control words).  The step path never uses hipMemsetAsync: inside a captured hipGraph
  * a memset node was seen to run into the kernel node that follows it. */
@@ -633,6 +656,33 @@ int stemgnn_eval_metrics(const float* target, const float* forecast, const doubl
 size_t stemgnn_eval_scratch_doubles_masked(long count, int H, int N);
 int stemgnn_eval_metrics_masked(const float* target, const float* forecast, const double* mul, const double* add,
                                 long count, int H, int N, double* scratch, double* out, void* stream);
+
+/* ---- quantile forecasts (a model with Q output rows per horizon step; csrc/data.hip) ---------------------------------
+ * stemgnn_roll_window for a quantile forecast [B, Q, L, N]: inputs_next is built from the POINT row (forecast[b, point]) exactly
+ * as stemgnn_roll_window builds it, and forecast_steps [B, Q, horizon, N] receives all Q rows:
+ * forecast_steps[b, q, step + j, :] = forecast[b, q, j, :] for j < min(horizon - step, L).  The argument checks of
+ * stemgnn_roll_window, plus Q > 0 and 0 <= point < Q. */
+int stemgnn_roll_window_quantile(const float* inputs, const float* forecast, float* inputs_next, float* forecast_steps, int B,
+                                 int W, int L, int N, int Q, int point, int step, int horizon, void* stream);
+/* Calibration metrics of a quantile forecast: target [count, H, N], forecast [count, Q, H, N], both fp32; taus = Q doubles in
+ * HOST memory (levels in (0, 1), Q <= 32); optional de-normalisation v * mul[n] + add[n] in fp64 ahead of everything else, as in
+ * stemgnn_eval_metrics.  One fp64 pass with fixed-order two-level sums (no atomics).  With P = Q / 2 and K = 2 Q + 2 P + 1,
+ * out (fp64) = overall[K] | by_step[K][H], where the K statistics are
+ *   [0, Q)            mean pinball loss of level q (l as in stemgnn_fc_tail_train_quantile, in fp64)
+ *   [Q, 2Q)           empirical coverage of level q: the share of target <= forecast_q
+ *   [2Q, 2Q + P)      interval coverage of the pair (i, Q - 1 - i): the share of forecast_i <= target <= forecast_{Q-1-i}
+ *   [2Q + P, 2Q + 2P) mean width forecast_{Q-1-i} - forecast_i of that pair
+ *   2Q + 2P           crossing rate: the share of elements whose Q forecasts are not non-decreasing in q.
+ * `_masked`: an element whose target is NaN is left out everywhere and every mean divides by its slice's valid count; a slice
+ * with nothing valid is NaN.  SG_EINVAL (nothing launched) on a NULL pointer other than mul / add, mul without add, count, Q, H
+ * or N <= 0, Q > 32, or a level that is NaN, <= 0 or >= 1; the size entries return 0 for such shapes. */
+size_t stemgnn_quantile_scratch_doubles(long count, int Q, int H, int N);
+size_t stemgnn_quantile_out_doubles(int Q, int H);
+int stemgnn_quantile_metrics(const float* target, const float* forecast, const double* taus, const double* mul,
+                             const double* add, long count, int Q, int H, int N, double* scratch, double* out, void* stream);
+int stemgnn_quantile_metrics_masked(const float* target, const float* forecast, const double* taus, const double* mul,
+                                    const double* add, long count, int Q, int H, int N, double* scratch, double* out,
+                                    void* stream);
 
 #ifdef __cplusplus
 }

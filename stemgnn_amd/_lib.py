@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("STEMGNN_HIP_LIB", os.path.join(_HERE, "libstemgnn_hip
 SG_BLOCK_NPARAMS = 33
 SG_EINVAL = -10001
 SG_LOSS = {"mse": 0, "mae": 1, "huber": 2}    # SG_LOSS_* in include/stemgnn_hip.h
+SG_LOSS_PINBALL = 3                           # the quantile head's loss: its own `_quantile` entries, not a `_loss` kind
 # bits of stemgnn_block_paths (SG_PATH_* in include/stemgnn_hip.h)
 SG_PATH = {"glu_fwd_fused": 1, "glu_dgrad_fused": 2, "heads_fwd_fused": 4, "heads_bwd_fused": 8, "heads_bwd_16w": 16,
            "long_k": 32, "wgrad_fused": 64, "glu_wgrad_fused": 128}
@@ -154,6 +155,16 @@ SIGNATURES = {
     "stemgnn_fc_tail_train_rows_loss": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P,
                                                 _P, _P]),
     "stemgnn_fc_tail_train_finish_loss": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "stemgnn_fc_tail_train_quantile": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), _P,
+                                               _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "stemgnn_fc_tail_train_rows_quantile": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, POINTER(c_float),
+                                                    _P, _P, _P, _P, _P]),
+    "stemgnn_fc_tail_train_finish_quantile": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "stemgnn_roll_window_quantile": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "stemgnn_quantile_scratch_doubles": (c_size_t, [c_long, c_int, c_int, c_int]),
+    "stemgnn_quantile_out_doubles": (c_size_t, [c_int, c_int]),
+    "stemgnn_quantile_metrics": (c_int, [_P, _P, POINTER(c_double), _P, _P, c_long, c_int, c_int, c_int, _P, _P, _P]),
+    "stemgnn_quantile_metrics_masked": (c_int, [_P, _P, POINTER(c_double), _P, _P, c_long, c_int, c_int, c_int, _P, _P, _P]),
     "stemgnn_infer_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
     "stemgnn_infer_workspace_split_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "stemgnn_gru_fwd_infer": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
@@ -197,6 +208,11 @@ def check(rc, what):
         if rc == SG_EINVAL:
             raise StemGNNHipError(f"{what}: invalid argument (SG_EINVAL)")
         raise StemGNNHipError(f"{what}: HIP error {-rc}")
+
+
+def host_floats(values, ctype=c_float):
+    """host array of the quantile levels (`taus` of the `_quantile` entries: read by the call itself, in host memory)."""
+    return (ctype * len(values))(*[float(v) for v in values])
 
 
 def ptr_array(tensors):

@@ -19,11 +19,27 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from .ops import FcTail, FcTailMse, GruFront, SpectralHotPath, StockBlockFn
+from .ops import FcTail, FcTailMse, FcTailQuantile, GruFront, SpectralHotPath, StockBlockFn
 
 _instance_counter = itertools.count()
 _BLOCK_FIELDS = ("forecast", "forecast_result", "backcast", "backcast_short_cut")
 _FC_TAIL_MAX_W, _FC_TAIL_MAX_H = 64, 32      # stemgnn_fc_tail_supported (csrc/tail.hip): both weight matrices of a row block in LDS
+
+
+def check_quantiles(quantiles):
+    """The levels of a quantile head as a tuple of floats: Q >= 1, each strictly inside (0, 1), strictly increasing."""
+    try:
+        q = tuple(float(t) for t in quantiles)
+    except (TypeError, ValueError):
+        raise ValueError(f"quantiles={quantiles!r}: expected a sequence of floats") from None
+    if len(q) < 1 or not all(0.0 < t < 1.0 for t in q) or any(b <= a for a, b in zip(q, q[1:])):
+        raise ValueError(f"quantiles={quantiles!r}: expected at least one level, each in (0, 1), strictly increasing")
+    return q
+
+
+def point_index(quantiles):
+    """Index of the level closest to 0.5 (the lower index on a tie): the row that stands for the point forecast."""
+    return min(range(len(quantiles)), key=lambda i: (abs(quantiles[i] - 0.5), i))
 
 
 class GLU(nn.Module):
@@ -88,8 +104,17 @@ class StockBlockLayer(nn.Module):
 
 
 class Model(nn.Module):
+    """`quantiles=(tau_0, ..., tau_{Q-1})` (keyword only; strictly increasing, each in (0, 1)) gives the model a quantile
+    HEAD: ``fc[2]`` becomes ``nn.Linear(time_step, Q * horizon)`` -- row q * horizon + h is level tau_q of step h -- and forward /
+    predict return the forecast as [B, Q, H, N], a view of the [B, Q*H, N] tensor the fc-tail kernels write.  Everything up to
+    the fc tail is the plain model (same parameters, same creation order: fc.2 is the last one created, so under one
+    torch.manual_seed every other parameter equals the plain model's).  ``loss(..., kind="pinball")`` trains all Q rows jointly;
+    ``point_index`` is the row closest to the median.  None (default): the model as it is without the keyword."""
+    quantiles = None          # class-level defaults: a whole-module pickle from before the keyword unpickles as a plain model
+    point_index = 0
+
     def __init__(self, units, stack_cnt, time_step, multi_layer, horizon=1, dropout_rate=0.5, leaky_rate=0.2,
-                 device='cpu'):
+                 device='cpu', *, quantiles=None):
         super().__init__()
         # Like the reference, the constructor builds `stack_cnt` blocks for ANY count (:93-95) -- same state_dict -- and it is
         # forward that only works for 2: it sums result[0] + result[1] (:174) and block >= 1 hands None on as the next
@@ -102,6 +127,14 @@ class Model(nn.Module):
             raise _lib.StemGNNHipError(
                 f"Model(time_step={time_step}, horizon={horizon}): the fc tail kernels (csrc/tail.hip) cover time_step <= "
                 f"{_FC_TAIL_MAX_W} and horizon <= {_FC_TAIL_MAX_H}; stemgnn_amd has no torch fallback for larger ones")
+        if quantiles is not None:
+            quantiles = check_quantiles(quantiles)
+            if len(quantiles) * horizon > _FC_TAIL_MAX_H:
+                raise _lib.StemGNNHipError(
+                    f"Model(time_step={time_step}, horizon={horizon}, quantiles of {len(quantiles)} levels): the fc tail kernels "
+                    f"(csrc/tail.hip) cover time_step <= {_FC_TAIL_MAX_W} and len(quantiles) * horizon <= {_FC_TAIL_MAX_H}; "
+                    "stemgnn_amd has no torch fallback for larger ones")
+            self.quantiles, self.point_index = quantiles, point_index(quantiles)
         self.dropout_rate = float(dropout_rate)
         self.weight_key = nn.Parameter(torch.zeros(units, 1))
         nn.init.xavier_uniform_(self.weight_key.data, gain=1.414)
@@ -110,7 +143,8 @@ class Model(nn.Module):
         self.GRU = nn.GRU(time_step, units)
         self.stock_block = nn.ModuleList(
             StockBlockLayer(time_step, units, multi_layer, stack_cnt=i) for i in range(stack_cnt))
-        self.fc = nn.Sequential(nn.Linear(time_step, time_step), nn.LeakyReLU(), nn.Linear(time_step, horizon))
+        self.fc = nn.Sequential(nn.Linear(time_step, time_step), nn.LeakyReLU(),
+                                nn.Linear(time_step, horizon * (len(quantiles) if quantiles is not None else 1)))
         self._seed = None          # device uint64[2] {seed, offset} of the dropout Philox stream (not a parameter)
         self._instance = next(_instance_counter)
         self.hot_state = ops.HotPathState()     # per-model scheduling mode (direct gradients / side-stream overlap)
@@ -295,15 +329,24 @@ class Model(nn.Module):
         graph rides on this fused node: ``torch.autograd.backward([loss, penalty], [one, one])`` (engine.TrainStep's
         ``attention_penalty``) or ``(loss + penalty).backward()`` without `unit_grad`.
         `kind`: "mse" (default), "mae" (``nn.L1Loss``) or "huber" (``nn.HuberLoss(delta=huber_delta)``), all on the same fused
-        node.  `ignore_nan`: a NaN in `target` is a missing reading -- it contributes to neither the loss nor any gradient, and
+        node; "pinball" on a quantile model (and only there; the other kinds are refused on one): the mean over B Q H N of the
+        pinball loss of row (q, h) at its level against target [B,H,N] -- the target is not replicated.
+        `ignore_nan`: a NaN in `target` is a missing reading -- it contributes to neither the loss nor any gradient, and
         the loss is the mean over the valid targets (0, with zero gradients, when there is none); one more launch
         (``ops.target_valid_count``).  Only NaN means missing (+-inf does not), and a NaN *forecast* on a valid target still
         propagates (the optimizers' ``skip_nonfinite`` is for that).  Data parallel: every rank normalises by its own count,
         and the gradient all-reduce averages the ranks -- a mean of per-rank masked means.
         `adjacency`: run from a given graph instead of the GRU + attention front (graph_path: no gradient for GRU / key / query,
         exact-fp32 GLU layers); the fused tail then runs both its launches in place -- nothing is left for a later backward."""
-        if kind not in _lib.SG_LOSS:
-            raise ValueError(f"unknown loss kind {kind!r}: one of {sorted(_lib.SG_LOSS)}")
+        if kind == "pinball":
+            if self.quantiles is None:
+                raise ValueError("kind='pinball' needs a quantile head: Model(..., quantiles=(...))")
+        elif kind not in _lib.SG_LOSS:
+            raise ValueError(f"unknown loss kind {kind!r}: one of {sorted(_lib.SG_LOSS)}"
+                             + (" or 'pinball'" if self.quantiles is not None else ""))
+        elif self.quantiles is not None:
+            raise ValueError(f"kind={kind!r} on a quantile model: the target is [B,H,N] and the head has Q * H rows -- "
+                             "use kind='pinball'")
         self._require_fc_tail()
         if adjacency is None:
             fsum, attention, _ = self.hot_path(x)
@@ -311,9 +354,14 @@ class Model(nn.Module):
             fsum, attention = self.graph_path(x, adjacency)
         self.hot_state.tail_may_defer = adjacency is None
         try:
-            loss = FcTailMse.apply(fsum, target, self.fc[0].weight, self.fc[0].bias, self.fc[2].weight, self.fc[2].bias,
-                                   self.hot_state, loss_out, accum, bool(unit_grad) and torch.is_grad_enabled(), kind,
-                                   float(huber_delta) if kind == "huber" else 0.0, bool(ignore_nan))
+            if kind == "pinball":
+                loss = FcTailQuantile.apply(fsum, target, self.fc[0].weight, self.fc[0].bias, self.fc[2].weight,
+                                            self.fc[2].bias, self.hot_state, loss_out, accum,
+                                            bool(unit_grad) and torch.is_grad_enabled(), self.quantiles, bool(ignore_nan))
+            else:
+                loss = FcTailMse.apply(fsum, target, self.fc[0].weight, self.fc[0].bias, self.fc[2].weight, self.fc[2].bias,
+                                       self.hot_state, loss_out, accum, bool(unit_grad) and torch.is_grad_enabled(), kind,
+                                       float(huber_delta) if kind == "huber" else 0.0, bool(ignore_nan))
         finally:
             self.hot_state.tail_may_defer = True
         return (loss, attention) if return_attention else loss
@@ -321,12 +369,13 @@ class Model(nn.Module):
     def _require_fc_tail(self):
         """The fc tail kernels (csrc/tail.hip) keep both weight matrices of a row block in LDS: time_step <= 64 and
         horizon <= 32 (every BASELINE configuration; the reference's own runs use 12 / 3).  No torch fallback exists."""
-        if not _lib.load().stemgnn_fc_tail_supported(self.time_step, self.horizon):
+        rows = self.horizon * (len(self.quantiles) if self.quantiles is not None else 1)
+        if not _lib.load().stemgnn_fc_tail_supported(self.time_step, rows):
             raise _lib.StemGNNHipError(f"fc tail: time_step={self.time_step}, horizon={self.horizon} outside the HIP kernels' "
                                        "range (time_step <= 64, horizon <= 32); stemgnn_amd has no torch fallback")
 
     def predict(self, x, adjacency=None):
-        """Inference forward: ``(forecast [B,H,N], attention [N,N])``, bit-identical to ``self.eval(); self(x)`` under
+        """Inference forward: ``(forecast [B,H,N], attention [N,N])`` ([B,Q,H,N] for a quantile model), bit-identical to ``self.eval(); self(x)`` under
         ``torch.no_grad()``, with nothing stored for a backward pass (ops.forecast_forward: the _infer kernels of
         include/stemgnn_hip.h).  Eval semantics whatever ``self.training`` is (no dropout); ``self.training``, the dropout
         stream and ``self.hot_state`` are neither read nor changed, so a call between two training steps leaves training
@@ -340,13 +389,20 @@ class Model(nn.Module):
         g = self.GRU
         blocks = self.stock_block[0].hip_params() + self.stock_block[1].hip_params()
         with torch.no_grad():
-            return ops.forecast_forward(x, (g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0), self.weight_key,
-                                        self.weight_query, self.multi_layer, self.alpha, self.dropout_rate, blocks,
-                                        (self.fc[0].weight, self.fc[0].bias, self.fc[2].weight, self.fc[2].bias),
-                                        adjacency=adjacency)
+            forecast, attention = ops.forecast_forward(
+                x, (g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0), self.weight_key, self.weight_query,
+                self.multi_layer, self.alpha, self.dropout_rate, blocks,
+                (self.fc[0].weight, self.fc[0].bias, self.fc[2].weight, self.fc[2].bias), adjacency=adjacency)
+        return self._quantile_view(forecast), attention
+
+    def _quantile_view(self, forecast):
+        """[B, Q*H, N] as the fc tail writes it -> [B, Q, H, N] for a quantile model (a view: no copy, no kernel)."""
+        if self.quantiles is None:
+            return forecast
+        return forecast.view(forecast.shape[0], len(self.quantiles), self.horizon, forecast.shape[2])
 
     def forward(self, x, adjacency=None):
-        """(forecast [B,H,N], attention [N,N]).  `adjacency`: see graph_path."""
+        """(forecast [B,H,N] -- [B,Q,H,N] for a quantile model --, attention [N,N]).  `adjacency`: see graph_path."""
         self._require_fc_tail()
         if adjacency is None:
             fsum, attention, _ = self.hot_path(x)
@@ -354,5 +410,5 @@ class Model(nn.Module):
             fsum, attention = self.graph_path(x, adjacency)
         # fused fc tail (csrc/tail.hip, models/base_model.py:175-179): Linear - LeakyReLU - Linear and the permute to [B,H,N]
         # in one kernel; for H == 1 the reference's unsqueeze/squeeze (:176-177) yields the same [B,1,N] tensor
-        return FcTail.apply(fsum, self.fc[0].weight, self.fc[0].bias, self.fc[2].weight, self.fc[2].bias,
-                            self.hot_state), attention
+        return self._quantile_view(FcTail.apply(fsum, self.fc[0].weight, self.fc[0].bias, self.fc[2].weight, self.fc[2].bias,
+                                                self.hot_state)), attention

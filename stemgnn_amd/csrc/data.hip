@@ -279,6 +279,40 @@ extern "C" int stemgnn_roll_window(const float* inputs, const float* forecast, f
   return 0;
 }
 
+// The same iteration for a quantile forecast [B,Q,L,N]: the window rows come from the POINT row forecast[b, point] exactly as
+// above, and all Q rows go to forecast_steps [B,Q,horizon,N].  r < W: window row; r >= W: row (q, j) = ((r - W) / L, (r - W) % L).
+__global__ void sg_roll_window_quantile_kernel(const float* __restrict__ inputs, const float* __restrict__ forecast,
+                                               float* __restrict__ inputs_next, float* __restrict__ forecast_steps, int W, int L,
+                                               int N, int Q, int point, int step, int horizon) {
+  const int r = blockIdx.x, b = blockIdx.y;
+  const int take = min(horizon - step, L);
+  const float* src;
+  float* dst;
+  if (r < W) {
+    src = r < W - L ? inputs + ((size_t)b * W + r + L) * N
+                    : forecast + (((size_t)b * Q + point) * L + (r - (W - L))) * N;
+    dst = inputs_next + ((size_t)b * W + r) * N;
+  } else {
+    const int q = (r - W) / L, j = (r - W) - q * L;
+    if (j >= take) return;
+    src = forecast + (((size_t)b * Q + q) * L + j) * N;
+    dst = forecast_steps + (((size_t)b * Q + q) * horizon + step + j) * N;
+  }
+  for (int i = threadIdx.x; i < N; i += blockDim.x) dst[i] = src[i];
+}
+
+extern "C" int stemgnn_roll_window_quantile(const float* inputs, const float* forecast, float* inputs_next,
+                                            float* forecast_steps, int B, int W, int L, int N, int Q, int point, int step,
+                                            int horizon, void* stream) {
+  if (!inputs || !forecast || !inputs_next || !forecast_steps || inputs == inputs_next) return SG_EINVAL;
+  if (B <= 0 || W <= 0 || N <= 0 || L <= 0 || L > W || step < 0 || step >= horizon) return SG_EINVAL;
+  if (Q <= 0 || point < 0 || point >= Q || B > 65535 || (long long)Q * L > (1 << 20)) return SG_EINVAL;
+  hipLaunchKernelGGL(sg_roll_window_quantile_kernel, dim3(W + Q * L, B), dim3(N >= 256 ? 256 : 64), 0, (hipStream_t)stream,
+                     inputs, forecast, inputs_next, forecast_steps, W, L, N, Q, point, step, horizon);
+  SG_TRY(hipGetLastError());
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // result slabs of a replayed rolling forecast (engine.ForecastStep): rows pos[0] + b of out_forecast / out_target [capacity, H, N]
 // := forecast / target [b] -- the position is the window queue's, read on the device (no per-batch host copy)
@@ -456,4 +490,153 @@ extern "C" int stemgnn_eval_metrics(const float* target, const float* forecast, 
 extern "C" int stemgnn_eval_metrics_masked(const float* target, const float* forecast, const double* mul, const double* add,
                                            long count, int H, int N, double* scratch, double* out, void* stream) {
   return eval_metrics_impl<true>(target, forecast, mul, add, count, H, N, scratch, out, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Calibration metrics of a quantile forecast (include/stemgnn_hip.h: stemgnn_quantile_metrics), in the style of the pass above:
+// target [count,H,N], forecast [count,Q,H,N]; K = 2Q + 2P + 1 statistics (P = Q / 2) plus one plane that counts the elements
+// kept.  Stage 1: thread = column c = (h, n) of one row chunk; blockIdx.z picks what it sums -- z < Q: level z (pinball sum,
+// target <= forecast count); Q <= z < Q + P: pair (i, Q-1-i) (inside count, width sum); z = Q + P: the crossing count and the
+// kept count.  No thread holds more than two sums, so no per-thread array whatever Q is.  Stage 2 (one workgroup): chunk sums ->
+// column sums -> per-step sums over n -> overall sums over h, each a fixed-order loop; every mean = sum / the kept count of its
+// slice (0 / 0 = NaN for a slice with nothing valid).
+struct SgTausD { double v[32]; };
+
+template <bool MASKED>
+__global__ __launch_bounds__(256) void sg_quantile_partial_kernel(const float* __restrict__ target,
+                                                                  const float* __restrict__ forecast, SgTausD taus,
+                                                                  const double* __restrict__ mul,
+                                                                  const double* __restrict__ add, long count, int Q, int HN,
+                                                                  int N, double* __restrict__ part) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= HN) return;
+  const int P = Q / 2, z = blockIdx.z;
+  const long r0 = (long)blockIdx.y * EVAL_CHUNK_ROWS;
+  const long r1 = min(count, r0 + (long)EVAL_CHUNK_ROWS);
+  const int n = c % N;
+  const bool dn = mul != nullptr;
+  const double mu = dn ? mul[n] : 1.0, ad = dn ? add[n] : 0.0;
+  const size_t nchunk = gridDim.y;
+  double s0 = 0.0, s1 = 0.0;
+  int k0, k1;
+  if (z < Q) {
+    const double tau = taus.v[z];
+    k0 = z, k1 = Q + z;
+    for (long r = r0; r < r1; ++r) {
+      double t = (double)target[(size_t)r * HN + c], f = (double)forecast[((size_t)r * Q + z) * HN + c];
+      if (MASKED && t != t) continue;
+      if (dn) {
+        t = __dadd_rn(__dmul_rn(t, mu), ad);
+        f = __dadd_rn(__dmul_rn(f, mu), ad);
+      }
+      const double d = __dsub_rn(f, t);
+      s0 += d >= 0.0 ? __dmul_rn(1.0 - tau, d) : __dmul_rn(-tau, d);
+      s1 += t <= f ? 1.0 : 0.0;
+    }
+  } else if (z < Q + P) {
+    const int i = z - Q, j = Q - 1 - i;
+    k0 = 2 * Q + i, k1 = 2 * Q + P + i;
+    for (long r = r0; r < r1; ++r) {
+      double t = (double)target[(size_t)r * HN + c];
+      double lo = (double)forecast[((size_t)r * Q + i) * HN + c], hi = (double)forecast[((size_t)r * Q + j) * HN + c];
+      if (MASKED && t != t) continue;
+      if (dn) {
+        t = __dadd_rn(__dmul_rn(t, mu), ad);
+        lo = __dadd_rn(__dmul_rn(lo, mu), ad);
+        hi = __dadd_rn(__dmul_rn(hi, mu), ad);
+      }
+      s0 += (lo <= t && t <= hi) ? 1.0 : 0.0;
+      s1 += __dsub_rn(hi, lo);
+    }
+  } else {
+    k0 = 2 * Q + 2 * P, k1 = k0 + 1;
+    for (long r = r0; r < r1; ++r) {
+      const double t = (double)target[(size_t)r * HN + c];
+      if (MASKED && t != t) continue;
+      bool cross = false;
+      double prev = 0.0;
+      for (int q = 0; q < Q; ++q) {
+        double f = (double)forecast[((size_t)r * Q + q) * HN + c];
+        if (dn) f = __dadd_rn(__dmul_rn(f, mu), ad);
+        if (q > 0 && f < prev) cross = true;
+        prev = f;
+      }
+      s0 += cross ? 1.0 : 0.0;
+      s1 += 1.0;
+    }
+  }
+  part[((size_t)k0 * nchunk + blockIdx.y) * HN + c] = s0;
+  part[((size_t)k1 * nchunk + blockIdx.y) * HN + c] = s1;
+}
+
+__global__ __launch_bounds__(256) void sg_quantile_final_kernel(const double* __restrict__ part, int nchunk, int K, int H, int N,
+                                                                double* __restrict__ colsum, double* __restrict__ out) {
+  const int HN = H * N, K1 = K + 1;                                // plane K: the kept counts
+  double* stepsum = colsum + (size_t)K1 * HN;                      // [K1][H]
+  for (int i = threadIdx.x; i < K1 * HN; i += blockDim.x) {
+    const int k = i / HN, c = i - k * HN;
+    double s = 0.0;
+    for (int j = 0; j < nchunk; ++j) s += part[((size_t)k * nchunk + j) * HN + c];
+    colsum[i] = s;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < K1 * H; i += blockDim.x) {
+    double s = 0.0;
+    for (int n = 0; n < N; ++n) s += colsum[(size_t)i * N + n];      // i = k * H + h
+    stepsum[i] = s;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < K * H; i += blockDim.x) out[K + i] = stepsum[i] / stepsum[(size_t)K * H + i % H];
+  for (int k = threadIdx.x; k < K; k += blockDim.x) {
+    double s = 0.0, cnt = 0.0;
+    for (int h = 0; h < H; ++h) s += stepsum[(size_t)k * H + h];
+    for (int h = 0; h < H; ++h) cnt += stepsum[(size_t)K * H + h];
+    out[k] = s / cnt;
+  }
+}
+
+static inline int quantile_nstat(int Q) { return 2 * Q + 2 * (Q / 2) + 1; }
+extern "C" size_t stemgnn_quantile_scratch_doubles(long count, int Q, int H, int N) {
+  if (count <= 0 || Q <= 0 || Q > 32 || H <= 0 || N <= 0) return 0;
+  const size_t K1 = (size_t)quantile_nstat(Q) + 1;
+  return K1 * H * N * ((size_t)eval_nchunk(count) + 1) + K1 * H;
+}
+extern "C" size_t stemgnn_quantile_out_doubles(int Q, int H) {
+  if (Q <= 0 || Q > 32 || H <= 0) return 0;
+  return (size_t)quantile_nstat(Q) * ((size_t)H + 1);
+}
+
+template <bool MASKED>
+static int quantile_metrics_impl(const float* target, const float* forecast, const double* taus, const double* mul,
+                                 const double* add, long count, int Q, int H, int N, double* scratch, double* out,
+                                 void* stream) {
+  if (!target || !forecast || !taus || !scratch || !out || count <= 0 || Q <= 0 || Q > 32 || H <= 0 || N <= 0) return SG_EINVAL;
+  if ((mul == nullptr) != (add == nullptr)) return SG_EINVAL;
+  if ((long long)H * N > (1ll << 30) / (quantile_nstat(Q) + 1)) return SG_EINVAL;       // the final kernel's int indices
+  SgTausD t;
+  for (int q = 0; q < 32; ++q) t.v[q] = 0.5;
+  for (int q = 0; q < Q; ++q) {
+    if (!(taus[q] > 0.0 && taus[q] < 1.0)) return SG_EINVAL;        // NaN fails both
+    t.v[q] = taus[q];
+  }
+  const int HN = H * N, nchunk = eval_nchunk(count), K = quantile_nstat(Q);
+  if (nchunk > 65535) return SG_EINVAL;
+  double* part = scratch;
+  double* colsum = scratch + (size_t)(K + 1) * HN * nchunk;
+  hipLaunchKernelGGL(sg_quantile_partial_kernel<MASKED>, dim3((HN + 255) / 256, nchunk, Q + Q / 2 + 1), dim3(256), 0,
+                     (hipStream_t)stream, target, forecast, t, mul, add, count, Q, HN, N, part);
+  SG_TRY(hipGetLastError());
+  hipLaunchKernelGGL(sg_quantile_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, part, nchunk, K, H, N, colsum, out);
+  SG_TRY(hipGetLastError());
+  return 0;
+}
+extern "C" int stemgnn_quantile_metrics(const float* target, const float* forecast, const double* taus, const double* mul,
+                                        const double* add, long count, int Q, int H, int N, double* scratch, double* out,
+                                        void* stream) {
+  return quantile_metrics_impl<false>(target, forecast, taus, mul, add, count, Q, H, N, scratch, out, stream);
+}
+extern "C" int stemgnn_quantile_metrics_masked(const float* target, const float* forecast, const double* taus, const double* mul,
+                                               const double* add, long count, int Q, int H, int N, double* scratch, double* out,
+                                               void* stream) {
+  return quantile_metrics_impl<true>(target, forecast, taus, mul, add, count, Q, H, N, scratch, out, stream);
 }

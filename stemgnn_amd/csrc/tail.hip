@@ -211,6 +211,13 @@ constexpr int TRAIN_RQ = 256 / TRAIN_RB;
 // missing one -- its d is SELECTED to 0 (never multiplied), so it adds nothing to the loss or to any gradient whatever the
 // forecast holds there, and the normaliser is norm[1] = 1 / (valid targets) from stemgnn_target_valid_count (0 when there is
 // none: loss and gradients are then exactly 0).  <MSE, false> is the kernel as it was before the template, bit for bit.
+// SG_LOSS_PINBALL (a quantile head): the tail has H = Q * HT output rows, row j = q * HT + h is level tau[q] of horizon step h
+// and reads target[b, j % HT, n] of the [B, HT, N] target (never replicated); l = d >= 0 ? (1 - tau) d : -tau d, derivative
+// 1 - tau | -tau | 0 at d == 0 (the MAE convention; a NaN d stays NaN), mean over B Q HT N; MASKED: normaliser norm[1] / Q.
+// The levels travel BY VALUE in the kernel arguments (SgTaus, 128 bytes: Q <= Q * HT <= TAIL_MAXH): nothing to allocate, copy or
+// keep alive around a launch that may be deferred to another stream, and a captured step holds them in its kernel node -- a
+// device buffer owned by the model would have bought nothing but a lifetime to get wrong.  The other kinds never read them.
+struct SgTaus { float v[32]; };
 __device__ __forceinline__ bool sg_is_nan_bits(float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; }
 
 template <int KIND, bool MASKED>
@@ -219,7 +226,8 @@ __global__ __launch_bounds__(256) void sg_fc_tail_train_kernel(const float* __re
                                                                const float* __restrict__ w2, const float* __restrict__ b2,
                                                                int B, int N, int W, int H, float param,
                                                                const float* __restrict__ norm, float* __restrict__ forecast,
-                                                               float* __restrict__ dfsum, float* __restrict__ partial) {
+                                                               float* __restrict__ dfsum, float* __restrict__ partial, int HT,
+                                                               SgTaus taus) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int nacc = W * W + W + H * W + H;
   float* sw0 = sm;
@@ -253,18 +261,21 @@ __global__ __launch_bounds__(256) void sg_fc_tail_train_kernel(const float* __re
   {
     const int mc = m < M ? m : 0, b = mc / N, n = mc - b * N;
     float scale;                                         // d(loss)/d(l) of one element, times 2 for MSE (dl/dd = 2 d)
-    if constexpr (MASKED) scale = (KIND == SG_LOSS_MSE ? 2.f : 1.f) * norm[1];
+    if constexpr (MASKED && KIND == SG_LOSS_PINBALL) scale = norm[1] / (float)(H / HT);
+    else if constexpr (MASKED) scale = (KIND == SG_LOSS_MSE ? 2.f : 1.f) * norm[1];
     else scale = (KIND == SG_LOSS_MSE ? 2.f : 1.f) / ((float)B * (float)H * (float)N);
     for (int h = q; h < H; h += TRAIN_RQ) {
       float y = sb2[h];
       for (int t = 0; t < W; ++t) y = fmaf(sa[r * (W + 1) + t], sw2[h * W + t], y);
       const size_t o = ((size_t)b * H + h) * N + n;
+      size_t ot = o;                                       // the target's element: [B,HT,N] under the Q * HT rows of a quantile head
+      if constexpr (KIND == SG_LOSS_PINBALL) ot = ((size_t)b * HT + h % HT) * N + n;
       float d;
       if constexpr (MASKED) {
-        const float tv = m < M ? target[o] : 0.f;
+        const float tv = m < M ? target[ot] : 0.f;
         d = (m < M && !sg_is_nan_bits(tv)) ? y - tv : 0.f;
       } else {
-        d = m < M ? y - target[o] : 0.f;
+        d = m < M ? y - target[ot] : 0.f;
       }
       if (m < M && forecast) forecast[o] = y;
       if constexpr (KIND == SG_LOSS_MSE) {
@@ -273,6 +284,10 @@ __global__ __launch_bounds__(256) void sg_fc_tail_train_kernel(const float* __re
       } else if constexpr (KIND == SG_LOSS_MAE) {            // a NaN d (NaN forecast on a valid target) stays NaN in both
         sq += fabsf(d);
         sdy[r * (H + 1) + h] = d > 0.f ? scale : (d < 0.f ? -scale : d * scale);
+      } else if constexpr (KIND == SG_LOSS_PINBALL) {
+        const float tau = taus.v[h / HT], up = (1.f - tau) * scale, dn = -tau * scale;
+        sq += d >= 0.f ? (1.f - tau) * d : -tau * d;          // NaN d: the second arm, NaN
+        sdy[r * (H + 1) + h] = d > 0.f ? up : (d < 0.f ? dn : d * scale);
       } else {
         const float a = fabsf(d);
         sq += a > param ? param * (a - 0.5f * param) : 0.5f * d * d;
@@ -318,7 +333,7 @@ __global__ __launch_bounds__(256) void sg_fc_tail_train_kernel(const float* __re
 
 __global__ __launch_bounds__(256) void sg_fc_tail_train_reduce_kernel(const float* __restrict__ partial, int nblocks, int W,
                                                                       int H, float inv_n, const float* __restrict__ norm,
-                                                                      float* __restrict__ dw0,
+                                                                      float qdiv, float* __restrict__ dw0,
                                                                       float* __restrict__ db0, float* __restrict__ dw2,
                                                                       float* __restrict__ db2, float* __restrict__ loss,
                                                                       double* __restrict__ accum) {
@@ -347,7 +362,8 @@ __global__ __launch_bounds__(256) void sg_fc_tail_train_reduce_kernel(const floa
   else if (i < W * W + W + H * W) dw2[i - W * W - W] = s;
   else if (i < nacc) db2[i - W * W - W - H * W] = s;
   else {
-    const float l = s * (norm ? norm[1] : inv_n);          // masked: 1 / (valid targets), 0 when there is none
+    // masked: 1 / (valid targets), 0 when there is none; a quantile head (qdiv = Q > 1) spreads every target over Q rows
+    const float l = s * (norm ? (qdiv > 1.f ? norm[1] / qdiv : norm[1]) : inv_n);
     loss[0] = l;
     if (accum) accum[0] += (double)l;
   }
@@ -362,24 +378,29 @@ extern "C" size_t stemgnn_fc_tail_train_scratch_floats(int B, int N, int W, int 
 template <int KIND, bool MASKED>
 static int fc_tail_train_rows_launch(const float* fsum, const float* target, const float* w0, const float* b0, const float* w2,
                                      const float* b2, int B, int N, int W, int H, float param, const float* norm,
-                                     float* scratch, float* forecast, float* dfsum, hipStream_t st) {
+                                     float* scratch, float* forecast, float* dfsum, hipStream_t st, int HT = 0,
+                                     const SgTaus& taus = SgTaus()) {
   const size_t lds = fc_tail_train_lds(W, H);
   static SgDynLds lds_guard;
   SG_TRY(sg_ensure_dyn_lds((const void*)sg_fc_tail_train_kernel<KIND, MASKED>, lds, lds_guard));
   hipLaunchKernelGGL((sg_fc_tail_train_kernel<KIND, MASKED>), dim3((B * N + TRAIN_RB - 1) / TRAIN_RB), dim3(256), lds, st, fsum,
-                     target, w0, b0, w2, b2, B, N, W, H, param, norm, forecast, dfsum, scratch);
+                     target, w0, b0, w2, b2, B, N, W, H, param, norm, forecast, dfsum, scratch, HT > 0 ? HT : H, taus);
   SG_TRY(hipGetLastError());
   return 0;
 }
 // parts: 1 = the per-row launch, 2 = the partial-sum launch.  norm == NULL: unmasked, normaliser B * H * N.
+// H = the tail's output rows.  Q > 0 (the `_quantile` entries only; H = Q * HT then): the pinball loss with the levels `taus`.
 static int fc_tail_train_impl(const float* fsum, const float* target, const float* w0, const float* b0, const float* w2,
                               const float* b2, int B, int N, int W, int H, int kind, float param, const float* norm,
                               float* scratch, float* forecast, float* loss, double* loss_accum, float* dfsum, float* dw0,
-                              float* db0, float* dw2, float* db2, void* stream, int parts) {
+                              float* db0, float* dw2, float* db2, void* stream, int parts, int Q = 0,
+                              const SgTaus* taus = nullptr) {
   if (!scratch || B <= 0 || N <= 0 || !stemgnn_fc_tail_supported(W, H) || fc_tail_train_lds(W, H) > 150 * 1024) return SG_EINVAL;
   if ((parts & 1) && (!fsum || !target || !w0 || !b0 || !w2 || !b2 || !dfsum)) return SG_EINVAL;
   if ((parts & 2) && (!loss || !dw0 || !db0 || !dw2 || !db2)) return SG_EINVAL;
-  if (parts & 1) {
+  if ((parts & 1) && Q > 0) {
+    if (kind != SG_LOSS_PINBALL || !taus || H % Q != 0) return SG_EINVAL;
+  } else if (parts & 1) {
     if (kind != SG_LOSS_MSE && kind != SG_LOSS_MAE && kind != SG_LOSS_HUBER) return SG_EINVAL;
     if (kind == SG_LOSS_HUBER && !(param > 0.f && param <= 3.402823466e+38f)) return SG_EINVAL;       // NaN fails both
   }
@@ -390,7 +411,12 @@ static int fc_tail_train_impl(const float* fsum, const float* target, const floa
     int rc;
 #define SG_TAIL_ROWS(K, MSK) \
   rc = fc_tail_train_rows_launch<K, MSK>(fsum, target, w0, b0, w2, b2, B, N, W, H, param, norm, scratch, forecast, dfsum, st)
-    if (kind == SG_LOSS_MSE) { if (norm) SG_TAIL_ROWS(SG_LOSS_MSE, true); else SG_TAIL_ROWS(SG_LOSS_MSE, false); }
+    if (kind == SG_LOSS_PINBALL) {
+      if (norm) rc = fc_tail_train_rows_launch<SG_LOSS_PINBALL, true>(fsum, target, w0, b0, w2, b2, B, N, W, H, 0.f, norm, scratch,
+                                                                      forecast, dfsum, st, H / Q, *taus);
+      else rc = fc_tail_train_rows_launch<SG_LOSS_PINBALL, false>(fsum, target, w0, b0, w2, b2, B, N, W, H, 0.f, norm, scratch,
+                                                                  forecast, dfsum, st, H / Q, *taus);
+    } else if (kind == SG_LOSS_MSE) { if (norm) SG_TAIL_ROWS(SG_LOSS_MSE, true); else SG_TAIL_ROWS(SG_LOSS_MSE, false); }
     else if (kind == SG_LOSS_MAE) { if (norm) SG_TAIL_ROWS(SG_LOSS_MAE, true); else SG_TAIL_ROWS(SG_LOSS_MAE, false); }
     else { if (norm) SG_TAIL_ROWS(SG_LOSS_HUBER, true); else SG_TAIL_ROWS(SG_LOSS_HUBER, false); }
 #undef SG_TAIL_ROWS
@@ -398,7 +424,8 @@ static int fc_tail_train_impl(const float* fsum, const float* target, const floa
   }
   if (parts & 2) {
     hipLaunchKernelGGL(sg_fc_tail_train_reduce_kernel, dim3((nacc + 1 + 63) / 64), dim3(256), 0, st, scratch, nblocks, W, H,
-                       1.f / ((float)B * (float)H * (float)N), norm, dw0, db0, dw2, db2, loss, loss_accum);
+                       1.f / ((float)B * (float)H * (float)N), norm, Q > 0 ? (float)Q : 1.f, dw0, db0, dw2, db2, loss,
+                       loss_accum);
     SG_TRY(hipGetLastError());
   }
   return 0;
@@ -470,6 +497,47 @@ extern "C" int stemgnn_fc_tail_train_finish_loss(const float* scratch, int B, in
                                                  float* db2, void* stream) {
   return fc_tail_train_impl(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, N, W, H, SG_LOSS_MSE, 0.f, norm,
                             const_cast<float*>(scratch), nullptr, loss, loss_accum, nullptr, dw0, db0, dw2, db2, stream, 2);
+}
+
+// ---- the same tail for a quantile head: pinball loss over Q * H rows against the [B,H,N] target --------------------
+// Every check of the three entries is here, ahead of fc_tail_train_impl (whose own checks see Q * H as the tail's row count).
+static int fc_tail_quantile_args(int B, int N, int W, int H, int Q, const float* taus, bool need_taus, SgTaus* out) {
+  if (B <= 0 || N <= 0 || W <= 0 || H <= 0 || Q <= 0) return SG_EINVAL;
+  if ((long long)Q * H > TAIL_MAXH || !stemgnn_fc_tail_supported(W, Q * H)) return SG_EINVAL;
+  if (!need_taus) return 0;
+  if (!taus) return SG_EINVAL;
+  for (int q = 0; q < 32; ++q) out->v[q] = 0.5f;
+  for (int q = 0; q < Q; ++q) {
+    if (!(taus[q] > 0.f && taus[q] < 1.f)) return SG_EINVAL;           // NaN fails both
+    out->v[q] = taus[q];
+  }
+  return 0;
+}
+extern "C" int stemgnn_fc_tail_train_quantile(const float* fsum, const float* target, const float* w0, const float* b0,
+                                              const float* w2, const float* b2, int B, int N, int W, int H, int Q,
+                                              const float* taus, const float* norm, float* scratch, float* forecast,
+                                              float* loss, double* loss_accum, float* dfsum, float* dw0, float* db0, float* dw2,
+                                              float* db2, void* stream) {
+  SgTaus t;
+  if (fc_tail_quantile_args(B, N, W, H, Q, taus, true, &t) != 0) return SG_EINVAL;
+  return fc_tail_train_impl(fsum, target, w0, b0, w2, b2, B, N, W, Q * H, SG_LOSS_PINBALL, 0.f, norm, scratch, forecast, loss,
+                            loss_accum, dfsum, dw0, db0, dw2, db2, stream, 3, Q, &t);
+}
+extern "C" int stemgnn_fc_tail_train_rows_quantile(const float* fsum, const float* target, const float* w0, const float* b0,
+                                                   const float* w2, const float* b2, int B, int N, int W, int H, int Q,
+                                                   const float* taus, const float* norm, float* scratch, float* forecast,
+                                                   float* dfsum, void* stream) {
+  SgTaus t;
+  if (fc_tail_quantile_args(B, N, W, H, Q, taus, true, &t) != 0) return SG_EINVAL;
+  return fc_tail_train_impl(fsum, target, w0, b0, w2, b2, B, N, W, Q * H, SG_LOSS_PINBALL, 0.f, norm, scratch, forecast, nullptr,
+                            nullptr, dfsum, nullptr, nullptr, nullptr, nullptr, stream, 1, Q, &t);
+}
+extern "C" int stemgnn_fc_tail_train_finish_quantile(const float* scratch, int B, int N, int W, int H, int Q, const float* norm,
+                                                     float* loss, double* loss_accum, float* dw0, float* db0, float* dw2,
+                                                     float* db2, void* stream) {
+  if (fc_tail_quantile_args(B, N, W, H, Q, nullptr, false, nullptr) != 0) return SG_EINVAL;
+  return fc_tail_train_impl(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, N, W, Q * H, SG_LOSS_PINBALL, 0.f, norm,
+                            const_cast<float*>(scratch), nullptr, loss, loss_accum, nullptr, dw0, db0, dw2, db2, stream, 2, Q);
 }
 
 // ---- fused RMSprop over flat buffers ------------------------------------------------------------------------------

@@ -166,7 +166,8 @@ class TrainStep:
         is constant along the rows of the symmetrised attention (``attention.sum()``) has no effect without dropout: the rows of the
         softmax sum to 1.  None (default): the step is exactly what it is without the argument.
         loss / huber_delta / ignore_nan: Model.loss's `kind`, `huber_delta`, `ignore_nan` (needs a model with the fused
-        ``loss``).  target_series: [T,N] fp32 of the series' shape and device; the targets `y` are gathered from it instead of
+        ``loss``).  "pinball": the loss of a quantile model (and the only one it takes); `horizon` and the step's `self.y` stay
+        the target's [B,H,N] -- the Q rows per step exist only inside the fused tail.  target_series: [T,N] fp32 of the series' shape and device; the targets `y` are gathered from it instead of
         from `series` (a copy that keeps missing readings as NaN while the inputs stay imputed).  Defaults: the step as it was.
         adjacency (a graph.LatentGraph or an [N,N] tensor): train from a fixed graph -- passed to Model.loss / Model.forward inside
         the (captured) step: no GRU, no attention, no gradient for GRU / key / query, exact-fp32 GLU layers.  Nothing of such a
@@ -179,8 +180,10 @@ class TrainStep:
             adjacency = prepare(adjacency, next(model.parameters()).device)
         self.adjacency = adjacency
         self.graph_kw = {} if adjacency is None else dict(adjacency=adjacency)
-        if loss not in _lib.SG_LOSS:
-            raise ValueError(f"unknown loss {loss!r}: one of {sorted(_lib.SG_LOSS)}")
+        if loss not in _lib.SG_LOSS and loss != "pinball":
+            raise ValueError(f"unknown loss {loss!r}: one of {sorted(_lib.SG_LOSS)} or 'pinball'")
+        if (loss == "pinball") != (getattr(model, "quantiles", None) is not None):
+            raise ValueError("loss='pinball' goes with a quantile model (Model(..., quantiles=...)), and only with one")
         self.loss_kw = {} if (loss == "mse" and not ignore_nan) else \
             dict(kind=loss, huber_delta=float(huber_delta), ignore_nan=bool(ignore_nan))
         if self.loss_kw and not hasattr(model, "loss"):
@@ -746,6 +749,9 @@ class ForecastStep:
         as NaN for the masked metrics) while the model's inputs come from `series`.
         adjacency (a graph.LatentGraph or an [N,N] tensor): every Model.predict of the pass runs from this graph (no GRU, no
         attention; a window's forecast no longer depends on its batch)."""
+        if getattr(model, "quantiles", None) is not None:
+            raise ValueError("ForecastStep does not take a quantile model: its result slabs hold one [H,N] forecast per window; "
+                             "use trainer.rolling_forecast")
         self.model = model
         self.B, self.W, self.horizon = int(batch_size), int(window), int(horizon)
         if series is None or series.dim() != 2:

@@ -45,6 +45,34 @@ class Scores:
         return m[0].copy(), m[1].copy(), m[2].copy()
 
 
+class QuantileScores:
+    """Calibration of a quantile forecast from one kernel pass (`stemgnn_quantile_metrics`): y [count, H, N] ground truth,
+    y_hat [count, Q, H, N], quantiles = the Q levels.  Attributes (numpy float64; `*_step` = the same per horizon step, a
+    trailing axis of H), with P = Q // 2 pairs (i, Q-1-i):
+      pinball [Q]            mean pinball loss per level        coverage [Q]          share of y <= y_hat_q (nominal: the level)
+      interval_coverage [P]  share of y_hat_i <= y <= y_hat_{Q-1-i}   interval_width [P]    mean y_hat_{Q-1-i} - y_hat_i
+      interval_nominal [P]   tau_{Q-1-i} - tau_i                crossing              share of elements whose Q forecasts are
+                                                                                      not non-decreasing in q
+    mul / add: per-node de-normalisation, applied in fp64 ahead of everything.  ignore_nan: elements whose ground truth is NaN
+    are left out everywhere (`stemgnn_quantile_metrics_masked`); a slice with none left is NaN."""
+
+    def __init__(self, y, y_hat, quantiles, mul=None, add=None, ignore_nan=False):
+        y_hat = _as_f32(y_hat)
+        y = _as_f32(y, like=y_hat)
+        q = tuple(float(t) for t in quantiles)
+        Q, P, H = len(q), len(q) // 2, y.shape[1]
+        K = 2 * Q + 2 * P + 1
+        v = ops.quantile_metrics(y, y_hat, q, mul, add, ignore_nan=bool(ignore_nan)).cpu().numpy()
+        self.quantiles = q
+        self.interval_nominal = np.array([q[Q - 1 - i] - q[i] for i in range(P)], dtype=np.float64)
+        for suffix, m in (("", v[:K]), ("_step", v[K:].reshape(K, H))):
+            setattr(self, "pinball" + suffix, m[:Q].copy())
+            setattr(self, "coverage" + suffix, m[Q:2 * Q].copy())
+            setattr(self, "interval_coverage" + suffix, m[2 * Q:2 * Q + P].copy())
+            setattr(self, "interval_width" + suffix, m[2 * Q + P:2 * Q + 2 * P].copy())
+            setattr(self, "crossing" + suffix, m[2 * Q + 2 * P].copy() if suffix else np.float64(m[2 * Q + 2 * P]))
+
+
 def evaluate(y, y_hat, by_step=False, by_node=False, ignore_nan=False):
     """utils/math_utils.py:59-74.  y: ground truth, y_hat: prediction, both [count, time_step, node] on the GPU.
     ignore_nan: leave the elements whose ground truth is NaN out of every mean."""

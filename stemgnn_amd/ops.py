@@ -437,6 +437,92 @@ class FcTail(torch.autograd.Function):
         return dfsum, dw0, db0, dw2, db2, None
 
 
+def _fc_tail_train_forward(ctx, fsum, target, prm, H, state, loss_out, accum, unit_grad, ignore_nan, entries):
+    """The fused training tail's forward, shared by FcTailMse and FcTailQuantile: the direct / deferred logic exists once.
+    prm = (fc.0.weight, fc.0.bias, fc.2.weight, fc.2.bias); H = the target's horizon ([B,H,N]; fc.2 has H rows, or Q * H for a
+    quantile head -- the scratch is sized by fc.2's rows).  entries(norm) -> (rows_call, finish_call, both_call, sel, fin_sel):
+    the three library entries and the arguments they take between `B, N, W, H` and the scratch (rows / both) or the loss
+    (finish); norm = the valid-target count buffer (ignore_nan) or None."""
+    lib = _lib.load()
+    ctx.state = _state(state)
+    _require_gpu(fsum, "fsum")
+    _require_gpu(target, "target")
+    fsum, target = fsum.contiguous(), target.contiguous()
+    B, N, W = fsum.shape
+    w0, b0, w2, b2 = prm
+    if tuple(target.shape) != (B, H, N):
+        raise _lib.StemGNNHipError(f"target must be [B,H,N]=({B},{H},{N}), got {tuple(target.shape)}")
+    dev, f32 = fsum.device, torch.float32
+    w0c, b0c, w2c, b2c = (t.contiguous() for t in prm)
+    # direct writes into p.grad only for a call that WILL be back-propagated with an upstream gradient of 1
+    # (unit_grad: the step driver's promise): a logging call under no_grad, or a scaled loss, must not clobber the
+    # flat gradient bucket -- those use temporaries that backward scales and returns
+    wanted = any(ctx.needs_input_grad[i] for i in (0, 2, 3, 4, 5))
+    direct = ctx.state.direct and bool(unit_grad) and wanted and \
+        all(p.grad is not None and p.grad.is_contiguous() for p in prm)
+    grads = [p.grad for p in prm] if direct else [torch.empty_like(p) for p in prm]
+    dfsum = torch.empty_like(fsum)
+    loss = loss_out if loss_out is not None else torch.empty((), device=dev, dtype=f32)
+    if accum is not None and (accum.dtype != torch.float64 or accum.device != dev):
+        raise _lib.StemGNNHipError("accum must be a float64 scalar on the forecast's device")
+    scratch = torch.empty(lib.stemgnn_fc_tail_train_scratch_floats(B, N, W, w2.shape[0]), device=dev, dtype=f32)
+
+    acc_ptr = accum.data_ptr() if accum is not None else None
+    norm = target_valid_count(target) if ignore_nan else None
+    # one shared direct / deferred logic; only the three library calls differ between the plain, the `_loss` and the
+    # `_quantile` form
+    rows_call, finish_call, both_call, sel, fin_sel = entries(norm)
+    # direct + unit_grad + side-stream mode: the step driver promises an immediate backward with an upstream gradient of 1
+    # (engine.TrainStep) -> only the per-row launch runs here; the partial-sum launch (loss, fc gradients: no consumer
+    # before the optimizer) is left for SpectralHotPath.backward to queue on the side branch (-10 us on the chain)
+    # (state.tail_may_defer False: a caller whose backward has no SpectralHotPath node -- Model.loss with an adjacency --
+    # nobody would run the thunk, so both launches run here)
+    defer = direct and ctx.state.overlap and ctx.state.tail_finish is None and ctx.state.tail_may_defer
+    if defer:
+        _lib.check(rows_call(
+            fsum.data_ptr(), target.data_ptr(), w0c.data_ptr(), b0c.data_ptr(), w2c.data_ptr(), b2c.data_ptr(), B, N, W, H,
+            *sel, scratch.data_ptr(), None, dfsum.data_ptr(), _stream()), "fc_tail_train_rows")
+        g0, g1, g2, g3 = grads
+
+        def finish(stream, scratch=scratch, loss=loss, g0=g0, g1=g1, g2=g2, g3=g3, norm=norm):   # norm: kept alive
+            _lib.check(finish_call(scratch.data_ptr(), B, N, W, H, *fin_sel, loss.data_ptr(), acc_ptr, g0.data_ptr(),
+                                   g1.data_ptr(), g2.data_ptr(), g3.data_ptr(), stream),
+                       "fc_tail_train_finish")
+        ctx.state.tail_finish = finish
+    else:
+        _lib.check(both_call(
+            fsum.data_ptr(), target.data_ptr(), w0c.data_ptr(), b0c.data_ptr(), w2c.data_ptr(), b2c.data_ptr(), B, N, W, H,
+            *sel, scratch.data_ptr(), None, loss.data_ptr(), acc_ptr, dfsum.data_ptr(),
+            grads[0].data_ptr(), grads[1].data_ptr(), grads[2].data_ptr(), grads[3].data_ptr(), _stream()), "fc_tail_train")
+    # (the reduction of the per-block partials -- loss, fc gradients -- stays a launch of its own on this stream.  Measured
+    # in round 4: on the side stream no gain (the cross-queue edge costs what the 9 us launch returns); as the job of the
+    # LAST workgroup to arrive of the first launch, 40 us instead of 12 + 10 -- one workgroup summing 114 partials that
+    # other XCDs just wrote is a serial chain of fabric round trips)
+    ctx.direct, ctx.unit_grad = direct, bool(unit_grad)
+    ctx.held = (dfsum, None if direct else grads)
+    ctx.set_materialize_grads(False)
+    if loss_out is not None:
+        ctx.mark_dirty(loss_out)
+    return loss
+
+
+def _fc_tail_train_backward(ctx, grad_loss, n_inputs):
+    """Hands out what _fc_tail_train_forward holds; `n_inputs`: the Function's forward arguments (fsum, target, the four fc
+    parameters in slots 0..5, then non-differentiable ones)."""
+    dfsum, grads = ctx.held
+    ctx.held = None
+    if ctx.state.tail_finish is not None and not ctx.state.overlap:      # the mode changed between forward and backward
+        fin, ctx.state.tail_finish = ctx.state.tail_finish, None
+        fin(_stream())
+    if not ctx.unit_grad:
+        dfsum = dfsum * grad_loss
+        if grads is not None:
+            grads = [g * grad_loss for g in grads]
+    if grads is None:
+        return (dfsum,) + (None,) * (n_inputs - 1)
+    return (dfsum, None, grads[0], grads[1], grads[2], grads[3]) + (None,) * (n_inputs - 6)
+
+
 class FcTailMse(torch.autograd.Function):
     """Training tail as one node: fc tail (reference models/base_model.py:175-179) + nn.MSELoss(reduction='mean')
     (models/handler.py:140,162) + both backwards, two launches (``stemgnn_fc_tail_train``).  forward returns the loss
@@ -454,89 +540,48 @@ class FcTailMse(torch.autograd.Function):
         if kind not in _lib.SG_LOSS:
             raise ValueError(f"unknown loss kind {kind!r}: one of {sorted(_lib.SG_LOSS)}")
         plain = kind == "mse" and not ignore_nan           # today's entries
-        ctx.state = _state(state)
-        _require_gpu(fsum, "fsum")
-        _require_gpu(target, "target")
-        fsum, target = fsum.contiguous(), target.contiguous()
-        B, N, W = fsum.shape
-        H = w2.shape[0]
-        if tuple(target.shape) != (B, H, N):
-            raise _lib.StemGNNHipError(f"target must be [B,H,N]=({B},{H},{N}), got {tuple(target.shape)}")
-        dev, f32 = fsum.device, torch.float32
-        prm = (w0, b0, w2, b2)
-        w0c, b0c, w2c, b2c = (t.contiguous() for t in prm)
-        # direct writes into p.grad only for a call that WILL be back-propagated with an upstream gradient of 1
-        # (unit_grad: the step driver's promise): a logging call under no_grad, or a scaled loss, must not clobber the
-        # flat gradient bucket -- those use temporaries that backward scales and returns
-        wanted = any(ctx.needs_input_grad[i] for i in (0, 2, 3, 4, 5))
-        direct = ctx.state.direct and bool(unit_grad) and wanted and \
-            all(p.grad is not None and p.grad.is_contiguous() for p in prm)
-        grads = [p.grad for p in prm] if direct else [torch.empty_like(p) for p in prm]
-        dfsum = torch.empty_like(fsum)
-        loss = loss_out if loss_out is not None else torch.empty((), device=dev, dtype=f32)
-        if accum is not None and (accum.dtype != torch.float64 or accum.device != dev):
-            raise _lib.StemGNNHipError("accum must be a float64 scalar on the forecast's device")
-        scratch = torch.empty(lib.stemgnn_fc_tail_train_scratch_floats(B, N, W, H), device=dev, dtype=f32)
 
-        acc_ptr = accum.data_ptr() if accum is not None else None
-        norm = target_valid_count(target) if ignore_nan else None
-        # one shared direct / deferred logic; only the three library calls differ between the plain and the `_loss` form
-        if plain:
-            rows_call, finish_call, both_call = (lib.stemgnn_fc_tail_train_rows, lib.stemgnn_fc_tail_train_finish,
-                                                 lib.stemgnn_fc_tail_train)
-            sel = fin_sel = ()
-        else:
-            rows_call, finish_call, both_call = (lib.stemgnn_fc_tail_train_rows_loss, lib.stemgnn_fc_tail_train_finish_loss,
-                                                 lib.stemgnn_fc_tail_train_loss)
+        def entries(norm):
+            if plain:
+                return (lib.stemgnn_fc_tail_train_rows, lib.stemgnn_fc_tail_train_finish, lib.stemgnn_fc_tail_train, (), ())
             norm_ptr = norm.data_ptr() if norm is not None else None
-            sel, fin_sel = (_lib.SG_LOSS[kind], float(param), norm_ptr), (norm_ptr,)
-        # direct + unit_grad + side-stream mode: the step driver promises an immediate backward with an upstream gradient of 1
-        # (engine.TrainStep) -> only the per-row launch runs here; the partial-sum launch (loss, fc gradients: no consumer
-        # before the optimizer) is left for SpectralHotPath.backward to queue on the side branch (-10 us on the chain)
-        # (state.tail_may_defer False: a caller whose backward has no SpectralHotPath node -- Model.loss with an adjacency --
-        # nobody would run the thunk, so both launches run here)
-        defer = direct and ctx.state.overlap and ctx.state.tail_finish is None and ctx.state.tail_may_defer
-        if defer:
-            _lib.check(rows_call(
-                fsum.data_ptr(), target.data_ptr(), w0c.data_ptr(), b0c.data_ptr(), w2c.data_ptr(), b2c.data_ptr(), B, N, W, H,
-                *sel, scratch.data_ptr(), None, dfsum.data_ptr(), _stream()), "fc_tail_train_rows")
-            g0, g1, g2, g3 = grads
-
-            def finish(stream, scratch=scratch, loss=loss, g0=g0, g1=g1, g2=g2, g3=g3, norm=norm):   # norm: kept alive
-                _lib.check(finish_call(scratch.data_ptr(), B, N, W, H, *fin_sel, loss.data_ptr(), acc_ptr, g0.data_ptr(),
-                                       g1.data_ptr(), g2.data_ptr(), g3.data_ptr(), stream),
-                           "fc_tail_train_finish")
-            ctx.state.tail_finish = finish
-        else:
-            _lib.check(both_call(
-                fsum.data_ptr(), target.data_ptr(), w0c.data_ptr(), b0c.data_ptr(), w2c.data_ptr(), b2c.data_ptr(), B, N, W, H,
-                *sel, scratch.data_ptr(), None, loss.data_ptr(), acc_ptr, dfsum.data_ptr(),
-                grads[0].data_ptr(), grads[1].data_ptr(), grads[2].data_ptr(), grads[3].data_ptr(), _stream()), "fc_tail_train")
-        # (the reduction of the per-block partials -- loss, fc gradients -- stays a launch of its own on this stream.  Measured
-        # in round 4: on the side stream no gain (the cross-queue edge costs what the 9 us launch returns); as the job of the
-        # LAST workgroup to arrive of the first launch, 40 us instead of 12 + 10 -- one workgroup summing 114 partials that
-        # other XCDs just wrote is a serial chain of fabric round trips)
-        ctx.direct, ctx.unit_grad = direct, bool(unit_grad)
-        ctx.held = (dfsum, None if direct else grads)
-        ctx.set_materialize_grads(False)
-        if loss_out is not None:
-            ctx.mark_dirty(loss_out)
-        return loss
+            return (lib.stemgnn_fc_tail_train_rows_loss, lib.stemgnn_fc_tail_train_finish_loss,
+                    lib.stemgnn_fc_tail_train_loss, (_lib.SG_LOSS[kind], float(param), norm_ptr), (norm_ptr,))
+        return _fc_tail_train_forward(ctx, fsum, target, (w0, b0, w2, b2), w2.shape[0], state, loss_out, accum, unit_grad,
+                                      ignore_nan, entries)
 
     @staticmethod
     def backward(ctx, grad_loss):
-        dfsum, grads = ctx.held
-        ctx.held = None
-        if ctx.state.tail_finish is not None and not ctx.state.overlap:      # the mode changed between forward and backward
-            fin, ctx.state.tail_finish = ctx.state.tail_finish, None
-            fin(_stream())
-        if not ctx.unit_grad:
-            dfsum = dfsum * grad_loss
-            if grads is not None:
-                grads = [g * grad_loss for g in grads]
-        if grads is None:
-            return (dfsum,) + (None,) * 12
-        return (dfsum, None, grads[0], grads[1], grads[2], grads[3]) + (None,) * 7
+        return _fc_tail_train_backward(ctx, grad_loss, 13)
+
+
+class FcTailQuantile(torch.autograd.Function):
+    """FcTailMse for a quantile head: fc.2 has Q * H rows (row q * H + h = level taus[q] of step h) and the loss is the pinball
+    loss against the [B,H,N] target, mean over B Q H N (``stemgnn_fc_tail_train_quantile`` and its rows / finish pair: the same
+    kernels, the same two launches, the same direct / deferred handling).
+    (fsum [B,N,W], target [B,H,N], fc.0.weight, fc.0.bias, fc.2.weight [Q*H,W], fc.2.bias [Q*H], state, loss_out, accum,
+    unit_grad, taus, ignore_nan) -> loss [].  taus: Q floats, strictly inside (0, 1); ignore_nan: a NaN target is missing for
+    all Q of its rows and the normaliser is (valid targets) * Q."""
+
+    @staticmethod
+    def forward(ctx, fsum, target, w0, b0, w2, b2, state=None, loss_out=None, accum=None, unit_grad=False, taus=(0.5,),
+                ignore_nan=False):
+        lib = _lib.load()
+        Q = len(taus)
+        if Q < 1 or w2.shape[0] % Q != 0:
+            raise _lib.StemGNNHipError(f"fc.2 has {w2.shape[0]} rows: not a multiple of the {Q} quantile levels")
+        tau_arr = _lib.host_floats(taus)
+
+        def entries(norm):
+            norm_ptr = norm.data_ptr() if norm is not None else None
+            return (lib.stemgnn_fc_tail_train_rows_quantile, lib.stemgnn_fc_tail_train_finish_quantile,
+                    lib.stemgnn_fc_tail_train_quantile, (Q, tau_arr, norm_ptr), (Q, norm_ptr))
+        return _fc_tail_train_forward(ctx, fsum, target, (w0, b0, w2, b2), w2.shape[0] // Q, state, loss_out, accum, unit_grad,
+                                      ignore_nan, entries)
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        return _fc_tail_train_backward(ctx, grad_loss, 12)
 
 
 def target_valid_count(y):
@@ -1524,6 +1569,56 @@ def roll_window(inputs, forecast, forecast_steps, step, horizon):
                                        forecast_steps.data_ptr(), B, W, L, N, int(step), int(horizon), _stream()),
                "roll_window")
     return nxt
+
+
+def roll_window_quantile(inputs, forecast, forecast_steps, step, horizon, point):
+    """roll_window for a quantile forecast [B,Q,L,N] (``stemgnn_roll_window_quantile``): the next inputs are built from the point
+    row forecast[:, point] exactly as roll_window builds them, and all Q rows go to forecast_steps [B,Q,horizon,N]."""
+    lib = _lib.load()
+    _require_gpu(inputs, "inputs")
+    _require_gpu(forecast, "forecast")
+    B, W, N = inputs.shape
+    if forecast.dim() != 4 or forecast.shape[0] != B or forecast.shape[3] != N:
+        raise _lib.StemGNNHipError(f"roll_window_quantile: forecast must be [B,Q,L,N], got {tuple(forecast.shape)}")
+    Q, L = forecast.shape[1], forecast.shape[2]
+    if L == 0:
+        raise Exception("Get blank inference result")                    # handler.py:54-55
+    if tuple(forecast_steps.shape) != (B, Q, int(horizon), N) or not forecast_steps.is_contiguous():
+        raise _lib.StemGNNHipError(f"roll_window_quantile: forecast_steps must be a contiguous [B,Q,horizon,N] tensor, got "
+                                   f"{tuple(forecast_steps.shape)}")
+    inputs, forecast = inputs.contiguous(), forecast.contiguous()
+    nxt = torch.empty_like(inputs)
+    _lib.check(lib.stemgnn_roll_window_quantile(inputs.data_ptr(), forecast.data_ptr(), nxt.data_ptr(),
+                                                forecast_steps.data_ptr(), B, W, L, N, Q, int(point), int(step), int(horizon),
+                                                _stream()), "roll_window_quantile")
+    return nxt
+
+
+def quantile_metrics(target, forecast, quantiles, mul=None, add=None, ignore_nan=False):
+    """target [count,H,N], forecast [count,Q,H,N] fp32 -> float64 device vector overall[K] | by_step[K][H] with P = Q // 2,
+    K = 2 Q + 2 P + 1: pinball[Q] | coverage[Q] | interval coverage[P] | interval width[P] | crossing rate
+    (``stemgnn_quantile_metrics``; ignore_nan: the ``_masked`` entry, NaN targets left out everywhere)."""
+    lib = _lib.load()
+    _require_gpu(target, "target")
+    _require_gpu(forecast, "forecast")
+    Q = len(quantiles)
+    if target.dim() != 3 or forecast.dim() != 4 or forecast.shape[1] != Q or \
+            (forecast.shape[0],) + tuple(forecast.shape[2:]) != tuple(target.shape):
+        raise _lib.StemGNNHipError(f"quantile_metrics: target must be [count,H,N] and forecast [count,{Q},H,N], got "
+                                   f"{tuple(target.shape)} / {tuple(forecast.shape)}")
+    target, forecast = target.contiguous(), forecast.contiguous()
+    C, H, N = target.shape
+    dev = target.device
+    entry = lib.stemgnn_quantile_metrics_masked if ignore_nan else lib.stemgnn_quantile_metrics
+    scratch = torch.empty(lib.stemgnn_quantile_scratch_doubles(C, Q, H, N), device=dev, dtype=torch.float64)
+    out = torch.empty(lib.stemgnn_quantile_out_doubles(Q, H), device=dev, dtype=torch.float64)
+    if mul is not None:
+        mul = mul.to(device=dev, dtype=torch.float64).contiguous()
+        add = add.to(device=dev, dtype=torch.float64).contiguous()
+    _lib.check(entry(target.data_ptr(), forecast.data_ptr(), _lib.host_floats(quantiles, _lib.c_double),
+                     mul.data_ptr() if mul is not None else None, add.data_ptr() if add is not None else None, C, Q, H, N,
+                     scratch.data_ptr(), out.data_ptr(), _stream()), "quantile_metrics")
+    return out
 
 
 def eval_metrics(target, forecast, mul=None, add=None, ignore_nan=False):

@@ -25,10 +25,10 @@ import numpy as np
 import torch
 
 from . import ops
-from .base_model import Model
+from .base_model import Model, check_quantiles, point_index
 from .engine import ForecastStep, TrainStep
 from .forecast_dataloader import ForecastDataset, WindowLoader, denorm_coefficients, mark_missing
-from .math_utils import Scores
+from .math_utils import QuantileScores, Scores
 from .optim import FusedAdam, FusedRMSprop
 
 BEST = "_stemgnn.pt"
@@ -58,20 +58,31 @@ def rolling_forecast(model, loader, horizon, adjacency=None):
     `horizon` steps exist (what the reference's validation does, models/handler.py:41-65), all on the device.
     adjacency (a graph.LatentGraph or an [N,N] tensor): every round is ``model.predict(window, adjacency=adjacency)`` -- the
     forecast from a fixed graph, independent of how the loader batches the windows.
-    Returns (forecast [count, horizon, N], target [count, horizon, N]) float32 device tensors."""
+    Returns (forecast [count, horizon, N], target [count, horizon, N]) float32 device tensors.
+    A quantile model (``model.quantiles``): the POINT row (``model.point_index``) is what is fed back as the next window, and the
+    forecast comes back as [count, Q, horizon, N] (``ops.roll_window_quantile``).  With `horizon` beyond the model's own, the
+    bands of the later rounds are therefore conditional on the point path: they describe the spread around a forecast made
+    from the model's own median-like outputs, not the wider uncertainty of the inputs those rounds never saw."""
+    quantiles = getattr(model, "quantiles", None)
     was_training = model.training
     model.eval()
     forecasts, targets = [], []
     with torch.no_grad():
         for window, target in loader:
-            steps = torch.zeros(window.shape[0], horizon, window.shape[2], device=window.device)
+            if quantiles is None:
+                steps = torch.zeros(window.shape[0], horizon, window.shape[2], device=window.device)
+            else:
+                steps = torch.zeros(window.shape[0], len(quantiles), horizon, window.shape[2], device=window.device)
             done = 0
             while done < horizon:
                 out, _ = model(window) if adjacency is None else model.predict(window, adjacency=adjacency)
-                if out.shape[1] == 0:
+                if out.shape[-2] == 0:
                     raise Exception("Get blank inference result")
-                window = ops.roll_window(window, out, steps, done, horizon)
-                done += min(horizon - done, out.shape[1])
+                if quantiles is None:
+                    window = ops.roll_window(window, out, steps, done, horizon)
+                else:
+                    window = ops.roll_window_quantile(window, out, steps, done, horizon, model.point_index)
+                done += min(horizon - done, out.shape[-2])
             forecasts.append(steps)
             targets.append(target)
     model.train(was_training)
@@ -83,6 +94,9 @@ def rolling_forecast_graph(model, dataset, horizon, batch_size, adjacency=None):
     hipGraph replay of window gather -> Model.predict -> roll_window rounds -> result slabs; the ragged last batch runs
     eagerly.  Same (forecast, target) [count, horizon, N], bit for bit; the model's training state is left untouched.
     The dataset's horizon (its target length) must equal `horizon`.  adjacency: as in rolling_forecast."""
+    if getattr(model, "quantiles", None) is not None:
+        raise ValueError("rolling_forecast_graph does not take a quantile model (engine.ForecastStep's result slabs hold one "
+                         "[H,N] forecast per window); use rolling_forecast")
     if int(dataset.horizon) != int(horizon):
         raise ValueError(f"rolling_forecast_graph: dataset horizon {dataset.horizon} != horizon {horizon}")
     n = len(dataset)
@@ -93,18 +107,37 @@ def rolling_forecast_graph(model, dataset, horizon, batch_size, adjacency=None):
     return step.result()
 
 
-def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=None, ignore_nan=False):
+def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=None, ignore_nan=False, quantiles=None):
     """Metrics of a rolling forecast in raw units (and normalised units under ``*_norm``).  With `dump_dir`, the first
     forecast step of every window is written as CSV (target / predict / absolute error / absolute percentage error).
-    ignore_nan: NaN targets (missing readings) are left out of every metric; the CSV files keep them as NaN."""
+    ignore_nan: NaN targets (missing readings) are left out of every metric; the CSV files keep them as NaN.
+    A 4-D forecast [count, Q, horizon, N] needs `quantiles` (the Q levels): every key above is computed from the point row
+    (the level closest to 0.5) through the same metrics kernel, and the calibration of the bands is added in raw units
+    (math_utils.QuantileScores): ``pinball`` (mean over the levels), ``pinball_q`` / ``coverage_q`` [Q], ``interval_coverage`` /
+    ``interval_width`` / ``interval_nominal`` [Q // 2] for the pairs (i, Q-1-i), and ``crossing``."""
     mul = add = None
     if norm_method and statistic:
         mul, add = denorm_coefficients(norm_method, statistic, forecast.device)
+    calibration = {}
+    if forecast.dim() == 4:
+        if quantiles is None:
+            raise ValueError("score_forecast: a [count, Q, horizon, N] forecast needs quantiles=")
+        quantiles = check_quantiles(quantiles)
+        if forecast.shape[1] != len(quantiles):
+            raise ValueError(f"score_forecast: forecast has {forecast.shape[1]} quantile rows, quantiles= names {len(quantiles)}")
+        qs = QuantileScores(target, forecast, quantiles, mul, add, ignore_nan=ignore_nan)
+        calibration = dict(pinball=float(qs.pinball.mean()), pinball_q=qs.pinball, coverage_q=qs.coverage,
+                           interval_coverage=qs.interval_coverage, interval_width=qs.interval_width,
+                           interval_nominal=qs.interval_nominal, crossing=float(qs.crossing))
+        forecast = forecast[:, point_index(quantiles)].contiguous()
+    elif quantiles is not None:
+        raise ValueError("score_forecast: quantiles= goes with a [count, Q, horizon, N] forecast")
     raw = Scores(target, forecast, mul, add, ignore_nan=ignore_nan)
     (mape, mae, rmse), (mape_n, mae_n, rmse_n) = raw.get(), raw.get(by_node=True)
     out = dict(mae=mae, mape=mape, rmse=rmse, mae_node=mae_n, mape_node=mape_n, rmse_node=rmse_n)
     normed = Scores(target, forecast, ignore_nan=ignore_nan).get() if mul is not None else (mape, mae, rmse)
     out.update(mape_norm=normed[0], mae_norm=normed[1], rmse_norm=normed[2])
+    out.update(calibration)
     if dump_dir is not None:
         d = pathlib.Path(dump_dir)
         d.mkdir(parents=True, exist_ok=True)
@@ -140,15 +173,22 @@ class DeviceTrainer:
     def __init__(self, units, window, horizon, multi, *, batch_size=32, lr=1e-4, optimizer="RMSProp", decay_rate=0.5,
                  decay_every=5, norm_method="z_score", device="cuda", model_factory=None, hipgraph=True,
                  dropout_seed=None, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False, loss="mse", huber_delta=1.0,
-                 missing=None):
-        """loss / huber_delta: the training loss of engine.TrainStep ("mse" | "mae" | "huber").  missing (a float, e.g. 0.0):
+                 missing=None, quantiles=None):
+        """loss / huber_delta: the training loss of engine.TrainStep ("mse" | "mae" | "huber").  quantiles (levels in (0, 1),
+        increasing): a quantile model (Model(..., quantiles=); a `model_factory` gets the keyword too) trained by the pinball loss
+        -- `loss` left at its default means "pinball" then; validation keeps selecting the best model on the point forecast's
+        MAE and prints the bands' coverage beside it.  missing (a float, e.g. 0.0):
         raw NaN entries and entries equal to it are missing readings -- left out of the column statistics, the training loss
         and the validation metrics, while the model's inputs stay imputed (ForecastDataset)."""
         self.units, self.window, self.horizon, self.multi = units, window, horizon, multi
         self.batch_size, self.norm_method, self.device, self.hipgraph = batch_size, norm_method, device, hipgraph
         self.decay_every = decay_every
+        self.quantiles = None if quantiles is None else check_quantiles(quantiles)
+        if self.quantiles is not None and loss == "mse":
+            loss = "pinball"
         self.loss, self.huber_delta, self.missing = loss, huber_delta, missing
-        self.model = (model_factory or Model)(units, 2, window, multi, horizon=horizon)
+        head = {} if self.quantiles is None else dict(quantiles=self.quantiles)
+        self.model = (model_factory or Model)(units, 2, window, multi, horizon=horizon, **head)
         self.model.to(device)
         if dropout_seed is not None and hasattr(self.model, "set_dropout_seed"):
             # an explicit Philox key for the attention dropout: by default the key follows the device generator's seed AND
@@ -172,7 +212,7 @@ class DeviceTrainer:
     def validate(self, loader, dump_dir=None):
         forecast, target = rolling_forecast(self.model, loader, self.horizon)
         return score_forecast(forecast, target, self.norm_method, self.statistic, dump_dir,
-                              ignore_nan=self.missing is not None)
+                              ignore_nan=self.missing is not None, quantiles=self.quantiles)
 
     def fit(self, train_series, valid_series, epochs, *, validate_every=1, patience=None, out_dir=None, on_step=None,
             on_validate=None, log=print):
@@ -228,6 +268,12 @@ class DeviceTrainer:
                 ops.check_gru_status(train_set.device)
                 log(f"  validation: MAPE {metrics['mape']:.6%}  MAE {metrics['mae']:.6f}  RMSE {metrics['rmse']:.6f}"
                     f"  (normalised MAE {metrics['mae_norm']:.6f})")
+                if self.quantiles is not None:
+                    bands = "  ".join(f"{c:.1%} of {n:.0%}" for c, n in
+                                      zip(metrics["interval_coverage"], metrics["interval_nominal"]))
+                    log(f"  quantiles: pinball {metrics['pinball']:.6f}  coverage "
+                        + " ".join(f"{t:g}:{c:.1%}" for t, c in zip(self.quantiles, metrics["coverage_q"]))
+                        + (f"  intervals {bands}" if bands else "") + f"  crossing {metrics['crossing']:.2%}")
                 if on_validate is not None:
                     on_validate(epoch, metrics)
                 if metrics["mae"] < best:
@@ -253,7 +299,8 @@ def train(train_data, valid_data, args, result_file, model_factory=None, on_step
                             model_factory=model_factory, hipgraph=getattr(args, "hipgraph", True),
                             weight_decay=getattr(args, "weight_decay", 0.0), max_grad_norm=getattr(args, "max_grad_norm", None),
                             skip_nonfinite=getattr(args, "skip_nonfinite", False), loss=getattr(args, "loss", "mse"),
-                            huber_delta=getattr(args, "huber_delta", 1.0), missing=getattr(args, "missing", None))
+                            huber_delta=getattr(args, "huber_delta", 1.0), missing=getattr(args, "missing", None),
+                            quantiles=getattr(args, "quantiles", None))
     patience = getattr(args, "early_stop_step", 10) if getattr(args, "early_stop", False) else None
     return trainer.fit(train_data, valid_data, args.epoch, validate_every=args.validate_freq, patience=patience,
                        out_dir=result_file, on_step=on_step, on_validate=on_validate)
@@ -268,6 +315,7 @@ def test(test_data, args, result_train_file, result_test_file):
                               normalize_method=args.norm_method, norm_statistic=statistic, device=args.device)
     loader = WindowLoader(dataset, batch_size=args.batch_size, drop_last=False, shuffle=False)
     forecast, target = rolling_forecast(model, loader, args.horizon)
-    metrics = score_forecast(forecast, target, args.norm_method, statistic, result_test_file)
+    metrics = score_forecast(forecast, target, args.norm_method, statistic, result_test_file,
+                             quantiles=getattr(model, "quantiles", None))
     print(f"test: MAPE {metrics['mape']:.4f}  MAE {metrics['mae']:.4f}  RMSE {metrics['rmse']:.4f}")
     return metrics
