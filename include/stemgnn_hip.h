@@ -166,7 +166,10 @@ int stemgnn_eigh_cluster_fixes(void);
  * taken as the sum of `splits` bf16 numbers and the cross products evaluated on the bf16 MFMA pipe with fp32
  * accumulation: splits = 3 -> 6 products (~2^-24 relative, fp32 class), 2 -> 3 products (~2^-16), 1 -> plain bf16.
  * B is pre-split by stemgnn_split_weights_bf16 into `planes` (stemgnn_split_planes_floats floats, 16-byte aligned);
- * A is split on the fly.  K % 4 == 0.  stemgnn_glu_gemm_f32 is the same product on the exact-fp32 MFMA core. */
+ * A is split on the fly.  K % 4 == 0 and A 16-byte aligned (SG_EINVAL otherwise).  Operands of the `_bf16` entries must
+ * be finite and smaller in magnitude than bf16's largest finite value (0x7f7f0000, ~3.39e38): the split rounds to nearest
+ * even on the bit pattern (sp_bf16_rne), which carries a larger value up to infinity and mangles NaN / Inf.
+ * stemgnn_glu_gemm_f32 is the same product on the exact-fp32 MFMA core (any K, no alignment rule). */
 size_t stemgnn_split_planes_floats(int N, int K, int splits);
 int stemgnn_split_weights_bf16(const float* B, int N, int K, int splits, void* planes, void* stream);
 int stemgnn_glu_gemm_bf16(const float* A, const void* planes, float* C, int M, int N, int K, int splits, void* stream);
@@ -175,11 +178,22 @@ int stemgnn_glu_gemm_f32(const float* A, const float* B, float* C, int M, int N,
 /* ---- stand-alone GLU (models/base_model.py:6-13) and the general fp32 GEMM it is composed from ---------------------
  * stemgnn_sgemm_f32: C[M,N] (+)= A B on the exact-fp32 MFMA core; element (i,k) of A at A[i*lda+k] (a_kcontig) or
  * A[k*lda+i]; element (k,j) of B at B[j*ldb+k] (b_kcontig) or B[k*ldb+j]; accumulate != 0 adds to C.
+ * Required (SG_EINVAL otherwise): lda >= (a_kcontig ? K : M), ldb >= (b_kcontig ? K : N), ldc >= N, positive sizes,
+ * non-NULL pointers.  No alignment is required of any pointer or leading dimension: operands whose base pointers are
+ * 16-byte aligned and whose lda, ldb (and K where an operand is k-contiguous, M where A is not, N where B is not) are
+ * multiples of 4 take the vector loaders (16-byte loads), every other call the scalar, fully predicated loaders -- same
+ * values either way.  Only [M, N] of C is written; the ldc - N gap columns are left alone.
+ * stemgnn_sgemm_paths: which of the two a call takes, host only (launches nothing, dereferences nothing; same operand
+ * checks): out = {vec (1 vector loaders, 0 scalar), nx = row tiles of 64, ny = column tiles of 128, blocks = the 1-D
+ * grid, nx rounded up to 8 times ny (block L -> row tile L % 8 + 8 * (L / 8 / ny), column tile L / 8 % ny)}.  It asks
+ * the launch's own plan (g2_plan, csrc/gemm2.h); tests use it to prove which loaders and tile orders their cases ran.
  * stemgnn_glu_combine_fwd: out = (U + bl) * sigmoid(V + br), saving gate = sigmoid(.) and lin = U + bl ([M,C] each);
  * stemgnn_glu_combine_bwd: dU = dout * gate, dV = dout * lin * gate * (1 - gate);  stemgnn_colsum: out[c] = sum_m X[m][c]
  * in a fixed order (bias gradients). */
 int stemgnn_sgemm_f32(const float* A, int lda, int a_kcontig, const float* B, int ldb, int b_kcontig, float* C, int ldc,
                       int M, int N, int K, int accumulate, void* stream);
+int stemgnn_sgemm_paths(const void* A, int lda, int a_kcontig, const void* B, int ldb, int b_kcontig, int M, int N, int K,
+                        int* out /* [4] */);
 int stemgnn_glu_combine_fwd(const float* U, const float* V, const float* bl, const float* br, float* out, float* gate,
                             float* lin, int M, int C, void* stream);
 int stemgnn_glu_combine_bwd(const float* dout, const float* lin, const float* gate, float* dU, float* dV, int M, int C,

@@ -71,6 +71,7 @@ SIGNATURES = {
     "stemgnn_glu_gemm_bf16": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "stemgnn_glu_gemm_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "stemgnn_sgemm_f32": (c_int, [_P, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "stemgnn_sgemm_paths": (c_int, [_P, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "stemgnn_glu_combine_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
     "stemgnn_glu_combine_bwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P]),
     "stemgnn_colsum": (c_int, [_P, c_int, c_int, _P, _P]),

@@ -265,6 +265,34 @@ struct G2SlabEpi {
 // 16-byte alignment rules of the VEC path
 static inline bool g2_aligned(const void* p, int ld) { return (((uintptr_t)p) & 15) == 0 && (ld & 3) == 0; }
 
+// Every host-side decision of a launch, in one place: the loader pair (vec), the tile counts and order written into `g`
+// (nx, ny, nz, xcd_mode) and the 1-D grid.  g2_launch acts on it; stemgnn_sgemm_paths (splitgemm.hip) reports it, so what a
+// test is told about a launch is what the launch does.  Reads the pointers' values only.  blocks == 0: nothing to launch.
+struct G2Plan {
+  bool vec;
+  unsigned blocks;
+};
+static inline G2Plan g2_plan(G2Args& g, int nbranch, bool a_kc, bool b_kc, int bm) {
+  int maxM = 0, maxN = 0;
+  bool vec = true;
+  for (int r = 0; r < nbranch; ++r) {
+    maxM = g.M[r] > maxM ? g.M[r] : maxM;
+    maxN = g.N[r] > maxN ? g.N[r] : maxN;
+    vec = vec && g2_aligned(g.A[r], g.lda[r]) && g2_aligned(g.B[r], g.ldb[r]);
+    if (a_kc || b_kc) vec = vec && (g.K[r] & 3) == 0 && (g.chunk & 3) == 0;
+    if (!a_kc) vec = vec && (g.M[r] & 3) == 0;
+    if (!b_kc) vec = vec && (((g.b_ones_col >= 0 ? g.b_ones_col : g.N[r]) & 3) == 0);
+  }
+  g.nx = (maxM + bm - 1) / bm;
+  g.ny = (maxN + G2_BN - 1) / G2_BN;
+  g.nz = nbranch * g.nsplit;
+  g.xcd_mode = g.nsplit > 1 ? 1 : 0;
+  if (g.nx == 0 || g.ny == 0 || g.nz == 0) return G2Plan{vec, 0u};
+  const int ngroups = g.xcd_mode ? g.nz : g.nx * g.nz;
+  const int gt = g.xcd_mode ? g.nx * g.ny : g.ny;
+  return G2Plan{vec, (unsigned)(8 * ((ngroups + 7) / 8) * gt)};
+}
+
 template <class Epi, bool A_KC, bool B_KC, int BM = 128, bool TL = false, int BK = 16>
 static inline hipError_t g2_launch(const G2Args& g_in, const Epi& epi, int nbranch, hipStream_t st) {
   G2Args g = g_in;
@@ -274,24 +302,10 @@ static inline hipError_t g2_launch(const G2Args& g_in, const Epi& epi, int nbran
 #else
   g.dbg = 0;
 #endif
-  int maxM = 0, maxN = 0;
-  bool vec = true;
-  for (int r = 0; r < nbranch; ++r) {
-    maxM = g.M[r] > maxM ? g.M[r] : maxM;
-    maxN = g.N[r] > maxN ? g.N[r] : maxN;
-    vec = vec && g2_aligned(g.A[r], g.lda[r]) && g2_aligned(g.B[r], g.ldb[r]);
-    if (A_KC || B_KC) vec = vec && (g.K[r] & 3) == 0 && (g.chunk & 3) == 0;
-    if (!A_KC) vec = vec && (g.M[r] & 3) == 0;
-    if (!B_KC) vec = vec && (((g.b_ones_col >= 0 ? g.b_ones_col : g.N[r]) & 3) == 0);
-  }
-  g.nx = (maxM + BM - 1) / BM;
-  g.ny = (maxN + G2_BN - 1) / G2_BN;
-  g.nz = nbranch * g.nsplit;
-  if (g.nx == 0 || g.ny == 0 || g.nz == 0) return hipSuccess;
-  g.xcd_mode = g.nsplit > 1 ? 1 : 0;
-  const int ngroups = g.xcd_mode ? g.nz : g.nx * g.nz;
-  const int gt = g.xcd_mode ? g.nx * g.ny : g.ny;
-  dim3 grid(8 * ((ngroups + 7) / 8) * gt);
+  const G2Plan plan = g2_plan(g, nbranch, A_KC, B_KC, BM);
+  if (plan.blocks == 0) return hipSuccess;
+  const bool vec = plan.vec;
+  dim3 grid(plan.blocks);
   if (vec) hipLaunchKernelGGL((sg_gemm2<Epi, A_KC, B_KC, true, BM, TL, BK>), grid, dim3(256), 0, st, g, epi);
   else hipLaunchKernelGGL((sg_gemm2<Epi, A_KC, B_KC, false, BM, TL, BK>), grid, dim3(256), 0, st, g, epi);
   return hipGetLastError();

@@ -245,14 +245,30 @@ struct SpAccEpi {
   }
 };
 
-extern "C" int stemgnn_sgemm_f32(const float* A, int lda, int a_kcontig, const float* B, int ldb, int b_kcontig, float* C,
-                                 int ldc, int M, int N, int K, int accumulate, void* stream) {
-  if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || lda <= 0 || ldb <= 0 || ldc < N) return SG_EINVAL;
-  G2Args g;
-  SpAccEpi e{C, ldc, accumulate};
-  for (int r = 0; r < 2; ++r) { g.A[r] = A; g.lda[r] = lda; g.B[r] = B; g.ldb[r] = ldb; }
+// operand checks and the G2Args of stemgnn_sgemm_f32, shared with stemgnn_sgemm_paths
+static inline int sp_sgemm_args(const void* A, int lda, int a_kcontig, const void* B, int ldb, int b_kcontig, int M, int N, int K,
+                                G2Args& g) {
+  if (!A || !B || M <= 0 || N <= 0 || K <= 0 || lda < (a_kcontig ? K : M) || ldb < (b_kcontig ? K : N)) return SG_EINVAL;
+  for (int r = 0; r < 2; ++r) { g.A[r] = (const float*)A; g.lda[r] = lda; g.B[r] = (const float*)B; g.ldb[r] = ldb; }
   g.M[0] = M; g.N[0] = N; g.K[0] = K; g.M[1] = 0; g.N[1] = 0; g.K[1] = 0;
   g.nsplit = 1; g.chunk = (K + 15) & ~15; g.b_ones_col = -1;
+  return 0;
+}
+
+extern "C" int stemgnn_sgemm_paths(const void* A, int lda, int a_kcontig, const void* B, int ldb, int b_kcontig, int M, int N,
+                                   int K, int* out) {
+  G2Args g;
+  if (!out || sp_sgemm_args(A, lda, a_kcontig, B, ldb, b_kcontig, M, N, K, g)) return SG_EINVAL;
+  const G2Plan plan = g2_plan(g, 1, a_kcontig != 0, b_kcontig != 0, 64);      // BM = 64: the tile stemgnn_sgemm_f32 launches
+  out[0] = plan.vec ? 1 : 0; out[1] = g.nx; out[2] = g.ny; out[3] = (int)plan.blocks;
+  return 0;
+}
+
+extern "C" int stemgnn_sgemm_f32(const float* A, int lda, int a_kcontig, const float* B, int ldb, int b_kcontig, float* C,
+                                 int ldc, int M, int N, int K, int accumulate, void* stream) {
+  G2Args g;
+  if (!C || ldc < N || sp_sgemm_args(A, lda, a_kcontig, B, ldb, b_kcontig, M, N, K, g)) return SG_EINVAL;
+  SpAccEpi e{C, ldc, accumulate};
   hipStream_t st = (hipStream_t)stream;
   if (a_kcontig && b_kcontig) SG_TRY((g2_launch<SpAccEpi, true, true, 64>(g, e, 1, st)));
   else if (a_kcontig) SG_TRY((g2_launch<SpAccEpi, true, false, 64>(g, e, 1, st)));
