@@ -698,6 +698,35 @@ int stemgnn_quantile_metrics_masked(const float* target, const float* forecast, 
                                     const double* add, long count, int Q, int H, int N, double* scratch, double* out,
                                     void* stream);
 
+/* ---- conformal calibration of quantile bands (split-conformal CQR; csrc/conformal.hip) -----------
+ * target [count, H, N], forecast [count, Q, H, N], fp32 and contiguous; P pairs of rows (lo_rows[p], hi_rows[p]) with nominal
+ * coverage coverage[p] in (0, 1).  lo_rows, hi_rows and coverage are P values each in HOST memory, read by the call itself and
+ * passed on by value (as the levels of stemgnn_fc_tail_train_quantile are).
+ * Score of element (i, h, n) for pair p, in fp32: s = max(f[i, lo, h, n] - y[i, h, n], y[i, h, n] - f[i, hi, h, n]); a NaN
+ * score counts as +inf.  masked: an element whose target is NaN is left out and does not count (without it the NaN target
+ * gives a NaN score, hence +inf, and counts).
+ * Groups: a group keeps its own h if per_step, else pools all H; likewise n and per_node.  offsets (fp32) and counts (int64) are
+ * [P, Hg, Ng] with Hg = per_step ? H : 1, Ng = per_node ? N : 1.  counts = m, the group's valid scores.
+ * Rank, in fp64: k = max(1, ceil(((m + 1) * coverage) * (1 - 1e-12))) -- two multiplies and a ceil; stemgnn_conformal_rank is
+ * that formula on the host, and the device uses the same operations.
+ * offsets = the k-th smallest (1-based) of the group's m scores in the total order of fp32 with -0 == +0, +inf if k > m: an
+ * exact MSB-first radix select over integer histograms (no sort, no floating-point atomics), so the same bits on every run and
+ * whatever the scratch held before.  No host synchronisation, no allocation; 9 launches whatever count and P are.
+ * scratch: stemgnn_conformal_scratch_bytes bytes, 16-byte aligned (histograms and per-group state only).
+ * SG_EINVAL (nothing launched; the size entry returns 0) on a NULL pointer, count, Q, H, N or P <= 0, Q > 32, P > 16, a pair
+ * outside 0 <= lo < hi < Q, a row named twice, a coverage that is NaN, <= 0 or >= 1, or count * H * N >= 2^31; fit alone also
+ * on a misaligned scratch and on H > 65535 pooled over the nodes per step. */
+long stemgnn_conformal_rank(long m, double coverage);
+size_t stemgnn_conformal_scratch_bytes(long count, int H, int N, int P, int per_step, int per_node);
+int stemgnn_conformal_fit(const float* target, const float* forecast, long count, int Q, int H, int N, int P,
+                          const int* lo_rows, const int* hi_rows, const double* coverage, int per_step, int per_node,
+                          int masked, void* scratch, float* offsets, long long* counts, void* stream);
+/* out[i, lo_p] = forecast[i, lo_p] - offsets[p, ..], out[i, hi_p] = forecast[i, hi_p] + offsets[p, ..] (one fp32 operation each,
+ * the group's offset broadcast over a pooled axis); rows in no pair are copied bit for bit.  out may be forecast itself.  One
+ * streaming launch, 16-byte accesses when N % 4 == 0 and both buffers are 16-byte aligned.  The shape and pair checks of fit. */
+int stemgnn_conformal_apply(const float* forecast, const float* offsets, long count, int Q, int H, int N, int P,
+                            const int* lo_rows, const int* hi_rows, int per_step, int per_node, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

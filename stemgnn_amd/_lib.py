@@ -166,6 +166,12 @@ SIGNATURES = {
     "stemgnn_quantile_out_doubles": (c_size_t, [c_int, c_int]),
     "stemgnn_quantile_metrics": (c_int, [_P, _P, POINTER(c_double), _P, _P, c_long, c_int, c_int, c_int, _P, _P, _P]),
     "stemgnn_quantile_metrics_masked": (c_int, [_P, _P, POINTER(c_double), _P, _P, c_long, c_int, c_int, c_int, _P, _P, _P]),
+    "stemgnn_conformal_rank": (c_long, [c_long, c_double]),
+    "stemgnn_conformal_scratch_bytes": (c_size_t, [c_long, c_int, c_int, c_int, c_int, c_int]),
+    "stemgnn_conformal_fit": (c_int, [_P, _P, c_long, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int),
+                                      POINTER(c_double), c_int, c_int, c_int, _P, _P, _P, _P]),
+    "stemgnn_conformal_apply": (c_int, [_P, _P, c_long, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), c_int,
+                                        c_int, _P, _P]),
     "stemgnn_infer_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
     "stemgnn_infer_workspace_split_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "stemgnn_gru_fwd_infer": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),

@@ -1621,6 +1621,78 @@ def quantile_metrics(target, forecast, quantiles, mul=None, add=None, ignore_nan
     return out
 
 
+def _conformal_pairs(pairs, Q):
+    pairs = [(int(lo), int(hi)) for lo, hi in pairs]
+    if not pairs:
+        raise ValueError("conformal: no pair of quantile rows")
+    lo = (_lib.c_int * len(pairs))(*[p[0] for p in pairs])
+    hi = (_lib.c_int * len(pairs))(*[p[1] for p in pairs])
+    return len(pairs), lo, hi
+
+
+def conformal_fit(target, forecast, pairs, coverage, per_step=True, per_node=False, ignore_nan=False):
+    """Split-conformal offsets of the quantile pairs (``stemgnn_conformal_fit``): target [count,H,N], forecast [count,Q,H,N] fp32,
+    pairs = P (lo, hi) rows, coverage = their P nominal coverages.  Returns (offsets fp32, counts int64), both device tensors
+    [P, H if per_step else 1, N if per_node else 1]: per group the k-th smallest score max(f_lo - y, y - f_hi),
+    k = ceil((m + 1) coverage (1 - 1e-12)) of its m scores, +inf where k > m.  ignore_nan: NaN targets are left out (otherwise
+    they count as +inf)."""
+    lib = _lib.load()
+    _require_gpu(target, "target")
+    _require_gpu(forecast, "forecast")
+    if target.dim() != 3 or forecast.dim() != 4 or (forecast.shape[0],) + tuple(forecast.shape[2:]) != tuple(target.shape):
+        raise _lib.StemGNNHipError(f"conformal_fit: target must be [count,H,N] and forecast [count,Q,H,N], got "
+                                   f"{tuple(target.shape)} / {tuple(forecast.shape)}")
+    if target.device != forecast.device:
+        raise _lib.StemGNNHipError(f"conformal_fit: target is on {target.device}, forecast on {forecast.device}")
+    target, forecast = target.contiguous(), forecast.contiguous()
+    C, H, N = target.shape
+    Q = forecast.shape[1]
+    P, lo, hi = _conformal_pairs(pairs, Q)
+    if len(coverage) != P:
+        raise ValueError(f"conformal_fit: {P} pairs but {len(coverage)} coverages")
+    dev = target.device
+    shape = (P, H if per_step else 1, N if per_node else 1)
+    nbytes = lib.stemgnn_conformal_scratch_bytes(C, H, N, P, int(bool(per_step)), int(bool(per_node)))
+    scratch = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    offsets = torch.empty(shape, device=dev, dtype=torch.float32)
+    counts = torch.empty(shape, device=dev, dtype=torch.int64)
+    _lib.check(lib.stemgnn_conformal_fit(target.data_ptr(), forecast.data_ptr(), C, Q, H, N, P, lo, hi,
+                                         _lib.host_floats(coverage, _lib.c_double), int(bool(per_step)), int(bool(per_node)),
+                                         int(bool(ignore_nan)), scratch.data_ptr(), offsets.data_ptr(), counts.data_ptr(),
+                                         _stream()), "conformal_fit")
+    return offsets, counts
+
+
+def conformal_apply(forecast, offsets, pairs, per_step=True, per_node=False, out=None):
+    """forecast [count,Q,H,N] with the pairs' rows moved by the offsets of conformal_fit (``stemgnn_conformal_apply``): the low
+    row minus, the high row plus, every other row copied.  out: a contiguous tensor of forecast's shape, or forecast itself
+    (in place); a new tensor by default."""
+    lib = _lib.load()
+    _require_gpu(forecast, "forecast")
+    _require_gpu(offsets, "offsets")
+    if forecast.dim() != 4:
+        raise _lib.StemGNNHipError(f"conformal_apply: forecast must be [count,Q,H,N], got {tuple(forecast.shape)}")
+    C, Q, H, N = forecast.shape
+    P, lo, hi = _conformal_pairs(pairs, Q)
+    shape = (P, H if per_step else 1, N if per_node else 1)
+    if tuple(offsets.shape) != shape or offsets.device != forecast.device:
+        raise _lib.StemGNNHipError(f"conformal_apply: offsets must be {shape} on {forecast.device}, got {tuple(offsets.shape)} "
+                                   f"on {offsets.device}")
+    if out is None:
+        forecast = forecast.contiguous()
+        out = torch.empty_like(forecast)
+    else:
+        _require_gpu(out, "out")
+        if not forecast.is_contiguous() or not out.is_contiguous() or out.shape != forecast.shape or \
+                out.device != forecast.device:
+            raise _lib.StemGNNHipError("conformal_apply: with out=, forecast and out must be contiguous tensors of one shape on "
+                                       "one device")
+    _lib.check(lib.stemgnn_conformal_apply(forecast.data_ptr(), offsets.contiguous().data_ptr(), C, Q, H, N, P, lo, hi,
+                                           int(bool(per_step)), int(bool(per_node)), out.data_ptr(), _stream()),
+               "conformal_apply")
+    return out
+
+
 def eval_metrics(target, forecast, mul=None, add=None, ignore_nan=False):
     """target / forecast [count,H,N] fp32 -> float64 device vector
     overall[3] | by_node[3][N] | by_step[3][H] | by_step_node[3][H][N]  (MAPE, MAE, RMSE each).

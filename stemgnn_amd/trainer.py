@@ -28,10 +28,11 @@ from . import ops
 from .base_model import Model, check_quantiles, point_index
 from .engine import ForecastStep, TrainStep
 from .forecast_dataloader import ForecastDataset, WindowLoader, denorm_coefficients, mark_missing
-from .math_utils import QuantileScores, Scores
+from .math_utils import ConformalCalibrator, QuantileScores, Scores
 from .optim import FusedAdam, FusedRMSprop
 
 BEST = "_stemgnn.pt"
+CONFORMAL = "conformal.pt"      # the calibrator fitted on the best model's validation pass, beside the best checkpoint
 
 
 def checkpoint_path(directory, tag=None):
@@ -51,6 +52,21 @@ def save_checkpoint(model, directory, tag=None):
 def load_checkpoint(directory, tag=None):
     path = checkpoint_path(directory, tag)
     return torch.load(path, weights_only=False) if path.is_file() else None
+
+
+def save_calibrator(calibrator, directory):
+    path = pathlib.Path(directory) / CONFORMAL
+    path.parent.mkdir(parents=True, exist_ok=True)
+    torch.save(calibrator.state_dict(), path)
+    return path
+
+
+def load_calibrator(directory, device=None):
+    """The ConformalCalibrator saved beside the best checkpoint, or None when the run was not calibrated."""
+    path = pathlib.Path(directory) / CONFORMAL
+    if not path.is_file():
+        return None
+    return ConformalCalibrator.from_state_dict(torch.load(path, weights_only=False), device)
 
 
 def rolling_forecast(model, loader, horizon, adjacency=None):
@@ -107,14 +123,18 @@ def rolling_forecast_graph(model, dataset, horizon, batch_size, adjacency=None):
     return step.result()
 
 
-def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=None, ignore_nan=False, quantiles=None):
+def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=None, ignore_nan=False, quantiles=None,
+                   calibrator=None):
     """Metrics of a rolling forecast in raw units (and normalised units under ``*_norm``).  With `dump_dir`, the first
     forecast step of every window is written as CSV (target / predict / absolute error / absolute percentage error).
     ignore_nan: NaN targets (missing readings) are left out of every metric; the CSV files keep them as NaN.
     A 4-D forecast [count, Q, horizon, N] needs `quantiles` (the Q levels): every key above is computed from the point row
     (the level closest to 0.5) through the same metrics kernel, and the calibration of the bands is added in raw units
     (math_utils.QuantileScores): ``pinball`` (mean over the levels), ``pinball_q`` / ``coverage_q`` [Q], ``interval_coverage`` /
-    ``interval_width`` / ``interval_nominal`` [Q // 2] for the pairs (i, Q-1-i), and ``crossing``."""
+    ``interval_width`` / ``interval_nominal`` [Q // 2] for the pairs (i, Q-1-i), and ``crossing``.
+    calibrator (a fitted math_utils.ConformalCalibrator): the bands are calibrated, in the forecast's normalised units, ahead of
+    those figures, and the uncalibrated ones are kept under ``interval_coverage_raw`` / ``interval_width_raw``; the point row and
+    every point metric are untouched."""
     mul = add = None
     if norm_method and statistic:
         mul, add = denorm_coefficients(norm_method, statistic, forecast.device)
@@ -125,13 +145,21 @@ def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=
         quantiles = check_quantiles(quantiles)
         if forecast.shape[1] != len(quantiles):
             raise ValueError(f"score_forecast: forecast has {forecast.shape[1]} quantile rows, quantiles= names {len(quantiles)}")
+        raw_bands = {}
+        if calibrator is not None:
+            qs = QuantileScores(target, forecast, quantiles, mul, add, ignore_nan=ignore_nan)
+            raw_bands = dict(interval_coverage_raw=qs.interval_coverage, interval_width_raw=qs.interval_width)
+            point_row = forecast[:, point_index(quantiles)].contiguous()
+            forecast = calibrator.apply(forecast)
         qs = QuantileScores(target, forecast, quantiles, mul, add, ignore_nan=ignore_nan)
         calibration = dict(pinball=float(qs.pinball.mean()), pinball_q=qs.pinball, coverage_q=qs.coverage,
                            interval_coverage=qs.interval_coverage, interval_width=qs.interval_width,
-                           interval_nominal=qs.interval_nominal, crossing=float(qs.crossing))
-        forecast = forecast[:, point_index(quantiles)].contiguous()
+                           interval_nominal=qs.interval_nominal, crossing=float(qs.crossing), **raw_bands)
+        forecast = point_row if calibrator is not None else forecast[:, point_index(quantiles)].contiguous()
     elif quantiles is not None:
         raise ValueError("score_forecast: quantiles= goes with a [count, Q, horizon, N] forecast")
+    elif calibrator is not None:
+        raise ValueError("score_forecast: calibrator= goes with a [count, Q, horizon, N] forecast")
     raw = Scores(target, forecast, mul, add, ignore_nan=ignore_nan)
     (mape, mae, rmse), (mape_n, mae_n, rmse_n) = raw.get(), raw.get(by_node=True)
     out = dict(mae=mae, mape=mape, rmse=rmse, mae_node=mae_n, mape_node=mape_n, rmse_node=rmse_n)
@@ -173,13 +201,16 @@ class DeviceTrainer:
     def __init__(self, units, window, horizon, multi, *, batch_size=32, lr=1e-4, optimizer="RMSProp", decay_rate=0.5,
                  decay_every=5, norm_method="z_score", device="cuda", model_factory=None, hipgraph=True,
                  dropout_seed=None, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False, loss="mse", huber_delta=1.0,
-                 missing=None, quantiles=None):
+                 missing=None, quantiles=None, calibrate=False, calibrate_per_step=True, calibrate_per_node=False):
         """loss / huber_delta: the training loss of engine.TrainStep ("mse" | "mae" | "huber").  quantiles (levels in (0, 1),
         increasing): a quantile model (Model(..., quantiles=); a `model_factory` gets the keyword too) trained by the pinball loss
         -- `loss` left at its default means "pinball" then; validation keeps selecting the best model on the point forecast's
         MAE and prints the bands' coverage beside it.  missing (a float, e.g. 0.0):
         raw NaN entries and entries equal to it are missing readings -- left out of the column statistics, the training loss
-        and the validation metrics, while the model's inputs stay imputed (ForecastDataset)."""
+        and the validation metrics, while the model's inputs stay imputed (ForecastDataset).
+        calibrate (a quantile model only): whenever validation finds a new best model, a math_utils.ConformalCalibrator
+        (calibrate_per_step / calibrate_per_node: its grouping) is fitted from that pass's forecast and target, kept as
+        `self.calibrator` and saved beside the best checkpoint as ``conformal.pt``; trainer.test applies it."""
         self.units, self.window, self.horizon, self.multi = units, window, horizon, multi
         self.batch_size, self.norm_method, self.device, self.hipgraph = batch_size, norm_method, device, hipgraph
         self.decay_every = decay_every
@@ -187,6 +218,12 @@ class DeviceTrainer:
         if self.quantiles is not None and loss == "mse":
             loss = "pinball"
         self.loss, self.huber_delta, self.missing = loss, huber_delta, missing
+        if calibrate and (self.quantiles is None or len(self.quantiles) < 2):
+            raise ValueError("DeviceTrainer: calibrate=True needs a quantile model with at least two levels (quantiles=)")
+        self.calibrate = bool(calibrate)
+        self.calibrate_per_step, self.calibrate_per_node = bool(calibrate_per_step), bool(calibrate_per_node)
+        self.calibrator = None
+        self._last_pass = None
         head = {} if self.quantiles is None else dict(quantiles=self.quantiles)
         self.model = (model_factory or Model)(units, 2, window, multi, horizon=horizon, **head)
         self.model.to(device)
@@ -211,8 +248,18 @@ class DeviceTrainer:
 
     def validate(self, loader, dump_dir=None):
         forecast, target = rolling_forecast(self.model, loader, self.horizon)
+        if self.calibrate:
+            self._last_pass = (forecast, target)      # what fit() calibrates from when this pass is the best one so far
         return score_forecast(forecast, target, self.norm_method, self.statistic, dump_dir,
                               ignore_nan=self.missing is not None, quantiles=self.quantiles)
+
+    def _calibrate_from_last_pass(self, out_dir=None):
+        forecast, target = self._last_pass
+        self.calibrator = ConformalCalibrator(self.quantiles, self.calibrate_per_step, self.calibrate_per_node)
+        self.calibrator.fit(target, forecast, ignore_nan=self.missing is not None)
+        if out_dir is not None:
+            save_calibrator(self.calibrator, out_dir)
+        return self.calibrator
 
     def fit(self, train_series, valid_series, epochs, *, validate_every=1, patience=None, out_dir=None, on_step=None,
             on_validate=None, log=print):
@@ -280,10 +327,17 @@ class DeviceTrainer:
                     best, stale = metrics["mae"], 0
                     if out_dir is not None:
                         save_checkpoint(self.model, out_dir)
+                    if self.calibrate:
+                        cal = self._calibrate_from_last_pass(out_dir)
+                        log("  conformal: offsets per pair "
+                            + "  ".join(f"{n:.0%}: {float(o.min()):+.4f} .. {float(o.max()):+.4f}"
+                                        for n, o in zip(cal.interval_nominal, cal.offsets))
+                            + f"  ({int(cal.offsets[0].numel())} group(s) per pair, normalised units)")
                 else:
                     stale += 1
             if patience is not None and stale >= patience:
                 break
+        self._last_pass = None
         return metrics, self.statistic
 
     def evaluate(self, series, dump_dir=None):
@@ -300,7 +354,9 @@ def train(train_data, valid_data, args, result_file, model_factory=None, on_step
                             weight_decay=getattr(args, "weight_decay", 0.0), max_grad_norm=getattr(args, "max_grad_norm", None),
                             skip_nonfinite=getattr(args, "skip_nonfinite", False), loss=getattr(args, "loss", "mse"),
                             huber_delta=getattr(args, "huber_delta", 1.0), missing=getattr(args, "missing", None),
-                            quantiles=getattr(args, "quantiles", None))
+                            quantiles=getattr(args, "quantiles", None), calibrate=getattr(args, "calibrate", False),
+                            calibrate_per_step=getattr(args, "calibrate_per_step", True),
+                            calibrate_per_node=getattr(args, "calibrate_per_node", False))
     patience = getattr(args, "early_stop_step", 10) if getattr(args, "early_stop", False) else None
     return trainer.fit(train_data, valid_data, args.epoch, validate_every=args.validate_freq, patience=patience,
                        out_dir=result_file, on_step=on_step, on_validate=on_validate)
@@ -315,7 +371,13 @@ def test(test_data, args, result_train_file, result_test_file):
                               normalize_method=args.norm_method, norm_statistic=statistic, device=args.device)
     loader = WindowLoader(dataset, batch_size=args.batch_size, drop_last=False, shuffle=False)
     forecast, target = rolling_forecast(model, loader, args.horizon)
-    metrics = score_forecast(forecast, target, args.norm_method, statistic, result_test_file,
-                             quantiles=getattr(model, "quantiles", None))
+    quantiles = getattr(model, "quantiles", None)
+    calibrator = load_calibrator(result_train_file, forecast.device) if quantiles is not None else None
+    metrics = score_forecast(forecast, target, args.norm_method, statistic, result_test_file, quantiles=quantiles,
+                             calibrator=calibrator)
     print(f"test: MAPE {metrics['mape']:.4f}  MAE {metrics['mae']:.4f}  RMSE {metrics['rmse']:.4f}")
+    if calibrator is not None:
+        print("test: interval coverage " + "  ".join(
+            f"{n:.0%}: raw {r:.1%} -> calibrated {c:.1%}" for n, r, c in
+            zip(metrics["interval_nominal"], metrics["interval_coverage_raw"], metrics["interval_coverage"])))
     return metrics
