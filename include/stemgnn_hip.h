@@ -727,6 +727,29 @@ int stemgnn_conformal_fit(const float* target, const float* forecast, long count
 int stemgnn_conformal_apply(const float* forecast, const float* offsets, long count, int Q, int H, int N, int P,
                             const int* lo_rows, const int* hi_rows, int per_step, int per_node, float* out, void* stream);
 
+/* ---- serving epilogue of a quantile forecast (csrc/quantile_serve.hip) ---------------------------
+ * forecast / steps / out are [count or B, Q, H, N], target is [B, H, N], fp32 and contiguous.  A column is the Q values of one
+ * (i, h, n).  Finishing a column is two stages, in this order:
+ *   a. rearrange != 0: the column's values in non-decreasing order -- torch.sort(dim=1, stable=True) bit for bit: fp32's order
+ *      with -0 == +0, NaN above everything (+inf included), ties (NaNs among themselves too) in row order; a selection of the
+ *      inputs, so the sign of a zero and a NaN's payload survive.
+ *   b. offsets != NULL: stemgnn_conformal_apply on the result of a (same pairs, groups, broadcast and fp32 operation; rows in no
+ *      pair untouched).  P, lo_rows and hi_rows are ignored when offsets is NULL.
+ * With neither stage both entries are plain copies.
+ * finish: out[i] = the finished forecast[i]; out may be forecast itself (a thread reads its whole column before it writes).
+ * store:  out_forecast[pos[0] + b] = the finished steps[b] and out_target[pos[0] + b] = target[b], with pos (int64[1]) read on
+ *         the device and rows outside [0, capacity) dropped: stemgnn_forecast_store for [capacity, Q, H, N] / [capacity, H, N].
+ * One launch each, no scratch, no allocation, no host synchronisation.  16-byte accesses when N % 4 == 0, Q <= 16 and every
+ * buffer is 16-byte aligned, a scalar path otherwise (a misaligned view included).
+ * SG_EINVAL (nothing launched) on a NULL pointer other than offsets, count / B, Q, H or N <= 0, Q > 32, H * N >= 2^31,
+ * capacity <= 0, and -- with offsets -- everything stemgnn_conformal_apply refuses. */
+int stemgnn_quantile_finish(const float* forecast, long count, int Q, int H, int N, int rearrange, const float* offsets,
+                            int P, const int* lo_rows, const int* hi_rows, int per_step, int per_node, float* out,
+                            void* stream);
+int stemgnn_quantile_store(const float* steps, const float* target, const long long* pos, int B, int Q, int H, int N,
+                           int rearrange, const float* offsets, int P, const int* lo_rows, const int* hi_rows, int per_step,
+                           int per_node, float* out_forecast, float* out_target, long capacity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,6 +172,10 @@ SIGNATURES = {
                                       POINTER(c_double), c_int, c_int, c_int, _P, _P, _P, _P]),
     "stemgnn_conformal_apply": (c_int, [_P, _P, c_long, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), c_int,
                                         c_int, _P, _P]),
+    "stemgnn_quantile_finish": (c_int, [_P, c_long, c_int, c_int, c_int, c_int, _P, c_int, POINTER(c_int), POINTER(c_int),
+                                        c_int, c_int, _P, _P]),
+    "stemgnn_quantile_store": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, POINTER(c_int),
+                                       POINTER(c_int), c_int, c_int, _P, _P, c_long, _P]),
     "stemgnn_infer_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
     "stemgnn_infer_workspace_split_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "stemgnn_gru_fwd_infer": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),

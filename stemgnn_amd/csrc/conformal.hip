@@ -29,6 +29,7 @@
 #include <algorithm>
 
 #include "../../include/stemgnn_hip.h"
+#include "conformal_args.h"
 #include "devattr.h"
 
 #define SG_TRY(e)                                \
@@ -39,7 +40,6 @@
 
 namespace {
 
-constexpr int CF_MAX_Q = 32, CF_MAX_P = 16;
 constexpr int CF_TILE = 32;                 // columns per workgroup (column form)
 constexpr int CF_PITCH = CF_TILE + 1;       // LDS row pitch in words
 constexpr int CF_COPIES = 16;               // histogram copies per workgroup (stream form)
@@ -48,9 +48,6 @@ constexpr int CF_THREADS = 256;
 struct CfPairs {                            // travels by value in the kernel arguments
   int lo[CF_MAX_P], hi[CF_MAX_P];
   double cov[CF_MAX_P];
-};
-struct CfRoles {                            // apply: 0 = copy, p + 1 = the low row of pair p, -(p + 1) = its high row
-  signed char role[CF_MAX_Q];
 };
 
 // the rank of the offset among m valid scores: two fp64 multiplies (no FMA can form) and a ceil; the factor keeps an exactly
@@ -260,22 +257,7 @@ __global__ __launch_bounds__(CF_THREADS) void cf_apply(const float* forecast, co
   }
 }
 
-// the shape and pair checks shared by fit and apply; cf_pairs_ok fills `roles` when asked
-bool cf_shapes_ok(long count, int Q, int H, int N, int P) {
-  if (count <= 0 || Q <= 0 || H <= 0 || N <= 0 || P <= 0 || Q > CF_MAX_Q || P > CF_MAX_P) return false;
-  return (long long)H * N < (1ll << 31) && (long long)count * ((long long)H * N) < (1ll << 31);
-}
-bool cf_pairs_ok(int Q, int P, const int* lo, const int* hi, CfRoles* roles) {
-  CfRoles r = {};
-  for (int p = 0; p < P; ++p) {
-    if (!(0 <= lo[p] && lo[p] < hi[p] && hi[p] < Q)) return false;
-    if (r.role[lo[p]] != 0 || r.role[hi[p]] != 0) return false;      // a row named twice
-    r.role[lo[p]] = (signed char)(p + 1);
-    r.role[hi[p]] = (signed char)-(p + 1);
-  }
-  if (roles) *roles = r;
-  return true;
-}
+// (the shape and pair checks shared by fit and apply: conformal_args.h)
 inline int cf_ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 }  // namespace

@@ -749,9 +749,7 @@ class ForecastStep:
         as NaN for the masked metrics) while the model's inputs come from `series`.
         adjacency (a graph.LatentGraph or an [N,N] tensor): every Model.predict of the pass runs from this graph (no GRU, no
         attention; a window's forecast no longer depends on its batch)."""
-        if getattr(model, "quantiles", None) is not None:
-            raise ValueError("ForecastStep does not take a quantile model: its result slabs hold one [H,N] forecast per window; "
-                             "use trainer.rolling_forecast")
+        self._check_model(model)
         self.model = model
         self.B, self.W, self.horizon = int(batch_size), int(window), int(horizon)
         if series is None or series.dim() != 2:
@@ -774,8 +772,8 @@ class ForecastStep:
         self.pos = torch.zeros(1, dtype=torch.int64, device=dev)                # queue position of the batch in flight
         self.x = torch.zeros(self.B, self.W, self.N, device=dev)
         self.y = torch.zeros(self.B, self.horizon, self.N, device=dev)
-        self.steps = torch.zeros(self.B, self.horizon, self.N, device=dev)
-        self.out_forecast = torch.zeros(cap, self.horizon, self.N, device=dev)
+        self.steps = self._new_steps(self.B, zero=True)
+        self.out_forecast = self._new_steps(cap, zero=True)
         self.out_target = torch.zeros(cap, self.horizon, self.N, device=dev)
         self.want_graph = bool(graph)
         self._replay = None
@@ -783,6 +781,30 @@ class ForecastStep:
         self._n = 0
         self._done = 0
 
+    # -- what a subclass with another forecast format replaces (QuantileForecastStep) ---------------------------
+    def _check_model(self, model):
+        if getattr(model, "quantiles", None) is not None:
+            raise ValueError("ForecastStep does not take a quantile model: its result slabs hold one [H,N] forecast per window; "
+                             "use engine.QuantileForecastStep (trainer.rolling_quantile_forecast_graph)")
+
+    def _new_steps(self, rows, zero=False):
+        """A forecast buffer of `rows` windows: the batch's steps, or the result slab."""
+        return (torch.zeros if zero else torch.empty)(rows, self.horizon, self.N, device=self.device)
+
+    def _roll_round(self, window, out, steps, done):
+        """One round's outputs into `steps`; returns the next window."""
+        return ops.roll_window(window, out, steps, done, self.horizon)
+
+    def _store(self):
+        """The captured batch's steps and targets into the slabs at the device-side position."""
+        ops.forecast_store(self.steps, self.y, self.pos, self.out_forecast, self.out_target)
+
+    def _store_rows(self, steps, y, p):
+        """The ragged last batch's steps and targets into the slab rows p .. p + len(steps)."""
+        self.out_forecast[p:p + steps.shape[0]].copy_(steps)
+        self.out_target[p:p + steps.shape[0]].copy_(y)
+
+    # -------------------------------------------------------------------------------------------------------------
     def _set_queue(self, position, count, wrap=0):
         h = self._q_header
         h[0], h[1], h[2], h[3] = int(position), 0, int(count), int(wrap)
@@ -793,15 +815,15 @@ class ForecastStep:
         done = 0
         while done < self.horizon:
             out, _ = self.model.predict(window, **self.graph_kw)
-            window = ops.roll_window(window, out, steps, done, self.horizon)
-            done += min(self.horizon - done, out.shape[1])
+            window = self._roll_round(window, out, steps, done)
+            done += min(self.horizon - done, out.shape[-2])
 
     def _body(self):
         self.pos.copy_(self.queue[:1])                  # device-side position before the gather advances it
         ops.window_gather_queue(self.series, self.order, self.queue, self.B, self.W, self.horizon, self.x, self.y,
                                 self.target_series)
         self._roll(self.x, self.steps)
-        ops.forecast_store(self.steps, self.y, self.pos, self.out_forecast, self.out_target)
+        self._store()
 
     def _arm(self):
         """Capture the replay.  The capture's warm-up runs read the order in wrap mode; the iterator is put back afterwards
@@ -839,10 +861,9 @@ class ForecastStep:
             p = self._done
             hi = self.order[p:p + left]
             x, y = ops.window_gather(self.series, hi, self.W, self.horizon, target_series=self.target_series)
-            steps = torch.empty(left, self.horizon, self.N, device=self.device)
+            steps = self._new_steps(left)
             self._roll(x, steps)
-            self.out_forecast[p:p + left].copy_(steps)
-            self.out_target[p:p + left].copy_(y)
+            self._store_rows(steps, y, p)
             self._done = self._n
             return
         if not self._armed:
@@ -856,3 +877,62 @@ class ForecastStep:
     def result(self):
         """(forecast, target) [count, horizon, N] of the windows run so far, in load_order's order (views of the slabs)."""
         return self.out_forecast[:self._done], self.out_target[:self._done]
+
+
+class QuantileForecastStep(ForecastStep):
+    """ForecastStep for a quantile model (``Model(..., quantiles=...)``): the same queue, ``load_order`` / ``run_next`` /
+    ``remaining`` / ``result()``, capture and re-arm; the result slabs are [count, Q, horizon, N] and [count, horizon, N].
+
+    A replay gathers the next batch_size windows, runs Model.predict + ops.roll_window_quantile rounds (the POINT row is what is
+    fed back, exactly as trainer.rolling_forecast does it) into steps [B, Q, horizon, N], and ONE ops.quantile_store writes the
+    batch's rows into the slabs finished:
+      rearrange   every (window, step, node)'s Q values in non-decreasing order (math_utils.rearrange_quantiles);
+      calibrator  a fitted math_utils.ConformalCalibrator, applied to the (rearranged) rows -- so one that was fitted on
+                  rearranged forecasts when rearrange is on.
+    Both act on the stored rows only, never on the window that is fed back: the point path -- and with both off the whole result
+    -- is trainer.rolling_forecast's, bit for bit.  The ragged last batch runs the same entries eagerly (ops.quantile_finish
+    into the slab rows)."""
+
+    def __init__(self, model, batch_size, window, horizon, series, order_capacity, graph=True, target_series=None,
+                 adjacency=None, rearrange=False, calibrator=None):
+        self._check_model(model)                  # every refusal below comes before anything touches the device
+        self.rearrange = bool(rearrange)
+        self.calibrator = calibrator
+        self._finish_kw = dict(rearrange=self.rearrange)
+        quantiles = model.quantiles
+        if calibrator is not None:
+            if calibrator.offsets is None:
+                raise ValueError("QuantileForecastStep: the calibrator is not fitted (call fit or load_state_dict first)")
+            if tuple(float(t) for t in calibrator.quantiles) != tuple(float(t) for t in quantiles):
+                raise ValueError(f"QuantileForecastStep: the calibrator's levels {tuple(calibrator.quantiles)} are not the "
+                                 f"model's {tuple(quantiles)}")
+            _, Hg, Ng = calibrator.offsets.shape
+            N = int(series.shape[1]) if series is not None and series.dim() == 2 else None
+            if (calibrator.per_step and Hg != int(horizon)) or (calibrator.per_node and N is not None and Ng != N):
+                raise ValueError(f"QuantileForecastStep: the calibrator's offsets {tuple(calibrator.offsets.shape)} "
+                                 f"(per_step={calibrator.per_step}, per_node={calibrator.per_node}) do not fit horizon {horizon}"
+                                 f" / {N} nodes")
+            dev = series.device if series is not None else calibrator.offsets.device
+            self._finish_kw.update(offsets=calibrator.offsets.to(dev).contiguous(), pairs=calibrator.pairs,
+                                   per_step=calibrator.per_step, per_node=calibrator.per_node)
+        super().__init__(model, batch_size, window, horizon, series, order_capacity, graph=graph, target_series=target_series,
+                         adjacency=adjacency)
+
+    def _check_model(self, model):
+        if getattr(model, "quantiles", None) is None:
+            raise ValueError("QuantileForecastStep needs a quantile model (Model(..., quantiles=...)); a point model goes to "
+                             "ForecastStep")
+        self.Q, self.point = len(model.quantiles), int(model.point_index)
+
+    def _new_steps(self, rows, zero=False):
+        return (torch.zeros if zero else torch.empty)(rows, self.Q, self.horizon, self.N, device=self.device)
+
+    def _roll_round(self, window, out, steps, done):
+        return ops.roll_window_quantile(window, out, steps, done, self.horizon, self.point)
+
+    def _store(self):
+        ops.quantile_store(self.steps, self.y, self.pos, self.out_forecast, self.out_target, **self._finish_kw)
+
+    def _store_rows(self, steps, y, p):
+        ops.quantile_finish(steps, out=self.out_forecast[p:p + steps.shape[0]], **self._finish_kw)
+        self.out_target[p:p + steps.shape[0]].copy_(y)

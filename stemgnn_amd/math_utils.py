@@ -153,6 +153,18 @@ class ConformalCalibrator:
         return cls(state["quantiles"], state["per_step"], state["per_node"]).load_state_dict(state, device)
 
 
+def rearrange_quantiles(y_hat, out=None):
+    """The monotone rearrangement of a quantile forecast [count, Q, H, N]: the Q values of every (window, step, node) in
+    non-decreasing order (``ops.quantile_finish``; ``torch.sort(y_hat, dim=1, stable=True).values`` bit for bit), so no two levels
+    cross and ``QuantileScores.crossing`` is 0 (swapping two crossed levels never raises their summed pinball loss).  out: as in
+    ``ConformalCalibrator.apply`` (y_hat itself: in place).
+    The one rule when it is combined with calibration: rearrange FIRST, and fit the calibrator on rearranged forecasts -- its
+    offsets are quantiles of the scores of the rows it will be applied to.  Nothing is sorted again after calibration (that
+    would move a nested inner band below its guarantee); nested pairs that still cross then are left alone and counted under
+    ``crossing``."""
+    return ops.quantile_finish(_as_f32(y_hat), rearrange=True, out=out)
+
+
 def evaluate(y, y_hat, by_step=False, by_node=False, ignore_nan=False):
     """utils/math_utils.py:59-74.  y: ground truth, y_hat: prediction, both [count, time_step, node] on the GPU.
     ignore_nan: leave the elements whose ground truth is NaN out of every mean."""

@@ -1693,6 +1693,76 @@ def conformal_apply(forecast, offsets, pairs, per_step=True, per_node=False, out
     return out
 
 
+def _finish_stages(what, forecast, offsets, pairs, per_step, per_node):
+    """The calibration stage's arguments of quantile_finish / quantile_store, checked as conformal_apply checks them; returns
+    (offsets pointer or None, P, lo, hi, keep-alive)."""
+    if offsets is None:
+        return None, 0, None, None, None
+    _require_gpu(offsets, "offsets")
+    if pairs is None:
+        raise ValueError(f"{what}: offsets= needs pairs= (the (lo, hi) rows they belong to)")
+    _, Q, H, N = forecast.shape
+    P, lo, hi = _conformal_pairs(pairs, Q)
+    shape = (P, H if per_step else 1, N if per_node else 1)
+    if tuple(offsets.shape) != shape or offsets.device != forecast.device or offsets.dtype != torch.float32:
+        raise _lib.StemGNNHipError(f"{what}: offsets must be float32 {shape} on {forecast.device}, got {offsets.dtype} "
+                                   f"{tuple(offsets.shape)} on {offsets.device}")
+    offsets = offsets.contiguous()
+    return offsets.data_ptr(), P, lo, hi, offsets
+
+
+def quantile_finish(forecast, rearrange=False, offsets=None, pairs=None, per_step=True, per_node=False, out=None):
+    """The finished rows of a quantile forecast [count,Q,H,N] (``stemgnn_quantile_finish``), one launch:
+    rearrange: every column's Q values in non-decreasing order (``torch.sort(forecast, dim=1, stable=True).values`` bit for bit);
+    offsets / pairs / per_step / per_node: then conformal_apply on that.  With neither, a copy.  out: a contiguous tensor of
+    forecast's shape, or forecast itself (in place); a new tensor by default."""
+    lib = _lib.load()
+    _require_gpu(forecast, "forecast")
+    if forecast.dim() != 4 or forecast.dtype != torch.float32:
+        raise _lib.StemGNNHipError(f"quantile_finish: forecast must be float32 [count,Q,H,N], got {forecast.dtype} "
+                                   f"{tuple(forecast.shape)}")
+    optr, P, lo, hi, keep = _finish_stages("quantile_finish", forecast, offsets, pairs, per_step, per_node)
+    if out is None:
+        forecast = forecast.contiguous()
+        out = torch.empty_like(forecast)
+    else:
+        _require_gpu(out, "out")
+        if not forecast.is_contiguous() or not out.is_contiguous() or out.shape != forecast.shape or \
+                out.device != forecast.device or out.dtype != torch.float32:
+            raise _lib.StemGNNHipError("quantile_finish: with out=, forecast and out must be contiguous float32 tensors of one "
+                                       "shape on one device")
+    C, Q, H, N = forecast.shape
+    _lib.check(lib.stemgnn_quantile_finish(forecast.data_ptr(), C, Q, H, N, int(bool(rearrange)), optr, P, lo, hi,
+                                           int(bool(per_step)), int(bool(per_node)), out.data_ptr(), _stream()),
+               "quantile_finish")
+    return out
+
+
+def quantile_store(steps, target, pos, out_forecast, out_target, rearrange=False, offsets=None, pairs=None, per_step=True,
+                   per_node=False):
+    """Result slabs of engine.QuantileForecastStep (``stemgnn_quantile_store``): out_forecast[pos + b] = the finished steps[b]
+    (quantile_finish's two stages) and out_target[pos + b] = target[b], with the row position read on the device (pos: int64[1]);
+    rows at or beyond the slabs' capacity are dropped.  steps [B,Q,H,N], target [B,H,N], slabs [capacity,Q,H,N] / [capacity,H,N]."""
+    lib = _lib.load()
+    _require_gpu(steps, "steps")
+    if steps.dim() != 4:
+        raise _lib.StemGNNHipError(f"quantile_store: steps must be [B,Q,H,N], got {tuple(steps.shape)}")
+    B, Q, H, N = steps.shape
+    if tuple(target.shape) != (B, H, N) or tuple(out_forecast.shape[1:]) != (Q, H, N) or out_forecast.dim() != 4 or \
+            tuple(out_target.shape) != (out_forecast.shape[0], H, N):
+        raise _lib.StemGNNHipError("quantile_store: shape mismatch")
+    for t, name in ((steps, "steps"), (target, "target"), (out_forecast, "out_forecast"), (out_target, "out_target")):
+        if t.device != steps.device or t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.StemGNNHipError(f"quantile_store: {name} must be a contiguous float32 tensor on the steps' device")
+    if pos.dtype != torch.int64 or pos.device != steps.device:
+        raise _lib.StemGNNHipError("quantile_store: pos must be an int64 tensor on the steps' device")
+    optr, P, lo, hi, keep = _finish_stages("quantile_store", steps, offsets, pairs, per_step, per_node)
+    _lib.check(lib.stemgnn_quantile_store(steps.data_ptr(), target.data_ptr(), pos.data_ptr(), B, Q, H, N,
+                                          int(bool(rearrange)), optr, P, lo, hi, int(bool(per_step)), int(bool(per_node)),
+                                          out_forecast.data_ptr(), out_target.data_ptr(), out_forecast.shape[0], _stream()),
+               "quantile_store")
+
+
 def eval_metrics(target, forecast, mul=None, add=None, ignore_nan=False):
     """target / forecast [count,H,N] fp32 -> float64 device vector
     overall[3] | by_node[3][N] | by_step[3][H] | by_step_node[3][H][N]  (MAPE, MAE, RMSE each).

@@ -26,7 +26,7 @@ import torch
 
 from . import ops
 from .base_model import Model, check_quantiles, point_index
-from .engine import ForecastStep, TrainStep
+from .engine import ForecastStep, QuantileForecastStep, TrainStep
 from .forecast_dataloader import ForecastDataset, WindowLoader, denorm_coefficients, mark_missing
 from .math_utils import ConformalCalibrator, QuantileScores, Scores
 from .optim import FusedAdam, FusedRMSprop
@@ -112,11 +112,31 @@ def rolling_forecast_graph(model, dataset, horizon, batch_size, adjacency=None):
     The dataset's horizon (its target length) must equal `horizon`.  adjacency: as in rolling_forecast."""
     if getattr(model, "quantiles", None) is not None:
         raise ValueError("rolling_forecast_graph does not take a quantile model (engine.ForecastStep's result slabs hold one "
-                         "[H,N] forecast per window); use rolling_forecast")
+                         "[H,N] forecast per window); use rolling_quantile_forecast_graph")
     if int(dataset.horizon) != int(horizon):
         raise ValueError(f"rolling_forecast_graph: dataset horizon {dataset.horizon} != horizon {horizon}")
     n = len(dataset)
     step = ForecastStep(model, batch_size, dataset.window_size, horizon, dataset.data, order_capacity=n, adjacency=adjacency)
+    step.load_order(dataset.hi_all)
+    while step.remaining > 0:
+        step.run_next()
+    return step.result()
+
+
+def rolling_quantile_forecast_graph(model, dataset, horizon, batch_size, adjacency=None, rearrange=False, calibrator=None):
+    """rolling_forecast of a quantile model on engine.QuantileForecastStep: each full batch is one hipGraph replay of window
+    gather -> Model.predict -> roll_window_quantile rounds -> ONE quantile_store into the result slabs; the ragged last batch
+    runs eagerly.  Returns (forecast [count, Q, horizon, N], target [count, horizon, N]).
+    rearrange: every (window, step, node)'s Q values leave the graph in non-decreasing order (math_utils.rearrange_quantiles);
+    calibrator (a fitted math_utils.ConformalCalibrator): its offsets are applied to the (rearranged) rows -- with rearrange on
+    it must have been fitted on rearranged forecasts.  With both off the result is rolling_forecast's, bit for bit; with them
+    it is ``calibrator.apply(torch.sort(forecast, dim=1, stable=True).values)`` of that, bit for bit.  Neither touches the window
+    that is fed back.  The dataset's horizon must equal `horizon`; adjacency: as in rolling_forecast."""
+    if int(dataset.horizon) != int(horizon):
+        raise ValueError(f"rolling_quantile_forecast_graph: dataset horizon {dataset.horizon} != horizon {horizon}")
+    n = len(dataset)
+    step = QuantileForecastStep(model, batch_size, dataset.window_size, horizon, dataset.data, order_capacity=n,
+                                adjacency=adjacency, rearrange=rearrange, calibrator=calibrator)
     step.load_order(dataset.hi_all)
     while step.remaining > 0:
         step.run_next()
