@@ -497,6 +497,19 @@ int stemgnn_igft_heads_fwd_infer(const float* const* params_host, const float* p
  * tells whether the fused kernels cover (W,H) (registers / LDS); otherwise the caller keeps its own fc. */
 int stemgnn_fc_tail_supported(int W, int H);
 size_t stemgnn_fc_tail_scratch_floats(int B, int N, int W, int H);
+/* stemgnn_fc_tail_plan: how the fc-tail entries launch for (B, N, W, H), host only (launches nothing).  It is computed from what the
+ * launchers use themselves -- the block-size constants, the LDS-size functions, both `*_scratch_floats` functions -- except [6] and
+ * [7], which mirror the partial-sum kernels' text (csrc/tail.hip says where); the launchers do not read it.  Tests use it to
+ * prove which block counts, ragged blocks and partial-sum trips their cases reach.  out = 12 ints for the 64-row entries
+ * (stemgnn_fc_tail_fwd / _bwd) followed by 12 for the 32-row training entries (`_train*`, H = Q * H for a quantile head):
+ *   [0] rows per block   [1] threads per row   [2] row blocks = ceil(B N / rows)   [3] nacc = (W + 1)(W + H) gradient elements
+ *   [4] floats per block in `scratch` (nacc; training: nacc + 1, the block's loss sum at index nacc)
+ *   [5] grid of the partial-sum launch = ceil([4] / 64)   [6] its block lanes   [7] blocks it sums per trip of all lanes
+ *   [8] dynamic LDS bytes of the first kernel (fwd; training: the row kernel)   [9] 1 if that exceeds the 64 KB default (the
+ *   launcher then raises the kernel's limit first)   [10], [11] the same for the second kernel (bwd; training: 0, 0).
+ * SG_EINVAL where stemgnn_fc_tail_supported(W, H) is 0, B or N <= 0, B N beyond int, or out is NULL. */
+enum { SG_TAIL_PLAN_WORDS = 24 };
+int stemgnn_fc_tail_plan(int B, int N, int W, int H, int* out /* [SG_TAIL_PLAN_WORDS] */);
 int stemgnn_fc_tail_fwd(const float* fsum, const float* w0, const float* b0, const float* w2, const float* b2,
                         int B, int N, int W, int H, float* forecast, void* stream);
 int stemgnn_fc_tail_bwd(const float* dforecast, const float* fsum, const float* w0, const float* b0, const float* w2,
@@ -530,7 +543,10 @@ int stemgnn_fc_tail_train_finish(const float* scratch, int B, int N, int W, int 
  * forecast holds there, and loss = (sum over the valid targets) * norm[1], with norm = the two floats
  * stemgnn_target_valid_count wrote for this target: norm[0] = (float)count of non-NaN values, norm[1] = (float)(1.0 / count),
  * or 0 when count == 0 (loss and every gradient are then exactly 0).  +-inf is a value, not a missing one; a NaN forecast on a
- * valid target still propagates.  `_rows_loss` and `_finish_loss` read norm[1] from device memory when they run; `_finish_loss`
+ * valid target still propagates.  What selection protects: the loss, dfsum, db0 and db2 whatever the forecast holds on a missing
+ * target (NaN or inf included), and dw0 / dw2 as long as the row's activations are finite -- the weight-gradient partials form
+ * dz * x and dy * a per row, so a row whose targets are ALL missing (dz = dy = 0) but whose fsum or activations are not finite gives
+ * 0 * inf = NaN in dw0 / dw2, as torch's matmul backward does.  `_rows_loss` and `_finish_loss` read norm[1] from device memory when they run; `_finish_loss`
  * must get the norm (or NULL) its `_rows_loss` got.  stemgnn_target_valid_count is ONE launch of one workgroup with no
  * host sync (capturable in a hipGraph); its count is an integer sum: exact, order-independent, independent of what norm held.
  * Scratch: stemgnn_fc_tail_train_scratch_floats.  SG_EINVAL (nothing launched) on a NULL pointer other than norm / forecast /

@@ -31,6 +31,19 @@ def gru_paths(B, S, Hd, W, cus=0):
     return {k: int(out[i]) for k, i in SG_GRU_WORD.items()}
 
 
+# words of one kernel family in stemgnn_fc_tail_plan (include/stemgnn_hip.h): 12 for the 64-row entries, then 12 for the training ones
+SG_TAIL_PLAN_WORDS = 24
+SG_TAIL_WORD = {"rows": 0, "row_threads": 1, "nblocks": 2, "nacc": 3, "slots": 4, "reduce_grid": 5, "reduce_lanes": 6,
+                "reduce_trip": 7, "lds0": 8, "lds0_raised": 9, "lds1": 10, "lds1_raised": 11}
+
+
+def fc_tail_plan(B, N, W, H):
+    """stemgnn_fc_tail_plan as {"plain": {...}, "train": {...}} of SG_TAIL_WORD names; raises on SG_EINVAL."""
+    out = (c_int * SG_TAIL_PLAN_WORDS)()
+    check(load().stemgnn_fc_tail_plan(B, N, W, H, out), "stemgnn_fc_tail_plan")
+    return {fam: {k: int(out[12 * f + i]) for k, i in SG_TAIL_WORD.items()} for f, fam in enumerate(("plain", "train"))}
+
+
 _P = c_void_p          # device pointer
 _PP = POINTER(c_void_p)  # host array of device pointers
 
@@ -99,6 +112,7 @@ SIGNATURES = {
     "stemgnn_keyquery_wgrad2": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P]),
     "stemgnn_fc_tail_supported": (c_int, [c_int, c_int]),
     "stemgnn_fc_tail_scratch_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "stemgnn_fc_tail_plan": (c_int, [c_int, c_int, c_int, c_int, _P]),
     "stemgnn_fc_tail_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "stemgnn_fc_tail_bwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
     "stemgnn_fill_zero": (c_int, [_P, c_size_t, _P]),

@@ -375,6 +375,32 @@ static size_t fc_tail_train_lds(int W, int H) {
 extern "C" size_t stemgnn_fc_tail_train_scratch_floats(int B, int N, int W, int H) {
   return (size_t)((B * N + TRAIN_RB - 1) / TRAIN_RB) * (W * W + W + H * W + H + 1);
 }
+// stemgnn_fc_tail_plan: what the launchers of this file do for (B, N, W, H), reported without launching.  It is built from what they
+// themselves use -- TAIL_RB / TRAIN_RB, stemgnn_fc_tail_supported, the three fc_tail_*_lds functions, the two `*_scratch_floats`
+// functions (floats per block = their answer / the block count) -- and from two numbers that mirror the partial-sum kernels'
+// text: their four block lanes (`q = threadIdx.x >> 6`, `b += 4`) and the eight loads per lane of the training one (`b += 32`).
+// The launchers do not read this plan (DESIGN 7g says why): a change of those two kernels' strides has to be made here too.
+constexpr int TAIL_RED_LANES = 4;
+constexpr int TRAIN_RED_LOADS = 8;
+extern "C" int stemgnn_fc_tail_plan(int B, int N, int W, int H, int* out) {
+  if (!out || B <= 0 || N <= 0 || !stemgnn_fc_tail_supported(W, H) || fc_tail_train_lds(W, H) > 150 * 1024 ||
+      (long long)B * N > 0x7fffffffLL - TAIL_RB)
+    return SG_EINVAL;
+  const int M = B * N, nacc = W * W + W + H * W + H;
+  for (int f = 0; f < 2; ++f) {
+    int* o = out + 12 * f;
+    const int rows = f ? TRAIN_RB : TAIL_RB, nblocks = (M + rows - 1) / rows;
+    const size_t floats = f ? stemgnn_fc_tail_train_scratch_floats(B, N, W, H) : stemgnn_fc_tail_scratch_floats(B, N, W, H);
+    const size_t lds[2] = {f ? fc_tail_train_lds(W, H) : fc_tail_fwd_lds(W, H), f ? 0 : fc_tail_bwd_lds(W, H)};
+    o[0] = rows; o[1] = 256 / rows; o[2] = nblocks; o[3] = nacc; o[4] = (int)(floats / nblocks);
+    o[5] = (o[4] + 63) / 64; o[6] = TAIL_RED_LANES; o[7] = f ? TAIL_RED_LANES * TRAIN_RED_LOADS : TAIL_RED_LANES;
+    for (int k = 0; k < 2; ++k) {
+      o[8 + 2 * k] = (int)lds[k];
+      o[9 + 2 * k] = lds[k] > 64 * 1024;                      // sg_ensure_dyn_lds raises the kernel's limit first
+    }
+  }
+  return 0;
+}
 template <int KIND, bool MASKED>
 static int fc_tail_train_rows_launch(const float* fsum, const float* target, const float* w0, const float* b0, const float* w2,
                                      const float* b2, int B, int N, int W, int H, float param, const float* norm,
