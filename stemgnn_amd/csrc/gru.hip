@@ -669,6 +669,32 @@ __device__ __forceinline__ void gru_matvec3(const gru_f2 (&w0)[32], const gru_f2
   o1 = (a1.x + b1.x) + (a1.y + b1.y);
   o2 = (a2.x + b2.x) + (a2.y + b2.y);
 }
+// The same with the three gates PACKED over the lanes (slices of U <= 40 units: 3 U <= 128 outputs): lane l of lane set
+// t holds the row of output o = 64 t + l = gate * U + unit, so a k-pair costs two v_pk_fma instead of three on 33 of 64
+// lanes.  Every output's chains and final adds are those of gru_matvec / gru_matvec3: the same bits.
+constexpr int GRU_PACK_KMAX = 40;
+template <int KU, int NR>
+__device__ __forceinline__ void gru_matvec2(const gru_f2 (&w0)[GRU_PACK_KMAX / 2], const gru_f2 (&w1)[GRU_PACK_KMAX / 2],
+                                            float hv, float* lrow, int lane, float& o0, float& o1) {
+  static_assert(KU <= GRU_PACK_KMAX && (KU & 1) == 0, "packed mat-vec: slices of at most 40 units");
+  const GruBcast<KU, NR> bc(hv, lrow, lane);
+  gru_f2 a0 = {0.f, 0.f}, b0 = {0.f, 0.f}, a1 = {0.f, 0.f}, b1 = {0.f, 0.f};
+#pragma unroll
+  for (int kk = 0; kk + 3 < KU; kk += 4) {
+    const gru_f2 h0 = bc.pair(kk), h1 = bc.pair(kk + 2);
+    a0 = __builtin_elementwise_fma(w0[kk >> 1], h0, a0);
+    a1 = __builtin_elementwise_fma(w1[kk >> 1], h0, a1);
+    b0 = __builtin_elementwise_fma(w0[(kk >> 1) + 1], h1, b0);
+    b1 = __builtin_elementwise_fma(w1[(kk >> 1) + 1], h1, b1);
+  }
+  if constexpr ((KU & 3) != 0) {
+    const gru_f2 h0 = bc.pair(KU - 2);
+    a0 = __builtin_elementwise_fma(w0[(KU - 2) >> 1], h0, a0);
+    a1 = __builtin_elementwise_fma(w1[(KU - 2) >> 1], h0, a1);
+  }
+  o0 = (a0.x + b0.x) + (a0.y + b0.y);
+  o1 = (a1.x + b1.x) + (a1.y + b1.y);
+}
 // backward.  LDS: part[2][3*P][64].  Wave (g, q): reduction slice j = g*Hd + units of owner q.
 template <int P, int KU, int OW>
 __global__ __launch_bounds__(3 * (P / OW) * 64) void gru_bwd_cluster2_kernel(const float* __restrict__ dout, const float* __restrict__ w_hh,
@@ -1150,8 +1176,14 @@ static int gru_fwd_impl(const float* x, const float* w_ih, const float* w_hh, co
     static const int allow_fast = !(getenv("STEMGNN_GRU_FAST_XCD") && atoi(getenv("STEMGNN_GRU_FAST_XCD")) == 0);
     const int PF = pl.PF, KF = pl.KF;                    // wave-specialised forward (gru_cluster4.h), sizes: gru_plan
     const dim3 grid4(8 * ((B + 7) / 8) * PF);
-#define GRU_F4K(PP, KK) hipLaunchKernelGGL((gru_fwd_cluster4_kernel<PP, KK, RS>), grid4, dim3((PP + 2) * 64), 0, st, gi, w_hh, \
-                                           b_hh, B, S, Hd, xbuf, status, h_all, reserve, xid, allow_fast)
+    // The packed instantiations need 100-126 registers per lane where the unpacked ones took 138-164: three waves per SIMD no
+    // longer fill the register file, and LDS-using kernels of the side branch (the GLU warm-up launch, the pack kernels) could
+    // move in beside the pollers, whose latency sets the step time.  Like the backward, the packed forward keeps its CU to
+    // itself by reserving the LDS it does not use (gru4_fwd_hog_bytes: 0 for the unpacked instantiations).
+#define GRU_F4K(PP, KK) do { const size_t hog = gru4_fwd_hog_bytes(PP, KK); \
+    if (hog) (void)hipFuncSetAttribute((const void*)gru_fwd_cluster4_kernel<PP, KK, RS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hog); \
+    hipLaunchKernelGGL((gru_fwd_cluster4_kernel<PP, KK, RS>), grid4, dim3((PP + 2) * 64), hog, st, gi, w_hh, \
+                       b_hh, B, S, Hd, xbuf, status, h_all, reserve, xid, allow_fast); } while (0)
 #define GRU_F4(PP) do { if (KF == 32) GRU_F4K(PP, 32); else if (KF == 34) GRU_F4K(PP, 34); else if (KF == 40) GRU_F4K(PP, 40); \
                         else if (KF == 48) GRU_F4K(PP, 48); else if (KF == 58) GRU_F4K(PP, 58); else GRU_F4K(PP, 64); } while (0)
     if (PF == 1) GRU_F4(1); else if (PF == 2) GRU_F4(2); else if (PF == 4) GRU_F4(4); else if (PF == 5) GRU_F4(5);

@@ -49,7 +49,8 @@ __device__ __forceinline__ void gru4_after_publish(const gru_u64* g) {
 #define GRU_POLL_MODE 0
 #endif
 #ifndef GRU_POLL_PRE_F
-#define GRU_POLL_PRE_F 10     // (12 with the libm gate math of rounds 2-3; retuned with GRU_FAST_GATES in round 4: 1.290 -> 1.277 ms per step)
+#define GRU_POLL_PRE_F 9      // (12 with the libm gate math of rounds 2-3; 10 with GRU_FAST_GATES in round 4; 9 with the packed mat-vec
+                              //  and the vector partial-sum reads, together with GRU_CHORE_SLEEP_F: profiles/gru_packed_ab.txt)
 #endif
 #ifndef GRU_POLL_PRE_B
 #define GRU_POLL_PRE_B 9
@@ -115,8 +116,69 @@ __device__ __forceinline__ void gru4_poll2(const gru_u64* g0, const gru_u64* g1,
   v[0] = act0 ? __uint_as_float((unsigned)x0) : 0.f;
   v[1] = act1 ? __uint_as_float((unsigned)x1) : 0.f;
 }
-constexpr int gru4_static_lds_floats(int P, int nin, int nout) { return 2 * 3 * P * 64 + 3 * P * 64 + 2 * nin * 64 + 2 * nout * 64; }
+// A/B hooks, default on; 0 restores the instruction streams they replaced (csrc/Makefile: libstemgnn_hip_gruref.so has
+// both off).  Neither changes a bit of the results (tests/test_hip_gru_packed.py).
+// GRU_FWD_PACK: forward mat-vec waves of the KU = 34 and 40 instantiations (slices of 33..40 units) hold lane -> (gate,
+//   unit) over two lane sets instead of lane -> unit for three gates: two v_pk_fma per k-pair instead of three
+//   (gru_matvec2).  KU = 32 (slices of <= 32 units: hidden <= 224, the small models) stays unpacked: nothing was measured
+//   to pay there, and the packed kernel's footprint moved the timing of those few-microsecond steps enough to flip the
+//   train step's overlapped-or-serialised schedule decision from run to run.
+// GRU_PART_VEC: the partial sums lie with the slice index contiguous per output, so the gate wave fetches them with
+//   ds_read_b128 (forward P = 7: six instead of 21 ds_read_b32; backward P = 4: three instead of 12).
+#ifndef GRU_FWD_PACK
+#define GRU_FWD_PACK 1
+#endif
+#ifndef GRU_PART_VEC
+#define GRU_PART_VEC 1
+#endif
+// Row stride (floats) of n contiguous partial sums: whole float4s, an ODD number of them -- the 16 lanes of a ds_read_b128
+// group then fall on 16 different 16-byte slots of the 256-byte bank row (the writers' ds_write_b32 are 4-way, off the
+// gate wave).  n <= 4: 4, n <= 12: 12.
+constexpr int gru4_part_stride(int n) { return 4 * (((n + 3) / 4) | 1); }
+// Partial sums of one step parity as rows x slices.  at(row, q): VEC row-major with the padded stride, else slice-major
+// (the unpacked forward and the backward then keep the [gate * P + q][lane] / [wave][lane] image they always had).
+template <int ROWS, int N, int P = 0>           // P > 0: the unpacked forward, row = 64 gate + lane
+struct Gru4Part {
+  static constexpr int PS = gru4_part_stride(N);
+  static constexpr int FLOATS = GRU_PART_VEC ? ROWS * PS : ROWS * N;
+  static __device__ __forceinline__ int at(int row, int q) {
+#if GRU_PART_VEC
+    return row * PS + q;
+#else
+    return P > 0 ? ((row >> 6) * P + q) * 64 + (row & 63) : q * ROWS + row;
+#endif
+  }
+  // acc + the N partial sums of `row`, added in slice order
+  static __device__ __forceinline__ float sum(const float* part, int row, float acc) {
+#if GRU_PART_VEC
+    float4 v[PS / 4];
+#pragma unroll
+    for (int i = 0; i < (N + 3) / 4; ++i) v[i] = *reinterpret_cast<const float4*>(part + row * PS + 4 * i);
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+      const float4 t = v[q >> 2];
+      acc += (q & 3) == 0 ? t.x : ((q & 3) == 1 ? t.y : ((q & 3) == 2 ? t.z : t.w));
+    }
+#else
+#pragma unroll
+    for (int q = 0; q < N; ++q) acc += part[at(row, q)];
+#endif
+    return acc;
+  }
+};
+// upper bound of the static LDS of the backward kernel (its `part` is 64 rows of up to 3 P partial sums)
+constexpr int gru4_static_lds_floats(int P, int nin, int nout) {
+  return 2 * 64 * (GRU_PART_VEC ? gru4_part_stride(3 * P) : 3 * P) + 3 * P * 64 + 2 * nin * 64 + 2 * nout * 64;
+}
 
+// dynamic LDS the PACKED forward instantiations reserve without using it (see the launcher): what is left of 156 KiB
+// beside their static part[2][128 rows] + lrow + gin + stash; 0 = the instantiation does not pack
+constexpr bool gru4_fwd_packs(int KU) { return GRU_FWD_PACK != 0 && KU > 32 && KU <= 40; }
+constexpr size_t gru4_fwd_hog_bytes(int P, int KU) {
+  return gru4_fwd_packs(KU)
+             ? (size_t)156 * 1024 - sizeof(float) * (2 * 128 * (GRU_PART_VEC ? gru4_part_stride(P) : P) + P * 64 + 2 * 3 * 64 + 2 * 5 * 64)
+             : 0;
+}
 // ---- forward ------------------------------------------------------------------------------------------------------
 // Waves 0 .. P-1: mat-vec of owner slice q for all three gates (one broadcast per k serves three v_pk_fma, as in the v3
 // kernel: 4 polling waves instead of 12), wave P: gates, wave P+1: chores.
@@ -127,8 +189,12 @@ constexpr int gru4_static_lds_floats(int P, int nin, int nout) { return 2 * 3 * 
 // The chore wave issues its global loads / stores only after a pause that lets the gate wave's granule stores go first:
 // the CU's memory pipeline is in order, and a granule store queued behind HBM loads costs the whole cluster a step time.
 constexpr int GRU4_WMAX = 16;            // window lengths up to this have dW_ih accumulated inside the backward recurrence
+// x 64 cycles after the barrier (the forward gate phase takes ~600).  The chore wave is IN the step's barrier: with the
+// packed mat-vec its pause of 20, not the mat-vec waves, closed the step.  Forward in the step at PEMS07, pause 24 / 20 / 18 /
+// 17 / 16 / 15 / 14: 242 / 220 / 210 / 206 / 202 / 201 / 217 us (profiles/gru_packed_ab.txt): below 15 its loads and stores
+// get in front of the granule stores; 16 keeps two notches from that edge.
 #ifndef GRU_CHORE_SLEEP_F
-#define GRU_CHORE_SLEEP_F 20            // x 64 cycles after the barrier (the forward gate phase takes ~700)
+#define GRU_CHORE_SLEEP_F 16
 #endif
 #ifndef GRU_SW_MODE
 #define GRU_SW_MODE 0                    // store wave of the backward (progress-publishing launches): 0 = write-through stores
@@ -145,7 +211,11 @@ __global__ __launch_bounds__((P + 2) * 64) void gru_fwd_cluster4_kernel(const fl
                                                                         gru_u64* __restrict__ xbuf, int* __restrict__ status,
                                                                         float* __restrict__ h_all, float* __restrict__ reserve,
                                                                         gru_u64* __restrict__ xid, int allow_fast) {
-  __shared__ float part[2][3 * P][64];
+  // PACK: the mat-vec waves' outputs are o = 64 set + lane = gate * U + unit (U by the cluster, the same in every
+  // workgroup); outputs with unit >= un or o >= 3 U hold zero weights.  Otherwise row 64 gate + lane, lane = unit.
+  constexpr bool PACK = gru4_fwd_packs(KU);
+  typedef Gru4Part<PACK ? 128 : 192, P, PACK ? 0 : P> Part;
+  __shared__ __attribute__((aligned(16))) float part[2][Part::FLOATS];
   __shared__ __attribute__((aligned(16))) float lrow[P][64];
   __shared__ float gin[2][3][64];
   __shared__ float stash[2][5][64];                      // r, z, n, W_hn h + b_hn, h
@@ -161,19 +231,39 @@ __global__ __launch_bounds__((P + 2) * 64) void gru_fwd_cluster4_kernel(const fl
   const int H3 = 3 * Hd;
   const bool lane_ok = lane < un;
   const int gu = u0 + (lane_ok ? lane : 0);
+  // A workgroup that owns no unit (the last ones of a cluster whose slices overshoot Hd: Hd = 16 on seven workgroups)
+  // has nothing to publish or to store, so no partner ever waits for it -- and then nothing keeps it in step either: two
+  // steps late (waves of another kernel on its CU; with the packed kernels' 100 registers they fit) it misses a granule
+  // for good and spins into the time-out.  It has taken part in the XCD check above, which its partners wait for.
+  if (un == 0) return;
 
   if (wave < P) {
     // ---------------- mat-vec wave: owner slot q (rotated by p), gates r, z, n ----------------
     const int q = wave;
     const int k0 = ((q + p) % P) * U, kn = max(0, min(Hd, k0 + U) - k0);
-    gru_f2 wr[3][32];
+    gru_f2 wr[3][32];                                    // lane = unit, three gates
+    gru_f2 wp[2][GRU_PACK_KMAX / 2];                     // PACK: lane = (gate, unit), two lane sets
+    if constexpr (PACK) {
 #pragma unroll
-    for (int g = 0; g < 3; ++g) {
-      const float* wrow = w_hh + ((size_t)g * Hd + gu) * Hd + (kn > 0 ? k0 : 0);
+      for (int t = 0; t < 2; ++t) {
+        const int o = 64 * t + lane, g = o / U, u = o - g * U;
+        const bool live = o < 3 * U && u < un;
+        const float* wrow = w_hh + (live ? ((size_t)g * Hd + u0 + u) * Hd : (size_t)0) + (kn > 0 ? k0 : 0);
 #pragma unroll
-      for (int kk = 0; kk < KU; ++kk) {
-        const float v = wrow[kk < kn ? kk : 0];
-        wr[g][kk >> 1][kk & 1] = (lane_ok && kk < kn) ? v : 0.f;
+        for (int kk = 0; kk < KU; ++kk) {
+          const float v = wrow[kk < kn ? kk : 0];
+          wp[t][kk >> 1][kk & 1] = (live && kk < kn) ? v : 0.f;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int g = 0; g < 3; ++g) {
+        const float* wrow = w_hh + ((size_t)g * Hd + gu) * Hd + (kn > 0 ? k0 : 0);
+#pragma unroll
+        for (int kk = 0; kk < KU; ++kk) {
+          const float v = wrow[kk < kn ? kk : 0];
+          wr[g][kk >> 1][kk & 1] = (lane_ok && kk < kn) ? v : 0.f;
+        }
       }
     }
     const gru_u64* pollp = xbuf + (size_t)b * Hd + k0 + (lane < kn ? lane : 0);      // parity 0; parity 1 is B*Hd further
@@ -187,11 +277,19 @@ __global__ __launch_bounds__((P + 2) * 64) void gru_fwd_cluster4_kernel(const fl
       if (s > 0) hv = gru4_poll<GRU_POLL_PRE_F>(pollp + (s & 1) * par, (unsigned)s, lane < kn, status);
       GRU_T(t1);
       GRU_ACC(c_a, t1, t0);
-      float o0, o1, o2;
-      gru_matvec3<KU, GRU_NR3(KU)>(wr[0], wr[1], wr[2], hv, lrow[q], lane, o0, o1, o2);
-      part[s & 1][0 * P + q][lane] = o0;
-      part[s & 1][1 * P + q][lane] = o1;
-      part[s & 1][2 * P + q][lane] = o2;
+      float* pw = part[s & 1];
+      if constexpr (PACK) {
+        float o0, o1;
+        gru_matvec2<KU, GRU_NR3(KU)>(wp[0], wp[1], hv, lrow[q], lane, o0, o1);
+        pw[Part::at(lane, q)] = o0;
+        pw[Part::at(64 + lane, q)] = o1;
+      } else {
+        float o0, o1, o2;
+        gru_matvec3<KU, GRU_NR3(KU)>(wr[0], wr[1], wr[2], hv, lrow[q], lane, o0, o1, o2);
+        pw[Part::at(lane, q)] = o0;
+        pw[Part::at(64 + lane, q)] = o1;
+        pw[Part::at(128 + lane, q)] = o2;
+      }
       GRU_T(t2);
       GRU_ACC(c_b, t2, t1);
       gru_lds_barrier();                                 // #s
@@ -248,6 +346,8 @@ __global__ __launch_bounds__((P + 2) * 64) void gru_fwd_cluster4_kernel(const fl
     // ---------------- gate wave ----------------
     const float bh0 = b_hh[gu], bh1 = b_hh[Hd + gu], bh2 = b_hh[2 * Hd + gu];
     float hown = 0.f;
+    // partial-sum rows of this lane's unit, gates r, z, n (PACK: lanes beyond the slice read unit 0's and are never stored)
+    const int row0 = PACK ? (lane < U ? lane : 0) : lane, rstep = PACK ? U : 64;
     gru_u64* pub = xbuf + (size_t)b * Hd + gu;           // parity 0
     const size_t par = (size_t)B * Hd;
 #ifdef GRU_PROF
@@ -258,13 +358,8 @@ __global__ __launch_bounds__((P + 2) * 64) void gru_fwd_cluster4_kernel(const fl
       gru_lds_barrier();                                 // #s
       GRU_T(t1);
       GRU_ACC(c_a, t1, t0);
-      float g0 = bh0, g1 = bh1, g2 = bh2;
-#pragma unroll
-      for (int qq = 0; qq < P; ++qq) {
-        g0 += part[s & 1][0 * P + qq][lane];
-        g1 += part[s & 1][1 * P + qq][lane];
-        g2 += part[s & 1][2 * P + qq][lane];
-      }
+      const float* pr = part[s & 1];
+      const float g0 = Part::sum(pr, row0, bh0), g1 = Part::sum(pr, row0 + rstep, bh1), g2 = Part::sum(pr, row0 + 2 * rstep, bh2);
       const float gp0 = gin[s & 1][0][lane], gp1 = gin[s & 1][1][lane], gp2 = gin[s & 1][2][lane];
       const float r = gru4_sigmoid(gp0 + g0);
       const float z = gru4_sigmoid(gp1 + g1);
@@ -323,7 +418,8 @@ __global__ __launch_bounds__((3 * P / OW + 2 + (SW ? 1 : 0)) * 64) void gru_bwd_
   // written or read and the kernel that formed it leaves the backward's critical chain; `dout` is unused then
   static_assert(P % OW == 0 && (OW == 1 || OW == 2), "owner slices per wave");
   constexpr int NMV = 3 * P / OW;
-  __shared__ float part[2][NMV][64];
+  typedef Gru4Part<64, NMV> Part;                        // row = lane (own unit), one partial sum per mat-vec wave
+  __shared__ __attribute__((aligned(16))) float part[2][Part::FLOATS];
   __shared__ __attribute__((aligned(16))) float lrow[NMV][64];
   __shared__ float bin[2][6][64];                        // dh_out, r, z, n, W_hn h + b_hn, h_prev
   __shared__ float bout[2][4][64];                       // dr, dz, dn, dn * r
@@ -339,7 +435,7 @@ __global__ __launch_bounds__((3 * P / OW + 2 + (SW ? 1 : 0)) * 64) void gru_bwd_
   const int H3 = 3 * Hd;
   const bool lane_ok = lane < un;
   const int gu = u0 + (lane_ok ? lane : 0);
-  for (int i = tid; i < 2 * NMV * 64; i += (int)blockDim.x) (&part[0][0][0])[i] = 0.f;
+  for (int i = tid; i < 2 * Part::FLOATS; i += (int)blockDim.x) (&part[0][0])[i] = 0.f;      // (the padding of the rows too)
 
   if (wave < NMV) {
     // ---------------- mat-vec wave (gate g, owner slot q rotated by p): reduction slice j = g*Hd + units of that owner
@@ -378,7 +474,7 @@ __global__ __launch_bounds__((3 * P / OW + 2 + (SW ? 1 : 0)) * 64) void gru_bwd_
         pv = gru_matvec<KU, 64>(wr[0], dv[0], lrow[wave], lane);
         pv += gru_matvec<KU, 64>(wr[OW - 1], dv[1], lrow[wave], lane);
       }
-      part[tag & 1][wave][lane] = pv;
+      part[tag & 1][Part::at(lane, wave)] = pv;
       GRU_T(t2);
       GRU_ACC(c_b, t2, t0);                              // (poll + mat-vec together: the poll's end is inside the if constexpr)
       gru_lds_barrier();                                 // B_s
@@ -533,9 +629,7 @@ __global__ __launch_bounds__((3 * P / OW + 2 + (SW ? 1 : 0)) * 64) void gru_bwd_
     for (int s = S - 1; s >= 0; --s) {
       const unsigned tag = (unsigned)(S - s);
       GRU_T(t1);
-      float dh = bin[s & 1][0][lane] + dhz;
-#pragma unroll
-      for (int w = 0; w < NMV; ++w) dh += part[(tag + 1) & 1][w][lane];      // partials of the step after this one
+      const float dh = Part::sum(part[(tag + 1) & 1], lane, bin[s & 1][0][lane] + dhz);      // partials of the step after this one
       const float r = bin[s & 1][1][lane], z = bin[s & 1][2][lane], n = bin[s & 1][3][lane], ghn = bin[s & 1][4][lane];
       const float hprev = s > 0 ? bin[s & 1][5][lane] : 0.f;
       const float dn = dh * (1.f - z) * (1.f - n * n);
