@@ -766,6 +766,34 @@ int stemgnn_quantile_store(const float* steps, const float* target, const long l
                            int rearrange, const float* offsets, int P, const int* lo_rows, const int* hi_rows, int per_step,
                            int per_node, float* out_forecast, float* out_target, long capacity, void* stream);
 
+/* ---- live forecasting: a stream of readings in a device ring (csrc/live.hip) ----------------------
+ * A ring is [C, N] fp32: the row with absolute index tau (0 = the first row ever pushed) lives in slot tau mod C.  ring_x holds
+ * the imputed, normalised rows (ForecastDataset.data), ring_y the same values with NaN at missing readings
+ * (ForecastDataset.target).  t_dev (int64[1], device) is the number of rows pushed so far.
+ * push:   raw [K, N] fp64 (device), rows in time order.  Per column n: a reading is missing when it is NaN or
+ *         (has_missing && raw == missing); a missing reading is replaced by last[n] (fp64 [N], the column's last valid RAW
+ *         reading; the caller sets it to the column's fill value before the first push), a valid one updates last[n].  The value
+ *         is normalised as stemgnn_normalize_series does -- (float)clip01?((v - sub[n]) / div[n]), IEEE fp64, one rounding --
+ *         and written to ring_x[(t0 + k) mod C]; ring_y gets the same value, or NaN where the reading was missing.  K > C: only
+ *         the last C rows are stored, every row still updates last.  Then t_dev[0] = t0 + K: t0 is the HOST's count of the rows
+ *         pushed before, nothing reads the old device value.
+ * gather: out[b, l, :] = ring[(s_b + l) mod C, :] for l < L, out [B, L, N]; s_b = starts[b] (int64 [B], device), or, with
+ *         starts == NULL, t_dev[0] - back with B == 1 (the current window: back = L = W).  A window that starts below 0, reaches
+ *         past the rows pushed (s_b + L > t) or into rows already overwritten (s_b < t - C) comes back as NaN rows and sets bit 0
+ *         of *status (int32, device; may be NULL).  16-byte accesses when N % 4 == 0 and ring and out are 16-byte aligned, a
+ *         scalar path otherwise.
+ * head:   pos[0] = t_dev[0] mod history and origins[pos[0]] = t_dev[0] (all int64, device; origins [history]): the position at
+ *         which stemgnn_forecast_store / stemgnn_quantile_store file the forecast made now.
+ * One launch each, no atomics, no scratch, no allocation, no host synchronisation.
+ * SG_EINVAL (nothing launched) on a NULL pointer other than starts / status, K, N, C, B or L <= 0, L > C, back < 0 or > C,
+ * t0 < 0, history <= 0, B > 65535, B != 1 without starts, C * N >= 2^31. */
+int stemgnn_live_push(const double* raw, int K, int N, long long t0, const double* sub, const double* div, int clip01,
+                      double missing, int has_missing, double* last, float* ring_x, float* ring_y, int C, long long* t_dev,
+                      void* stream);
+int stemgnn_ring_gather(const float* ring, int C, int N, const long long* starts, const long long* t_dev, int back, int B,
+                        int L, float* out, int* status, void* stream);
+int stemgnn_live_head(const long long* t_dev, long history, long long* pos, long long* origins, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

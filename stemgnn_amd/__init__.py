@@ -8,5 +8,13 @@ fallback: calling the model without the HIP library or on a non-GPU tensor raise
 from .base_model import GLU, Model, StockBlockLayer  # noqa: F401
 from .graph import LatentGraph  # noqa: F401
 
-__all__ = ["Model", "StockBlockLayer", "GLU", "LatentGraph"]
+__all__ = ["Model", "StockBlockLayer", "GLU", "LatentGraph", "LiveForecaster"]
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # engine pulls in torch.distributed: loaded when the serving class is first asked for, not with the package
+    if name == "LiveForecaster":
+        from .engine import LiveForecaster
+        return LiveForecaster
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

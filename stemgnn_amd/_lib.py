@@ -4,7 +4,7 @@ Fails loudly: a missing / unloadable library raises at first use -- there is no 
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_long, c_longlong, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STEMGNN_HIP_LIB", os.path.join(_HERE, "libstemgnn_hip.so"))   # override: A/B builds only
@@ -190,6 +190,9 @@ SIGNATURES = {
                                         c_int, c_int, _P, _P]),
     "stemgnn_quantile_store": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, POINTER(c_int),
                                        POINTER(c_int), c_int, c_int, _P, _P, c_long, _P]),
+    "stemgnn_live_push": (c_int, [_P, c_int, c_int, c_longlong, _P, _P, c_int, c_double, c_int, _P, _P, _P, c_int, _P, _P]),
+    "stemgnn_ring_gather": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    "stemgnn_live_head": (c_int, [_P, c_long, _P, _P, _P]),
     "stemgnn_infer_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
     "stemgnn_infer_workspace_split_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "stemgnn_gru_fwd_infer": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),

@@ -936,3 +936,299 @@ class QuantileForecastStep(ForecastStep):
     def _store_rows(self, steps, y, p):
         ops.quantile_finish(steps, out=self.out_forecast[p:p + steps.shape[0]], **self._finish_kw)
         self.out_target[p:p + steps.shape[0]].copy_(y)
+
+
+class LiveForecaster:
+    """Forecasting from a stream: raw sensor rows go into a device-side ring as they arrive (``push``), and ``forecast`` is the
+    rolling forecast of the window that ends NOW, as one replayed hipGraph.  The counterpart of ForecastStep /
+    QuantileForecastStep for deployment, where no ForecastDataset matrix exists and windows cannot be named by row index.
+
+        live = LiveForecaster(model, window, horizon, normalize_method="z_score", norm_statistic=stat, missing=0.0)
+        live.push(rows)                        # [N] or [K,N]: numpy, host or device tensor, float32 / float64
+        if live.ready: f = live.forecast()     # [horizon,N]; [Q,horizon,N] for a quantile model
+        fc, tg, origins = live.matured()       # the stored forecasts whose targets have arrived since, with those targets
+
+    The rings.  Two [C, N] fp32 rings, C = window + horizon + history; the row with absolute index tau (0 = the first row ever
+    pushed) lives in slot tau mod C.  ``ring_x`` holds what ForecastDataset.data holds (imputed, normalised), ``ring_y`` what
+    ForecastDataset.target holds (NaN at missing readings).  The number of rows pushed is kept twice: ``t_dev`` on the device
+    (the captured graph reads it from memory) and ``rows`` on the host (which knows every K) -- nothing ever syncs to read it.
+
+    Missing readings.  A reading is missing when it is NaN or equals `missing` (None: only NaN).  It is replaced by the column's
+    last valid reading -- the forward fill of the dataset.  `fill` ([N] raw values, default the column's `sub` statistic, which
+    normalises to exactly 0) is what a column holds until its FIRST valid reading.  This is the one place the stream differs from
+    ForecastDataset: the dataset back-fills such leading gaps from the future, a stream cannot see the future.  From a column's
+    first valid reading on both forward-fill, and the ring equals the dataset's rows bit for bit.
+
+    forecast().  All in normalised units: the window at the device-side head, Model.predict, ceil(horizon / H) - 1 rounds of
+    roll_window(_quantile) + predict exactly as ForecastStep runs them, and one forecast_store / quantile_store into the history
+    slab [history, (Q,) horizon, N] at slot rows mod history.  For a quantile model `rearrange` and `calibrator` act on the stored
+    rows only, rearrangement first, never on the window that is fed back, and nothing is sorted after calibration
+    (QuantileForecastStep's rule).  graph=True captures this body once and replays it; graph=False runs it eagerly.  Two calls
+    at the same `rows` overwrite the same slot.
+
+    A live forecast is Model.predict at batch 1: its latent graph is the attention of that ONE window, not the batch mean a
+    validation pass at batch 32 saw, so its numbers differ from that pass's for the same window.  For serving that does not depend
+    on batch composition at all, pass ``adjacency=model.average_graph(loader)`` (or any graph.LatentGraph).
+
+    matured() returns the stored forecasts whose `horizon` target rows have all arrived -- origin o with o + horizon <= rows,
+    slot not overwritten, targets still in the ring (o >= rows - C) -- as (forecasts [m,(Q,)horizon,N], targets [m,horizon,N]
+    from ring_y, origins int64 [m] ascending): ``ConformalCalibrator.fit(tg, fc, ignore_nan=True)`` and
+    ``Scores / QuantileScores(tg, fc, ..., ignore_nan=True)`` take them as they are.  A forecast made every row needs
+    history >= horizon to survive until it matures.
+
+    Device buffers are made at the first push (or load_state_dict): every refusal of the constructor, of forecast() before
+    `ready` and of a push of the wrong width comes before anything touches the device."""
+
+    def __init__(self, model, window, horizon, *, normalize_method=None, norm_statistic=None, missing=None, fill=None,
+                 history=64, adjacency=None, rearrange=False, calibrator=None, graph=True, device=None):
+        import numpy as np
+        from .forecast_dataloader import _stat_arrays
+        self.model = model
+        self.N, self.W, self.horizon, self.history = int(model.unit), int(window), int(horizon), int(history)
+        if self.W != int(model.time_step):
+            raise ValueError(f"LiveForecaster: window {window} is not the model's time_step {model.time_step}")
+        if self.horizon < 1:
+            raise ValueError(f"LiveForecaster: horizon must be at least 1, got {horizon}")
+        if self.history < 1:
+            raise ValueError(f"LiveForecaster: history must be at least 1, got {history}")
+        self.normalize_method, self.norm_statistic = normalize_method, norm_statistic
+        if normalize_method in ("z_score", "min_max"):
+            if not norm_statistic:
+                raise ValueError(f"LiveForecaster: normalize_method={normalize_method!r} needs norm_statistic -- a stream has no "
+                                 "column statistics of its own (pass the training split's)")
+            sub, div, clip, self.norm_statistic = _stat_arrays(None, normalize_method, norm_statistic)
+        else:
+            sub, div, clip = np.zeros(self.N), np.ones(self.N), False
+        sub, div = np.ascontiguousarray(sub, dtype=np.float64).reshape(-1), np.ascontiguousarray(div, dtype=np.float64).reshape(-1)
+        if sub.shape != (self.N,) or div.shape != (self.N,):
+            raise ValueError(f"LiveForecaster: the statistics have {sub.size} / {div.size} columns, the model {self.N} nodes")
+        fill = sub.copy() if fill is None else np.ascontiguousarray(np.broadcast_to(np.asarray(fill, dtype=np.float64),
+                                                                                   (self.N,)))
+        self._host = dict(sub=sub, div=div, fill=fill)
+        self._clip = bool(clip)
+        self.missing = None if missing is None else float(missing)
+        self.quantiles = getattr(model, "quantiles", None)
+        self.Q = len(self.quantiles) if self.quantiles is not None else None
+        self.point = int(model.point_index) if self.quantiles is not None else 0
+        self.rearrange = bool(rearrange)
+        if self.quantiles is None and (self.rearrange or calibrator is not None):
+            raise ValueError("LiveForecaster: rearrange / calibrator go with a quantile model (Model(..., quantiles=...)); a "
+                             "point model has no bands")
+        self._check_calibrator(calibrator)
+        self.calibrator = calibrator
+        self.C = self.W + self.horizon + self.history
+        self.want_graph = bool(graph)
+        self._adjacency = adjacency
+        self._device = device
+        self.rows = 0
+        self._origins = [-1] * self.history             # host mirror of the slab's origins (-1: empty slot)
+        self._ready_buffers = False
+        self._replay = None
+        self._armed = False
+
+    # -- checks that need no device -----------------------------------------------------------------------------
+    def _check_calibrator(self, calibrator):
+        """QuantileForecastStep's refusals: fitted, the model's levels, offsets that fit horizon / N."""
+        if calibrator is None:
+            return
+        if self.quantiles is None:
+            raise ValueError("LiveForecaster: a calibrator goes with a quantile model (Model(..., quantiles=...))")
+        if calibrator.offsets is None:
+            raise ValueError("LiveForecaster: the calibrator is not fitted (call fit or load_state_dict first)")
+        if tuple(float(t) for t in calibrator.quantiles) != tuple(float(t) for t in self.quantiles):
+            raise ValueError(f"LiveForecaster: the calibrator's levels {tuple(calibrator.quantiles)} are not the model's "
+                             f"{tuple(self.quantiles)}")
+        _, Hg, Ng = calibrator.offsets.shape
+        if (calibrator.per_step and Hg != self.horizon) or (calibrator.per_node and Ng != self.N):
+            raise ValueError(f"LiveForecaster: the calibrator's offsets {tuple(calibrator.offsets.shape)} "
+                             f"(per_step={calibrator.per_step}, per_node={calibrator.per_node}) do not fit horizon "
+                             f"{self.horizon} / {self.N} nodes")
+
+    @property
+    def ready(self):
+        return self.rows >= self.W
+
+    # -- device state -------------------------------------------------------------------------------------------
+    def _alloc(self):
+        if self._ready_buffers:
+            return
+        from .forecast_dataloader import _device, denorm_coefficients
+        from .graph import prepare
+        dev = self._device if self._device is not None else next(self.model.parameters()).device
+        dev = self.device = _device(dev)
+        N, C = self.N, self.C
+        self.sub, self.div = (torch.from_numpy(self._host[k]).to(dev) for k in ("sub", "div"))
+        self.last = torch.from_numpy(self._host["fill"].copy()).to(dev)
+        self.ring_x = torch.zeros(C, N, device=dev)
+        self.ring_y = torch.full((C, N), float("nan"), device=dev)
+        self.t_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.origins = torch.full((self.history,), -1, dtype=torch.int64, device=dev)
+        self._t_header = torch.zeros(1, dtype=torch.int64).pin_memory()
+        lead = () if self.Q is None else (self.Q,)
+        self.x = torch.zeros(1, self.W, N, device=dev)
+        self.steps = torch.zeros((1,) + lead + (self.horizon, N), device=dev)
+        self.out_forecast = torch.zeros((self.history,) + lead + (self.horizon, N), device=dev)
+        # the store entries want a target: a static NaN buffer, filled here, outside any capture (the runtime mis-replays
+        # memset nodes of a captured graph) -- the true targets come later, from ring_y (matured)
+        self._nan_target = torch.full((1, self.horizon, N), float("nan"), device=dev)
+        self._out_target = torch.full((self.history, self.horizon, N), float("nan"), device=dev)
+        self.graph_kw = {} if self._adjacency is None else dict(adjacency=prepare(self._adjacency, dev))
+        self._mul, self._add = denorm_coefficients(self.normalize_method, self.norm_statistic, dev)
+        self._offsets = None
+        self._set_finish_kw()
+        ops.ring_status_word(dev)
+        self._ready_buffers = True
+
+    def _set_finish_kw(self):
+        """The store's stage arguments; the offsets live in a buffer of this object's own (what the captured graph reads)."""
+        self._finish_kw = dict(rearrange=self.rearrange)
+        cal = self.calibrator
+        if cal is None:
+            self._offsets = None
+            return
+        if self._offsets is None or self._offsets.shape != cal.offsets.shape:
+            self._offsets = torch.empty(tuple(cal.offsets.shape), dtype=torch.float32, device=self.device)
+        self._offsets.copy_(cal.offsets)
+        self._finish_kw.update(offsets=self._offsets, pairs=cal.pairs, per_step=cal.per_step, per_node=cal.per_node)
+
+    # -- ingest -------------------------------------------------------------------------------------------------
+    def _as_raw(self, rows):
+        """rows -> (float64 [K,N], on the host or on a device), converted as ForecastDataset converts its input."""
+        import numpy as np
+        if torch.is_tensor(rows) and rows.is_cuda:
+            raw = rows.detach().double()
+        else:
+            raw = torch.from_numpy(np.ascontiguousarray(np.asarray(rows.detach().numpy() if torch.is_tensor(rows) else rows,
+                                                                   dtype=np.float64)))
+        if raw.dim() == 1:
+            raw = raw[None, :]
+        if raw.dim() != 2 or raw.shape[1] != self.N or raw.shape[0] < 1:
+            raise ValueError(f"LiveForecaster.push: rows must be [{self.N}] or [K,{self.N}], got {tuple(raw.shape)}")
+        return raw
+
+    def push(self, rows):
+        """K new rows, oldest first; returns the number of rows pushed so far.  Host rows are staged through pinned memory (a
+        block of torch's caching host allocator: it is reused only once its copy has run, so consecutive pushes need no wait);
+        one launch, no sync."""
+        raw = self._as_raw(rows)
+        self._alloc()
+        if raw.is_cuda:
+            raw = raw.to(self.device).contiguous()
+        else:
+            stage = torch.empty(raw.shape, dtype=torch.float64, pin_memory=True)
+            stage.copy_(raw)
+            raw = stage.to(self.device, non_blocking=True)
+        ops.live_push(raw, self.rows, self.sub, self.div, self._clip, self.missing, self.last, self.ring_x, self.ring_y,
+                      self.t_dev)
+        self.rows += int(raw.shape[0])
+        return self.rows
+
+    # -- forecast -----------------------------------------------------------------------------------------------
+    def _roll(self, window, steps):
+        done = 0
+        while done < self.horizon:
+            out, _ = self.model.predict(window, **self.graph_kw)
+            if self.Q is None:
+                window = ops.roll_window(window, out, steps, done, self.horizon)
+            else:
+                window = ops.roll_window_quantile(window, out, steps, done, self.horizon, self.point)
+            done += min(self.horizon - done, out.shape[-2])
+
+    def _body(self):
+        """Kernels and device-to-device copies only (no zero_ / fill_: memset nodes are mis-replayed)."""
+        ops.live_head(self.t_dev, self.history, self.pos, self.origins)
+        ops.ring_gather(self.ring_x, self.t_dev, self.W, back=self.W, out=self.x)
+        self._roll(self.x, self.steps)
+        if self.Q is None:
+            ops.forecast_store(self.steps, self._nan_target, self.pos, self.out_forecast, self._out_target)
+        else:
+            ops.quantile_store(self.steps, self._nan_target, self.pos, self.out_forecast, self._out_target, **self._finish_kw)
+
+    def forecast(self, denormalize=False):
+        """The rolling forecast of the window that ends at the last row pushed: a fresh [horizon,N] ([Q,horizon,N]) tensor in
+        normalised units, or, with denormalize=True, forecast_dataloader.de_normalized of it (float64)."""
+        if not self.ready:
+            raise RuntimeError(f"LiveForecaster.forecast: {self.rows} rows pushed, a window needs {self.W}")
+        if not self._armed:
+            self._armed = True
+            if self.want_graph:
+                # the capture's warm-up runs write the slot this very call writes: nothing to put back
+                self._replay = capture(self._body, warmups=1)
+        if self._replay is not None:
+            self._replay()
+        else:
+            self._body()
+        slot = self.rows % self.history
+        self._origins[slot] = self.rows
+        f = self.out_forecast[slot].clone()
+        if denormalize and self._mul is not None:
+            return f.double() * self._mul + self._add
+        return f.double() if denormalize else f
+
+    # -- matured pairs ------------------------------------------------------------------------------------------
+    def matured(self):
+        """(forecasts [m,(Q,)horizon,N], targets [m,horizon,N], origins int64 [m] ascending) of the stored forecasts whose targets
+        have all arrived; empty tensors of the same rank when there is none."""
+        self._alloc()
+        pairs = sorted((o, s) for s, o in enumerate(self._origins)
+                       if o >= 0 and o + self.horizon <= self.rows and o >= self.rows - self.C)
+        if not pairs:
+            return (self.out_forecast[:0].clone(), torch.empty(0, self.horizon, self.N, device=self.device),
+                    torch.empty(0, dtype=torch.int64, device=self.device))
+        idx = torch.tensor([[o for o, _ in pairs], [s for _, s in pairs]], dtype=torch.int64, device=self.device)
+        origins, slots = idx[0].contiguous(), idx[1].contiguous()
+        fc = self.out_forecast.index_select(0, slots)
+        tg = ops.ring_gather(self.ring_y, self.t_dev, self.horizon, starts=origins)
+        return fc, tg, origins
+
+    # -- calibrator ---------------------------------------------------------------------------------------------
+    def set_calibrator(self, calibrator):
+        """Swap the calibrator (None: off).  A fitted one of the same per_step / per_node shape is copied into the buffer the
+        captured graph already reads -- no re-capture; only a change between present and absent, or of that shape, captures
+        again (at the next forecast)."""
+        self._check_calibrator(calibrator)
+        if calibrator is None and self.calibrator is None:
+            return
+        old = self.calibrator
+        self.calibrator = calibrator
+        if not self._ready_buffers:
+            return
+        same = old is not None and calibrator is not None and self._offsets is not None and \
+            tuple(calibrator.offsets.shape) == tuple(self._offsets.shape) and \
+            (calibrator.per_step, calibrator.per_node) == (old.per_step, old.per_node)
+        if same:
+            self._offsets.copy_(calibrator.offsets)
+            return
+        self._set_finish_kw()
+        self._replay, self._armed = None, False
+
+    # -- restart ------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        """Everything a restarted server needs to go on without replaying the stream: both rings, the fill state, the row
+        count, the history slab and its origins (device tensors are cloned)."""
+        self._alloc()
+        return dict(rows=int(self.rows), window=self.W, horizon=self.horizon, history=self.history, units=self.N,
+                    ring_x=self.ring_x.clone(), ring_y=self.ring_y.clone(), last=self.last.clone(),
+                    history_forecast=self.out_forecast.clone(), origins=torch.tensor(self._origins, dtype=torch.int64))
+
+    def load_state_dict(self, state):
+        for k, mine in (("window", self.W), ("horizon", self.horizon), ("history", self.history), ("units", self.N)):
+            if int(state[k]) != mine:
+                raise ValueError(f"LiveForecaster.load_state_dict: saved with {k}={state[k]}, this one has {mine}")
+        self._alloc()
+        for k, dst in (("ring_x", self.ring_x), ("ring_y", self.ring_y), ("last", self.last),
+                       ("history_forecast", self.out_forecast)):
+            if tuple(state[k].shape) != tuple(dst.shape):
+                raise ValueError(f"LiveForecaster.load_state_dict: {k} is {tuple(state[k].shape)}, expected {tuple(dst.shape)}")
+        if state["origins"].numel() != self.history:
+            raise ValueError(f"LiveForecaster.load_state_dict: {state['origins'].numel()} origins for {self.history} slots")
+        for k, dst in (("ring_x", self.ring_x), ("ring_y", self.ring_y), ("last", self.last),
+                       ("history_forecast", self.out_forecast)):
+            dst.copy_(state[k])
+        self._origins = [int(v) for v in state["origins"].tolist()]
+        self.origins.copy_(torch.tensor(self._origins, dtype=torch.int64))
+        self.rows = int(state["rows"])
+        self._t_header[0] = self.rows
+        self.t_dev.copy_(self._t_header, non_blocking=False)
+        return self

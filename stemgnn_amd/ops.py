@@ -1763,6 +1763,97 @@ def quantile_store(steps, target, pos, out_forecast, out_target, rearrange=False
                "quantile_store")
 
 
+def _ring_ok(what, ring, t_dev):
+    _require_gpu(ring, "ring")
+    if ring.dim() != 2 or ring.dtype != torch.float32 or not ring.is_contiguous():
+        raise _lib.StemGNNHipError(f"{what}: a ring must be a contiguous float32 [C,N] tensor, got {ring.dtype} "
+                                   f"{tuple(ring.shape)}")
+    if t_dev.dtype != torch.int64 or t_dev.device != ring.device or t_dev.numel() < 1:
+        raise _lib.StemGNNHipError(f"{what}: t_dev must be an int64 tensor on the ring's device")
+
+
+def live_push(raw, t0, sub, div, clip01, missing, last, ring_x, ring_y, t_dev):
+    """K new rows of a stream into the rings (``stemgnn_live_push``): raw [K,N] float64 on the device, t0 the HOST's count of the
+    rows pushed before.  Forward fill from `last` (float64 [N], updated), the normalisation of normalize_series, ring_x the
+    imputed rows, ring_y the same with NaN at the missing readings (NaN, or `missing` when it is not None); then
+    t_dev[0] = t0 + K.  One launch, nothing synchronises."""
+    lib = _lib.load()
+    _ring_ok("live_push", ring_x, t_dev)
+    _ring_ok("live_push", ring_y, t_dev)
+    C, N = ring_x.shape
+    if ring_y.shape != ring_x.shape or ring_y.device != ring_x.device:
+        raise _lib.StemGNNHipError("live_push: ring_x and ring_y must have one shape and device")
+    if raw.dim() != 2 or raw.shape[1] != N or raw.dtype != torch.float64 or raw.device != ring_x.device or \
+            not raw.is_contiguous():
+        raise _lib.StemGNNHipError(f"live_push: raw must be a contiguous float64 [K,{N}] tensor on the rings' device")
+    for t, name in ((sub, "sub"), (div, "div"), (last, "last")):
+        if t.dtype != torch.float64 or t.device != ring_x.device or t.numel() != N or not t.is_contiguous():
+            raise _lib.StemGNNHipError(f"live_push: {name} must be a contiguous float64 [{N}] tensor on the rings' device")
+    _lib.check(lib.stemgnn_live_push(raw.data_ptr(), raw.shape[0], N, int(t0), sub.data_ptr(), div.data_ptr(),
+                                     int(bool(clip01)), 0.0 if missing is None else float(missing), int(missing is not None),
+                                     last.data_ptr(), ring_x.data_ptr(), ring_y.data_ptr(), C, t_dev.data_ptr(), _stream()),
+               "live_push")
+
+
+_ring_status = {}
+
+
+def ring_status_word(device):
+    """The device's int32 status word of ring_gather (created on first use: a caller that captures a ring_gather into a hipGraph
+    asks for it once ahead of the capture, so that its zero fill is not a node of the graph)."""
+    key = str(device)
+    st = _ring_status.get(key)
+    if st is None:
+        st = _ring_status[key] = torch.zeros(1, dtype=torch.int32, device=device)
+    return st
+
+
+def ring_gather(ring, t_dev, L, starts=None, back=0, out=None):
+    """out[b, l] = ring[(s_b + l) mod C] for l < L (``stemgnn_ring_gather``): s_b = starts[b] (int64 [B], device), or the one
+    window that starts `back` rows behind the device-side head t_dev[0] when starts is None.  A window that is not (or no longer)
+    in the ring comes back as NaN rows (and sets bit 0 of the device's ring status word: check_ring_status)."""
+    lib = _lib.load()
+    _ring_ok("ring_gather", ring, t_dev)
+    C, N = ring.shape
+    if starts is not None:
+        if starts.dtype != torch.int64 or starts.device != ring.device or starts.dim() != 1 or not starts.is_contiguous():
+            raise _lib.StemGNNHipError("ring_gather: starts must be a contiguous int64 [B] tensor on the ring's device")
+        B = starts.numel()
+    else:
+        B = 1
+    if out is None:
+        out = torch.empty(B, int(L), N, device=ring.device, dtype=torch.float32)
+    elif tuple(out.shape) != (B, int(L), N) or out.dtype != torch.float32 or out.device != ring.device or \
+            not out.is_contiguous():
+        raise _lib.StemGNNHipError(f"ring_gather: out must be a contiguous float32 {(B, int(L), N)} tensor on the ring's device")
+    st = ring_status_word(ring.device)
+    _lib.check(lib.stemgnn_ring_gather(ring.data_ptr(), C, N, starts.data_ptr() if starts is not None else None,
+                                       t_dev.data_ptr(), int(back), B, int(L), out.data_ptr(), st.data_ptr(), _stream()),
+               "ring_gather")
+    return out
+
+
+def check_ring_status(device):
+    """Raise if any ring_gather since the last check asked for rows the ring does not hold (one sync)."""
+    st = _ring_status.get(str(device))
+    if st is not None and int(st.item()) != 0:
+        st.zero_()
+        raise IndexError("ring_gather: a window outside the rows the ring holds (NaN rows were returned)")
+
+
+def live_head(t_dev, history, pos, origins):
+    """pos[0] = t_dev[0] mod history and origins[pos[0]] = t_dev[0] on the device (``stemgnn_live_head``): the slab position of
+    the forecast made now, for forecast_store / quantile_store."""
+    lib = _lib.load()
+    for t, name in ((t_dev, "t_dev"), (pos, "pos"), (origins, "origins")):
+        if not t.is_cuda or t.dtype != torch.int64 or t.device != t_dev.device or not t.is_contiguous():
+            raise _lib.StemGNNHipError(f"live_head: {name} must be a contiguous int64 tensor on one HIP device")
+    if origins.numel() != int(history):
+        raise _lib.StemGNNHipError(f"live_head: origins must hold history = {history} entries, got {origins.numel()}")
+    _lib.check(lib.stemgnn_live_head(t_dev.data_ptr(), int(history), pos.data_ptr(), origins.data_ptr(), _stream()),
+               "live_head")
+
+
 def eval_metrics(target, forecast, mul=None, add=None, ignore_nan=False):
     """target / forecast [count,H,N] fp32 -> float64 device vector
     overall[3] | by_node[3][N] | by_step[3][H] | by_step_node[3][H][N]  (MAPE, MAE, RMSE each).
