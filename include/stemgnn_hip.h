@@ -794,6 +794,38 @@ int stemgnn_ring_gather(const float* ring, int C, int N, const long long* starts
                         int L, float* out, int* status, void* stream);
 int stemgnn_live_head(const long long* t_dev, long history, long long* pos, long long* origins, void* stream);
 
+/* ---- adaptive conformal inference for live forecasts (Gibbs & Candes 2021; csrc/aci.hip) -----------
+ * One call processes ONE matured forecast (one origin) for all P pairs and all groups; pairs and groups are those of
+ * stemgnn_conformal_fit (per_step / per_node, state [P, Hg, Ng]).  issued [Q, H, N] = the finished rows that were served,
+ * raw [Q, H, N] = the same forecast ahead of calibration, fp32 and contiguous.  The targets are a ring [C, N]: target row h sits
+ * in slot (origin + h) mod C (a plain [H, N] tensor is C = H, origin = 0).  lo_rows, hi_rows and target_alpha (= 1 - coverage,
+ * in (0, 1)) are P values each in HOST memory, read by the call itself and passed on by value.
+ * Device state, owned by the caller and persistent between calls: scores [M, P, H, N] fp32 (NaN = absent; a new window is all
+ * NaN), alpha fp64 (initialised to target_alpha[p]), offsets fp32 (the buffer stemgnn_quantile_store reads), counts, miss_sum,
+ * valid_sum int64, the last five [P, Hg, Ng].
+ * Per pair p and group g, in this order:
+ *   1. score: for every (h, n) of the group s = max(raw_lo - y, y - raw_hi) as stemgnn_conformal_fit computes it (fp32, one
+ *      rounding each, a NaN from the forecast gives +inf, -0 becomes +0); a NaN target makes the element invalid: its score
+ *      slot gets NaN and it counts nowhere.  The origin's scores overwrite slot `slot` (= the host's n_done mod M) of the window.
+ *   2. error: valid = the group's valid elements of this origin, miss = those with !(issued_lo <= y && y <= issued_hi) (a NaN
+ *      band is a miss, an infinite one covers); miss_sum += miss, valid_sum += valid.
+ *   3. level: m = the group's non-NaN scores in the whole window after step 1; counts = m.  If valid == 0 or m < min_scores,
+ *      alpha and the offset stay exactly as they are.  Otherwise alpha = alpha + gamma * (target_alpha - miss / valid), four
+ *      individually rounded IEEE fp64 operations (divide, subtract, multiply, add; no FMA).  alpha is NOT clamped.
+ *   4. offset: c = 1 - alpha.  !(c > 0): -inf (the empty band).  Otherwise k = stemgnn_conformal_rank(m, c); k > m: +inf; else
+ *      the k-th smallest of the m scores in the total order of fp32 with -0 == +0: an exact MSB-first radix select, four 8-bit
+ *      passes over integer histograms in LDS inside the one launch.  No sort, no floating-point atomics: the same bits on
+ *      every run.
+ * gamma == 0 is a rolling-window split-conformal refit at the nominal level.  One launch, no scratch, no allocation, no host
+ * synchronisation; 16-byte accesses pooled over the nodes when N % 4 == 0 and issued, raw, ring_y and scores are 16-byte aligned.
+ * SG_EINVAL (nothing launched) on a NULL pointer, Q, H, N, P, M or C <= 0, Q > 32, P > 16, a pair outside 0 <= lo < hi < Q, a row
+ * named twice, gamma NaN or < 0, a target_alpha that is NaN, <= 0 or >= 1, slot outside [0, M), origin < 0, H > C,
+ * M * H * N >= 2^31, C * N >= 2^31, min_scores < 0. */
+int stemgnn_aci_update(const float* issued, const float* raw, const float* ring_y, int C, long long origin, int Q, int H, int N,
+                       int P, const int* lo_rows, const int* hi_rows, const double* target_alpha, double gamma, int M, int slot,
+                       long long min_scores, int per_step, int per_node, float* scores, double* alpha, float* offsets,
+                       long long* counts, long long* miss_sum, long long* valid_sum, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

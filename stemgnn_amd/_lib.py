@@ -193,6 +193,9 @@ SIGNATURES = {
     "stemgnn_live_push": (c_int, [_P, c_int, c_int, c_longlong, _P, _P, c_int, c_double, c_int, _P, _P, _P, c_int, _P, _P]),
     "stemgnn_ring_gather": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "stemgnn_live_head": (c_int, [_P, c_long, _P, _P, _P]),
+    "stemgnn_aci_update": (c_int, [_P, _P, _P, c_int, c_longlong, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int),
+                                   POINTER(c_double), c_double, c_int, c_int, c_longlong, c_int, c_int, _P, _P, _P, _P, _P, _P,
+                                   _P]),
     "stemgnn_infer_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
     "stemgnn_infer_workspace_split_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "stemgnn_gru_fwd_infer": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),

@@ -976,8 +976,18 @@ class LiveForecaster:
     ``Scores / QuantileScores(tg, fc, ..., ignore_nan=True)`` take them as they are.  A forecast made every row needs
     history >= horizon to survive until it matures.
 
-    Device buffers are made at the first push (or load_state_dict): every refusal of the constructor, of forecast() before
-    `ready` and of a push of the wrong width comes before anything touches the device."""
+    set_adaptive(adaptive): adapting bands (math_utils.AdaptiveConformal; None switches it off).  The captured body gains one
+    launch, a second quantile_store of the same steps into out_raw [history, Q, horizon, N] (rearranged as the first, no
+    offsets), and the first store reads the adaptive object's offsets buffer.  Every forecast() first feeds the stored forecasts
+    that have matured since the last call -- origin o > done, o + horizon <= rows, targets still in the ring -- to
+    adaptive.update(issued = out_forecast[slot], raw = out_raw[slot], ring = ring_y, origin = o), oldest first: eager launches
+    with host-known arguments, as push is; the replay that follows reads the new offsets through stream order, so nothing is ever
+    captured again.  With one forecast per row that is one update per forecast.  All `horizon` steps of an origin are scored
+    when its LAST target arrives, so the feedback is `horizon` rows late; the long-run coverage bound of ACI loosens with that
+    delay (the level in force was set `horizon` updates ago).  Forecasts stored before set_adaptive are not learnt from.
+
+    Device buffers are made at the first push (or load_state_dict): every refusal of the constructor, of set_adaptive, of
+    forecast() before `ready` and of a push of the wrong width comes before anything touches the device."""
 
     def __init__(self, model, window, horizon, *, normalize_method=None, norm_statistic=None, missing=None, fill=None,
                  history=64, adjacency=None, rearrange=False, calibrator=None, graph=True, device=None):
@@ -1016,6 +1026,7 @@ class LiveForecaster:
                              "point model has no bands")
         self._check_calibrator(calibrator)
         self.calibrator = calibrator
+        self.adaptive, self.done, self._adaptive_init = None, -1, None
         self.C = self.W + self.horizon + self.history
         self.want_graph = bool(graph)
         self._adjacency = adjacency
@@ -1076,6 +1087,8 @@ class LiveForecaster:
         self.graph_kw = {} if self._adjacency is None else dict(adjacency=prepare(self._adjacency, dev))
         self._mul, self._add = denorm_coefficients(self.normalize_method, self.norm_statistic, dev)
         self._offsets = None
+        self.out_raw = None
+        self._attach_adaptive()
         self._set_finish_kw()
         ops.ring_status_word(dev)
         self._ready_buffers = True
@@ -1084,6 +1097,11 @@ class LiveForecaster:
         """The store's stage arguments; the offsets live in a buffer of this object's own (what the captured graph reads)."""
         self._finish_kw = dict(rearrange=self.rearrange)
         cal = self.calibrator
+        if self.adaptive is not None:                   # the adaptive object's own buffer: every update is seen by the replay
+            ad = self.adaptive
+            self._offsets = None
+            self._finish_kw.update(offsets=ad.offsets, pairs=ad.pairs, per_step=ad.per_step, per_node=ad.per_node)
+            return
         if cal is None:
             self._offsets = None
             return
@@ -1144,12 +1162,25 @@ class LiveForecaster:
             ops.forecast_store(self.steps, self._nan_target, self.pos, self.out_forecast, self._out_target)
         else:
             ops.quantile_store(self.steps, self._nan_target, self.pos, self.out_forecast, self._out_target, **self._finish_kw)
+            if self.adaptive is not None:               # the same rows ahead of calibration: what the scores are taken on
+                ops.quantile_store(self.steps, self._nan_target, self.pos, self.out_raw, self._out_target,
+                                   rearrange=self.rearrange)
+
+    def _feed_adaptive(self):
+        """The stored forecasts that matured since the last call, oldest first, one eager update launch each (no sync)."""
+        due = sorted((o, s) for s, o in enumerate(self._origins)
+                     if o > self.done and o + self.horizon <= self.rows and o >= self.rows - self.C)
+        for o, s in due:
+            self.adaptive.update(None, self.out_forecast[s], self.out_raw[s], ring=self.ring_y, origin=o)
+            self.done = o
 
     def forecast(self, denormalize=False):
         """The rolling forecast of the window that ends at the last row pushed: a fresh [horizon,N] ([Q,horizon,N]) tensor in
         normalised units, or, with denormalize=True, forecast_dataloader.de_normalized of it (float64)."""
         if not self.ready:
             raise RuntimeError(f"LiveForecaster.forecast: {self.rows} rows pushed, a window needs {self.W}")
+        if self.adaptive is not None:
+            self._feed_adaptive()                       # ahead of the replay, which may reuse a matured slot
         if not self._armed:
             self._armed = True
             if self.want_graph:
@@ -1187,6 +1218,9 @@ class LiveForecaster:
         """Swap the calibrator (None: off).  A fitted one of the same per_step / per_node shape is copied into the buffer the
         captured graph already reads -- no re-capture; only a change between present and absent, or of that shape, captures
         again (at the next forecast)."""
+        if self.adaptive is not None:
+            raise ValueError("LiveForecaster.set_calibrator: adaptive bands are on and own the offsets; call set_adaptive(None) "
+                             "first")
         self._check_calibrator(calibrator)
         if calibrator is None and self.calibrator is None:
             return
@@ -1203,19 +1237,73 @@ class LiveForecaster:
         self._set_finish_kw()
         self._replay, self._armed = None, False
 
+    # -- adaptive bands -----------------------------------------------------------------------------------------
+    def set_adaptive(self, adaptive):
+        """Switch adaptive conformal bands on (a math_utils.AdaptiveConformal) or off (None); see the class docstring.  A static
+        calibrator that is set must have the same levels and grouping: its offsets become the initial offsets and it is taken
+        over (`calibrator` becomes None); without one the initial offsets are 0 -- unless the adaptive object already carries
+        state (a restart), which it then keeps.  The body is captured again at the next forecast, and never after that."""
+        if adaptive is None:
+            if self.adaptive is None:
+                return
+            self.adaptive, self._adaptive_init = None, None
+        else:
+            if self.quantiles is None:
+                raise ValueError("LiveForecaster.set_adaptive: adaptive bands go with a quantile model (Model(..., "
+                                 "quantiles=...)); a point model has no bands")
+            if tuple(float(t) for t in adaptive.quantiles) != tuple(float(t) for t in self.quantiles):
+                raise ValueError(f"LiveForecaster.set_adaptive: the adaptive object's levels {tuple(adaptive.quantiles)} are not "
+                                 f"the model's {tuple(self.quantiles)}")
+            if adaptive.offsets is not None and tuple(adaptive.offsets.shape) != adaptive.group_shape(self.horizon, self.N):
+                raise ValueError(f"LiveForecaster.set_adaptive: the adaptive object's offsets {tuple(adaptive.offsets.shape)} "
+                                 f"(per_step={adaptive.per_step}, per_node={adaptive.per_node}) do not fit horizon "
+                                 f"{self.horizon} / {self.N} nodes")
+            if self.history < self.horizon:
+                raise ValueError(f"LiveForecaster.set_adaptive: history {self.history} < horizon {self.horizon}: a forecast made "
+                                 "every row would be overwritten before it matures and nothing would ever be learnt")
+            cal = self.calibrator
+            if cal is not None and (cal.per_step, cal.per_node) != (adaptive.per_step, adaptive.per_node):
+                raise ValueError(f"LiveForecaster.set_adaptive: the calibrator in force has per_step={cal.per_step}, "
+                                 f"per_node={cal.per_node}, the adaptive object {adaptive.per_step}, {adaptive.per_node}")
+            self._adaptive_init = None if cal is None else cal.offsets
+            self.adaptive, self.calibrator = adaptive, None
+            self.done = max([-1] + self._origins)       # what the slab holds now has no raw rows beside it
+        if self._ready_buffers:
+            self._attach_adaptive()
+            self._set_finish_kw()
+            self._replay, self._armed = None, False
+
+    def _attach_adaptive(self):
+        """The adaptive object's device state and the raw slab (fill kernels, outside any capture)."""
+        ad = self.adaptive
+        if ad is None:
+            return
+        ad.init_state(self.horizon, self.N, self.device)
+        if self._adaptive_init is not None:
+            ad.offsets.copy_(self._adaptive_init.reshape(ad.offsets.shape))
+            self._adaptive_init = None
+        if self.out_raw is None:
+            self.out_raw = torch.zeros_like(self.out_forecast)
+
     # -- restart ------------------------------------------------------------------------------------------------
     def state_dict(self):
         """Everything a restarted server needs to go on without replaying the stream: both rings, the fill state, the row
-        count, the history slab and its origins (device tensors are cloned)."""
+        count, the history slab and its origins (device tensors are cloned); with adaptive bands also the raw slab, `done` and
+        the adaptive object's state."""
         self._alloc()
-        return dict(rows=int(self.rows), window=self.W, horizon=self.horizon, history=self.history, units=self.N,
-                    ring_x=self.ring_x.clone(), ring_y=self.ring_y.clone(), last=self.last.clone(),
-                    history_forecast=self.out_forecast.clone(), origins=torch.tensor(self._origins, dtype=torch.int64))
+        state = dict(rows=int(self.rows), window=self.W, horizon=self.horizon, history=self.history, units=self.N,
+                     ring_x=self.ring_x.clone(), ring_y=self.ring_y.clone(), last=self.last.clone(),
+                     history_forecast=self.out_forecast.clone(), origins=torch.tensor(self._origins, dtype=torch.int64))
+        if self.adaptive is not None:
+            state.update(history_raw=self.out_raw.clone(), done=int(self.done), adaptive=self.adaptive.state_dict())
+        return state
 
     def load_state_dict(self, state):
         for k, mine in (("window", self.W), ("horizon", self.horizon), ("history", self.history), ("units", self.N)):
             if int(state[k]) != mine:
                 raise ValueError(f"LiveForecaster.load_state_dict: saved with {k}={state[k]}, this one has {mine}")
+        if self.adaptive is not None and "adaptive" not in state:
+            raise ValueError("LiveForecaster.load_state_dict: adaptive bands are on, but the state was saved without them")
         self._alloc()
         for k, dst in (("ring_x", self.ring_x), ("ring_y", self.ring_y), ("last", self.last),
                        ("history_forecast", self.out_forecast)):
@@ -1231,4 +1319,17 @@ class LiveForecaster:
         self.rows = int(state["rows"])
         self._t_header[0] = self.rows
         self.t_dev.copy_(self._t_header, non_blocking=False)
+        if self.adaptive is not None:
+            if tuple(state["history_raw"].shape) != tuple(self.out_raw.shape):
+                raise ValueError(f"LiveForecaster.load_state_dict: history_raw is {tuple(state['history_raw'].shape)}, expected "
+                                 f"{tuple(self.out_raw.shape)}")
+            loaded = type(self.adaptive)(self.adaptive.quantiles, self.adaptive.gamma, self.adaptive.window,
+                                         self.adaptive.per_step, self.adaptive.per_node, self.adaptive.min_scores)
+            loaded.load_state_dict(state["adaptive"], device=self.device)
+            if loaded.offsets is not None:              # into the buffers the captured graph may already read
+                for k in self.adaptive._STATE:
+                    getattr(self.adaptive, k).copy_(getattr(loaded, k))
+            self.adaptive.n_done = loaded.n_done
+            self.out_raw.copy_(state["history_raw"])
+            self.done = int(state["done"])
         return self

@@ -153,6 +153,137 @@ class ConformalCalibrator:
         return cls(state["quantiles"], state["per_step"], state["per_node"]).load_state_dict(state, device)
 
 
+class AdaptiveConformal:
+    """Adaptive conformal inference (ACI, Gibbs & Candes 2021) for the bands of a live quantile forecast, on the device.
+
+    A `ConformalCalibrator` fitted once covers "in expectation on exchangeable new data"; a stream whose regime changes is not
+    exchangeable.  This object keeps, per pair and group, a working miscoverage level alpha_t and a rolling window of the last
+    `window` forecasts' scores, and after every realised target (`update`, one launch of ``ops.aci_update``)
+        alpha <- alpha + gamma * (alpha* - miss / valid)            alpha* = 1 - interval_nominal
+        offset <- the (1 - alpha) quantile of the window's valid scores (the calibrator's rank formula and exact select)
+    alpha is not clamped: 1 - alpha <= 0 gives the offset -inf (an empty band, every target missed), a rank beyond the window's
+    scores +inf (the whole line) -- those two excursions are what makes the long-run miscoverage of the ISSUED bands approach
+    alpha* whatever the stream does: |miss rate - alpha*| <= (max(alpha_1, 1 - alpha_1) + gamma) / (gamma T) after T updates.
+    gamma = 0 never moves alpha: a rolling-window split-conformal refit at the nominal level.  min_scores: a group's alpha and
+    offset stay as they are until its window holds that many valid scores.
+
+    The pairs, interval_nominal, per_step and per_node are `ConformalCalibrator`'s.  update(y, issued, raw): y [H, N] the realised
+    targets (NaN = missing, left out), issued [Q, H, N] the rows that were served (the miss is counted on them), raw [Q, H, N] the
+    same forecast ahead of calibration, rearranged if the server rearranges (the scores are taken on them); or
+    update(None, issued, raw, ring=ring_y, origin=o) with the targets in a [C, N] ring at slots (o + h) mod C.
+    `offsets` (device fp32 [P, Hg, Ng]) is the live buffer: a captured graph that reads it sees every update without re-capture;
+    apply(y_hat) moves a [count, Q, H, N] forecast by it.  report() -> dict of numpy arrays alpha, offsets, counts, miss_sum,
+    valid_sum, miscoverage (= miss_sum / valid_sum, NaN where nothing was valid), with one host sync.  The device state is made
+    at the first update (or load_state_dict); state_dict() carries all of it, n_done included."""
+
+    def __init__(self, quantiles, gamma=0.005, window=256, per_step=True, per_node=False, min_scores=0):
+        base = ConformalCalibrator(quantiles, per_step, per_node)          # its refusals: two levels, increasing in (0, 1)
+        self.quantiles, self.pairs, self.interval_nominal = base.quantiles, base.pairs, base.interval_nominal
+        self.per_step, self.per_node = base.per_step, base.per_node
+        gamma = float(gamma)
+        if not gamma >= 0.0:
+            raise ValueError(f"AdaptiveConformal: gamma must be >= 0, got {gamma}")
+        if int(window) < 1:
+            raise ValueError(f"AdaptiveConformal: window must be at least 1, got {window}")
+        if int(min_scores) < 0:
+            raise ValueError(f"AdaptiveConformal: min_scores must be >= 0, got {min_scores}")
+        self.gamma, self.window, self.min_scores = gamma, int(window), int(min_scores)
+        self.target_alpha = [1.0 - float(c) for c in self.interval_nominal]          # fp64, on the host
+        self.n_done = 0
+        self.scores = self.alpha = self.offsets = self.counts = self.miss_sum = self.valid_sum = None
+
+    _STATE = ("scores", "alpha", "offsets", "counts", "miss_sum", "valid_sum")
+
+    def group_shape(self, H, N):
+        return (len(self.pairs), int(H) if self.per_step else 1, int(N) if self.per_node else 1)
+
+    def init_state(self, H, N, device, offsets=None):
+        """Make the device state for forecasts [Q, H, N] (update does it by itself; a caller that wants other initial offsets
+        than 0, or the offsets buffer ahead of the first update, calls it first).  Fill kernels, never inside a capture.  With
+        the state already there nothing changes."""
+        if self.offsets is not None:
+            if tuple(self.scores.shape[2:]) != (int(H), int(N)):
+                raise ValueError(f"AdaptiveConformal: the state is for forecasts [Q, {self.scores.shape[2]}, "
+                                 f"{self.scores.shape[3]}], got [Q, {H}, {N}]")
+            return self
+        shape = self.group_shape(H, N)
+        self.scores = torch.full((self.window, shape[0], int(H), int(N)), float("nan"), device=device)
+        ta = torch.tensor(self.target_alpha, dtype=torch.float64).reshape(-1, 1, 1)
+        self.alpha = ta.expand(shape).contiguous().to(device)
+        self.offsets = torch.zeros(shape, device=device) if offsets is None else \
+            offsets.detach().to(device=device, dtype=torch.float32).reshape(shape).clone()
+        self.counts, self.miss_sum, self.valid_sum = (torch.zeros(shape, dtype=torch.int64, device=device) for _ in range(3))
+        return self
+
+    def update(self, y, issued, raw, *, ring=None, origin=0):
+        issued, raw = _as_f32(issued), _as_f32(raw)
+        if issued.dim() != 3 or issued.shape[0] != len(self.quantiles) or raw.shape != issued.shape:
+            raise ValueError(f"AdaptiveConformal.update: issued and raw must be [{len(self.quantiles)}, H, N], got "
+                             f"{tuple(issued.shape)} / {tuple(raw.shape)}")
+        if ring is None:
+            ring, origin = _as_f32(y, like=issued).contiguous(), 0
+            if tuple(ring.shape) != tuple(issued.shape[1:]):
+                raise ValueError(f"AdaptiveConformal.update: y must be {tuple(issued.shape[1:])}, got {tuple(ring.shape)}")
+        _, H, N = issued.shape
+        self.init_state(H, N, issued.device)
+        ops.aci_update(issued.contiguous(), raw.contiguous(), ring, origin, self.pairs, self.target_alpha, self.gamma,
+                       self.n_done % self.window, self.min_scores, self.per_step, self.per_node, self.scores, self.alpha,
+                       self.offsets, self.counts, self.miss_sum, self.valid_sum)
+        self.n_done += 1
+        return self
+
+    def apply(self, y_hat, out=None):
+        if self.offsets is None:
+            raise ValueError("AdaptiveConformal.apply: no state yet (call update or load_state_dict first)")
+        return ops.conformal_apply(_as_f32(y_hat), self.offsets, self.pairs, self.per_step, self.per_node, out=out)
+
+    def report(self):
+        if self.offsets is None:
+            raise ValueError("AdaptiveConformal.report: no state yet (call update or load_state_dict first)")
+        shape, n = tuple(self.offsets.shape), self.offsets.numel()
+        flat = torch.cat([self.alpha.reshape(-1), self.offsets.double().reshape(-1)] +
+                         [t.double().reshape(-1) for t in (self.counts, self.miss_sum, self.valid_sum)]).cpu().numpy()
+        alpha, offsets, counts, miss, valid = (flat[i * n:(i + 1) * n].reshape(shape) for i in range(5))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rate = np.where(valid > 0, miss / valid, np.nan)
+        return dict(alpha=alpha.copy(), offsets=offsets.astype(np.float32), counts=counts.astype(np.int64),
+                    miss_sum=miss.astype(np.int64), valid_sum=valid.astype(np.int64), miscoverage=rate)
+
+    def state_dict(self):
+        state = dict(quantiles=self.quantiles, pairs=self.pairs, per_step=self.per_step, per_node=self.per_node,
+                     gamma=self.gamma, window=self.window, min_scores=self.min_scores, n_done=int(self.n_done))
+        for k in self._STATE:
+            t = getattr(self, k)
+            state[k] = None if t is None else t.clone()
+        return state
+
+    def load_state_dict(self, state, device=None):
+        q = tuple(float(t) for t in state["quantiles"])
+        if q != self.quantiles or bool(state["per_step"]) != self.per_step or bool(state["per_node"]) != self.per_node or \
+                int(state["window"]) != self.window:
+            raise ValueError(f"AdaptiveConformal.load_state_dict: saved for levels {q}, per_step={state['per_step']}, "
+                             f"per_node={state['per_node']}, window={state['window']}; this one has {self.quantiles}, "
+                             f"{self.per_step}, {self.per_node}, {self.window}")
+        if state["scores"] is None:
+            for k in self._STATE:
+                setattr(self, k, None)
+        else:
+            sc = state["scores"]
+            if sc.dim() != 4 or sc.shape[0] != self.window or sc.shape[1] != len(self.pairs):
+                raise ValueError(f"AdaptiveConformal.load_state_dict: scores {tuple(sc.shape)} do not fit window {self.window} / "
+                                 f"{len(self.pairs)} pairs")
+            shape = self.group_shape(sc.shape[2], sc.shape[3])
+            dev = sc.device if device is None else device
+            types = dict(scores=torch.float32, alpha=torch.float64, offsets=torch.float32)
+            for k in self._STATE:
+                t = state[k]
+                if k != "scores" and tuple(t.shape) != shape:
+                    raise ValueError(f"AdaptiveConformal.load_state_dict: {k} is {tuple(t.shape)}, expected {shape}")
+                setattr(self, k, t.detach().to(device=dev, dtype=types.get(k, torch.int64)).contiguous().clone())
+        self.n_done = int(state["n_done"])
+        return self
+
+
 def rearrange_quantiles(y_hat, out=None):
     """The monotone rearrangement of a quantile forecast [count, Q, H, N]: the Q values of every (window, step, node) in
     non-decreasing order (``ops.quantile_finish``; ``torch.sort(y_hat, dim=1, stable=True).values`` bit for bit), so no two levels

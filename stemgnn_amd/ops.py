@@ -1854,6 +1854,41 @@ def live_head(t_dev, history, pos, origins):
                "live_head")
 
 
+def aci_update(issued, raw, ring_y, origin, pairs, target_alpha, gamma, slot, min_scores, per_step, per_node, scores, alpha,
+               offsets, counts, miss_sum, valid_sum):
+    """One adaptive-conformal update from ONE matured forecast (``stemgnn_aci_update``): issued / raw [Q,H,N] (the served rows and
+    the same forecast ahead of calibration), the targets in the ring ring_y [C,N] at slots (origin + h) mod C, pairs = P (lo, hi)
+    rows with target_alpha = 1 - coverage each.  State, updated in place: scores [M,P,H,N] fp32 (NaN = absent; slot `slot` is
+    overwritten), alpha fp64, offsets fp32, counts / miss_sum / valid_sum int64, all [P, H if per_step else 1, N if per_node
+    else 1].  One launch, nothing synchronises."""
+    lib = _lib.load()
+    _require_gpu(issued, "issued")
+    dev = issued.device
+    if issued.dim() != 3 or raw.shape != issued.shape:
+        raise _lib.StemGNNHipError(f"aci_update: issued and raw must be [Q,H,N], got {tuple(issued.shape)} / {tuple(raw.shape)}")
+    Q, H, N = issued.shape
+    P, lo, hi = _conformal_pairs(pairs, Q)
+    if len(target_alpha) != P:
+        raise ValueError(f"aci_update: {P} pairs but {len(target_alpha)} target levels")
+    if ring_y.dim() != 2 or ring_y.shape[1] != N:
+        raise _lib.StemGNNHipError(f"aci_update: ring_y must be [C,{N}], got {tuple(ring_y.shape)}")
+    if scores.dim() != 4 or tuple(scores.shape[1:]) != (P, H, N):
+        raise _lib.StemGNNHipError(f"aci_update: scores must be [M,{P},{H},{N}], got {tuple(scores.shape)}")
+    for t, name in ((issued, "issued"), (raw, "raw"), (ring_y, "ring_y"), (scores, "scores")):
+        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.StemGNNHipError(f"aci_update: {name} must be a contiguous float32 tensor on {dev}")
+    shape = (P, H if per_step else 1, N if per_node else 1)
+    for t, name, dt in ((alpha, "alpha", torch.float64), (offsets, "offsets", torch.float32), (counts, "counts", torch.int64),
+                        (miss_sum, "miss_sum", torch.int64), (valid_sum, "valid_sum", torch.int64)):
+        if tuple(t.shape) != shape or t.device != dev or t.dtype != dt or not t.is_contiguous():
+            raise _lib.StemGNNHipError(f"aci_update: {name} must be a contiguous {dt} {shape} tensor on {dev}")
+    _lib.check(lib.stemgnn_aci_update(issued.data_ptr(), raw.data_ptr(), ring_y.data_ptr(), ring_y.shape[0], int(origin), Q, H, N,
+                                      P, lo, hi, _lib.host_floats(target_alpha, _lib.c_double), float(gamma), scores.shape[0],
+                                      int(slot), int(min_scores), int(bool(per_step)), int(bool(per_node)), scores.data_ptr(),
+                                      alpha.data_ptr(), offsets.data_ptr(), counts.data_ptr(), miss_sum.data_ptr(),
+                                      valid_sum.data_ptr(), _stream()), "aci_update")
+
+
 def eval_metrics(target, forecast, mul=None, add=None, ignore_nan=False):
     """target / forecast [count,H,N] fp32 -> float64 device vector
     overall[3] | by_node[3][N] | by_step[3][H] | by_step_node[3][H][N]  (MAPE, MAE, RMSE each).
