@@ -826,6 +826,50 @@ int stemgnn_aci_update(const float* issued, const float* raw, const float* ring_
                        long long min_scores, int per_step, int per_node, float* scores, double* alpha, float* offsets,
                        long long* counts, long long* miss_sum, long long* valid_sum, void* stream);
 
+/* ---- conformal anomaly p-values for live readings (csrc/anomaly.hip) ---------------------------------
+ * One call judges ONE arrived row `row` (= tau): every stored forecast of it -- step h of origin tau - h, h < H -- is scored and
+ * ranked against a rolling window of the scores of earlier rows.
+ * slab [S, R, H, N] fp32 is the forecast slab (R rows per forecast: 1 for a point model, Q for a quantile model), origins [S]
+ * int64 on the device the origin filed in every slot; ring_y [C, N] the targets, row tau in slot tau mod C, NaN = missing.
+ * lo_row == hi_row scores the absolute residual of that row, lo_row < hi_row the band's conformity score.
+ * Device state, owned by the caller and persistent between calls: scores [M, H, N] fp32 (NaN = absent; a new window is all
+ * NaN), alarm_sum / judged_sum int64 [N] (initialised to 0), log_p [keep, N] fp32.  Written in full by every call: pvalues
+ * [H, N] fp32, node_p [N] fp32, alarm [N] int32, counts int64 [H if per_step else 1, N if per_node else 1], row log_slot of log_p,
+ * slot `slot` of scores.
+ * Per element (h, n), in this order:
+ *   1. forecast: o = tau - h, s = o mod S; present iff o >= 0 and origins[s] == o.  origins == NULL: the slab is [1, R, H, N]
+ *      (S is not used) and every step is present.  f_lo = slab[s, lo_row, h, n], f_hi = slab[s, hi_row, h, n].
+ *   2. score: y = ring_y[tau mod C, n].  A NaN y or an absent forecast makes the element absent: its score slot gets NaN, its
+ *      p-value is NaN and it counts nowhere.  Otherwise score = max(f_lo - y, y - f_hi) as stemgnn_conformal_fit computes it
+ *      (fp32, one rounding each, a NaN from the forecast gives +inf, -0 becomes +0).
+ *   3. population: the group's non-NaN scores in every window slot EXCEPT `slot` (= the host's n_done mod M), i.e. the last
+ *      M - 1 judged rows; the group is step h alone with per_step, all H steps without, node n alone with per_node, all nodes
+ *      without.  m = its size; counts[g] = m.  (Leaving `slot` out is what makes one pass possible: nothing reads what the call
+ *      writes, and a row's own elements are never in its population.)
+ *   4. p-value: ge = the population's scores >= score in the total order of fp32 with -0 == +0 and +inf largest;
+ *      p = (float)((double)(ge + 1) / (double)(m + 1)), or NaN if m < min_scores.  pvalues[h, n] = p.
+ *   5. file: scores[slot, h, n] = score, or NaN when absent.
+ * Per node: v = the number of non-NaN p over h, pmin = the smallest; node_p[n] = v ? (float)min(1.0, (double)v * (double)pmin)
+ * : NaN (Bonferroni over the opinions about one reading, valid under any dependence between them); alarm[n] = v &&
+ * (double)node_p[n] <= alpha; judged_sum[n] += (v > 0); alarm_sum[n] += alarm[n]; log_p[log_slot, n] = node_p[n].
+ * work: 2 * H * N uint32 on the device, owned by the caller, ZERO before the first call; every call leaves it zero again.
+ * Where a group's window is dealt over several workgroups (pooled over the nodes: up to 64 per group; per_node with H > 4:
+ * node tiles x steps x parts of the rows), their integer partial counts -- scores >= the query of (h, n) at [h * N + n], the
+ * m of group g at [H * N + g] -- meet there by integer atomic adds; the second launch reads the totals and clears them.
+ * per_node with H <= 4 never touches it.
+ * Integer counts, integer atomics only, no floating-point atomics: the same bits on every run.  No allocation, no host
+ * synchronisation.  Launches: per_node with H <= 4: one; otherwise two (the ranking, then p-values and the per-node
+ * combination in one workgroup).  16-byte loads of the window pooled over the nodes when N % 4 == 0 and scores is 16-byte
+ * aligned.
+ * SG_EINVAL (nothing launched) on a NULL pointer other than origins, S, R, C, H, N, M or keep <= 0, R > 32, rows outside
+ * 0 <= lo_row <= hi_row < R, slot outside [0, M), log_slot outside [0, keep), row < 0, alpha NaN or outside (0, 1),
+ * min_scores < 0, M * H * N, C * N, S * R * H * N or keep * N >= 2^31. */
+int stemgnn_anomaly_update(const float* slab, int S, int R, int lo_row, int hi_row, const long long* origins, long long row,
+                           const float* ring_y, int C, int H, int N, int M, int slot, long long min_scores, double alpha,
+                           int per_step, int per_node, float* scores, float* pvalues, float* node_p, int* alarm,
+                           long long* counts, long long* alarm_sum, long long* judged_sum, float* log_p, int keep, int log_slot,
+                           unsigned int* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -196,6 +196,9 @@ SIGNATURES = {
     "stemgnn_aci_update": (c_int, [_P, _P, _P, c_int, c_longlong, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int),
                                    POINTER(c_double), c_double, c_int, c_int, c_longlong, c_int, c_int, _P, _P, _P, _P, _P, _P,
                                    _P]),
+    "stemgnn_anomaly_update": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_longlong, _P, c_int, c_int, c_int, c_int, c_int,
+                                       c_longlong, c_double, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P,
+                                       _P]),
     "stemgnn_infer_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
     "stemgnn_infer_workspace_split_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "stemgnn_gru_fwd_infer": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),

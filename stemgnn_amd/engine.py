@@ -987,7 +987,11 @@ class LiveForecaster:
     delay (the level in force was set `horizon` updates ago).  Forecasts stored before set_adaptive are not learnt from.
 
     Device buffers are made at the first push (or load_state_dict): every refusal of the constructor, of set_adaptive, of
-    forecast() before `ready` and of a push of the wrong width comes before anything touches the device."""
+    forecast() before `ready` and of a push of the wrong width comes before anything touches the device.
+
+    set_anomaly(detector): conformal anomaly p-values of every arriving reading (math_utils.ConformalAnomaly; None switches it
+    off).  push() then judges each new row against the forecasts of it that the slab holds; anomalies() returns the last judged
+    row's (node_p, alarm, row).  The forecast path, the captured graph and every existing signature are untouched."""
 
     def __init__(self, model, window, horizon, *, normalize_method=None, norm_statistic=None, missing=None, fill=None,
                  history=64, adjacency=None, rearrange=False, calibrator=None, graph=True, device=None):
@@ -1027,6 +1031,7 @@ class LiveForecaster:
         self._check_calibrator(calibrator)
         self.calibrator = calibrator
         self.adaptive, self.done, self._adaptive_init = None, -1, None
+        self.anomaly, self._anomaly_rows = None, (0, 0)
         self.C = self.W + self.horizon + self.history
         self.want_graph = bool(graph)
         self._adjacency = adjacency
@@ -1089,6 +1094,7 @@ class LiveForecaster:
         self._offsets = None
         self.out_raw = None
         self._attach_adaptive()
+        self._attach_anomaly()
         self._set_finish_kw()
         ops.ring_status_word(dev)
         self._ready_buffers = True
@@ -1140,7 +1146,18 @@ class LiveForecaster:
         ops.live_push(raw, self.rows, self.sub, self.div, self._clip, self.missing, self.last, self.ring_x, self.ring_y,
                       self.t_dev)
         self.rows += int(raw.shape[0])
+        if self.anomaly is not None:
+            self._feed_anomaly(int(raw.shape[0]))
         return self.rows
+
+    def _feed_anomaly(self, K):
+        """One eager detector update per row just pushed that is still in the ring and has a stored forecast (host mirror),
+        oldest first; host-known arguments, no sync.  The update reads out_forecast and the device origins through stream order."""
+        stored = {o for o in self._origins if o >= 0}
+        for tau in range(max(self.rows - K, self.rows - self.C), self.rows):
+            if any((tau - h) in stored for h in range(self.horizon)):
+                self.anomaly.update(None, None, slab=self.out_forecast, origins=self.origins, row=tau, ring=self.ring_y,
+                                    rows=self._anomaly_rows)
 
     # -- forecast -----------------------------------------------------------------------------------------------
     def _roll(self, window, steps):
@@ -1285,6 +1302,47 @@ class LiveForecaster:
         if self.out_raw is None:
             self.out_raw = torch.zeros_like(self.out_forecast)
 
+    # -- anomaly detection --------------------------------------------------------------------------------------
+    def set_anomaly(self, detector):
+        """Switch the scoring of arriving readings on (a math_utils.ConformalAnomaly) or off (None).  After its one live_push
+        launch every push() issues one detector.update per pushed row that is still in the ring and has a stored forecast: the
+        steps h of the forecasts made at rows tau - h, read from the history slab, are ranked against the detector's window.
+        Rows scored: a point model's only row; for a quantile model model.point_index with score="point", the outermost pair
+        (0, Q - 1) of the rows as served with score="band".  Eager launches with host-known arguments: the captured graph is not
+        touched and nothing is captured again.  A detector that already carries state (a restart, or one switched off and on
+        again) keeps it."""
+        if detector is None:
+            self.anomaly = None
+            return
+        R = 1 if self.Q is None else self.Q
+        if detector.score == "band" and self.Q is None:
+            raise ValueError("LiveForecaster.set_anomaly: score='band' goes with a quantile model (Model(..., quantiles=...)); a "
+                             "point model has no bands")
+        if self.history < self.horizon:
+            raise ValueError(f"LiveForecaster.set_anomaly: history {self.history} < horizon {self.horizon}: a forecast made "
+                             "every row would be overwritten before its last step's reading arrives")
+        if detector.scores is not None and tuple(detector.scores.shape[1:]) != (self.horizon, self.N):
+            raise ValueError(f"LiveForecaster.set_anomaly: the detector's state {tuple(detector.scores.shape)} does not fit "
+                             f"horizon {self.horizon} / {self.N} nodes")
+        detector.check_shape(self.horizon, self.N)
+        self._anomaly_rows = (0, R - 1) if detector.score == "band" else (self.point, self.point)
+        self.anomaly = detector
+        if self._ready_buffers:
+            self._attach_anomaly()
+
+    def _attach_anomaly(self):
+        """The detector's device state (fill kernels, outside any capture)."""
+        if self.anomaly is not None:
+            self.anomaly.init_state(self.horizon, self.N, 1 if self.Q is None else self.Q, self.device)
+
+    def anomalies(self):
+        """(node_p [N], alarm int32 [N], row) of the last judged row: the detector's live device buffers and the host's row
+        index (-1: none judged yet)."""
+        if self.anomaly is None:
+            raise RuntimeError("LiveForecaster.anomalies: no detector is set (set_anomaly)")
+        self._alloc()
+        return self.anomaly.node_p, self.anomaly.alarm, self.anomaly.last_row
+
     # -- restart ------------------------------------------------------------------------------------------------
     def state_dict(self):
         """Everything a restarted server needs to go on without replaying the stream: both rings, the fill state, the row
@@ -1296,6 +1354,8 @@ class LiveForecaster:
                      history_forecast=self.out_forecast.clone(), origins=torch.tensor(self._origins, dtype=torch.int64))
         if self.adaptive is not None:
             state.update(history_raw=self.out_raw.clone(), done=int(self.done), adaptive=self.adaptive.state_dict())
+        if self.anomaly is not None:
+            state.update(anomaly=self.anomaly.state_dict())
         return state
 
     def load_state_dict(self, state):
@@ -1304,6 +1364,8 @@ class LiveForecaster:
                 raise ValueError(f"LiveForecaster.load_state_dict: saved with {k}={state[k]}, this one has {mine}")
         if self.adaptive is not None and "adaptive" not in state:
             raise ValueError("LiveForecaster.load_state_dict: adaptive bands are on, but the state was saved without them")
+        if self.anomaly is not None and "anomaly" not in state:
+            raise ValueError("LiveForecaster.load_state_dict: a detector is set, but the state was saved without one")
         self._alloc()
         for k, dst in (("ring_x", self.ring_x), ("ring_y", self.ring_y), ("last", self.last),
                        ("history_forecast", self.out_forecast)):
@@ -1332,4 +1394,11 @@ class LiveForecaster:
             self.adaptive.n_done = loaded.n_done
             self.out_raw.copy_(state["history_raw"])
             self.done = int(state["done"])
+        if self.anomaly is not None:
+            det = self.anomaly
+            loaded = type(det)(**det._config()).load_state_dict(state["anomaly"], device=self.device)
+            if loaded.scores is not None:
+                for k in det._STATE:
+                    getattr(det, k).copy_(getattr(loaded, k))
+            det.n_done, det.last_row, det._log_rows = loaded.n_done, loaded.last_row, list(loaded._log_rows)
         return self

@@ -284,6 +284,192 @@ class AdaptiveConformal:
         return self
 
 
+class ConformalAnomaly:
+    """Streaming conformal anomaly detection: is the reading that just arrived normal?  On the device, one call per row.
+
+    When row tau arrives, every stored forecast of it -- step h of the forecast made at origin tau - h, h < H -- is scored
+    (score="point": |forecast - y| of one row; "band": max(lo - y, y - hi) of a quantile pair, the calibrator's score) and ranked
+    against a rolling window of the scores of the last `window - 1` judged rows, grouped as `ConformalCalibrator` groups
+    (per_step: against step h only; per_node: against node n only):
+        p[h, n]   = (#{window scores >= score} + 1) / (m + 1)       the exact conformal p-value, NaN until m >= min_scores
+        node_p[n] = min(1, v * min_h p[h, n])                       Bonferroni over the v judged steps: valid under any dependence
+        alarm[n]  = node_p[n] <= alpha
+    On an exchangeable stream P(p <= a) <= a, so the false-alarm rate per judged reading is at most alpha.  A missing reading
+    (NaN) or a step with no stored forecast is absent: NaN p-value, counted nowhere.  The row's own scores enter the window only
+    after it is judged, so a row is never compared with itself.
+
+    update(y, forecasts): y [N], forecasts [H, N] or [R, H, N] (step h = the forecast of THIS row made h rows ago), rows=(lo, hi)
+    the rows scored (default (0, 0) for "point", (0, R - 1) for "band"); or update(None, None, slab=out_forecast,
+    origins=origins, row=tau, ring=ring_y, rows=(lo, hi)) on a forecast slab [S, (R,) H, N] with its device-side origins and the
+    target ring, which is what LiveForecaster.set_anomaly issues.  One ``ops.anomaly_update``, no sync.
+    Attributes (live device buffers of the last row): pvalues [H, N], node_p [N], alarm int32 [N]; counts (int64, the m of every
+    group), alarm_sum / judged_sum (int64 [N]), n_done, last_row.  recent() -> (node_p [k, N], rows int64 [k]) ascending from the
+    log of the last `keep` rows (the rows from a host mirror: no sync).  report() -> dict of numpy arrays with one sync,
+    alarm_rate = alarm_sum / judged_sum and resolution = 1 / (counts + 1) (the smallest p a group can give) included.  The device
+    state is made at the first update (or load_state_dict); state_dict() carries all of it."""
+
+    def __init__(self, alpha=0.01, window=1024, per_step=True, per_node=True, min_scores=32, score="point", keep=64):
+        alpha = float(alpha)
+        if not (alpha > 0.0 and alpha < 1.0):
+            raise ValueError(f"ConformalAnomaly: alpha must be inside (0, 1), got {alpha}")
+        if int(window) < 2:
+            raise ValueError(f"ConformalAnomaly: window must be at least 2 (the arriving row's own slot is left out, so a window "
+                             f"of 1 has an empty population for ever), got {window}")
+        if int(min_scores) < 0:
+            raise ValueError(f"ConformalAnomaly: min_scores must be >= 0, got {min_scores}")
+        if int(keep) < 1:
+            raise ValueError(f"ConformalAnomaly: keep must be at least 1, got {keep}")
+        if score not in ("point", "band"):
+            raise ValueError(f"ConformalAnomaly: score must be 'point' or 'band', got {score!r}")
+        self.alpha, self.window, self.min_scores, self.keep, self.score = alpha, int(window), int(min_scores), int(keep), score
+        self.per_step, self.per_node = bool(per_step), bool(per_node)
+        self.n_done, self.last_row = 0, -1
+        self._log_rows = [-1] * self.keep
+        self._work = None                                          # the entry's work buffer: zero between calls, no state
+        for k in self._STATE:
+            setattr(self, k, None)
+
+    _STATE = ("scores", "pvalues", "node_p", "alarm", "counts", "alarm_sum", "judged_sum", "log_p")
+    _TYPES = dict(alarm=torch.int32, counts=torch.int64, alarm_sum=torch.int64, judged_sum=torch.int64)
+
+    def group_shape(self, H, N):
+        return (int(H) if self.per_step else 1, int(N) if self.per_node else 1)
+
+    def check_shape(self, H, N):
+        """Refuse a configuration that can never raise an alarm: the smallest node_p is H / (m + 1), and m is at most
+        (window - 1) * (group's steps) * (group's nodes).  Nothing touches the device."""
+        import math
+        per_row = (1 if self.per_step else int(H)) * (1 if self.per_node else int(N))
+        need = math.ceil(int(H) / self.alpha * (1.0 - 1e-12))                    # m + 1 must reach this
+        if (self.window - 1) * per_row + 1 < need:
+            raise ValueError(f"ConformalAnomaly: window {self.window} can never alarm at alpha {self.alpha} with horizon {H}: "
+                             f"the smallest p-value is {H} / {(self.window - 1) * per_row + 1}; window >= "
+                             f"{-(-(need - 1) // per_row) + 1} would do")
+        return self
+
+    def _shapes(self, H, N):
+        H, N = int(H), int(N)
+        return dict(scores=(self.window, H, N), pvalues=(H, N), node_p=(N,), alarm=(N,), counts=self.group_shape(H, N),
+                    alarm_sum=(N,), judged_sum=(N,), log_p=(self.keep, N))
+
+    def init_state(self, H, N, R, device):
+        """Make the device state for forecasts [R, H, N] (update does it by itself).  Fill kernels, never inside a capture.  With
+        the state already there nothing changes."""
+        if self.scores is not None:
+            if tuple(self.scores.shape[1:]) != (int(H), int(N)):
+                raise ValueError(f"ConformalAnomaly: the state is for forecasts [R, {self.scores.shape[1]}, "
+                                 f"{self.scores.shape[2]}], got [R, {H}, {N}]")
+            return self
+        if not 1 <= int(R) <= 32:
+            raise ValueError(f"ConformalAnomaly: forecasts of {R} rows (1 to 32 are served)")
+        if self.score == "band" and int(R) < 2:
+            raise ValueError("ConformalAnomaly: score='band' needs a forecast of at least two rows (a point forecast has no band)")
+        self.check_shape(H, N)
+        for k, shape in self._shapes(H, N).items():
+            dt = self._TYPES.get(k, torch.float32)
+            fill = float("nan") if dt == torch.float32 else 0
+            setattr(self, k, torch.full(shape, fill, dtype=dt, device=device))
+        return self
+
+    def update(self, y, forecasts, *, slab=None, origins=None, row=None, ring=None, rows=None):
+        if slab is None:
+            f = _as_f32(forecasts)
+            if f.dim() == 2:
+                f = f[None]
+            if f.dim() != 3:
+                raise ValueError(f"ConformalAnomaly.update: forecasts must be [H, N] or [R, H, N], got {tuple(f.shape)}")
+            slab, origins = f.contiguous()[None], None
+            ring = _as_f32(y, like=f).contiguous()
+            if tuple(ring.shape) != (f.shape[2],):
+                raise ValueError(f"ConformalAnomaly.update: y must be [{f.shape[2]}], got {tuple(ring.shape)}")
+            ring = ring[None]
+            row = self.n_done if row is None else int(row)
+        else:
+            if ring is None or row is None:
+                raise ValueError("ConformalAnomaly.update: the slab form needs ring= and row=")
+            if slab.dim() == 3:                                    # a point model's slab [S, H, N]
+                slab = slab[:, None]
+            if slab.dim() != 4:
+                raise ValueError(f"ConformalAnomaly.update: slab must be [S, H, N] or [S, R, H, N], got {tuple(slab.shape)}")
+        _, R, H, N = slab.shape
+        if rows is None:
+            rows = (0, 0) if self.score == "point" else (0, R - 1)
+        lo, hi = int(rows[0]), int(rows[1])
+        if not 0 <= lo <= hi < R or (self.score == "band") != (lo < hi):
+            raise ValueError(f"ConformalAnomaly.update: rows {(lo, hi)} do not name a {self.score} score of a forecast of {R} rows")
+        self.init_state(H, N, R, slab.device)
+        if self._work is None or self._work.device != self.scores.device:
+            self._work = torch.zeros(2 * H * N, dtype=torch.int32, device=self.scores.device)
+        log_slot = self.n_done % self.keep
+        ops.anomaly_update(slab, origins, int(row), ring, (lo, hi), self.n_done % self.window, self.min_scores, self.alpha,
+                           self.per_step, self.per_node, self.scores, self.pvalues, self.node_p, self.alarm, self.counts,
+                           self.alarm_sum, self.judged_sum, self.log_p, log_slot, self._work)
+        self._log_rows[log_slot] = int(row)
+        self.n_done += 1
+        self.last_row = int(row)
+        return self
+
+    def recent(self):
+        """(node_p [k, N], rows int64 [k]) of the last k = min(n_done, keep) judged rows, oldest first."""
+        if self.scores is None:
+            raise ValueError("ConformalAnomaly.recent: no state yet (call update or load_state_dict first)")
+        k = min(self.n_done, self.keep)
+        first = (self.n_done - k) % self.keep
+        order = [(first + i) % self.keep for i in range(k)]
+        parts = [self.log_p[first:first + k]] if first + k <= self.keep else [self.log_p[first:], self.log_p[:first + k - self.keep]]
+        return torch.cat(parts).clone(), torch.tensor([self._log_rows[s] for s in order], dtype=torch.int64)
+
+    def report(self):
+        if self.scores is None:
+            raise ValueError("ConformalAnomaly.report: no state yet (call update or load_state_dict first)")
+        names = ("pvalues", "node_p", "alarm", "counts", "alarm_sum", "judged_sum")
+        flat = torch.cat([getattr(self, k).double().reshape(-1) for k in names]).cpu().numpy()
+        out, at = {}, 0
+        for k in names:
+            t = getattr(self, k)
+            out[k] = flat[at:at + t.numel()].reshape(tuple(t.shape)).astype(
+                {torch.float32: np.float32, torch.int32: np.int32, torch.int64: np.int64}[t.dtype])
+            at += t.numel()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["alarm_rate"] = np.where(out["judged_sum"] > 0, out["alarm_sum"] / out["judged_sum"], np.nan)
+        out["resolution"] = 1.0 / (out["counts"] + 1.0)
+        out["n_done"], out["row"] = int(self.n_done), int(self.last_row)
+        return out
+
+    def _config(self):
+        return dict(alpha=self.alpha, window=self.window, per_step=self.per_step, per_node=self.per_node,
+                    min_scores=self.min_scores, score=self.score, keep=self.keep)
+
+    def state_dict(self):
+        state = dict(self._config(), n_done=int(self.n_done), last_row=int(self.last_row), log_rows=list(self._log_rows))
+        for k in self._STATE:
+            t = getattr(self, k)
+            state[k] = None if t is None else t.clone()
+        return state
+
+    def load_state_dict(self, state, device=None):
+        saved = {k: state[k] for k in self._config()}
+        saved.update(alpha=float(saved["alpha"]), per_step=bool(saved["per_step"]), per_node=bool(saved["per_node"]))
+        if saved != self._config():
+            raise ValueError(f"ConformalAnomaly.load_state_dict: saved with {saved}; this one has {self._config()}")
+        if state["scores"] is None:
+            for k in self._STATE:
+                setattr(self, k, None)
+        else:
+            sc = state["scores"]
+            if sc.dim() != 3 or sc.shape[0] != self.window:
+                raise ValueError(f"ConformalAnomaly.load_state_dict: scores {tuple(sc.shape)} do not fit window {self.window}")
+            dev = sc.device if device is None else device
+            for k, shape in self._shapes(sc.shape[1], sc.shape[2]).items():
+                t = state[k]
+                if tuple(t.shape) != shape:
+                    raise ValueError(f"ConformalAnomaly.load_state_dict: {k} is {tuple(t.shape)}, expected {shape}")
+                setattr(self, k, t.detach().to(device=dev, dtype=self._TYPES.get(k, torch.float32)).contiguous().clone())
+        self.n_done, self.last_row = int(state["n_done"]), int(state["last_row"])
+        self._log_rows = [int(v) for v in state["log_rows"]]
+        return self
+
+
 def rearrange_quantiles(y_hat, out=None):
     """The monotone rearrangement of a quantile forecast [count, Q, H, N]: the Q values of every (window, step, node) in
     non-decreasing order (``ops.quantile_finish``; ``torch.sort(y_hat, dim=1, stable=True).values`` bit for bit), so no two levels

@@ -1889,6 +1889,50 @@ def aci_update(issued, raw, ring_y, origin, pairs, target_alpha, gamma, slot, mi
                                       valid_sum.data_ptr(), _stream()), "aci_update")
 
 
+def anomaly_update(slab, origins, row, ring_y, rows, slot, min_scores, alpha, per_step, per_node, scores, pvalues, node_p, alarm,
+                   counts, alarm_sum, judged_sum, log_p, log_slot, work):
+    """Conformal anomaly p-values of ONE arrived row (``stemgnn_anomaly_update``): slab [S,R,H,N] the stored forecasts with their
+    origins (int64 [S] on the device; None: slab [1,R,H,N] holds the row's forecasts, step h at [0,:,h]), row = the arrived row's
+    absolute index, its targets in the ring ring_y [C,N] at slot row mod C, rows = (lo, hi) the slab rows scored (lo == hi: the
+    absolute residual).  State, updated in place: scores [M,H,N] fp32 (NaN = absent; slot `slot` is overwritten), alarm_sum /
+    judged_sum int64 [N], row log_slot of log_p [keep,N]; written in full: pvalues [H,N], node_p [N], alarm int32 [N], counts
+    int64 [H if per_step else 1, N if per_node else 1].  work: int32 [2 * H * N], zero before the first call and left zero by
+    every call (where the workgroups of the two-launch forms meet).  One or two launches; nothing synchronises."""
+    lib = _lib.load()
+    _require_gpu(slab, "slab")
+    dev = slab.device
+    if slab.dim() != 4:
+        raise _lib.StemGNNHipError(f"anomaly_update: slab must be [S,R,H,N], got {tuple(slab.shape)}")
+    S, R, H, N = slab.shape
+    lo, hi = (int(v) for v in rows)
+    if origins is None:
+        if S != 1:
+            raise _lib.StemGNNHipError(f"anomaly_update: without origins the slab is [1,R,H,N], got {tuple(slab.shape)}")
+    elif origins.dtype != torch.int64 or origins.device != dev or tuple(origins.shape) != (S,) or not origins.is_contiguous():
+        raise _lib.StemGNNHipError(f"anomaly_update: origins must be a contiguous int64 [{S}] tensor on {dev}")
+    if ring_y.dim() != 2 or ring_y.shape[1] != N:
+        raise _lib.StemGNNHipError(f"anomaly_update: ring_y must be [C,{N}], got {tuple(ring_y.shape)}")
+    if scores.dim() != 3 or tuple(scores.shape[1:]) != (H, N):
+        raise _lib.StemGNNHipError(f"anomaly_update: scores must be [M,{H},{N}], got {tuple(scores.shape)}")
+    if log_p.dim() != 2 or log_p.shape[1] != N:
+        raise _lib.StemGNNHipError(f"anomaly_update: log_p must be [keep,{N}], got {tuple(log_p.shape)}")
+    gshape = (H if per_step else 1, N if per_node else 1)
+    for t, name, dt, shape in ((slab, "slab", torch.float32, None), (ring_y, "ring_y", torch.float32, None),
+                               (scores, "scores", torch.float32, None), (log_p, "log_p", torch.float32, None),
+                               (pvalues, "pvalues", torch.float32, (H, N)), (node_p, "node_p", torch.float32, (N,)),
+                               (alarm, "alarm", torch.int32, (N,)), (counts, "counts", torch.int64, gshape),
+                               (alarm_sum, "alarm_sum", torch.int64, (N,)), (judged_sum, "judged_sum", torch.int64, (N,)),
+                               (work, "work", torch.int32, (2 * H * N,))):
+        if t.device != dev or t.dtype != dt or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
+            raise _lib.StemGNNHipError(f"anomaly_update: {name} must be a contiguous {dt} {shape or ''} tensor on {dev}")
+    _lib.check(lib.stemgnn_anomaly_update(slab.data_ptr(), S, R, lo, hi, None if origins is None else origins.data_ptr(), int(row),
+                                          ring_y.data_ptr(), ring_y.shape[0], H, N, scores.shape[0], int(slot), int(min_scores),
+                                          float(alpha), int(bool(per_step)), int(bool(per_node)), scores.data_ptr(),
+                                          pvalues.data_ptr(), node_p.data_ptr(), alarm.data_ptr(), counts.data_ptr(),
+                                          alarm_sum.data_ptr(), judged_sum.data_ptr(), log_p.data_ptr(), log_p.shape[0],
+                                          int(log_slot), work.data_ptr(), _stream()), "anomaly_update")
+
+
 def eval_metrics(target, forecast, mul=None, add=None, ignore_nan=False):
     """target / forecast [count,H,N] fp32 -> float64 device vector
     overall[3] | by_node[3][N] | by_step[3][H] | by_step_node[3][H][N]  (MAPE, MAE, RMSE each).
