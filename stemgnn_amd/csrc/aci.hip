@@ -3,12 +3,12 @@
 // One call takes ONE matured forecast (one origin), for all P pairs and all groups, in one launch: the origin's scores go into
 // slot `slot` of the rolling window scores [M, P, H, N]; every group counts its valid and its missed targets, moves its working
 // level alpha by gamma * (target_alpha - miss / valid), and takes the (1 - alpha) quantile of the window's valid scores as its
-// new offset -- the exact MSB-first radix select of conformal.hip (same key, same rank formula: conformal_select.h), but with
+// new offset -- the exact MSB-first radix select of conformal.hip (its key, rank formula and wave pick: conformal_select.h), but with
 // all four 8-bit passes inside the launch: a (pair, group) belongs to ONE workgroup, its histograms live in LDS, and the phases
 // are separated by __syncthreads().  No grid-wide synchronisation, no scratch, no floating-point atomics: the only atomics are
 // integer adds in LDS, so the result is the same bits on every run.
 //
-// Two forms, chosen by the grouping (the two of conformal.hip, for the same reasons):
+// Two forms, chosen by the grouping (the two of conformal.hip, for the same reasons; their geometry: cf_grouping, conformal_args.h):
 //   * columns (per_node): a group's scores are strided by N (or H * N).  The window is a matrix [R, C] whose column is the
 //     group (R = M, C = H * N with per_step; R = M * H, C = N without); a workgroup owns 32 adjacent columns and ALL rows,
 //     consecutive lanes on consecutive columns, one 256-bin histogram per column in LDS ([bin][column], pitch 33).
@@ -25,12 +25,7 @@
 #include "../../include/stemgnn_hip.h"
 #include "conformal_args.h"
 #include "conformal_select.h"
-
-#define SG_TRY(e)                                \
-  do {                                           \
-    hipError_t _e = (e);                         \
-    if (_e != hipSuccess) return -(int)_e;       \
-  } while (0)
+#include "sg_host.h"
 
 namespace {
 
@@ -41,7 +36,6 @@ constexpr int ACI_PITCH = ACI_TILE + 1;       // LDS row pitch in words
 constexpr int ACI_SEGS = ACI_THREADS / ACI_TILE;   // 32 segments of 8 bins per column in the pick
 constexpr int ACI_COPIES = 16;                // histogram copies (stream form)
 constexpr int ACI_KEEP = 16;                  // loads of the window a thread keeps in registers over the passes (stream form)
-constexpr uint32_t ACI_NAN = 0x7fc00000u, ACI_PINF = 0x7f800000u, ACI_NINF = 0xff800000u;
 
 struct AciPairs {                             // travels by value in the kernel arguments
   int lo[CF_MAX_P], hi[CF_MAX_P];
@@ -55,17 +49,11 @@ struct AciState {
   long long *counts, *miss_sum, *valid_sum;
 };
 
-// the key of a stored score (already NaN-free: NaN = absent is skipped by the caller; -0 cannot be stored, but a loaded
-// state may hold one)
-__device__ inline uint32_t aci_key(float s) {
-  uint32_t u = __float_as_uint(s);
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+// (the key of a stored score: cf_score_key of conformal_select.h; NaN = absent is skipped by the caller)
 
 // one element of the new origin: its score slot's value, and whether it is valid / missed
 __device__ inline float aci_score(float y, float rlo, float rhi, float ilo, float ihi, int& valid, int& miss) {
-  if (y != y) return __uint_as_float(ACI_NAN);
+  if (y != y) return __uint_as_float(CF_NAN_BITS);
   ++valid;
   miss += !(ilo <= y && y <= ihi);
   return cf_unkey(cf_key(rlo, y, rhi));
@@ -93,12 +81,12 @@ __device__ inline uint32_t aci_level(long long m, int miss, int valid, double ta
   }
   st.alpha[pg] = a;
   if (!(c > 0.0)) {                                 // the level left [0, 1] upwards: the empty band
-    st.offsets[pg] = __uint_as_float(ACI_NINF);
+    st.offsets[pg] = __uint_as_float(CF_NINF_BITS);
     return 0u;
   }
   const double kk = cf_rank(m, c);
   if (kk > (double)m) {                             // too few scores for the level (or alpha < 0): the whole line
-    st.offsets[pg] = __uint_as_float(ACI_PINF);
+    st.offsets[pg] = __uint_as_float(CF_PINF_BITS);
     return 0u;
   }
   return (uint32_t)kk;
@@ -150,7 +138,7 @@ __global__ __launch_bounds__(ACI_THREADS) void aci_columns(const float* __restri
         const uint32_t i = r / Hr;
         const float s = st.scores[((size_t)i * P + p) * HN + (size_t)(r - i * Hr) * Cc + c0 + lc];
         if (s != s) continue;
-        const uint32_t key = aci_key(s);
+        const uint32_t key = cf_score_key(s);
         if (cf_match(key, d, pre)) atomicAdd(&h[cf_bin(key, d) * ACI_PITCH + lc], 1u);
       }
     }
@@ -201,16 +189,6 @@ __global__ __launch_bounds__(ACI_THREADS) void aci_columns(const float* __restri
 // grid (G, P).  Group g = the L contiguous floats at offset g * L of every [H * N] slab.  VEC = 4: L % 4 == 0, N % 4 == 0 and
 // every buffer 16-byte aligned, so a float4 never leaves a row of N.
 template <int VEC>
-__device__ inline void aci_load(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = p[0];
-  }
-}
-
-template <int VEC>
 __global__ __launch_bounds__(ACI_THREADS) void aci_stream(const float* __restrict__ issued, const float* __restrict__ raw,
                                                           const float* __restrict__ ring_y, int C, long long origin, int H,
                                                           int N, int P, AciPairs pairs, double gamma, int M, int slot,
@@ -232,17 +210,14 @@ __global__ __launch_bounds__(ACI_THREADS) void aci_stream(const float* __restric
     for (int t = tid * VEC; t < L; t += ACI_THREADS * VEC) {
       const int e = base + t, hh = e / N, n = e - hh * N;
       float y[VEC], rlo[VEC], rhi[VEC], ilo[VEC], ihi[VEC], s[VEC];
-      aci_load<VEC>(ring_y + (size_t)((origin + hh) % C) * N + n, y);
-      aci_load<VEC>(raw + lo_off + t, rlo);
-      aci_load<VEC>(raw + hi_off + t, rhi);
-      aci_load<VEC>(issued + lo_off + t, ilo);
-      aci_load<VEC>(issued + hi_off + t, ihi);
+      cf_load<VEC>(ring_y + (size_t)((origin + hh) % C) * N + n, y);
+      cf_load<VEC>(raw + lo_off + t, rlo);
+      cf_load<VEC>(raw + hi_off + t, rhi);
+      cf_load<VEC>(issued + lo_off + t, ilo);
+      cf_load<VEC>(issued + hi_off + t, ihi);
 #pragma unroll
       for (int j = 0; j < VEC; ++j) s[j] = aci_score(y[j], rlo[j], rhi[j], ilo[j], ihi[j], valid, miss);
-      if constexpr (VEC == 4)
-        *reinterpret_cast<float4*>(dst + t) = make_float4(s[0], s[1], s[2], s[3]);
-      else
-        dst[t] = s[0];
+      cf_store<VEC>(dst + t, s);
     }
     if (valid) atomicAdd(&s_valid, valid);
     if (miss) atomicAdd(&s_miss, miss);
@@ -262,10 +237,10 @@ __global__ __launch_bounds__(ACI_THREADS) void aci_stream(const float* __restric
       const uint32_t e = (uint32_t)(tid + q * ACI_THREADS) * VEC;
       if (e < total) {
         const uint32_t i = e / L, t = e - i * L;
-        aci_load<VEC>(win + (size_t)i * pitch + t, kept[q]);
+        cf_load<VEC>(win + (size_t)i * pitch + t, kept[q]);
       } else {
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) kept[q][j] = __uint_as_float(ACI_NAN);
+        for (int j = 0; j < VEC; ++j) kept[q][j] = __uint_as_float(CF_NAN_BITS);
       }
     }
   }
@@ -278,7 +253,7 @@ __global__ __launch_bounds__(ACI_THREADS) void aci_stream(const float* __restric
         for (int j = 0; j < VEC; ++j) {
           const float sc = kept[q][j];
           if (sc != sc) continue;
-          const uint32_t key = aci_key(sc);
+          const uint32_t key = cf_score_key(sc);
           if (cf_match(key, d, pre)) atomicAdd(&h[cf_bin(key, d) * ACI_COPIES + copy], 1u);
         }
       }
@@ -287,11 +262,11 @@ __global__ __launch_bounds__(ACI_THREADS) void aci_stream(const float* __restric
       for (uint32_t e = tid * VEC; e < total; e += ACI_THREADS * VEC) {
         const uint32_t i = e / L, t = e - i * L;
         float s[VEC];
-        aci_load<VEC>(win + (size_t)i * pitch + t, s);
+        cf_load<VEC>(win + (size_t)i * pitch + t, s);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
           if (s[j] != s[j]) continue;
-          const uint32_t key = aci_key(s[j]);
+          const uint32_t key = cf_score_key(s[j]);
           if (cf_match(key, d, pre)) atomicAdd(&h[cf_bin(key, d) * ACI_COPIES + copy], 1u);
         }
       }
@@ -308,15 +283,9 @@ __global__ __launch_bounds__(ACI_THREADS) void aci_stream(const float* __restric
       binsum[tid] = v;
     }
     __syncthreads();
-    if (tid < 64) {                               // wave 0: lane l owns bins 4l .. 4l+3 (the pick of conformal.hip)
+    if (tid < 64) {                               // wave 0: lane l owns bins 4l .. 4l+3 (the pick of conformal_select.h)
       const uint4 c = reinterpret_cast<const uint4*>(binsum)[tid];
-      const uint32_t own = c.x + c.y + c.z + c.w;
-      uint32_t incl = own;
-#pragma unroll
-      for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t up = __shfl_up(incl, s, 64);
-        if (tid >= s) incl += up;
-      }
+      const uint32_t incl = cf_wave_scan(c, tid);
       uint32_t k = 0u;
       if (d == 0) {
         const long long m = (long long)__shfl(incl, 63, 64);
@@ -325,18 +294,11 @@ __global__ __launch_bounds__(ACI_THREADS) void aci_stream(const float* __restric
       } else {
         k = s_k;
       }
-      const unsigned long long reached = k != 0u ? __ballot(incl >= k) : 0ull;
-      if (k == 0u || reached == 0ull) {
+      uint32_t bin, before;
+      const int at = k != 0u ? cf_wave_pick(c, incl, k, tid, bin, before) : -1;
+      if (at < 0) {
         if (tid == 0) s_k = 0u;
-      } else if (tid == __ffsll((long long)reached) - 1) {
-        uint32_t before = incl - own, bin = 4u * tid;
-        if (before + c.x < k) {
-          before += c.x; ++bin;
-          if (before + c.y < k) {
-            before += c.y; ++bin;
-            if (before + c.z < k) { before += c.z; ++bin; }
-          }
-        }
+      } else if (tid == at) {
         const uint32_t np = pre | (bin << (24 - 8 * d));
         if (d == 3) st.offsets[pg] = cf_unkey(np);
         s_pre = np;
@@ -347,8 +309,6 @@ __global__ __launch_bounds__(ACI_THREADS) void aci_stream(const float* __restric
     if (s_k == 0u) break;                         // uniform: read after the barrier, written before it
   }
 }
-
-inline bool aci_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -372,23 +332,20 @@ extern "C" int stemgnn_aci_update(const float* issued, const float* raw, const f
   }
   const AciState st = {scores, alpha, offsets, counts, miss_sum, valid_sum};
   hipStream_t s = (hipStream_t)stream;
-  const int HN = H * N;
+  const CfGrouping gr = cf_grouping(per_step, per_node, H, N);
   if (per_node) {
-    const int Cc = per_step ? HN : N, Hr = per_step ? 1 : H;
-    const dim3 grid((unsigned)((Cc + ACI_TILE - 1) / ACI_TILE), (unsigned)P);
+    const dim3 grid((unsigned)sg_ceil_div(gr.Cc, ACI_TILE), (unsigned)P);
     hipLaunchKernelGGL(aci_columns, grid, dim3(ACI_THREADS), 0, s, issued, raw, ring_y, C, origin, H, N, P, pairs, gamma, M,
-                       slot, min_scores, Cc, Hr, st);
+                       slot, min_scores, gr.Cc, gr.Hr, st);
   } else {
-    const int L = per_step ? N : HN, G = per_step ? H : 1;
-    const dim3 grid((unsigned)G, (unsigned)P);
-    const bool vec = (N & 3) == 0 && aci_aligned16(issued) && aci_aligned16(raw) && aci_aligned16(ring_y) &&
-                     aci_aligned16(scores);
+    const dim3 grid((unsigned)gr.G, (unsigned)P);
+    const bool vec = (N & 3) == 0 && sg_aligned16(issued) && sg_aligned16(raw) && sg_aligned16(ring_y) && sg_aligned16(scores);
     if (vec)
       hipLaunchKernelGGL(aci_stream<4>, grid, dim3(ACI_THREADS), 0, s, issued, raw, ring_y, C, origin, H, N, P, pairs, gamma,
-                         M, slot, min_scores, L, st);
+                         M, slot, min_scores, gr.L, st);
     else
       hipLaunchKernelGGL(aci_stream<1>, grid, dim3(ACI_THREADS), 0, s, issued, raw, ring_y, C, origin, H, N, P, pairs, gamma,
-                         M, slot, min_scores, L, st);
+                         M, slot, min_scores, gr.L, st);
   }
   SG_TRY(hipGetLastError());
   return 0;

@@ -7,7 +7,7 @@
 // (in LDS, and of per-workgroup partial counts into the work buffer), the two divisions are single fp64 operations: the same
 // bits on every run.
 //
-// Two forms, chosen by the grouping (those of aci.hip, for the same reasons):
+// Two forms, chosen by the grouping (those of aci.hip, for the same reasons; the groups themselves: cf_grouping, conformal_args.h):
 //   * columns (per_node): a query meets at most (M - 1) * H scores, strided by N.  A workgroup owns 32 adjacent nodes:
 //     consecutive lanes on consecutive nodes (coalesced 128-byte rows), 32 row lanes split the window's rows, up to four
 //     queries per node ride one pass over the population, the row lanes meet in integer LDS adds.  With H <= 4 a workgroup
@@ -30,14 +30,12 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../include/stemgnn_hip.h"
-#include "conformal_select.h"
+#include <algorithm>
 
-#define SG_TRY(e)                                \
-  do {                                           \
-    hipError_t _e = (e);                         \
-    if (_e != hipSuccess) return -(int)_e;       \
-  } while (0)
+#include "../../include/stemgnn_hip.h"
+#include "conformal_args.h"
+#include "conformal_select.h"
+#include "sg_host.h"
 
 namespace {
 
@@ -50,8 +48,6 @@ constexpr int AN_COL_BLOCKS = 192;                // workgroups the column form 
 constexpr int AN_MAX_RPARTS = 16;
 constexpr int AN_PART_KEYS = 8192;                // population keys per workgroup the pooled form aims at
 constexpr int AN_MAX_PARTS = 64;
-constexpr uint32_t AN_NAN = 0x7fc00000u;
-constexpr uint32_t AN_ABSENT = 0xffffffffu;       // above every key: key(+inf) = 0xff800000
 
 struct AnIn {
   const float* slab;
@@ -68,40 +64,35 @@ struct AnOut {
   float* log_row;
 };
 
-// the key of a stored score (NaN = absent is skipped by the caller; a loaded state may hold a -0)
-__device__ inline uint32_t an_key(float s) {
-  uint32_t u = __float_as_uint(s);
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+// (the key of a stored score: cf_score_key of conformal_select.h; NaN = absent is skipped by the caller)
 
-// steps 1 and 2 of element (h, n) of the arrived row: the key of its score, AN_ABSENT without a target or a forecast
+// steps 1 and 2 of element (h, n) of the arrived row: the key of its score, CF_KEY_ABSENT without a target or a forecast
 __device__ inline uint32_t an_query(const AnIn& in, int h, int n) {
   const float y = in.ring_y[(size_t)(in.row % in.C) * in.N + n];
-  if (y != y) return AN_ABSENT;
+  if (y != y) return CF_KEY_ABSENT;
   size_t s = 0;
   if (in.origins) {
     const long long o = in.row - h;
-    if (o < 0) return AN_ABSENT;
+    if (o < 0) return CF_KEY_ABSENT;
     s = (size_t)(o % in.S);
-    if (in.origins[s] != o) return AN_ABSENT;
+    if (in.origins[s] != o) return CF_KEY_ABSENT;
   }
   const size_t HN = (size_t)in.H * in.N, at = (size_t)h * in.N + n;
   const float* f = in.slab + s * in.R * HN + at;
   return cf_key(f[in.lo * HN], y, f[in.hi * HN]);
 }
 
-__device__ inline float an_score(uint32_t key) { return key == AN_ABSENT ? __uint_as_float(AN_NAN) : cf_unkey(key); }
+__device__ inline float an_score(uint32_t key) { return key == CF_KEY_ABSENT ? __uint_as_float(CF_NAN_BITS) : cf_unkey(key); }
 
 // step 4: one fp64 division, rounded once more to fp32
 __device__ inline float an_pvalue(bool absent, uint32_t ge, uint32_t m, long long min_scores) {
-  if (absent || (long long)m < min_scores) return __uint_as_float(AN_NAN);
+  if (absent || (long long)m < min_scores) return __uint_as_float(CF_NAN_BITS);
   return (float)((double)(ge + 1u) / (double)(m + 1u));
 }
 
 // the per-node combination, by ONE thread per node
 __device__ inline void an_node(int n, int v, float pmin, double alpha, const AnOut& out) {
-  float np = __uint_as_float(AN_NAN);
+  float np = __uint_as_float(CF_NAN_BITS);
   int al = 0;
   if (v) {
     const double t = (double)v * (double)pmin;
@@ -137,7 +128,7 @@ __global__ __launch_bounds__(AN_THREADS) void anomaly_columns(AnIn in, int M, in
     uint32_t q[AN_QC], ge[AN_QC], m[AN_QC];
 #pragma unroll
     for (int j = 0; j < AN_QC; ++j) {
-      q[j] = (live && h0 + j < h_end) ? an_query(in, h0 + j, n) : AN_ABSENT;
+      q[j] = (live && h0 + j < h_end) ? an_query(in, h0 + j, n) : CF_KEY_ABSENT;
       ge[j] = m[j] = 0u;
     }
     if (live) {
@@ -151,7 +142,7 @@ __global__ __launch_bounds__(AN_THREADS) void anomaly_columns(AnIn in, int M, in
             const float s = col[(size_t)i * HN];
             const uint32_t ok = (i != slot) & (s == s);
             m[j] += ok;
-            ge[j] += ok & (uint32_t)(an_key(s) >= q[j]);
+            ge[j] += ok & (uint32_t)(cf_score_key(s) >= q[j]);
           }
         }
       } else {                                    // the population of node n: scores[i, :, n], i != slot; row r = i * H + h
@@ -161,7 +152,7 @@ __global__ __launch_bounds__(AN_THREADS) void anomaly_columns(AnIn in, int M, in
 #pragma unroll 8
         for (uint32_t r = row0; r < rows; r += row_step) {
           const float s = out.scores[(size_t)r * N + n];
-          const uint32_t ok = ((r - slot0) >= (uint32_t)H) & (s == s), k = an_key(s);    // (unsigned: below slot0 wraps high)
+          const uint32_t ok = ((r - slot0) >= (uint32_t)H) & (s == s), k = cf_score_key(s);    // (unsigned: below slot0 wraps high)
           mm += ok;
 #pragma unroll
           for (int j = 0; j < AN_QC; ++j) ge[j] += ok & (uint32_t)(k >= q[j]);
@@ -189,7 +180,7 @@ __global__ __launch_bounds__(AN_THREADS) void anomaly_columns(AnIn in, int M, in
           if (mt && (per_step || h == 0)) atomicAdd(&work[HN + (per_step ? at : (size_t)n)], mt);
           continue;
         }
-        const float p = an_pvalue(q[j] == AN_ABSENT, s_ge[j * AN_TILE + lc], mt, min_scores);
+        const float p = an_pvalue(q[j] == CF_KEY_ABSENT, s_ge[j * AN_TILE + lc], mt, min_scores);
         out.scores[(size_t)slot * HN + at] = an_score(q[j]);
         out.pvalues[at] = p;
         if (p == p) {
@@ -212,16 +203,6 @@ __global__ __launch_bounds__(AN_THREADS) void anomaly_columns(AnIn in, int M, in
 // without); part y ranks every parts-th stretch of 1024 * VEC population keys and adds its counts into work: [h * N + n] the
 // scores >= the query of (h, n), [H * N + g] the group's m.  VEC = 4: N % 4 == 0 and scores 16-byte aligned, so a float4 of
 // the population never leaves a row of N.
-template <int VEC>
-__device__ inline void an_load(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = p[0];
-  }
-}
-
 template <int VEC>
 __global__ __launch_bounds__(AN_THREADS) void anomaly_pooled(AnIn in, int M, int slot, int L, float* __restrict__ scores,
                                                              uint32_t* __restrict__ work) {
@@ -267,11 +248,11 @@ __global__ __launch_bounds__(AN_THREADS) void anomaly_pooled(AnIn in, int M, int
       const uint32_t i = e / L, t = e - i * L;
       if ((int)i == slot) continue;
       float s[VEC];
-      an_load<VEC>(scores + (size_t)i * HN + base + t, s);
+      cf_load<VEC>(scores + (size_t)i * HN + base + t, s);
 #pragma unroll
       for (int c = 0; c < VEC; ++c) {
         if (s[c] != s[c]) continue;
-        const uint32_t key = an_key(s[c]);
+        const uint32_t key = cf_score_key(s[c]);
         int lo = 0, hi = nb;
         while (lo < hi) {
           const int mid = (lo + hi) >> 1;
@@ -322,6 +303,8 @@ __global__ __launch_bounds__(AN_THREADS) void anomaly_pooled(AnIn in, int M, int
 __global__ __launch_bounds__(AN_THREADS) void anomaly_finish(int H, int N, int slot, long long min_scores, double alpha,
                                                              int per_step, int per_node, uint32_t* __restrict__ work,
                                                              AnOut out) {
+  // (the group of (h, n) and the number of groups are CfGrouping::group / groups of conformal_args.h written out: through the
+  // struct this kernel compiled to other code that timed slower than the spread allows in two isolated figures)
   const size_t HN = (size_t)H * N;
   for (int n = threadIdx.x; n < N; n += AN_THREADS) {
     int v = 0;
@@ -348,8 +331,6 @@ __global__ __launch_bounds__(AN_THREADS) void anomaly_finish(int H, int N, int s
   }
 }
 
-inline bool an_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int stemgnn_anomaly_update(const float* slab, int S, int R, int lo_row, int hi_row, const long long* origins,
@@ -373,7 +354,7 @@ extern "C" int stemgnn_anomaly_update(const float* slab, int S, int R, int lo_ro
   hipStream_t s = (hipStream_t)stream;
   if (per_node) {
     const int hspan = H <= AN_QC ? H : (per_step ? 1 : AN_QC), spans = (H + hspan - 1) / hspan;
-    const int tiles = (N + AN_TILE - 1) / AN_TILE;
+    const int tiles = sg_ceil_div(N, AN_TILE);
     if (spans > 65535) return SG_EINVAL;
     int rparts = 1;
     if (spans > 1) {                              // a long horizon: enough workgroups, none without rows
@@ -391,12 +372,10 @@ extern "C" int stemgnn_anomaly_update(const float* slab, int S, int R, int lo_ro
     }
     return 0;
   }
-  const int L = per_step ? N : (int)HN, G = per_step ? H : 1;
-  const long long total = (long long)M * L;
-  const int parts = (int)((total + AN_PART_KEYS - 1) / AN_PART_KEYS < AN_MAX_PARTS ? (total + AN_PART_KEYS - 1) / AN_PART_KEYS
-                                                                                   : AN_MAX_PARTS);
-  const dim3 grid((unsigned)G, (unsigned)parts);
-  if ((N & 3) == 0 && an_aligned16(scores))
+  const CfGrouping gr = cf_grouping(per_step, 0, H, N);
+  const int L = gr.L, parts = std::min(sg_ceil_div((long long)M * L, AN_PART_KEYS), AN_MAX_PARTS);
+  const dim3 grid((unsigned)gr.G, (unsigned)parts);
+  if ((N & 3) == 0 && sg_aligned16(scores))
     hipLaunchKernelGGL(anomaly_pooled<4>, grid, dim3(AN_THREADS), 0, s, in, M, slot, L, scores, work);
   else
     hipLaunchKernelGGL(anomaly_pooled<1>, grid, dim3(AN_THREADS), 0, s, in, M, slot, L, scores, work);

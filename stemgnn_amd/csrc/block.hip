@@ -20,12 +20,7 @@
 #include "heads.h"
 #include "glu_fused.h"
 #include "glu_fused_bf16.h"
-
-#define SG_TRY(e)                                \
-  do {                                           \
-    hipError_t _e = (e);                         \
-    if (_e != hipSuccess) return -(int)_e;       \
-  } while (0)
+#include "sg_host.h"
 
 // sigmoid on the hardware transcendental units (v_exp_f32 + v_rcp_f32, ~1e-7 relative): the GLU epilogue evaluates it for
 // every output element, where the libm expf + IEEE divide (~50 VALU instructions) cost ~25 % of the whole GEMM
@@ -768,7 +763,6 @@ static int glu_fused_mode() {
   const char* ef = getenv("STEMGNN_GLU_FUSED");
   return ef ? atoi(ef) : 1;
 }
-static inline bool sg_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 // fp32 GLU forward: ONE fused three-layer launch (csrc/glu_fused.h), else three per-layer launches
 static bool glu_fwd_fused_ok(const SgDims& d, int fmode, const void* packed) {
   return gf_geom(d).ok && fmode != 0 && sg_aligned16(packed);

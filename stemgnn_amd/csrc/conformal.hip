@@ -22,6 +22,8 @@
 //     case: the top byte is sign and exponent -- do not serialise on one LDS address.
 // Both add their non-zero LDS bins to the group's global histogram with integer atomics; the pick launch (one wave per
 // (pair, group)) scans the 256 bins, narrows the prefix, and clears the bins again for the next pass.
+// The key, the wave pick and the vector load / store live in conformal_select.h, the band widening and the grouping geometry in
+// conformal_args.h: aci.hip, anomaly.hip and quantile_serve.hip use the same definitions.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -32,12 +34,7 @@
 #include "conformal_args.h"
 #include "conformal_select.h"
 #include "devattr.h"
-
-#define SG_TRY(e)                                \
-  do {                                           \
-    hipError_t _e = (e);                         \
-    if (_e != hipSuccess) return -(int)_e;       \
-  } while (0)
+#include "sg_host.h"
 
 namespace {
 
@@ -51,7 +48,8 @@ struct CfPairs {                            // travels by value in the kernel ar
   double cov[CF_MAX_P];
 };
 
-// (cf_rank, cf_key / cf_unkey, cf_match, cf_bin: conformal_select.h, shared with aci.hip)
+// (cf_rank, cf_key / cf_unkey, cf_match, cf_bin, the wave pick, cf_load / cf_store: conformal_select.h;
+//  cf_widen, cf_grouping: conformal_args.h -- shared with quantile_serve.hip, aci.hip and anomaly.hip)
 
 // ---- column form ------------------------------------------------------------------------------------------------------
 // grid (column tiles, row chunks, P).  Hr = rows of the matrix per window (1 or H); HN = H * N.
@@ -150,13 +148,7 @@ __global__ __launch_bounds__(CF_THREADS) void cf_pick(uint32_t* __restrict__ his
   uint4* bins = reinterpret_cast<uint4*>(hist + (size_t)pg * 256) + lane;
   const uint4 c = *bins;
   *bins = make_uint4(0u, 0u, 0u, 0u);
-  const uint32_t own = c.x + c.y + c.z + c.w;
-  uint32_t incl = own;
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) {
-    const uint32_t up = __shfl_up(incl, s, 64);
-    if (lane >= s) incl += up;
-  }
+  const uint32_t incl = cf_wave_scan(c, lane);
   uint32_t k, pre;
   if (d == 0) {
     const long long m = (long long)__shfl(incl, 63, 64);
@@ -167,7 +159,7 @@ __global__ __launch_bounds__(CF_THREADS) void cf_pick(uint32_t* __restrict__ his
     if (lane == 0) {
       counts[pg] = m;
       if (beyond) {
-        offsets[pg] = __uint_as_float(0x7f800000u);
+        offsets[pg] = __uint_as_float(CF_PINF_BITS);
         krem[pg] = 0u;
         prefix[pg] = 0u;
       }
@@ -177,16 +169,8 @@ __global__ __launch_bounds__(CF_THREADS) void cf_pick(uint32_t* __restrict__ his
     pre = prefix[pg];
   }
   if (k == 0u) return;
-  const unsigned long long reached = __ballot(incl >= k);
-  if (reached == 0ull || lane != __ffsll((long long)reached) - 1) return;
-  uint32_t before = incl - own, bin = 4u * lane;
-  if (before + c.x < k) {
-    before += c.x; ++bin;
-    if (before + c.y < k) {
-      before += c.y; ++bin;
-      if (before + c.z < k) { before += c.z; ++bin; }
-    }
-  }
+  uint32_t bin, before;
+  if (lane != cf_wave_pick(c, incl, k, lane, bin, before)) return;
   pre |= bin << (24 - 8 * d);
   if (d == 3) {
     offsets[pg] = cf_unkey(pre);
@@ -206,42 +190,21 @@ __global__ __launch_bounds__(CF_THREADS) void cf_apply(const float* forecast, co
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total / VEC; i += stride) {
     const size_t e = i * VEC, row = e / (size_t)N;
     const int n = (int)(e - row * N), h = (int)(row % (size_t)H), q = (int)((row / (size_t)H) % (size_t)Q);
-    const int role = roles.role[q];
     float v[VEC];
-    if constexpr (VEC == 4) {
-      const float4 t = *reinterpret_cast<const float4*>(forecast + e);
-      v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-      v[0] = forecast[e];
-    }
-    if (role != 0) {
-      const int p = (role > 0 ? role : -role) - 1;
-      const float* o = offsets + ((size_t)p * Hg + (Hg > 1 ? h : 0)) * Ng;
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        const float off = o[Ng > 1 ? n + j : 0];
-        v[j] = role > 0 ? __fsub_rn(v[j], off) : __fadd_rn(v[j], off);
-      }
-    }
-    if constexpr (VEC == 4) {
-      *reinterpret_cast<float4*>(out + e) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-      out[e] = v[0];
-    }
+    cf_load<VEC>(forecast + e, v);
+    cf_widen<VEC>(v, roles.role[q], offsets, Hg, Ng, h, n);
+    cf_store<VEC>(out + e, v);
   }
 }
 
 // (the shape and pair checks shared by fit and apply: conformal_args.h)
-inline int cf_ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
-
 }  // namespace
 
 extern "C" long stemgnn_conformal_rank(long m, double coverage) { return (long)cf_rank((long long)m, coverage); }
 
 extern "C" size_t stemgnn_conformal_scratch_bytes(long count, int H, int N, int P, int per_step, int per_node) {
   if (!cf_shapes_ok(count, 1, H, N, P)) return 0;
-  const size_t G = (size_t)(per_step ? H : 1) * (size_t)(per_node ? N : 1);
-  return (size_t)P * G * (256 + 2) * sizeof(uint32_t);               // histograms | prefix | remaining rank
+  return (size_t)P * cf_grouping(per_step, per_node, H, N).groups() * (256 + 2) * sizeof(uint32_t);               // histograms | prefix | remaining rank
 }
 
 extern "C" int stemgnn_conformal_fit(const float* target, const float* forecast, long count, int Q, int H, int N, int P,
@@ -250,7 +213,7 @@ extern "C" int stemgnn_conformal_fit(const float* target, const float* forecast,
                                      void* stream) {
   if (!target || !forecast || !lo_rows || !hi_rows || !coverage || !scratch || !offsets || !counts) return SG_EINVAL;
   if (!cf_shapes_ok(count, Q, H, N, P) || !cf_pairs_ok(Q, P, lo_rows, hi_rows, nullptr)) return SG_EINVAL;
-  if (((uintptr_t)scratch & 15) != 0) return SG_EINVAL;
+  if (!sg_aligned16(scratch)) return SG_EINVAL;
   CfPairs pairs = {};
   for (int p = 0; p < P; ++p) {
     if (!(coverage[p] > 0.0 && coverage[p] < 1.0)) return SG_EINVAL;  // NaN fails both
@@ -259,7 +222,8 @@ extern "C" int stemgnn_conformal_fit(const float* target, const float* forecast,
     pairs.cov[p] = coverage[p];
   }
   hipStream_t st = (hipStream_t)stream;
-  const int HN = H * N, G = (per_step ? H : 1) * (per_node ? N : 1);
+  const CfGrouping gr = cf_grouping(per_step, per_node, H, N);
+  const int HN = H * N, G = (int)gr.groups();
   const long long PG = (long long)P * G;
   if (PG >= (1ll << 31) / 4) return SG_EINVAL;                         // the pick kernel's int indices
   uint32_t* hist = reinterpret_cast<uint32_t*>(scratch);
@@ -269,12 +233,12 @@ extern "C" int stemgnn_conformal_fit(const float* target, const float* forecast,
   const int blocks_wanted = 4 * sg_num_cus();
   for (int d = 0; d < 4; ++d) {
     if (per_node) {
-      const int R = per_step ? (int)count : (int)(count * H), C = per_step ? HN : N, Hr = per_step ? 1 : H;
-      const int tiles = cf_ceil_div(C, CF_TILE);
-      int chunks = cf_ceil_div(blocks_wanted, (long long)tiles * P);
-      chunks = std::max(1, std::min(std::min(chunks, cf_ceil_div(R, 64)), 65535));
-      const int rows_per_chunk = cf_ceil_div(R, chunks);
-      const dim3 grid((unsigned)tiles, (unsigned)cf_ceil_div(R, rows_per_chunk), (unsigned)P);
+      const int C = gr.Cc, Hr = gr.Hr, R = (int)(count * Hr);
+      const int tiles = sg_ceil_div(C, CF_TILE);
+      int chunks = sg_ceil_div(blocks_wanted, (long long)tiles * P);
+      chunks = std::max(1, std::min(std::min(chunks, sg_ceil_div(R, 64)), 65535));
+      const int rows_per_chunk = sg_ceil_div(R, chunks);
+      const dim3 grid((unsigned)tiles, (unsigned)sg_ceil_div(R, rows_per_chunk), (unsigned)P);
       if (masked)
         hipLaunchKernelGGL(cf_hist_columns<true>, grid, dim3(CF_THREADS), 0, st, target, forecast, R, C, Hr, Q, HN, pairs, d,
                            prefix, krem, hist, rows_per_chunk);
@@ -282,13 +246,13 @@ extern "C" int stemgnn_conformal_fit(const float* target, const float* forecast,
         hipLaunchKernelGGL(cf_hist_columns<false>, grid, dim3(CF_THREADS), 0, st, target, forecast, R, C, Hr, Q, HN, pairs, d,
                            prefix, krem, hist, rows_per_chunk);
     } else {
-      const int L = per_step ? N : HN;
+      const int L = gr.L;
       const int M = (int)(count * L);
       if (G > 65535) return SG_EINVAL;
-      int chunks = cf_ceil_div(blocks_wanted, PG);
-      chunks = std::max(1, std::min(chunks, cf_ceil_div(M, 4 * CF_THREADS)));
-      const int per_chunk = cf_ceil_div(M, chunks);
-      const dim3 grid((unsigned)cf_ceil_div(M, per_chunk), (unsigned)G, (unsigned)P);
+      int chunks = sg_ceil_div(blocks_wanted, PG);
+      chunks = std::max(1, std::min(chunks, sg_ceil_div(M, 4 * CF_THREADS)));
+      const int per_chunk = sg_ceil_div(M, chunks);
+      const dim3 grid((unsigned)sg_ceil_div(M, per_chunk), (unsigned)G, (unsigned)P);
       if (masked)
         hipLaunchKernelGGL(cf_hist_stream<true>, grid, dim3(CF_THREADS), 0, st, target, forecast, M, L, G, Q, HN, pairs, d,
                            prefix, krem, hist, per_chunk);
@@ -297,7 +261,7 @@ extern "C" int stemgnn_conformal_fit(const float* target, const float* forecast,
                            prefix, krem, hist, per_chunk);
     }
     SG_TRY(hipGetLastError());
-    hipLaunchKernelGGL(cf_pick, dim3((unsigned)cf_ceil_div(PG, CF_THREADS / 64)), dim3(CF_THREADS), 0, st, hist, prefix, krem,
+    hipLaunchKernelGGL(cf_pick, dim3((unsigned)sg_ceil_div(PG, CF_THREADS / 64)), dim3(CF_THREADS), 0, st, hist, prefix, krem,
                        (int)PG, G, pairs, d, offsets, counts);
     SG_TRY(hipGetLastError());
   }
@@ -311,17 +275,17 @@ extern "C" int stemgnn_conformal_apply(const float* forecast, const float* offse
   CfRoles roles;
   if (!cf_shapes_ok(count, Q, H, N, P) || !cf_pairs_ok(Q, P, lo_rows, hi_rows, &roles)) return SG_EINVAL;
   const size_t total = (size_t)count * Q * H * N;
-  const int Hg = per_step ? H : 1, Ng = per_node ? N : 1;
-  const bool vec = (N & 3) == 0 && ((((uintptr_t)forecast | (uintptr_t)out) & 15) == 0);
+  const CfGrouping gr = cf_grouping(per_step, per_node, H, N);
+  const bool vec = (N & 3) == 0 && sg_aligned16(forecast) && sg_aligned16(out);
   const size_t items = vec ? total / 4 : total;
   const size_t cap = (size_t)sg_num_cus() * 8;
   const unsigned blocks = (unsigned)std::max<size_t>(1, std::min(cap, (items + CF_THREADS - 1) / CF_THREADS));
   if (vec)
     hipLaunchKernelGGL(cf_apply<4>, dim3(blocks), dim3(CF_THREADS), 0, (hipStream_t)stream, forecast, offsets, total, Q, H, N,
-                       roles, Hg, Ng, out);
+                       roles, gr.Hg, gr.Ng, out);
   else
     hipLaunchKernelGGL(cf_apply<1>, dim3(blocks), dim3(CF_THREADS), 0, (hipStream_t)stream, forecast, offsets, total, Q, H, N,
-                       roles, Hg, Ng, out);
+                       roles, gr.Hg, gr.Ng, out);
   SG_TRY(hipGetLastError());
   return 0;
 }

@@ -10,12 +10,7 @@
 #include <stdint.h>
 
 #include "../../include/stemgnn_hip.h"
-
-#define SG_TRY(e)                                \
-  do {                                           \
-    hipError_t _e = (e);                         \
-    if (_e != hipSuccess) return -(int)_e;       \
-  } while (0)
+#include "sg_host.h"
 
 // ---------------------------------------------------------------------------------------------------------------
 // out[t,n] = float( clip01?( (raw[t,n] - sub[n]) / div[n] ) ) -- IEEE fp64 subtract and divide, as numpy does

@@ -16,12 +16,7 @@
 #include "../../include/stemgnn_hip.h"
 #include "devattr.h"
 #include "gemm_core.h"
-
-#define SG_TRY(e)                                \
-  do {                                           \
-    hipError_t _e = (e);                         \
-    if (_e != hipSuccess) return -(int)_e;       \
-  } while (0)
+#include "sg_host.h"
 
 __device__ __forceinline__ double eig_wave_sum(double v) {
 #pragma unroll

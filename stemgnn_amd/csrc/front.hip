@@ -15,12 +15,7 @@
 #include "gemm_core.h"
 #include "gemm_phased.h"
 #include "layout.h"
-
-#define SG_TRY(e)                                \
-  do {                                           \
-    hipError_t _e = (e);                         \
-    if (_e != hipSuccess) return -(int)_e;       \
-  } while (0)
+#include "sg_host.h"
 
 constexpr size_t SG_ATTN_FWD_LDS_BYTES = 64 * 1024;   // dynamic LDS of sg_attention_fwd_kernel: (ceil(B / min(B, 8)) + 4 N) floats
 constexpr int ATTN_NBC = 8;     // batch chunks of the attention forward (more waves; partial sums reduced in fixed order)

@@ -31,12 +31,7 @@
 #include "dq_reduce.h"
 #include "gemm_core.h"
 #include "gru_wide.h"
-
-#define SG_TRY(e)                                \
-  do {                                           \
-    hipError_t _e = (e);                         \
-    if (_e != hipSuccess) return -(int)_e;       \
-  } while (0)
+#include "sg_host.h"
 
 __device__ __forceinline__ float gru_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
 __device__ __forceinline__ int gru_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }

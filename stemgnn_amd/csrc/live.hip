@@ -10,22 +10,19 @@
 // n, every row access of a wave is one coalesced run.  The normalisation is sg_normalize_kernel's expression (csrc/data.hip):
 // IEEE fp64 subtract and divide by intrinsics (no contraction), optional clip, one rounding to fp32.
 // gather: one workgroup per (row, b), a row is one coalesced N-float copy -- 16-byte accesses when the host found N % 4 == 0
-// and both buffers 16-byte aligned.  A window that is not (or no longer) in the ring comes back as NaN rows.
+// and both buffers 16-byte aligned (a plain float4 copy: nothing is unpacked, so it does not go through cf_load / cf_store).  A
+// window that is not (or no longer) in the ring comes back as NaN rows: CF_NAN_BITS of conformal_select.h, the quiet NaN torch
+// writes for float("nan"), as in ring_y.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/stemgnn_hip.h"
-
-#define SG_TRY(e)                                \
-  do {                                           \
-    hipError_t _e = (e);                         \
-    if (_e != hipSuccess) return -(int)_e;       \
-  } while (0)
+#include "conformal_select.h"
+#include "sg_host.h"
 
 namespace {
 
 constexpr int LV_PUSH_THREADS = 64;
-constexpr unsigned LV_NAN_BITS = 0x7fc00000u;       // the quiet NaN torch writes for float("nan")
 
 __global__ __launch_bounds__(LV_PUSH_THREADS) void lv_push_kernel(
     const double* __restrict__ raw, int K, int N, long long t0, const double* __restrict__ sub,
@@ -37,7 +34,7 @@ __global__ __launch_bounds__(LV_PUSH_THREADS) void lv_push_kernel(
     double lv = last[n];
     const int k0 = K > C ? K - C : 0;               // rows before k0 would be overwritten by this very call: fill state only
     int slot = (int)((t0 + k0) % C);
-    const float nanf32 = __uint_as_float(LV_NAN_BITS);
+    const float nanf32 = __uint_as_float(CF_NAN_BITS);
     for (int k = 0; k < K; ++k) {
       const double r = raw[(size_t)k * N + n];
       const bool miss = r != r || (has_missing && r == missing);
@@ -70,7 +67,7 @@ __global__ void lv_gather_kernel(const float* __restrict__ ring, int C, int N, c
   const int slot = ok ? (int)((s + l) % C) : 0;
   const float* src = ring + (size_t)slot * N;
   float* dst = out + ((size_t)b * L + l) * N;
-  const float nanf32 = __uint_as_float(LV_NAN_BITS);
+  const float nanf32 = __uint_as_float(CF_NAN_BITS);
   if (VEC) {
     const float4* s4 = reinterpret_cast<const float4*>(src);
     float4* d4 = reinterpret_cast<float4*>(dst);
@@ -90,8 +87,6 @@ __global__ void lv_head_kernel(const long long* __restrict__ t_dev, long long hi
     origins[p] = t;
   }
 }
-
-inline bool lv_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -116,7 +111,7 @@ extern "C" int stemgnn_ring_gather(const float* ring, int C, int N, const long l
   if ((long long)C * N >= (1ll << 31)) return SG_EINVAL;
   const int threads = N >= 1024 ? 256 : (N >= 256 ? 128 : 64);
   const dim3 grid((unsigned)L, (unsigned)B);
-  if ((N & 3) == 0 && lv_aligned16(ring) && lv_aligned16(out))
+  if ((N & 3) == 0 && sg_aligned16(ring) && sg_aligned16(out))
     hipLaunchKernelGGL(lv_gather_kernel<true>, grid, dim3(threads), 0, (hipStream_t)stream, ring, C, N, starts, t_dev, back, L,
                        out, status);
   else

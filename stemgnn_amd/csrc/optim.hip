@@ -15,12 +15,7 @@
 #include <stdlib.h>
 
 #include "../../include/stemgnn_hip.h"
-
-#define SG_TRY(e)                                \
-  do {                                           \
-    hipError_t _e = (e);                         \
-    if (_e != hipSuccess) return -(int)_e;       \
-  } while (0)
+#include "sg_host.h"
 
 constexpr int OPT_THREADS = 256;
 constexpr int OPT_LOADS = 8;                                        // independent 16-byte loads in flight per thread

@@ -14,12 +14,7 @@
 #include "devattr.h"
 #include "glu_fused.h"
 #include "layout.h"
-
-#define SG_TRY(e)                                \
-  do {                                           \
-    hipError_t _e = (e);                         \
-    if (_e != hipSuccess) return -(int)_e;       \
-  } while (0)
+#include "sg_host.h"
 
 struct SgBlockParams { const float* p[SG_BLOCK_NPARAMS]; };
 struct SgBlockGrads { float* p[SG_BLOCK_NPARAMS]; };

@@ -5,7 +5,8 @@
 //      fp32's with -0 == +0, NaN above everything (+inf included), ties (NaNs among themselves too) in row order: what
 //      torch.sort(dim=1, stable=True) gives.  By rank: rank_q = #{j : v_j before v_q}, the row index breaking ties, and v_q goes
 //      to row rank_q.
-//   b. calibrate: stemgnn_conformal_apply on the result of a (one fp32 subtract / add per pair row, same broadcast).
+//   b. calibrate: stemgnn_conformal_apply on the result of a (one fp32 subtract / add per pair row, same broadcast: the
+//      cf_widen of conformal_args.h that conformal.hip calls).
 // finish writes the column back where it came from (or to `out`); store writes it to the result slab row pos[0] + b, the
 // position read on the device, and copies the batch's target beside it (the contract of stemgnn_forecast_store).
 //
@@ -24,13 +25,9 @@
 
 #include "../../include/stemgnn_hip.h"
 #include "conformal_args.h"
+#include "conformal_select.h"
 #include "devattr.h"
-
-#define SG_TRY(e)                                \
-  do {                                           \
-    hipError_t _e = (e);                         \
-    if (_e != hipSuccess) return -(int)_e;       \
-  } while (0)
+#include "sg_host.h"
 
 namespace {
 
@@ -97,15 +94,7 @@ __global__ __launch_bounds__(QS_THREADS) void qs_finish_kernel(const QsArgs a) {
       float v[QS_CHUNK][VEC] = {};
 #pragma unroll
       for (int j = 0; j < QS_CHUNK; ++j) {
-        if (q0 + j < Q) {
-          const float* sq = s + (size_t)(q0 + j) * HN;
-          if constexpr (VEC == 4) {
-            const float4 x = *reinterpret_cast<const float4*>(sq);
-            v[j][0] = x.x; v[j][1] = x.y; v[j][2] = x.z; v[j][3] = x.w;
-          } else {
-            v[j][0] = *sq;
-          }
-        }
+        if (q0 + j < Q) cf_load<VEC>(s + (size_t)(q0 + j) * HN, v[j]);
       }
 #pragma unroll
       for (int j = 0; j < QS_CHUNK; ++j) {
@@ -140,27 +129,11 @@ __global__ __launch_bounds__(QS_THREADS) void qs_finish_kernel(const QsArgs a) {
       float v[VEC];
 #pragma unroll
       for (int k = 0; k < VEC; ++k) v[k] = R[(k * Q + r) * T];
-      const int role = a.offsets ? (int)a.roles.role[r] : 0;
-      if (role != 0) {
-        const int p = (role > 0 ? role : -role) - 1;
-        const float* o = a.offsets + ((size_t)p * a.Hg + (a.Hg > 1 ? h : 0)) * a.Ng;
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-          const float off = o[a.Ng > 1 ? n + k : 0];
-          v[k] = role > 0 ? __fsub_rn(v[k], off) : __fadd_rn(v[k], off);
-        }
-      }
-      float* dr = d + (size_t)r * HN;
-      if constexpr (VEC == 4) {
-        *reinterpret_cast<float4*>(dr) = make_float4(v[0], v[1], v[2], v[3]);
-      } else {
-        *dr = v[0];
-      }
+      cf_widen<VEC>(v, a.offsets ? (int)a.roles.role[r] : 0, a.offsets, a.Hg, a.Ng, h, n);
+      cf_store<VEC>(d + (size_t)r * HN, v);
     }
   }
 }
-
-inline bool qs_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // the stage arguments both entries share; fills Q .. roles of `a`
 bool qs_stages_ok(long count, int Q, int H, int N, int rearrange, const float* offsets, int P, const int* lo_rows,
@@ -176,8 +149,9 @@ bool qs_stages_ok(long count, int Q, int H, int N, int rearrange, const float* o
   a->HN = H * N;
   a->N = N;
   a->rearrange = rearrange != 0;
-  a->Hg = per_step ? H : 1;
-  a->Ng = per_node ? N : 1;
+  const CfGrouping gr = cf_grouping(per_step, per_node, H, N);
+  a->Hg = gr.Hg;
+  a->Ng = gr.Ng;
   return true;
 }
 
@@ -191,7 +165,7 @@ int qs_launch(QsArgs& a, long count, bool vec, hipStream_t st) {
   a.count = count;
   a.cpb = std::min(per, T);
   a.wpb = T / a.cpb;
-  a.col_blocks = (per + a.cpb - 1) / a.cpb;
+  a.col_blocks = sg_ceil_div(per, a.cpb);
   const long long wins = ((long long)count + a.wpb - 1) / a.wpb;
   const long long cap = (long long)sg_num_cus() * 16;
   a.win_blocks = (int)std::max<long long>(1, std::min(wins, cap / a.col_blocks));
@@ -214,7 +188,7 @@ extern "C" int stemgnn_quantile_finish(const float* forecast, long count, int Q,
   if (!qs_stages_ok(count, Q, H, N, rearrange, offsets, P, lo_rows, hi_rows, per_step, per_node, &a)) return SG_EINVAL;
   a.src = forecast;
   a.dst = out;
-  const bool vec = (N & 3) == 0 && Q <= QS_VEC_MAX_Q && qs_aligned16(forecast) && qs_aligned16(out);
+  const bool vec = (N & 3) == 0 && Q <= QS_VEC_MAX_Q && sg_aligned16(forecast) && sg_aligned16(out);
   return qs_launch(a, count, vec, (hipStream_t)stream);
 }
 
@@ -231,7 +205,7 @@ extern "C" int stemgnn_quantile_store(const float* steps, const float* target, c
   a.out_target = out_target;
   a.pos = pos;
   a.capacity = capacity;
-  a.tvec = (a.HN & 3) == 0 && qs_aligned16(target) && qs_aligned16(out_target);
-  const bool vec = (N & 3) == 0 && Q <= QS_VEC_MAX_Q && qs_aligned16(steps) && qs_aligned16(out_forecast);
+  a.tvec = (a.HN & 3) == 0 && sg_aligned16(target) && sg_aligned16(out_target);
+  const bool vec = (N & 3) == 0 && Q <= QS_VEC_MAX_Q && sg_aligned16(steps) && sg_aligned16(out_forecast);
   return qs_launch(a, B, vec, (hipStream_t)stream);
 }

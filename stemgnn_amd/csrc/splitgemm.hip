@@ -17,12 +17,7 @@
 
 #include "../../include/stemgnn_hip.h"
 #include "gemm2.h"
-
-#define SG_TRY(e)                                \
-  do {                                           \
-    hipError_t _e = (e);                         \
-    if (_e != hipSuccess) return -(int)_e;       \
-  } while (0)
+#include "sg_host.h"
 
 typedef __bf16 sp_bf8 __attribute__((ext_vector_type(8)));
 constexpr int SP_BM = 64, SP_BN = 128, SP_BK = 32, SP_LD = 40;     // LDS row stride in bf16 elements

@@ -10,12 +10,7 @@
 
 #include "../../include/stemgnn_hip.h"
 #include "devattr.h"
-
-#define SG_TRY(e)                                \
-  do {                                           \
-    hipError_t _e = (e);                         \
-    if (_e != hipSuccess) return -(int)_e;       \
-  } while (0)
+#include "sg_host.h"
 
 constexpr int TAIL_MAXW = 64;    // window sizes up to 64 / horizons up to 32
 constexpr int TAIL_MAXH = 32;

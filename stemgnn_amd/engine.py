@@ -1043,6 +1043,17 @@ class LiveForecaster:
         self._armed = False
 
     # -- checks that need no device -----------------------------------------------------------------------------
+    def _check_bands(self, who, what, obj):
+        """The refusals a calibrator and an adaptive object share: the model's levels, offsets (when there are any) that fit
+        horizon / N."""
+        if tuple(float(t) for t in obj.quantiles) != tuple(float(t) for t in self.quantiles):
+            raise ValueError(f"{who}: the {what}'s levels {tuple(obj.quantiles)} are not the model's {tuple(self.quantiles)}")
+        if obj.offsets is not None:
+            _, Hg, Ng = obj.offsets.shape
+            if (obj.per_step and Hg != self.horizon) or (obj.per_node and Ng != self.N):
+                raise ValueError(f"{who}: the {what}'s offsets {tuple(obj.offsets.shape)} (per_step={obj.per_step}, "
+                                 f"per_node={obj.per_node}) do not fit horizon {self.horizon} / {self.N} nodes")
+
     def _check_calibrator(self, calibrator):
         """QuantileForecastStep's refusals: fitted, the model's levels, offsets that fit horizon / N."""
         if calibrator is None:
@@ -1051,14 +1062,7 @@ class LiveForecaster:
             raise ValueError("LiveForecaster: a calibrator goes with a quantile model (Model(..., quantiles=...))")
         if calibrator.offsets is None:
             raise ValueError("LiveForecaster: the calibrator is not fitted (call fit or load_state_dict first)")
-        if tuple(float(t) for t in calibrator.quantiles) != tuple(float(t) for t in self.quantiles):
-            raise ValueError(f"LiveForecaster: the calibrator's levels {tuple(calibrator.quantiles)} are not the model's "
-                             f"{tuple(self.quantiles)}")
-        _, Hg, Ng = calibrator.offsets.shape
-        if (calibrator.per_step and Hg != self.horizon) or (calibrator.per_node and Ng != self.N):
-            raise ValueError(f"LiveForecaster: the calibrator's offsets {tuple(calibrator.offsets.shape)} "
-                             f"(per_step={calibrator.per_step}, per_node={calibrator.per_node}) do not fit horizon "
-                             f"{self.horizon} / {self.N} nodes")
+        self._check_bands("LiveForecaster", "calibrator", calibrator)
 
     @property
     def ready(self):
@@ -1268,13 +1272,7 @@ class LiveForecaster:
             if self.quantiles is None:
                 raise ValueError("LiveForecaster.set_adaptive: adaptive bands go with a quantile model (Model(..., "
                                  "quantiles=...)); a point model has no bands")
-            if tuple(float(t) for t in adaptive.quantiles) != tuple(float(t) for t in self.quantiles):
-                raise ValueError(f"LiveForecaster.set_adaptive: the adaptive object's levels {tuple(adaptive.quantiles)} are not "
-                                 f"the model's {tuple(self.quantiles)}")
-            if adaptive.offsets is not None and tuple(adaptive.offsets.shape) != adaptive.group_shape(self.horizon, self.N):
-                raise ValueError(f"LiveForecaster.set_adaptive: the adaptive object's offsets {tuple(adaptive.offsets.shape)} "
-                                 f"(per_step={adaptive.per_step}, per_node={adaptive.per_node}) do not fit horizon "
-                                 f"{self.horizon} / {self.N} nodes")
+            self._check_bands("LiveForecaster.set_adaptive", "adaptive object", adaptive)
             if self.history < self.horizon:
                 raise ValueError(f"LiveForecaster.set_adaptive: history {self.history} < horizon {self.horizon}: a forecast made "
                                  "every row would be overwritten before it matures and nothing would ever be learnt")
@@ -1385,20 +1383,9 @@ class LiveForecaster:
             if tuple(state["history_raw"].shape) != tuple(self.out_raw.shape):
                 raise ValueError(f"LiveForecaster.load_state_dict: history_raw is {tuple(state['history_raw'].shape)}, expected "
                                  f"{tuple(self.out_raw.shape)}")
-            loaded = type(self.adaptive)(self.adaptive.quantiles, self.adaptive.gamma, self.adaptive.window,
-                                         self.adaptive.per_step, self.adaptive.per_node, self.adaptive.min_scores)
-            loaded.load_state_dict(state["adaptive"], device=self.device)
-            if loaded.offsets is not None:              # into the buffers the captured graph may already read
-                for k in self.adaptive._STATE:
-                    getattr(self.adaptive, k).copy_(getattr(loaded, k))
-            self.adaptive.n_done = loaded.n_done
+            self.adaptive.restore_(state["adaptive"], self.device)    # into the buffers the captured graph may already read
             self.out_raw.copy_(state["history_raw"])
             self.done = int(state["done"])
         if self.anomaly is not None:
-            det = self.anomaly
-            loaded = type(det)(**det._config()).load_state_dict(state["anomaly"], device=self.device)
-            if loaded.scores is not None:
-                for k in det._STATE:
-                    getattr(det, k).copy_(getattr(loaded, k))
-            det.n_done, det.last_row, det._log_rows = loaded.n_done, loaded.last_row, list(loaded._log_rows)
+            self.anomaly.restore_(state["anomaly"], self.device)
         return self

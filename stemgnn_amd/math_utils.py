@@ -153,7 +153,42 @@ class ConformalCalibrator:
         return cls(state["quantiles"], state["per_step"], state["per_node"]).load_state_dict(state, device)
 
 
-class AdaptiveConformal:
+class _DeviceState:
+    """The device tensors a streaming object owns: `_STATE` names them (all None until the state is made), `_TYPES` gives the
+    dtypes that are not `_DTYPE`.  One definition of how they are saved, loaded and restored in place."""
+    _STATE, _TYPES, _DTYPE = (), {}, torch.float32
+
+    def _save_state(self):
+        return {k: None if getattr(self, k) is None else getattr(self, k).clone() for k in self._STATE}
+
+    def _drop_state(self):
+        for k in self._STATE:
+            setattr(self, k, None)
+
+    def _take_state(self, state, shapes, device, in_place):
+        """state[k] of shape shapes[k] for every k: a typed clone on `device`, or (in_place) copied into the tensor already
+        owned, which a captured graph may read.  Nothing is written before every shape has passed."""
+        for k in self._STATE:
+            if tuple(state[k].shape) != tuple(shapes[k]):
+                raise ValueError(f"{type(self).__name__}.load_state_dict: {k} is {tuple(state[k].shape)}, expected "
+                                 f"{tuple(shapes[k])}")
+        for k in self._STATE:
+            if in_place:
+                getattr(self, k).copy_(state[k])
+            else:
+                setattr(self, k, state[k].detach().to(device=device, dtype=self._TYPES.get(k, self._DTYPE)).contiguous().clone())
+
+    def load_state_dict(self, state, device=None):
+        return self._load(state, device, False)
+
+    def restore_(self, state, device=None):
+        """load_state_dict into the buffers already owned (same checks, same host counters): their addresses stay, so a
+        captured graph that reads them goes on without re-capture.  Without device state yet it is load_state_dict; a state
+        saved without device state leaves the buffers as they are."""
+        return self._load(state, device, self.scores is not None)
+
+
+class AdaptiveConformal(_DeviceState):
     """Adaptive conformal inference (ACI, Gibbs & Candes 2021) for the bands of a live quantile forecast, on the device.
 
     A `ConformalCalibrator` fitted once covers "in expectation on exchangeable new data"; a stream whose regime changes is not
@@ -193,6 +228,7 @@ class AdaptiveConformal:
         self.scores = self.alpha = self.offsets = self.counts = self.miss_sum = self.valid_sum = None
 
     _STATE = ("scores", "alpha", "offsets", "counts", "miss_sum", "valid_sum")
+    _TYPES, _DTYPE = dict(scores=torch.float32, alpha=torch.float64, offsets=torch.float32), torch.int64
 
     def group_shape(self, H, N):
         return (len(self.pairs), int(H) if self.per_step else 1, int(N) if self.per_node else 1)
@@ -252,39 +288,32 @@ class AdaptiveConformal:
     def state_dict(self):
         state = dict(quantiles=self.quantiles, pairs=self.pairs, per_step=self.per_step, per_node=self.per_node,
                      gamma=self.gamma, window=self.window, min_scores=self.min_scores, n_done=int(self.n_done))
-        for k in self._STATE:
-            t = getattr(self, k)
-            state[k] = None if t is None else t.clone()
+        state.update(self._save_state())
         return state
 
-    def load_state_dict(self, state, device=None):
+    def _load(self, state, device, in_place):
         q = tuple(float(t) for t in state["quantiles"])
         if q != self.quantiles or bool(state["per_step"]) != self.per_step or bool(state["per_node"]) != self.per_node or \
                 int(state["window"]) != self.window:
             raise ValueError(f"AdaptiveConformal.load_state_dict: saved for levels {q}, per_step={state['per_step']}, "
                              f"per_node={state['per_node']}, window={state['window']}; this one has {self.quantiles}, "
                              f"{self.per_step}, {self.per_node}, {self.window}")
-        if state["scores"] is None:
-            for k in self._STATE:
-                setattr(self, k, None)
+        sc = state["scores"]
+        if sc is None:
+            if not in_place:
+                self._drop_state()
         else:
-            sc = state["scores"]
             if sc.dim() != 4 or sc.shape[0] != self.window or sc.shape[1] != len(self.pairs):
                 raise ValueError(f"AdaptiveConformal.load_state_dict: scores {tuple(sc.shape)} do not fit window {self.window} / "
                                  f"{len(self.pairs)} pairs")
-            shape = self.group_shape(sc.shape[2], sc.shape[3])
-            dev = sc.device if device is None else device
-            types = dict(scores=torch.float32, alpha=torch.float64, offsets=torch.float32)
-            for k in self._STATE:
-                t = state[k]
-                if k != "scores" and tuple(t.shape) != shape:
-                    raise ValueError(f"AdaptiveConformal.load_state_dict: {k} is {tuple(t.shape)}, expected {shape}")
-                setattr(self, k, t.detach().to(device=dev, dtype=types.get(k, torch.int64)).contiguous().clone())
+            own = self.scores if in_place else sc
+            shapes = dict(dict.fromkeys(self._STATE, self.group_shape(own.shape[2], own.shape[3])), scores=tuple(own.shape))
+            self._take_state(state, shapes, sc.device if device is None else device, in_place)
         self.n_done = int(state["n_done"])
         return self
 
 
-class ConformalAnomaly:
+class ConformalAnomaly(_DeviceState):
     """Streaming conformal anomaly detection: is the reading that just arrived normal?  On the device, one call per row.
 
     When row tau arrives, every stored forecast of it -- step h of the forecast made at origin tau - h, h < H -- is scored
@@ -326,8 +355,7 @@ class ConformalAnomaly:
         self.n_done, self.last_row = 0, -1
         self._log_rows = [-1] * self.keep
         self._work = None                                          # the entry's work buffer: zero between calls, no state
-        for k in self._STATE:
-            setattr(self, k, None)
+        self._drop_state()
 
     _STATE = ("scores", "pvalues", "node_p", "alarm", "counts", "alarm_sum", "judged_sum", "log_p")
     _TYPES = dict(alarm=torch.int32, counts=torch.int64, alarm_sum=torch.int64, judged_sum=torch.int64)
@@ -441,30 +469,23 @@ class ConformalAnomaly:
                     min_scores=self.min_scores, score=self.score, keep=self.keep)
 
     def state_dict(self):
-        state = dict(self._config(), n_done=int(self.n_done), last_row=int(self.last_row), log_rows=list(self._log_rows))
-        for k in self._STATE:
-            t = getattr(self, k)
-            state[k] = None if t is None else t.clone()
-        return state
+        return dict(self._config(), n_done=int(self.n_done), last_row=int(self.last_row), log_rows=list(self._log_rows),
+                    **self._save_state())
 
-    def load_state_dict(self, state, device=None):
+    def _load(self, state, device, in_place):
         saved = {k: state[k] for k in self._config()}
         saved.update(alpha=float(saved["alpha"]), per_step=bool(saved["per_step"]), per_node=bool(saved["per_node"]))
         if saved != self._config():
             raise ValueError(f"ConformalAnomaly.load_state_dict: saved with {saved}; this one has {self._config()}")
-        if state["scores"] is None:
-            for k in self._STATE:
-                setattr(self, k, None)
+        sc = state["scores"]
+        if sc is None:
+            if not in_place:
+                self._drop_state()
         else:
-            sc = state["scores"]
             if sc.dim() != 3 or sc.shape[0] != self.window:
                 raise ValueError(f"ConformalAnomaly.load_state_dict: scores {tuple(sc.shape)} do not fit window {self.window}")
-            dev = sc.device if device is None else device
-            for k, shape in self._shapes(sc.shape[1], sc.shape[2]).items():
-                t = state[k]
-                if tuple(t.shape) != shape:
-                    raise ValueError(f"ConformalAnomaly.load_state_dict: {k} is {tuple(t.shape)}, expected {shape}")
-                setattr(self, k, t.detach().to(device=dev, dtype=self._TYPES.get(k, torch.float32)).contiguous().clone())
+            own = self.scores if in_place else sc
+            self._take_state(state, self._shapes(own.shape[1], own.shape[2]), sc.device if device is None else device, in_place)
         self.n_done, self.last_row = int(state["n_done"]), int(state["last_row"])
         self._log_rows = [int(v) for v in state["log_rows"]]
         return self

@@ -62,6 +62,7 @@ class AciRef:
                     self.valid_sum[g] += valid
                     w = self.scores[:, p, hs, ns].reshape(-1)
                     w = w[~np.isnan(w)]
+                    w = np.where(w == 0, F32(0.0), w)          # a loaded window may hold -0: it orders, and comes back, as +0
                     m = int(w.size)
                     self.counts[g] = m
                     if valid == 0 or m < self.min_scores:

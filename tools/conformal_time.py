@@ -98,7 +98,7 @@ def main():
     y_nan[torch.rand(y.shape, generator=g) < 0.1] = float("nan")
     y, y_nan, f = y.to(dev), y_nan.to(dev), f.contiguous().to(dev)
     out = {"shape": dict(count=COUNT, Q=Q, H=H, N=N, P=len(PAIRS)), "reps": args.reps, "rounds": args.rounds, "fit_us": {},
-           "fit_us_windows": {}, "apply_us": {}}
+           "fit_us_windows": {}, "apply_us": {}, "apply_us_windows": {}}
     for per_step, per_node in GROUPINGS:
         for masked in (False, True):
             name = f"step{int(per_step)}_node{int(per_node)}" + ("_masked" if masked else "")
@@ -112,9 +112,10 @@ def main():
             out["fit_us"][name] = med
             out["fit_us_windows"][name] = windows
         offsets = got[0]
-        med, _ = alternate({"apply": lambda: ops.conformal_apply(f, offsets, PAIRS, per_step, per_node),
-                            "torch_apply": lambda: torch_apply(f, offsets)}, args.reps, args.rounds, 10)
+        med, windows = alternate({"apply": lambda: ops.conformal_apply(f, offsets, PAIRS, per_step, per_node),
+                                  "torch_apply": lambda: torch_apply(f, offsets)}, args.reps, args.rounds, 10)
         out["apply_us"][f"step{int(per_step)}_node{int(per_node)}"] = med
+        out["apply_us_windows"][f"step{int(per_step)}_node{int(per_node)}"] = windows
     line = json.dumps(out)
     print(line)
     if args.out:
