@@ -766,6 +766,44 @@ int stemgnn_quantile_store(const float* steps, const float* target, const long l
                            int rearrange, const float* offsets, int P, const int* lo_rows, const int* hi_rows, int per_step,
                            int per_node, float* out_forecast, float* out_target, long capacity, void* stream);
 
+/* ---- seasonal conformal calibration: offsets per time-of-day bucket (csrc/seasonal.hip) -----------
+ * Mondrian (category-conditional) split-conformal calibration with a bucket of the target's time as the category.
+ * Time: every target has an integer time index t.  Row i of target [count, H, N] / forecast [count, Q, H, N] has an origin o_i,
+ * the time index of its step-0 target; step h has t = o_i + h.  o_i = origins[i] (int64 [count] on the device: any order,
+ * repeats and gaps allowed, negative values too) or, with origins == NULL, origin0 + i.
+ * Bucket: u = (t + phase) mod period in the floor sense (0 <= u < period for negative t too), bucket = (u * K) / period in
+ * integer division; period >= 1, 1 <= K <= period, 0 <= phase < period.  stemgnn_season_bucket is that formula on the host
+ * (-1 on a bad period / K / phase); the device uses the same integer operations.  The bucket is the TARGET's: step h of row i
+ * is scored in, and widened with, bucket(o_i + h), so the steps of one row may fall into different buckets.
+ * offsets (fp32) and counts (int64) are [K, P, Hg, Ng], the bucket slowest: slice s is a table of stemgnn_conformal_fit.
+ * fit:   within a bucket everything is stemgnn_conformal_fit's definition -- score, NaN -> +inf, masked, the rank, the k-th
+ *        smallest in fp32's total order with -0 == +0, +inf when k > m (an empty bucket: count 0, +inf) -- by the same exact
+ *        radix select: the same bits on every run, under any permutation of the rows and whatever the scratch held before.
+ *        period == K == 1 gives stemgnn_conformal_fit's offsets and counts bit for bit.  No host synchronisation, no
+ *        allocation, 9 launches; scratch: stemgnn_seasonal_scratch_bytes bytes, 16-byte aligned, K times the unseasoned one.
+ * apply: out[i, lo_p, h, n] = forecast - offsets[bucket(o_i + h), p, ..], out[i, hi_p, h, n] = forecast + ... (one fp32
+ *        operation each); rows in no pair are copied bit for bit; out may be forecast itself.  rearrange != 0: the column is
+ *        first put in non-decreasing order exactly as stemgnn_quantile_finish does it.  One launch; 16-byte accesses when
+ *        N % 4 == 0 and both buffers are 16-byte aligned (with rearrange also Q <= 16).
+ * store: stemgnn_quantile_store with the table slice chosen on the device: batch row b has origin t_dev[0] + b (t_dev: the
+ *        int64[1] row count of the live ring), step h is widened with slice bucket(t_dev[0] + b + h).  One launch, no scratch.
+ * SG_EINVAL (nothing launched; the size entry returns 0) on everything the unseasoned entries refuse, a NULL offsets / t_dev,
+ * period < 1 or >= 2^31, K < 1, K > period, phase outside [0, period), P * K > 65535, K * P * Hg * Ng >= 2^29. */
+int stemgnn_season_bucket(long long t, long long period, int K, long long phase);
+size_t stemgnn_seasonal_scratch_bytes(long count, int H, int N, int P, int K, int per_step, int per_node);
+int stemgnn_seasonal_fit(const float* target, const float* forecast, const long long* origins, long long origin0, long count,
+                         int Q, int H, int N, int P, const int* lo_rows, const int* hi_rows, const double* coverage,
+                         int per_step, int per_node, int masked, long long period, int K, long long phase, void* scratch,
+                         float* offsets, long long* counts, void* stream);
+int stemgnn_seasonal_apply(const float* forecast, const float* offsets, const long long* origins, long long origin0,
+                           long count, int Q, int H, int N, int rearrange, int P, const int* lo_rows, const int* hi_rows,
+                           int per_step, int per_node, long long period, int K, long long phase, float* out, void* stream);
+int stemgnn_quantile_store_seasonal(const float* steps, const float* target, const long long* pos, const long long* t_dev,
+                                    int B, int Q, int H, int N, int rearrange, const float* offsets, int P,
+                                    const int* lo_rows, const int* hi_rows, int per_step, int per_node, long long period,
+                                    int K, long long phase, float* out_forecast, float* out_target, long capacity,
+                                    void* stream);
+
 /* ---- live forecasting: a stream of readings in a device ring (csrc/live.hip) ----------------------
  * A ring is [C, N] fp32: the row with absolute index tau (0 = the first row ever pushed) lives in slot tau mod C.  ring_x holds
  * the imputed, normalised rows (ForecastDataset.data), ring_y the same values with NaN at missing readings

@@ -190,6 +190,16 @@ SIGNATURES = {
                                         c_int, c_int, _P, _P]),
     "stemgnn_quantile_store": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, POINTER(c_int),
                                        POINTER(c_int), c_int, c_int, _P, _P, c_long, _P]),
+    "stemgnn_season_bucket": (c_int, [c_longlong, c_longlong, c_int, c_longlong]),
+    "stemgnn_seasonal_scratch_bytes": (c_size_t, [c_long, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "stemgnn_seasonal_fit": (c_int, [_P, _P, _P, c_longlong, c_long, c_int, c_int, c_int, c_int, POINTER(c_int),
+                                     POINTER(c_int), POINTER(c_double), c_int, c_int, c_int, c_longlong, c_int, c_longlong,
+                                     _P, _P, _P, _P]),
+    "stemgnn_seasonal_apply": (c_int, [_P, _P, _P, c_longlong, c_long, c_int, c_int, c_int, c_int, c_int, POINTER(c_int),
+                                       POINTER(c_int), c_int, c_int, c_longlong, c_int, c_longlong, _P, _P]),
+    "stemgnn_quantile_store_seasonal": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, POINTER(c_int),
+                                                POINTER(c_int), c_int, c_int, c_longlong, c_int, c_longlong, _P, _P, c_long,
+                                                _P]),
     "stemgnn_live_push": (c_int, [_P, c_int, c_int, c_longlong, _P, _P, c_int, c_double, c_int, _P, _P, _P, c_int, _P, _P]),
     "stemgnn_ring_gather": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "stemgnn_live_head": (c_int, [_P, c_long, _P, _P, _P]),

@@ -901,6 +901,10 @@ class QuantileForecastStep(ForecastStep):
         self._finish_kw = dict(rearrange=self.rearrange)
         quantiles = model.quantiles
         if calibrator is not None:
+            if getattr(calibrator, "kind", None) == "seasonal":
+                raise ValueError("QuantileForecastStep: a seasonal calibrator needs every row's time index, and a batch of the "
+                                 "order queue holds the windows in the loaded order, not in time order; apply it to the result "
+                                 "(SeasonalConformalCalibrator.apply(forecast, origin)) or serve through LiveForecaster")
             if calibrator.offsets is None:
                 raise ValueError("QuantileForecastStep: the calibrator is not fitted (call fit or load_state_dict first)")
             if tuple(float(t) for t in calibrator.quantiles) != tuple(float(t) for t in quantiles):
@@ -974,7 +978,9 @@ class LiveForecaster:
     slot not overwritten, targets still in the ring (o >= rows - C) -- as (forecasts [m,(Q,)horizon,N], targets [m,horizon,N]
     from ring_y, origins int64 [m] ascending): ``ConformalCalibrator.fit(tg, fc, ignore_nan=True)`` and
     ``Scores / QuantileScores(tg, fc, ..., ignore_nan=True)`` take them as they are.  A forecast made every row needs
-    history >= horizon to survive until it matures.
+    history >= horizon to survive until it matures.  A math_utils.SeasonalConformalCalibrator (offsets per time-of-day bucket)
+    takes the origins too, on the user's clock: ``cal.fit(tg, fc, origins + t_offset, ignore_nan=True)`` and
+    ``live.set_calibrator(cal, t_offset=t_offset)`` with t_offset the time index of the first row ever pushed.
 
     set_adaptive(adaptive): adapting bands (math_utils.AdaptiveConformal; None switches it off).  The captured body gains one
     launch, a second quantile_store of the same steps into out_raw [history, Q, horizon, N] (rearranged as the first, no
@@ -1030,6 +1036,7 @@ class LiveForecaster:
                              "point model has no bands")
         self._check_calibrator(calibrator)
         self.calibrator = calibrator
+        self.t_offset = 0                               # the time index of the first row ever pushed (set_calibrator)
         self.adaptive, self.done, self._adaptive_init = None, -1, None
         self.anomaly, self._anomaly_rows = None, (0, 0)
         self.C = self.W + self.horizon + self.history
@@ -1049,7 +1056,7 @@ class LiveForecaster:
         if tuple(float(t) for t in obj.quantiles) != tuple(float(t) for t in self.quantiles):
             raise ValueError(f"{who}: the {what}'s levels {tuple(obj.quantiles)} are not the model's {tuple(self.quantiles)}")
         if obj.offsets is not None:
-            _, Hg, Ng = obj.offsets.shape
+            Hg, Ng = obj.offsets.shape[-2:]
             if (obj.per_step and Hg != self.horizon) or (obj.per_node and Ng != self.N):
                 raise ValueError(f"{who}: the {what}'s offsets {tuple(obj.offsets.shape)} (per_step={obj.per_step}, "
                                  f"per_node={obj.per_node}) do not fit horizon {self.horizon} / {self.N} nodes")
@@ -1119,6 +1126,15 @@ class LiveForecaster:
             self._offsets = torch.empty(tuple(cal.offsets.shape), dtype=torch.float32, device=self.device)
         self._offsets.copy_(cal.offsets)
         self._finish_kw.update(offsets=self._offsets, pairs=cal.pairs, per_step=cal.per_step, per_node=cal.per_node)
+        if self._season(cal) is not None:               # the table slice is chosen on the device, from the ring's row count
+            self._finish_kw.update(seasonal=self._season(cal), t_dev=self.t_dev)
+
+    def _season(self, cal):
+        """(period, buckets, folded phase) of a seasonal calibrator -- ring row tau has time index tau + t_offset, which is
+        folded into the phase handed to the store -- or None for a static one / none."""
+        if getattr(cal, "kind", None) != "seasonal":
+            return None
+        return (cal.period, cal.buckets, (cal.phase + self.t_offset) % cal.period)
 
     # -- ingest -------------------------------------------------------------------------------------------------
     def _as_raw(self, rows):
@@ -1182,8 +1198,9 @@ class LiveForecaster:
         if self.Q is None:
             ops.forecast_store(self.steps, self._nan_target, self.pos, self.out_forecast, self._out_target)
         else:
-            ops.quantile_store(self.steps, self._nan_target, self.pos, self.out_forecast, self._out_target, **self._finish_kw)
-            if self.adaptive is not None:               # the same rows ahead of calibration: what the scores are taken on
+            store = ops.quantile_store_seasonal if "seasonal" in self._finish_kw else ops.quantile_store
+            store(self.steps, self._nan_target, self.pos, self.out_forecast, self._out_target, **self._finish_kw)
+            if self.adaptive is not None:              # the same rows ahead of calibration: what the scores are taken on
                 ops.quantile_store(self.steps, self._nan_target, self.pos, self.out_raw, self._out_target,
                                    rearrange=self.rearrange)
 
@@ -1235,23 +1252,31 @@ class LiveForecaster:
         return fc, tg, origins
 
     # -- calibrator ---------------------------------------------------------------------------------------------
-    def set_calibrator(self, calibrator):
+    def set_calibrator(self, calibrator, t_offset=0):
         """Swap the calibrator (None: off).  A fitted one of the same per_step / per_node shape is copied into the buffer the
         captured graph already reads -- no re-capture; only a change between present and absent, or of that shape, captures
-        again (at the next forecast)."""
+        again (at the next forecast).
+        A fitted math_utils.SeasonalConformalCalibrator is served too: t_offset is the time index of the first row ever pushed
+        (ring row tau has t = tau + t_offset), folded into the phase handed to the store, which picks the table slice of every
+        step on the device from t_dev.  A refit of the same shape, (period, buckets) and folded phase is again a copy into the
+        buffer the graph reads; anything else captures again.  Refit from the stream with
+        ``fc, tg, origins = live.matured(); cal.fit(tg, fc, origins + t_offset, ignore_nan=True)``."""
         if self.adaptive is not None:
             raise ValueError("LiveForecaster.set_calibrator: adaptive bands are on and own the offsets; call set_adaptive(None) "
                              "first")
         self._check_calibrator(calibrator)
         if calibrator is None and self.calibrator is None:
             return
-        old = self.calibrator
+        old, old_season = self.calibrator, self._season(self.calibrator)
         self.calibrator = calibrator
+        if getattr(calibrator, "kind", None) == "seasonal":
+            self.t_offset = int(t_offset)
         if not self._ready_buffers:
             return
         same = old is not None and calibrator is not None and self._offsets is not None and \
             tuple(calibrator.offsets.shape) == tuple(self._offsets.shape) and \
-            (calibrator.per_step, calibrator.per_node) == (old.per_step, old.per_node)
+            (calibrator.per_step, calibrator.per_node) == (old.per_step, old.per_node) and \
+            self._season(calibrator) == old_season
         if same:
             self._offsets.copy_(calibrator.offsets)
             return
@@ -1272,6 +1297,9 @@ class LiveForecaster:
             if self.quantiles is None:
                 raise ValueError("LiveForecaster.set_adaptive: adaptive bands go with a quantile model (Model(..., "
                                  "quantiles=...)); a point model has no bands")
+            if self._season(self.calibrator) is not None:
+                raise ValueError("LiveForecaster.set_adaptive: a seasonal calibrator is set, and adaptive bands keep one table, "
+                                 "not one per bucket; call set_calibrator(None) (or set a static calibrator) first")
             self._check_bands("LiveForecaster.set_adaptive", "adaptive object", adaptive)
             if self.history < self.horizon:
                 raise ValueError(f"LiveForecaster.set_adaptive: history {self.history} < horizon {self.horizon}: a forecast made "
@@ -1349,7 +1377,9 @@ class LiveForecaster:
         self._alloc()
         state = dict(rows=int(self.rows), window=self.W, horizon=self.horizon, history=self.history, units=self.N,
                      ring_x=self.ring_x.clone(), ring_y=self.ring_y.clone(), last=self.last.clone(),
-                     history_forecast=self.out_forecast.clone(), origins=torch.tensor(self._origins, dtype=torch.int64))
+                     history_forecast=self.out_forecast.clone(), origins=torch.tensor(self._origins, dtype=torch.int64),
+                     calibrator_kind=getattr(self.calibrator, "kind", "static") if self.calibrator is not None else None,
+                     t_offset=int(self.t_offset))
         if self.adaptive is not None:
             state.update(history_raw=self.out_raw.clone(), done=int(self.done), adaptive=self.adaptive.state_dict())
         if self.anomaly is not None:
@@ -1364,6 +1394,15 @@ class LiveForecaster:
             raise ValueError("LiveForecaster.load_state_dict: adaptive bands are on, but the state was saved without them")
         if self.anomaly is not None and "anomaly" not in state:
             raise ValueError("LiveForecaster.load_state_dict: a detector is set, but the state was saved without one")
+        seasonal = self._season(self.calibrator) is not None
+        if state.get("calibrator_kind") == "seasonal" and not seasonal:
+            raise ValueError("LiveForecaster.load_state_dict: the state was saved while a seasonal calibrator was served; set one "
+                             "(set_calibrator) before loading it")
+        if seasonal and "t_offset" in state and int(state["t_offset"]) != self.t_offset:
+            self.t_offset = int(state["t_offset"])      # the saved clock: the store's phase changes, so capture again
+            if self._ready_buffers:
+                self._set_finish_kw()
+                self._replay, self._armed = None, False
         self._alloc()
         for k, dst in (("ring_x", self.ring_x), ("ring_y", self.ring_y), ("last", self.last),
                        ("history_forecast", self.out_forecast)):

@@ -153,6 +153,135 @@ class ConformalCalibrator:
         return cls(state["quantiles"], state["per_step"], state["per_node"]).load_state_dict(state, device)
 
 
+class SeasonalConformalCalibrator:
+    """`ConformalCalibrator` per time-of-day bucket (Mondrian / category-conditional split-conformal calibration), on the device.
+
+    A traffic model's residuals at 8 am are several times those at 3 am; offsets pooled over the day cover the nominal level on
+    average but over-cover the quiet hours and under-cover the busy ones.  Here every target has an integer time index t on the
+    user's clock (e.g. minutes / 5 since some midnight) and is calibrated within its bucket
+        bucket(t) = ((t + phase) mod period) * buckets // period          (floor mod; `bucket_of` is this formula on the host)
+    e.g. period=288, buckets=24 for hourly offsets of 5-minute data.  The bucket is the TARGET's: row i has an origin o_i, the
+    time index of its step-0 target, and its step h is scored in, and widened with, bucket(o_i + h).
+
+    fit(y, y_hat, origin): y [count, H, N], y_hat [count, Q, H, N]; origin an int (row i has origin + i: the rows of a
+    validation pass) or an int64 tensor [count] (any order, repeats and gaps allowed; a host tensor is moved to the device
+    once).  Within a bucket everything is `ConformalCalibrator.fit`'s definition (`ops.seasonal_fit`); period = buckets = 1 is
+    `ConformalCalibrator` bit for bit.
+    apply(y_hat, origin, out=None, rearrange=False): the pairs' rows moved by their bucket's offsets (`ops.seasonal_apply`);
+    rearrange: the levels are first put in non-decreasing order (`rearrange_quantiles`), in the same launch.
+
+    Thin buckets.  A bucket may hold too few scores for the level, and +inf (the whole line) is a poor band to serve.  With
+    fallback="pooled" fit also runs the pooled `ops.conformal_fit` on the same tensors and every entry (s, p, g) whose count is
+    below max(min_scores, m_min(c_p)) -- m_min(c) the smallest m whose rank ceil((m + 1) c (1 - 1e-12)) is <= m -- takes the
+    pooled entry (on the device, no sync).  `offsets_seasonal` keeps the untouched tables and `pooled_offsets` the pooled one.
+    fallback="inf" keeps the raw definition.
+
+    Attributes: offsets (device fp32 [K, P, Hg, Ng], what apply and the live store use), counts (int64, the m of every bucket's
+    group), pairs, interval_nominal, per_step, per_node, period, buckets, phase."""
+
+    kind = "seasonal"
+
+    def __init__(self, quantiles, period, buckets, phase=0, per_step=True, per_node=False, min_scores=0, fallback="pooled"):
+        base = ConformalCalibrator(quantiles, per_step, per_node)          # its refusals: two levels, increasing in (0, 1)
+        self.quantiles, self.pairs, self.interval_nominal = base.quantiles, base.pairs, base.interval_nominal
+        self.per_step, self.per_node = base.per_step, base.per_node
+        self.period, self.buckets, self.phase = int(period), int(buckets), int(phase)
+        self.season = ops._season("SeasonalConformalCalibrator", (period, buckets, phase))
+        if fallback not in ("pooled", "inf"):
+            raise ValueError(f"SeasonalConformalCalibrator: fallback must be 'pooled' or 'inf', got {fallback!r}")
+        if int(min_scores) < 0:
+            raise ValueError(f"SeasonalConformalCalibrator: min_scores must be >= 0, got {min_scores}")
+        self.min_scores, self.fallback = int(min_scores), fallback
+        self.offsets = self.counts = self.offsets_seasonal = self.pooled_offsets = None
+
+    def bucket_of(self, t):
+        period, K, phase = self.season
+        return ((int(t) + phase) % period) * K // period
+
+    @staticmethod
+    def min_count(c):
+        """m_min(c): the smallest m whose rank is within the group, i.e. the fewest scores that give a finite offset."""
+        import math
+        m = 0
+        while max(1, math.ceil(((m + 1) * float(c)) * (1 - 1e-12))) > m:
+            m += 1
+        return m
+
+    def thresholds(self):
+        """max(min_scores, m_min(c_p)) per pair: below it an entry falls back to the pooled one (fallback="pooled")."""
+        return [max(self.min_scores, self.min_count(c)) for c in self.interval_nominal]
+
+    def fit(self, y, y_hat, origin, ignore_nan=False):
+        y_hat = _as_f32(y_hat)
+        y = _as_f32(y, like=y_hat)
+        if y_hat.dim() != 4 or y_hat.shape[1] != len(self.quantiles):
+            raise ValueError(f"SeasonalConformalCalibrator.fit: y_hat must be [count, {len(self.quantiles)}, H, N], got "
+                             f"{tuple(y_hat.shape)}")
+        cov = [float(c) for c in self.interval_nominal]
+        seasonal, self.counts = ops.seasonal_fit(y, y_hat, origin, self.pairs, cov, self.season, self.per_step,
+                                                 self.per_node, ignore_nan=bool(ignore_nan))
+        self.offsets_seasonal, self.pooled_offsets = seasonal, None
+        self.offsets = seasonal
+        if self.fallback == "pooled":
+            self.pooled_offsets, _ = ops.conformal_fit(y, y_hat, self.pairs, cov, self.per_step, self.per_node,
+                                                       ignore_nan=bool(ignore_nan))
+            need = torch.tensor(self.thresholds(), dtype=torch.int64, device=seasonal.device).view(1, -1, 1, 1)
+            self.offsets = torch.where(self.counts < need, self.pooled_offsets[None], seasonal).contiguous()
+        return self
+
+    def apply(self, y_hat, origin, out=None, rearrange=False):
+        if self.offsets is None:
+            raise ValueError("SeasonalConformalCalibrator.apply: not fitted (call fit or load_state_dict first)")
+        y_hat = _as_f32(y_hat)
+        _, _, Hg, Ng = self.offsets.shape
+        if y_hat.dim() != 4 or y_hat.shape[1] != len(self.quantiles) or (self.per_step and y_hat.shape[2] != Hg) or \
+                (self.per_node and y_hat.shape[3] != Ng):
+            raise ValueError(f"SeasonalConformalCalibrator.apply: y_hat must be [count, {len(self.quantiles)}, "
+                             f"{Hg if self.per_step else 'H'}, {Ng if self.per_node else 'N'}], got {tuple(y_hat.shape)}")
+        offsets = self.offsets if self.offsets.device == y_hat.device or not y_hat.is_cuda else self.offsets.to(y_hat.device)
+        return ops.seasonal_apply(y_hat, offsets, origin, self.pairs, self.season, self.per_step, self.per_node,
+                                  rearrange=rearrange, out=out)
+
+    def state_dict(self):
+        return dict(kind=self.kind, quantiles=self.quantiles, pairs=self.pairs, per_step=self.per_step, per_node=self.per_node,
+                    period=self.period, buckets=self.buckets, phase=self.phase, min_scores=self.min_scores,
+                    fallback=self.fallback, interval_nominal=torch.from_numpy(self.interval_nominal.copy()),
+                    offsets=self.offsets, counts=self.counts, offsets_seasonal=self.offsets_seasonal,
+                    pooled_offsets=self.pooled_offsets)
+
+    def load_state_dict(self, state, device=None):
+        if state.get("kind") != self.kind:
+            raise ValueError(f"SeasonalConformalCalibrator.load_state_dict: the state's kind is {state.get('kind')!r}, not "
+                             f"{self.kind!r}")
+        q = tuple(float(t) for t in state["quantiles"])
+        mine = (self.quantiles, self.per_step, self.per_node, self.period, self.buckets, self.phase)
+        saved = (q, bool(state["per_step"]), bool(state["per_node"]), int(state["period"]), int(state["buckets"]),
+                 int(state["phase"]))
+        if saved != mine:
+            raise ValueError(f"SeasonalConformalCalibrator.load_state_dict: saved for (levels, per_step, per_node, period, "
+                             f"buckets, phase) = {saved}; this one has {mine}")
+        offsets, counts = state["offsets"], state["counts"]
+        extra = [state.get("offsets_seasonal"), state.get("pooled_offsets")]
+        if offsets is not None:
+            if offsets.dim() != 4 or tuple(offsets.shape[:2]) != (self.buckets, len(self.pairs)) or \
+                    counts.shape != offsets.shape:
+                raise ValueError(f"SeasonalConformalCalibrator.load_state_dict: offsets {tuple(offsets.shape)} / counts "
+                                 f"{tuple(counts.shape)} do not fit {self.buckets} buckets of {len(self.pairs)} pairs")
+            if device is not None:
+                offsets, counts = offsets.to(device), counts.to(device)
+                extra = [None if t is None else t.to(device) for t in extra]
+            offsets, counts = offsets.float().contiguous(), counts.long().contiguous()
+            extra = [None if t is None else t.float().contiguous() for t in extra]
+        self.offsets, self.counts = offsets, counts
+        self.offsets_seasonal, self.pooled_offsets = extra
+        return self
+
+    @classmethod
+    def from_state_dict(cls, state, device=None):
+        return cls(state["quantiles"], state["period"], state["buckets"], state["phase"], state["per_step"], state["per_node"],
+                   state.get("min_scores", 0), state.get("fallback", "pooled")).load_state_dict(state, device)
+
+
 class _DeviceState:
     """The device tensors a streaming object owns: `_STATE` names them (all None until the state is made), `_TYPES` gives the
     dtypes that are not `_DTYPE`.  One definition of how they are saved, loaded and restored in place."""

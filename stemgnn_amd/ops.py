@@ -1693,6 +1693,95 @@ def conformal_apply(forecast, offsets, pairs, per_step=True, per_node=False, out
     return out
 
 
+def _season(what, season):
+    """(period, buckets, phase) as ints, refused here when it names no bucketing (so that the error names the reason)."""
+    period, K, phase = (int(v) for v in season)
+    if not (1 <= period < 2 ** 31 and 1 <= K <= period and 0 <= phase < period):
+        raise ValueError(f"{what}: season (period, buckets, phase) = {(period, K, phase)} needs 1 <= buckets <= period < 2^31 "
+                         f"and 0 <= phase < period")
+    return period, K, phase
+
+
+def _origins(what, origin, count, device):
+    """origin: an int (row i has origin + i) or an int64 tensor [count] (a host tensor is moved to the device once);
+    returns (device pointer or None, origin0, keep-alive)."""
+    if torch.is_tensor(origin):
+        if origin.dim() != 1 or origin.shape[0] != count or origin.dtype != torch.int64:
+            raise _lib.StemGNNHipError(f"{what}: origin must be an int or an int64 tensor [{count}], got {origin.dtype} "
+                                       f"{tuple(origin.shape)}")
+        origin = origin.to(device).contiguous()
+        return origin.data_ptr(), 0, origin
+    return None, int(origin), None
+
+
+def seasonal_fit(target, forecast, origin, pairs, coverage, season, per_step=True, per_node=False, ignore_nan=False):
+    """conformal_fit per time-of-day bucket (``stemgnn_seasonal_fit``): step h of row i belongs to bucket
+    ((o_i + h + phase) mod period) * K // period with o_i = origin + i (an int) or origin[i] (int64 [count]); season =
+    (period, K, phase).  Returns (offsets fp32, counts int64) [K, P, Hg, Ng]: slice s is conformal_fit over the bucket's
+    elements (+inf / 0 for an empty bucket)."""
+    lib = _lib.load()
+    _require_gpu(target, "target")
+    _require_gpu(forecast, "forecast")
+    if target.dim() != 3 or forecast.dim() != 4 or (forecast.shape[0],) + tuple(forecast.shape[2:]) != tuple(target.shape):
+        raise _lib.StemGNNHipError(f"seasonal_fit: target must be [count,H,N] and forecast [count,Q,H,N], got "
+                                   f"{tuple(target.shape)} / {tuple(forecast.shape)}")
+    if target.device != forecast.device:
+        raise _lib.StemGNNHipError(f"seasonal_fit: target is on {target.device}, forecast on {forecast.device}")
+    target, forecast = target.contiguous(), forecast.contiguous()
+    C, H, N = target.shape
+    Q = forecast.shape[1]
+    P, lo, hi = _conformal_pairs(pairs, Q)
+    if len(coverage) != P:
+        raise ValueError(f"seasonal_fit: {P} pairs but {len(coverage)} coverages")
+    period, K, phase = _season("seasonal_fit", season)
+    dev = target.device
+    optr, origin0, keep = _origins("seasonal_fit", origin, C, dev)
+    shape = (K, P, H if per_step else 1, N if per_node else 1)
+    nbytes = lib.stemgnn_seasonal_scratch_bytes(C, H, N, P, K, int(bool(per_step)), int(bool(per_node)))
+    scratch = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    offsets = torch.empty(shape, device=dev, dtype=torch.float32)
+    counts = torch.empty(shape, device=dev, dtype=torch.int64)
+    _lib.check(lib.stemgnn_seasonal_fit(target.data_ptr(), forecast.data_ptr(), optr, origin0, C, Q, H, N, P, lo, hi,
+                                        _lib.host_floats(coverage, _lib.c_double), int(bool(per_step)), int(bool(per_node)),
+                                        int(bool(ignore_nan)), period, K, phase, scratch.data_ptr(), offsets.data_ptr(),
+                                        counts.data_ptr(), _stream()), "seasonal_fit")
+    return offsets, counts
+
+
+def seasonal_apply(forecast, offsets, origin, pairs, season, per_step=True, per_node=False, rearrange=False, out=None):
+    """forecast [count,Q,H,N] with the pairs' rows of step h of row i moved by the offsets of bucket(o_i + h)
+    (``stemgnn_seasonal_apply``); offsets [K,P,Hg,Ng] of seasonal_fit, origin and season as there.  rearrange: every column's
+    Q values are first put in non-decreasing order (quantile_finish's stage a).  out: a contiguous tensor of forecast's shape,
+    or forecast itself (in place); a new tensor by default."""
+    lib = _lib.load()
+    _require_gpu(forecast, "forecast")
+    _require_gpu(offsets, "offsets")
+    if forecast.dim() != 4 or forecast.dtype != torch.float32:
+        raise _lib.StemGNNHipError(f"seasonal_apply: forecast must be float32 [count,Q,H,N], got {forecast.dtype} "
+                                   f"{tuple(forecast.shape)}")
+    C, Q, H, N = forecast.shape
+    P, lo, hi = _conformal_pairs(pairs, Q)
+    period, K, phase = _season("seasonal_apply", season)
+    shape = (K, P, H if per_step else 1, N if per_node else 1)
+    if tuple(offsets.shape) != shape or offsets.device != forecast.device or offsets.dtype != torch.float32:
+        raise _lib.StemGNNHipError(f"seasonal_apply: offsets must be float32 {shape} on {forecast.device}, got {offsets.dtype} "
+                                   f"{tuple(offsets.shape)} on {offsets.device}")
+    if out is None:
+        forecast = forecast.contiguous()
+        out = torch.empty_like(forecast)
+    else:
+        _require_gpu(out, "out")
+        if not forecast.is_contiguous() or not out.is_contiguous() or out.shape != forecast.shape or \
+                out.device != forecast.device or out.dtype != torch.float32:
+            raise _lib.StemGNNHipError("seasonal_apply: with out=, forecast and out must be contiguous float32 tensors of one "
+                                       "shape on one device")
+    optr, origin0, keep = _origins("seasonal_apply", origin, C, forecast.device)
+    _lib.check(lib.stemgnn_seasonal_apply(forecast.data_ptr(), offsets.contiguous().data_ptr(), optr, origin0, C, Q, H, N,
+                                          int(bool(rearrange)), P, lo, hi, int(bool(per_step)), int(bool(per_node)), period, K,
+                                          phase, out.data_ptr(), _stream()), "seasonal_apply")
+    return out
+
+
 def _finish_stages(what, forecast, offsets, pairs, per_step, per_node):
     """The calibration stage's arguments of quantile_finish / quantile_store, checked as conformal_apply checks them; returns
     (offsets pointer or None, P, lo, hi, keep-alive)."""
@@ -1738,29 +1827,59 @@ def quantile_finish(forecast, rearrange=False, offsets=None, pairs=None, per_ste
     return out
 
 
+def _store_shapes(what, steps, target, pos, out_forecast, out_target):
+    _require_gpu(steps, "steps")
+    if steps.dim() != 4:
+        raise _lib.StemGNNHipError(f"{what}: steps must be [B,Q,H,N], got {tuple(steps.shape)}")
+    B, Q, H, N = steps.shape
+    if tuple(target.shape) != (B, H, N) or tuple(out_forecast.shape[1:]) != (Q, H, N) or out_forecast.dim() != 4 or \
+            tuple(out_target.shape) != (out_forecast.shape[0], H, N):
+        raise _lib.StemGNNHipError(f"{what}: shape mismatch")
+    for t, name in ((steps, "steps"), (target, "target"), (out_forecast, "out_forecast"), (out_target, "out_target")):
+        if t.device != steps.device or t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.StemGNNHipError(f"{what}: {name} must be a contiguous float32 tensor on the steps' device")
+    if pos.dtype != torch.int64 or pos.device != steps.device:
+        raise _lib.StemGNNHipError(f"{what}: pos must be an int64 tensor on the steps' device")
+    return B, Q, H, N
+
+
 def quantile_store(steps, target, pos, out_forecast, out_target, rearrange=False, offsets=None, pairs=None, per_step=True,
                    per_node=False):
     """Result slabs of engine.QuantileForecastStep (``stemgnn_quantile_store``): out_forecast[pos + b] = the finished steps[b]
     (quantile_finish's two stages) and out_target[pos + b] = target[b], with the row position read on the device (pos: int64[1]);
     rows at or beyond the slabs' capacity are dropped.  steps [B,Q,H,N], target [B,H,N], slabs [capacity,Q,H,N] / [capacity,H,N]."""
     lib = _lib.load()
-    _require_gpu(steps, "steps")
-    if steps.dim() != 4:
-        raise _lib.StemGNNHipError(f"quantile_store: steps must be [B,Q,H,N], got {tuple(steps.shape)}")
-    B, Q, H, N = steps.shape
-    if tuple(target.shape) != (B, H, N) or tuple(out_forecast.shape[1:]) != (Q, H, N) or out_forecast.dim() != 4 or \
-            tuple(out_target.shape) != (out_forecast.shape[0], H, N):
-        raise _lib.StemGNNHipError("quantile_store: shape mismatch")
-    for t, name in ((steps, "steps"), (target, "target"), (out_forecast, "out_forecast"), (out_target, "out_target")):
-        if t.device != steps.device or t.dtype != torch.float32 or not t.is_contiguous():
-            raise _lib.StemGNNHipError(f"quantile_store: {name} must be a contiguous float32 tensor on the steps' device")
-    if pos.dtype != torch.int64 or pos.device != steps.device:
-        raise _lib.StemGNNHipError("quantile_store: pos must be an int64 tensor on the steps' device")
+    B, Q, H, N = _store_shapes("quantile_store", steps, target, pos, out_forecast, out_target)
     optr, P, lo, hi, keep = _finish_stages("quantile_store", steps, offsets, pairs, per_step, per_node)
     _lib.check(lib.stemgnn_quantile_store(steps.data_ptr(), target.data_ptr(), pos.data_ptr(), B, Q, H, N,
                                           int(bool(rearrange)), optr, P, lo, hi, int(bool(per_step)), int(bool(per_node)),
                                           out_forecast.data_ptr(), out_target.data_ptr(), out_forecast.shape[0], _stream()),
                "quantile_store")
+
+
+def quantile_store_seasonal(steps, target, pos, out_forecast, out_target, rearrange=False, offsets=None, pairs=None,
+                            per_step=True, per_node=False, seasonal=None, t_dev=None):
+    """quantile_store with the offsets of a seasonal calibrator (``stemgnn_quantile_store_seasonal``): offsets are the [K,P,Hg,Ng]
+    tables of seasonal_fit, seasonal = (period, K, phase), t_dev int64[1] on the device; batch row b has origin t_dev[0] + b and
+    its step h is widened with the tables' slice bucket(t_dev[0] + b + h), worked out on the device."""
+    lib = _lib.load()
+    B, Q, H, N = _store_shapes("quantile_store_seasonal", steps, target, pos, out_forecast, out_target)
+    if seasonal is None or offsets is None or pairs is None:
+        raise ValueError("quantile_store_seasonal: needs seasonal= (period, K, phase), offsets= (the [K,P,Hg,Ng] tables) and pairs=")
+    period, K, phase = _season("quantile_store_seasonal", seasonal)
+    if t_dev is None or t_dev.dtype != torch.int64 or t_dev.device != steps.device or t_dev.numel() < 1:
+        raise _lib.StemGNNHipError("quantile_store_seasonal: t_dev must be an int64 tensor on the steps' device")
+    P, lo, hi = _conformal_pairs(pairs, Q)
+    shape = (K, P, H if per_step else 1, N if per_node else 1)
+    if tuple(offsets.shape) != shape or offsets.device != steps.device or offsets.dtype != torch.float32 or \
+            not offsets.is_contiguous():
+        raise _lib.StemGNNHipError(f"quantile_store_seasonal: offsets must be contiguous float32 {shape} on {steps.device}, "
+                                   f"got {offsets.dtype} {tuple(offsets.shape)} on {offsets.device}")
+    _lib.check(lib.stemgnn_quantile_store_seasonal(steps.data_ptr(), target.data_ptr(), pos.data_ptr(), t_dev.data_ptr(),
+                                                   B, Q, H, N, int(bool(rearrange)), offsets.data_ptr(), P, lo, hi,
+                                                   int(bool(per_step)), int(bool(per_node)), period, K, phase,
+                                                   out_forecast.data_ptr(), out_target.data_ptr(), out_forecast.shape[0],
+                                                   _stream()), "quantile_store_seasonal")
 
 
 def _ring_ok(what, ring, t_dev):

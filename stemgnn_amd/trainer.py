@@ -144,7 +144,7 @@ def rolling_quantile_forecast_graph(model, dataset, horizon, batch_size, adjacen
 
 
 def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=None, ignore_nan=False, quantiles=None,
-                   calibrator=None):
+                   calibrator=None, origin=None):
     """Metrics of a rolling forecast in raw units (and normalised units under ``*_norm``).  With `dump_dir`, the first
     forecast step of every window is written as CSV (target / predict / absolute error / absolute percentage error).
     ignore_nan: NaN targets (missing readings) are left out of every metric; the CSV files keep them as NaN.
@@ -154,7 +154,13 @@ def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=
     ``interval_width`` / ``interval_nominal`` [Q // 2] for the pairs (i, Q-1-i), and ``crossing``.
     calibrator (a fitted math_utils.ConformalCalibrator): the bands are calibrated, in the forecast's normalised units, ahead of
     those figures, and the uncalibrated ones are kept under ``interval_coverage_raw`` / ``interval_width_raw``; the point row and
-    every point metric are untouched."""
+    every point metric are untouched.  A math_utils.SeasonalConformalCalibrator also needs `origin`, the time index of every
+    window's step-0 target (an int: window i has origin + i; or an int64 tensor [count])."""
+    seasonal = getattr(calibrator, "kind", None) == "seasonal"
+    if seasonal and origin is None:
+        raise ValueError("score_forecast: a seasonal calibrator needs origin= (the time index of every window's first target)")
+    if origin is not None and not seasonal:
+        raise ValueError("score_forecast: origin= goes with a seasonal calibrator")
     mul = add = None
     if norm_method and statistic:
         mul, add = denorm_coefficients(norm_method, statistic, forecast.device)
@@ -170,7 +176,7 @@ def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=
             qs = QuantileScores(target, forecast, quantiles, mul, add, ignore_nan=ignore_nan)
             raw_bands = dict(interval_coverage_raw=qs.interval_coverage, interval_width_raw=qs.interval_width)
             point_row = forecast[:, point_index(quantiles)].contiguous()
-            forecast = calibrator.apply(forecast)
+            forecast = calibrator.apply(forecast, origin) if seasonal else calibrator.apply(forecast)
         qs = QuantileScores(target, forecast, quantiles, mul, add, ignore_nan=ignore_nan)
         calibration = dict(pinball=float(qs.pinball.mean()), pinball_q=qs.pinball, coverage_q=qs.coverage,
                            interval_coverage=qs.interval_coverage, interval_width=qs.interval_width,
