@@ -908,6 +908,46 @@ int stemgnn_anomaly_update(const float* slab, int S, int R, int lo_row, int hi_r
                            long long* counts, long long* alarm_sum, long long* judged_sum, float* log_p, int keep, int log_slot,
                            unsigned int* work, void* stream);
 
+/* ---- scenario forecasts: sampled rolling paths and their order statistics (csrc/scenario.hip) --------
+ * roll:  one round of a roll that feeds SAMPLED rows back instead of the point row, for Bo origins x S paths.  inputs
+ *        [Bsrc, W, N], forecast [Bsrc, Q, L, N], fp32 and contiguous; taus = the Q levels as fp32 in HOST memory, read by the call
+ *        itself and passed on by value.  Path p = b * S + s reads source row p / fan: fan == S is round 0 (Bsrc == Bo, the model
+ *        ran once per origin), fan == 1 a later round (Bsrc == Bo * S).  For every path, step j < L and node n:
+ *          1. v_(0) <= .. <= v_(Q-1): the column forecast[src, :, j, n] in the order of stemgnn_quantile_finish's rearrange
+ *             (-0 == +0, NaN last, ties in row order; a selection, bit patterns kept).
+ *          2. u = ((w >> 9) + 0.5f) * 2^-23, exact in fp32 and strictly inside (0, 1); w is a Philox4x32-10 word under key
+ *             seed with `offset` as the counter's high 64 bits.  coupling == SG_SCENARIO_INDEPENDENT: word n & 3 of counter
+ *             ((((origin0 + b) * S + s) * horizon + (step + j)) * ceil(N / 4) + (n >> 2)) (64-bit, wrapping).
+ *             SG_SCENARIO_PATH: word 0 of the counter of (j = 0, n = 0), for every j and n of the round.
+ *          3. i = the largest index in [0, Q - 2] with taus[i] <= u, 0 when there is none.
+ *          4. wt = (u - taus[i]) / (taus[i + 1] - taus[i]), two fp32 subtractions and one correctly rounded division;
+ *             tails == SG_SCENARIO_CLAMP clamps wt to [0, 1], SG_SCENARIO_LINEAR extends the outermost segments.
+ *          5. y = v_(i) + (v_(i+1) - v_(i)) * wt, the subtraction, the product and the sum rounded separately (no FMA).
+ *        NaN and infinite values follow from this arithmetic.  Outputs: paths[b, s, step + j, n] = y for j < min(L, horizon -
+ *        step) (paths [Bo, S, horizon, N]); inputs_next [Bo * S, W, N] (may be NULL: the last round) = the window of
+ *        stemgnn_roll_window with y where that takes the forecast row; bands [Bo, Q, horizon, N] (round 0 only, else NULL):
+ *        bands[b, :, step + j, n] = the model's own column, unsorted, bit for bit.
+ * bands: bands[b, q, h, n] = the ranks[q]-th smallest (1-based) of the S values paths[b, :, h, n] in the same order, for every
+ *        h >= step_from; the steps below step_from are not written.  ranks = Q ints in HOST memory, passed on by value.
+ * rank:  k = min(S, max(1, ceil((tau * S) * (1 - 1e-12)))) in fp64 -- two multiplies and a ceil -- on the host.
+ * One launch each, no scratch, no atomics, no allocation, no host synchronisation.  roll uses 16-byte accesses when N % 4 == 0
+ * and every buffer is 16-byte aligned, a scalar path otherwise.
+ * SG_EINVAL (nothing launched): a NULL pointer other than inputs_next / bands of roll; Bo, W, L, N <= 0, L > W, step outside
+ * [0, horizon), inputs_next == inputs; Q < 2 or Q > 32 (bands: Q < 1); levels not strictly increasing inside (0, 1); S outside
+ * [1, 1024]; fan not in {1, S}; bands with fan != S; an unknown coupling / tails; Bo * S, W * N, Q * L * N, Q * horizon * N or
+ * S * horizon >= 2^31; bands: step_from outside [0, horizon], a rank outside [1, S], horizon * N >= 2^31. */
+#define SG_SCENARIO_INDEPENDENT 0
+#define SG_SCENARIO_PATH 1
+#define SG_SCENARIO_LINEAR 0
+#define SG_SCENARIO_CLAMP 1
+long stemgnn_scenario_rank(double tau, long S);
+int stemgnn_scenario_roll(const float* inputs, const float* forecast, const float* taus, int Bo, int S, int fan, int W, int L,
+                          int N, int Q, int step, int horizon, long long origin0, unsigned long long seed,
+                          unsigned long long offset, int coupling, int tails, float* inputs_next, float* paths, float* bands,
+                          void* stream);
+int stemgnn_scenario_bands(const float* paths, int Bo, int S, int horizon, int N, int Q, const int* ranks, int step_from,
+                           float* bands, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,13 +4,15 @@ Fails loudly: a missing / unloadable library raises at first use -- there is no 
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_long, c_longlong, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_long, c_longlong, c_size_t, c_ulonglong, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STEMGNN_HIP_LIB", os.path.join(_HERE, "libstemgnn_hip.so"))   # override: A/B builds only
 SG_BLOCK_NPARAMS = 33
 SG_EINVAL = -10001
 SG_LOSS = {"mse": 0, "mae": 1, "huber": 2}    # SG_LOSS_* in include/stemgnn_hip.h
+SG_SCENARIO_COUPLING = {"independent": 0, "path": 1}    # SG_SCENARIO_* in include/stemgnn_hip.h
+SG_SCENARIO_TAILS = {"linear": 0, "clamp": 1}
 SG_LOSS_PINBALL = 3                           # the quantile head's loss: its own `_quantile` entries, not a `_loss` kind
 # bits of stemgnn_block_paths (SG_PATH_* in include/stemgnn_hip.h)
 SG_PATH = {"glu_fwd_fused": 1, "glu_dgrad_fused": 2, "heads_fwd_fused": 4, "heads_bwd_fused": 8, "heads_bwd_16w": 16,
@@ -209,6 +211,10 @@ SIGNATURES = {
     "stemgnn_anomaly_update": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_longlong, _P, c_int, c_int, c_int, c_int, c_int,
                                        c_longlong, c_double, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P,
                                        _P]),
+    "stemgnn_scenario_rank": (c_long, [c_double, c_long]),
+    "stemgnn_scenario_roll": (c_int, [_P, _P, POINTER(c_float), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      c_longlong, c_ulonglong, c_ulonglong, c_int, c_int, _P, _P, _P, _P]),
+    "stemgnn_scenario_bands": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), c_int, _P, _P]),
     "stemgnn_infer_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
     "stemgnn_infer_workspace_split_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "stemgnn_gru_fwd_infer": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),

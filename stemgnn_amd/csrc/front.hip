@@ -15,6 +15,7 @@
 #include "gemm_core.h"
 #include "gemm_phased.h"
 #include "layout.h"
+#include "philox.h"
 #include "sg_host.h"
 
 constexpr size_t SG_ATTN_FWD_LDS_BYTES = 64 * 1024;   // dynamic LDS of sg_attention_fwd_kernel: (ceil(B / min(B, 8)) + 4 N) floats
@@ -25,18 +26,6 @@ constexpr int ATTN_NBC = 8;     // batch chunks of the attention forward (more w
 // step).  Element (row r = b N + i, column j) takes word (j >> 6) & 3 of counter r * NQ + (j >> 8) * 64 + (j & 63), NQ = 64 *
 // ceil(N / 256): the four columns j, j + 64, j + 128, j + 192 a lane of the attention kernels walks share one call.  The
 // forward, the backward and the mask export (stemgnn_dropout_mask, what the parity tests hand to the oracle) use this one map.
-__device__ __forceinline__ void sg_philox4(uint64_t seed, uint64_t offset, uint64_t idx, uint32_t (&w)[4]) {
-  uint32_t c0 = (uint32_t)idx, c1 = (uint32_t)(idx >> 32), c2 = (uint32_t)offset, c3 = (uint32_t)(offset >> 32);
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
-}
 __device__ __forceinline__ int sg_drop_nq(int N) { return 64 * ((N + 255) >> 8); }
 __device__ __forceinline__ bool sg_keep_word(uint32_t w, float p) { return (float)w * 2.3283064365386963e-10f >= p; }
 

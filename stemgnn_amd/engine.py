@@ -942,6 +942,26 @@ class QuantileForecastStep(ForecastStep):
         self.out_target[p:p + steps.shape[0]].copy_(y)
 
 
+def scenario_rounds(model, window, horizon, paths, origin0, seed, coupling, tails, graph_kw):
+    """The rounds of one batch of rolling_scenarios (LiveForecaster.scenarios runs the same on its head window):
+    window [Bo,W,N] -> (bands [Bo,Q,horizon,N], paths [Bo,S,horizon,N])."""
+    quantiles = model.quantiles
+    Bo, _, N = window.shape
+    steps = torch.empty(Bo, paths, horizon, N, device=window.device)
+    bands = torch.empty(Bo, len(quantiles), horizon, N, device=window.device)
+    done, L = 0, None
+    while done < horizon:
+        out, _ = model.predict(window, **graph_kw)
+        if out.shape[-2] == 0:
+            raise Exception("Get blank inference result")
+        L = out.shape[-2] if L is None else L
+        window = ops.scenario_roll(window, out, quantiles, steps, done, origin0=origin0, seed=seed, coupling=coupling,
+                                   tails=tails, bands=bands if done == 0 else None, last=done + out.shape[-2] >= horizon)
+        done += min(horizon - done, out.shape[-2])
+    ops.scenario_bands(steps, quantiles, min(L, horizon), bands)
+    return bands, steps
+
+
 class LiveForecaster:
     """Forecasting from a stream: raw sensor rows go into a device-side ring as they arrive (``push``), and ``forecast`` is the
     rolling forecast of the window that ends NOW, as one replayed hipGraph.  The counterpart of ForecastStep /
@@ -997,7 +1017,10 @@ class LiveForecaster:
 
     set_anomaly(detector): conformal anomaly p-values of every arriving reading (math_utils.ConformalAnomaly; None switches it
     off).  push() then judges each new row against the forecasts of it that the slab holds; anomalies() returns the last judged
-    row's (node_p, alarm, row).  The forecast path, the captured graph and every existing signature are untouched."""
+    row's (node_p, alarm, row).  The forecast path, the captured graph and every existing signature are untouched.
+
+    scenarios(paths=64, ...): sampled rolling paths from the same head window and their bands (trainer.rolling_scenarios' rounds,
+    run eagerly beside the replayed forecast; uncalibrated; ``self.seed`` is the Philox key)."""
 
     def __init__(self, model, window, horizon, *, normalize_method=None, norm_statistic=None, missing=None, fill=None,
                  history=64, adjacency=None, rearrange=False, calibrator=None, graph=True, device=None):
@@ -1048,6 +1071,7 @@ class LiveForecaster:
         self._ready_buffers = False
         self._replay = None
         self._armed = False
+        self.seed = 0                                   # the Philox key of scenarios() (an attribute: set it to choose another)
 
     # -- checks that need no device -----------------------------------------------------------------------------
     def _check_bands(self, who, what, obj):
@@ -1234,6 +1258,29 @@ class LiveForecaster:
         if denormalize and self._mul is not None:
             return f.double() * self._mul + self._add
         return f.double() if denormalize else f
+
+    def scenarios(self, paths=64, horizon=None, seed=None, coupling="independent", tails="linear", return_paths=False):
+        """Sampled rolling paths from the window that ends at the last row pushed: trainer.rolling_scenarios' rounds, run
+        eagerly on the ring's head window with the forecaster's own `adjacency` -- one predict on the window, the later rounds
+        at batch `paths`.  Returns bands [Q,horizon,N] (the model's own rows for its first steps, order statistics of the paths
+        beyond them), and paths [S,horizon,N] as well with return_paths, in normalised units.  horizon: None takes the
+        forecaster's.  The origin index of the draws is the number of rows pushed; seed: None takes ``self.seed`` (0 unless
+        set).  The bands are UNCALIBRATED: neither `rearrange` nor the calibrator, the adaptive offsets or the anomaly detector
+        act on them, and the captured graph, the history slab and every calibrator are left untouched."""
+        if self.quantiles is None or self.Q < 2:
+            raise ValueError("LiveForecaster.scenarios needs a quantile model with at least two levels (Model(..., "
+                             "quantiles=...)): a point model has no quantile function to draw from")
+        horizon = self.horizon if horizon is None else int(horizon)
+        if horizon < 1 or not 1 <= int(paths) <= 1024:
+            raise ValueError(f"LiveForecaster.scenarios: horizon must be at least 1 and paths within [1, 1024], got {horizon}, "
+                             f"{paths}")
+        if not self.ready:
+            raise RuntimeError(f"LiveForecaster.scenarios: {self.rows} rows pushed, a window needs {self.W}")
+        with torch.no_grad():
+            window = ops.ring_gather(self.ring_x, self.t_dev, self.W, back=self.W)
+            bands, steps = scenario_rounds(self.model, window, horizon, int(paths), self.rows,
+                                           self.seed if seed is None else seed, coupling, tails, self.graph_kw)
+        return (bands[0], steps[0]) if return_paths else bands[0]
 
     # -- matured pairs ------------------------------------------------------------------------------------------
     def matured(self):

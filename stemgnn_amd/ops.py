@@ -6,6 +6,7 @@ autograd graph; every number on the hot path is produced by libstemgnn_hip.so.
 Stage order (reference models/base_model.py): attention+Laplacian (:139-147) -> Chebyshev (:148)
 -> per StockBlock: pack, GFT (:62-64), spectral GLU (:46-54), IGFT+heads (:55-58, :65-74).
 """
+import ctypes
 import os
 import weakref
 
@@ -1880,6 +1881,86 @@ def quantile_store_seasonal(steps, target, pos, out_forecast, out_target, rearra
                                                    int(bool(per_step)), int(bool(per_node)), period, K, phase,
                                                    out_forecast.data_ptr(), out_target.data_ptr(), out_forecast.shape[0],
                                                    _stream()), "quantile_store_seasonal")
+
+
+def scenario_rank(tau, S):
+    """The 1-based rank of level `tau` among S path values (``stemgnn_scenario_rank``):
+    min(S, max(1, ceil(tau * S * (1 - 1e-12)))) in fp64."""
+    return int(_lib.load().stemgnn_scenario_rank(float(tau), int(S)))
+
+
+def scenario_roll(inputs, forecast, quantiles, paths, step, origin0=0, seed=0, offset=0, coupling="independent",
+                  tails="linear", bands=None, last=False):
+    """One round of a sampled roll (``stemgnn_scenario_roll``): every path draws its next window rows from the quantile
+    function through (quantiles, forecast column) -- the definition in include/stemgnn_hip.h -- instead of taking the point row.
+    inputs [Bsrc,W,N], forecast [Bsrc,Q,L,N], paths [Bo,S,horizon,N] (rows step .. step + L - 1 are written).  Bsrc == Bo is
+    round 0 (fan = S: every path of an origin reads the origin's one forecast) and takes bands [Bo,Q,horizon,N], which receives
+    the model's own rows of those steps; Bsrc == Bo * S is a later round (fan = 1, no bands).  origin0: the global index of
+    the batch's first origin; seed / offset: the Philox key and the counter's high words.  Returns the next inputs
+    [Bo * S,W,N], or None with last=True (the round whose windows nobody reads)."""
+    lib = _lib.load()
+    _require_gpu(inputs, "inputs")
+    _require_gpu(forecast, "forecast")
+    _require_gpu(paths, "paths")
+    if inputs.dim() != 3 or forecast.dim() != 4 or paths.dim() != 4:
+        raise _lib.StemGNNHipError(f"scenario_roll: inputs [Bsrc,W,N], forecast [Bsrc,Q,L,N] and paths [Bo,S,horizon,N] wanted, "
+                                   f"got {tuple(inputs.shape)}, {tuple(forecast.shape)}, {tuple(paths.shape)}")
+    Bsrc, W, N = inputs.shape
+    Q, L = forecast.shape[1], forecast.shape[2]
+    Bo, S, horizon = paths.shape[:3]
+    if L == 0:
+        raise Exception("Get blank inference result")                    # handler.py:54-55
+    if forecast.shape[0] != Bsrc or forecast.shape[3] != N or paths.shape[3] != N or len(quantiles) != Q:
+        raise _lib.StemGNNHipError(f"scenario_roll: shape mismatch: inputs {tuple(inputs.shape)}, forecast "
+                                   f"{tuple(forecast.shape)}, paths {tuple(paths.shape)}, {len(quantiles)} levels")
+    if Bsrc == Bo * S and (S > 1 or bands is None):
+        fan = 1
+    elif Bsrc == Bo:
+        fan = S
+    else:
+        raise _lib.StemGNNHipError(f"scenario_roll: {Bsrc} source windows fit neither {Bo} origins nor {Bo} x {S} paths")
+    for t, name in ((inputs, "inputs"), (forecast, "forecast"), (paths, "paths")) + (() if bands is None else ((bands, "bands"),)):
+        if t.device != inputs.device or t.dtype != torch.float32:
+            raise _lib.StemGNNHipError(f"scenario_roll: {name} must be a float32 tensor on the inputs' device")
+    if not paths.is_contiguous():
+        raise _lib.StemGNNHipError("scenario_roll: paths must be contiguous")
+    if bands is not None and (tuple(bands.shape) != (Bo, Q, horizon, N) or not bands.is_contiguous()):
+        raise _lib.StemGNNHipError(f"scenario_roll: bands must be a contiguous [Bo,Q,horizon,N] tensor, got {tuple(bands.shape)}")
+    if coupling not in _lib.SG_SCENARIO_COUPLING or tails not in _lib.SG_SCENARIO_TAILS:
+        raise ValueError(f"scenario_roll: coupling is one of {tuple(_lib.SG_SCENARIO_COUPLING)}, tails one of "
+                         f"{tuple(_lib.SG_SCENARIO_TAILS)}, got {coupling!r}, {tails!r}")
+    inputs, forecast = inputs.contiguous(), forecast.contiguous()
+    nxt = None if last else torch.empty(Bo * S, W, N, device=inputs.device, dtype=torch.float32)
+    mask = (1 << 64) - 1
+    _lib.check(lib.stemgnn_scenario_roll(inputs.data_ptr(), forecast.data_ptr(), _lib.host_floats(quantiles), Bo, S, fan, W, L,
+                                         N, Q, int(step), horizon, int(origin0), int(seed) & mask, int(offset) & mask,
+                                         _lib.SG_SCENARIO_COUPLING[coupling], _lib.SG_SCENARIO_TAILS[tails],
+                                         None if nxt is None else nxt.data_ptr(), paths.data_ptr(),
+                                         None if bands is None else bands.data_ptr(), _stream()), "scenario_roll")
+    return nxt
+
+
+def scenario_bands(paths, quantiles, step_from, bands):
+    """The bands of sampled paths (``stemgnn_scenario_bands``): bands[b, q, h, n] = the scenario_rank(quantiles[q], S)-th
+    smallest of paths[b, :, h, n] for every step h >= step_from (NaN last: a selection, bit patterns kept); the steps below
+    step_from are left as they are.  paths [Bo,S,horizon,N], bands [Bo,Q,horizon,N], contiguous float32; returns bands."""
+    lib = _lib.load()
+    _require_gpu(paths, "paths")
+    _require_gpu(bands, "bands")
+    if paths.dim() != 4 or bands.dim() != 4:
+        raise _lib.StemGNNHipError(f"scenario_bands: paths [Bo,S,horizon,N] and bands [Bo,Q,horizon,N] wanted, got "
+                                   f"{tuple(paths.shape)}, {tuple(bands.shape)}")
+    Bo, S, horizon, N = paths.shape
+    Q = len(quantiles)
+    if tuple(bands.shape) != (Bo, Q, horizon, N):
+        raise _lib.StemGNNHipError(f"scenario_bands: bands must be {(Bo, Q, horizon, N)}, got {tuple(bands.shape)}")
+    for t, name in ((paths, "paths"), (bands, "bands")):
+        if t.device != paths.device or t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.StemGNNHipError(f"scenario_bands: {name} must be a contiguous float32 tensor on the paths' device")
+    ranks = (ctypes.c_int * Q)(*[scenario_rank(t, S) for t in quantiles])
+    _lib.check(lib.stemgnn_scenario_bands(paths.data_ptr(), Bo, S, horizon, N, Q, ranks, int(step_from), bands.data_ptr(),
+                                          _stream()), "scenario_bands")
+    return bands
 
 
 def _ring_ok(what, ring, t_dev):

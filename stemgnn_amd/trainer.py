@@ -26,7 +26,7 @@ import torch
 
 from . import ops
 from .base_model import Model, check_quantiles, point_index
-from .engine import ForecastStep, QuantileForecastStep, TrainStep
+from .engine import ForecastStep, QuantileForecastStep, TrainStep, scenario_rounds
 from .forecast_dataloader import ForecastDataset, WindowLoader, denorm_coefficients, mark_missing
 from .math_utils import ConformalCalibrator, QuantileScores, Scores
 from .optim import FusedAdam, FusedRMSprop
@@ -78,7 +78,8 @@ def rolling_forecast(model, loader, horizon, adjacency=None):
     A quantile model (``model.quantiles``): the POINT row (``model.point_index``) is what is fed back as the next window, and the
     forecast comes back as [count, Q, horizon, N] (``ops.roll_window_quantile``).  With `horizon` beyond the model's own, the
     bands of the later rounds are therefore conditional on the point path: they describe the spread around a forecast made
-    from the model's own median-like outputs, not the wider uncertainty of the inputs those rounds never saw."""
+    from the model's own median-like outputs, not the wider uncertainty of the inputs those rounds never saw
+    (rolling_scenarios rolls sampled paths and reads those bands off them)."""
     quantiles = getattr(model, "quantiles", None)
     was_training = model.training
     model.eval()
@@ -103,6 +104,57 @@ def rolling_forecast(model, loader, horizon, adjacency=None):
             targets.append(target)
     model.train(was_training)
     return torch.cat(forecasts), torch.cat(targets)
+
+
+def _check_scenarios(who, model, horizon, paths):
+    quantiles = getattr(model, "quantiles", None)
+    if quantiles is None or len(quantiles) < 2:
+        raise ValueError(f"{who} needs a quantile model with at least two levels (Model(..., quantiles=...)): a point "
+                         "model has no quantile function to draw from")
+    if int(horizon) < 1 or not 1 <= int(paths) <= 1024:
+        raise ValueError(f"{who}: horizon must be at least 1 and paths within [1, 1024], got {horizon}, {paths}")
+
+
+def rolling_scenarios(model, loader, horizon, paths=64, seed=0, adjacency=None, coupling="independent", tails="linear",
+                      return_paths=False, origin=0):
+    """Multi-step forecast of every window the loader yields from SAMPLED trajectories: where rolling_forecast feeds the point
+    row back, each of `paths` trajectories per window draws its next rows from the predicted quantile function (the piecewise-
+    linear one through the model's levels and rearranged rows: ops.scenario_roll) and the model runs on all of them as one
+    batch.  The bands of the first round (the model's own horizon L) are the model's rows, rolling_forecast's bit for bit;
+    the bands of the later steps are order statistics of the paths (ops.scenario_bands), so they carry the uncertainty of
+    the inputs those rounds never saw.
+    Per loader batch of Bo windows: one predict on the windows, then ceil(horizon / L) - 1 predicts at batch Bo * paths.
+    coupling: "independent" draws every (step, node) on its own, "path" moves all nodes of a path and round with one uniform;
+    the two bracket the real dependence between nodes.  tails: "linear" extends the outermost segments of the quantile
+    function beyond the outer levels, "clamp" stops at them.  seed: the Philox key; origin: the global index of the loader's
+    first window.  The origin index runs on over the batches, so a window's draws do not depend on how the loader batches it;
+    with adjacency= (as in rolling_forecast) nor does anything else.  Without adjacency= the latent graph of a round is the
+    mean over all paths of the batch.
+    Returns (bands [count, Q, horizon, N], target [count, horizon, N]) and, with return_paths, paths [count, S, horizon, N],
+    float32 device tensors in the forecast's normalised units: ConformalCalibrator.fit and QuantileScores take them as they are.
+    A calibrator fitted on point-path bands (rolling_forecast's) is not valid for these bands.  The model's training state is
+    restored on exit."""
+    _check_scenarios("rolling_scenarios", model, horizon, paths)
+    horizon, paths = int(horizon), int(paths)
+    graph_kw = {} if adjacency is None else dict(adjacency=adjacency)
+    was_training = getattr(model, "training", False)
+    model.eval()
+    bands, targets, trajectories = [], [], []
+    count = int(origin)
+    try:
+        with torch.no_grad():
+            for window, target in loader:
+                b, p = scenario_rounds(model, window, horizon, paths, count, seed, coupling, tails, graph_kw)
+                count += window.shape[0]
+                bands.append(b)
+                targets.append(target)
+                if return_paths:
+                    trajectories.append(p)
+    finally:
+        model.train(was_training)
+    if return_paths:
+        return torch.cat(bands), torch.cat(targets), torch.cat(trajectories)
+    return torch.cat(bands), torch.cat(targets)
 
 
 def rolling_forecast_graph(model, dataset, horizon, batch_size, adjacency=None):
