@@ -948,6 +948,40 @@ int stemgnn_scenario_roll(const float* inputs, const float* forecast, const floa
 int stemgnn_scenario_bands(const float* paths, int Bo, int S, int horizon, int N, int Q, const int* ranks, int step_from,
                            float* bands, void* stream);
 
+/* ---- ensemble scores of scenario paths: CRPS, energy score, rank histogram (csrc/ensemble.hip) --------
+ * target [count, H, N] and paths [count, S, H, N] (stemgnn_scenario_roll's layout), fp32 and contiguous, 1 <= S <= 1024; optional
+ * de-normalisation v * mul[n] + add[n] in fp64 ahead of everything else, as in stemgnn_eval_metrics (mul > 0 is the caller's
+ * contract).  All arithmetic is fp64 from the fp32 inputs.  D = S^2, or S (S - 1) with fair != 0 (the estimator that is unbiased
+ * in S; needs S >= 2).
+ * Per element (c, h, n), with x_s = paths[c, s, h, n] and y = target[c, h, n]:
+ *   crps = (1 / S) sum_s |x_s - y| - (1 / (2 D)) sum_s sum_s' |x_s - x_s'|
+ *   mean = (1 / S) sum_s x_s;  se = (mean - y)^2;  var = sum_s (x_s - mean)^2 / (S - 1), NaN when S == 1
+ *   rank = #{s : x_s < y} + #{s : x_s == y} / 2 (integer division), compared on the raw fp32 values (-0 == +0; a NaN path
+ *          value is in neither set), so 0 <= rank <= S.
+ * Per row (c, h), over its node set V (every n; `_masked`: those whose target is not NaN):
+ *   energy = (1 / S) sum_s ||x_s - y|| - (1 / (2 D)) sum_s sum_s' ||x_s - x_s'||, Euclidean norms over n in V of the
+ *            de-normalised values; a pair distance is sqrt(sum_n (x_sn - x_s'n)^2), formed from the differences.
+ * out (fp64) = overall[6] | by_step[6][H]:
+ *   0 mean crps over the valid elements     1 mean energy over the valid rows
+ *   2 sqrt(mean se), the RMSE of the ensemble mean     3 sqrt(mean var), the spread ([3] / [2] near 1: spread matches skill)
+ *   4 the number of valid elements          5 the number of valid rows
+ * hist (int64 [H][S + 1]) = the count of every rank per step over the valid elements; the call zeroes it itself.
+ * Plain entry: every element and row is valid; a NaN target makes the statistics of its slices NaN and is left out of hist (it
+ * has no rank).  `_masked`: a NaN target is missing: left out of [0], [2], [3], [4], hist and the V of its row; a row with empty
+ * V is left out of [1] and [5]; a slice with nothing valid is NaN in [0..3].  Both: a NaN path value on a valid target
+ * propagates.
+ * Fixed-order two-level fp64 sums; integer atomics for hist only, no floating-point atomics: the same bits on every run.  No
+ * allocation, no host synchronisation, three launches.  scratch: stemgnn_ensemble_scratch_doubles doubles on the device.
+ * SG_EINVAL (nothing launched) on a NULL pointer other than mul / add, mul without add, count, S, H or N <= 0, S > 1024, fair
+ * with S < 2, or one of the kernels' int products >= 2^31: the two grids count * H * ceil(N / C) (C the node tile, 4 .. 64) and
+ * count * H * T (T + 1) / 2 (T = ceil(S / 32)), H * (S + 1), S * H * N; the size entries return 0 for such shapes. */
+size_t stemgnn_ensemble_scratch_doubles(long count, int S, int H, int N);
+size_t stemgnn_ensemble_out_doubles(int H);
+int stemgnn_ensemble_scores(const float* target, const float* paths, const double* mul, const double* add, long count, int S,
+                            int H, int N, int fair, double* scratch, double* out, long long* hist, void* stream);
+int stemgnn_ensemble_scores_masked(const float* target, const float* paths, const double* mul, const double* add, long count,
+                                   int S, int H, int N, int fair, double* scratch, double* out, long long* hist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,42 @@ class QuantileScores:
             setattr(self, "crossing" + suffix, m[2 * Q + 2 * P].copy() if suffix else np.float64(m[2 * Q + 2 * P]))
 
 
+class EnsembleScores:
+    """Proper scores of sampled paths from one call (`stemgnn_ensemble_scores`): y [count, H, N] ground truth, paths
+    [count, S, H, N] (`trainer.rolling_scenarios(..., return_paths=True)`).  Attributes (numpy; `*_step` = the same per horizon
+    step [H]):
+      crps     mean continuous ranked probability score over the elements: marginal, per (step, node)
+      energy   mean energy score over the (origin, step) rows: multivariate over the nodes of a row, so it sees the dependence
+               between nodes -- the score that compares `coupling=` choices (their marginals, hence their crps, are the same)
+      rmse     RMSE of the ensemble mean           spread   sqrt(mean ensemble variance); spread / rmse near 1: spread matches skill
+      valid    elements scored                     valid_rows   rows scored
+      rank_histogram [S + 1] (the sum over steps) and rank_histogram_step [H, S + 1], int64: where the truth falls among the S
+               sorted path values (ties at the midrank); flat when calibrated, U-shaped when the paths are too narrow
+      rank_uniformity   the chi-square statistic of rank_histogram against flat, rank_uniformity_dof = S its degrees of freedom
+    mul / add: per-node de-normalisation in fp64 ahead of everything.  ignore_nan: NaN targets are missing readings
+    (`stemgnn_ensemble_scores_masked`); a slice with nothing valid is NaN.  fair: the pair terms of crps and energy are divided by
+    S (S - 1) instead of S^2, unbiased in S: for comparing runs with different `paths=`.  One host sync."""
+
+    def __init__(self, y, paths, mul=None, add=None, ignore_nan=False, fair=False):
+        paths = _as_f32(paths)
+        y = _as_f32(y, like=paths)
+        out, hist = ops.ensemble_scores(y, paths, mul, add, ignore_nan=bool(ignore_nan), fair=bool(fair))
+        H, S = int(hist.shape[0]), int(hist.shape[1]) - 1
+        flat = torch.cat([out, hist.reshape(-1).double()]).cpu().numpy()         # (counts below 2^53: exact as doubles)
+        v, h = flat[:out.numel()], flat[out.numel():].astype(np.int64).reshape(H, S + 1)
+        names = ("crps", "energy", "rmse", "spread", "valid", "valid_rows")
+        for k, name in enumerate(names):
+            kind = np.float64 if k < 4 else np.int64                         # the two counts are integers
+            setattr(self, name, kind(v[k]))
+            setattr(self, name + "_step", v[6 + k * H:6 + (k + 1) * H].astype(kind))
+        self.rank_histogram_step = h.copy()
+        self.rank_histogram = h.sum(axis=0)
+        total = int(self.rank_histogram.sum())
+        expect = total / (S + 1.0)
+        self.rank_uniformity_dof = S
+        self.rank_uniformity = np.float64(((self.rank_histogram - expect) ** 2).sum() / expect) if total else np.float64("nan")
+
+
 class ConformalCalibrator:
     """Split-conformal calibration of the bands of a quantile forecast (conformalized quantile regression), on the device.
 

@@ -1963,6 +1963,44 @@ def scenario_bands(paths, quantiles, step_from, bands):
     return bands
 
 
+def ensemble_scores(y, paths, mul=None, add=None, ignore_nan=False, fair=False):
+    """Scores of sampled paths against what happened (``stemgnn_ensemble_scores``; the definitions are in include/stemgnn_hip.h):
+    y [count,H,N], paths [count,S,H,N] (rolling_scenarios' layout), contiguous float32 on one device ->
+    (out float64 [6 * (1 + H)] = overall | by_step[6][H] of mean CRPS, mean energy score, RMSE of the ensemble mean, spread,
+    valid elements, valid rows; hist int64 [H, S + 1], the rank histogram per step), both on the device, no sync.
+    mul / add: per-node de-normalisation in fp64 ahead of everything.  ignore_nan: the ``_masked`` entry, NaN targets are missing.
+    fair: the pair terms are divided by S (S - 1) instead of S^2 (unbiased in S; needs S >= 2)."""
+    if y.dim() != 3 or paths.dim() != 4 or (paths.shape[0],) + tuple(paths.shape[2:]) != tuple(y.shape):
+        raise _lib.StemGNNHipError(f"ensemble_scores: y must be [count,H,N] and paths [count,S,H,N], got "
+                                   f"{tuple(y.shape)} / {tuple(paths.shape)}")
+    for t, name in ((y, "y"), (paths, "paths")):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.StemGNNHipError(f"ensemble_scores: {name} must be a contiguous float32 tensor, got {t.dtype}, "
+                                       f"strides {tuple(t.stride())}")
+    if (mul is None) != (add is None):
+        raise _lib.StemGNNHipError("ensemble_scores: mul and add go together")
+    C, S, H, N = paths.shape
+    if not 1 <= S <= 1024 or (fair and S < 2):
+        raise _lib.StemGNNHipError(f"ensemble_scores: {S} paths (1 to 1024 are scored; fair=True needs at least 2)")
+    _require_gpu(y, "y")
+    _require_gpu(paths, "paths")
+    if paths.device != y.device:
+        raise _lib.StemGNNHipError(f"ensemble_scores: y is on {y.device}, paths on {paths.device}")
+    lib = _lib.load()
+    dev = y.device
+    entry = lib.stemgnn_ensemble_scores_masked if ignore_nan else lib.stemgnn_ensemble_scores
+    scratch = torch.empty(lib.stemgnn_ensemble_scratch_doubles(C, S, H, N), device=dev, dtype=torch.float64)
+    out = torch.empty(lib.stemgnn_ensemble_out_doubles(H), device=dev, dtype=torch.float64)
+    hist = torch.empty(H, S + 1, device=dev, dtype=torch.int64)
+    if mul is not None:
+        mul = mul.to(device=dev, dtype=torch.float64).contiguous()
+        add = add.to(device=dev, dtype=torch.float64).contiguous()
+    _lib.check(entry(y.data_ptr(), paths.data_ptr(), mul.data_ptr() if mul is not None else None,
+                     add.data_ptr() if add is not None else None, C, S, H, N, int(bool(fair)), scratch.data_ptr(),
+                     out.data_ptr(), hist.data_ptr(), _stream()), "ensemble_scores")
+    return out, hist
+
+
 def _ring_ok(what, ring, t_dev):
     _require_gpu(ring, "ring")
     if ring.dim() != 2 or ring.dtype != torch.float32 or not ring.is_contiguous():

@@ -28,7 +28,7 @@ from . import ops
 from .base_model import Model, check_quantiles, point_index
 from .engine import ForecastStep, QuantileForecastStep, TrainStep, scenario_rounds
 from .forecast_dataloader import ForecastDataset, WindowLoader, denorm_coefficients, mark_missing
-from .math_utils import ConformalCalibrator, QuantileScores, Scores
+from .math_utils import ConformalCalibrator, EnsembleScores, QuantileScores, Scores
 from .optim import FusedAdam, FusedRMSprop
 
 BEST = "_stemgnn.pt"
@@ -196,7 +196,7 @@ def rolling_quantile_forecast_graph(model, dataset, horizon, batch_size, adjacen
 
 
 def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=None, ignore_nan=False, quantiles=None,
-                   calibrator=None, origin=None):
+                   calibrator=None, origin=None, paths=None, fair=False):
     """Metrics of a rolling forecast in raw units (and normalised units under ``*_norm``).  With `dump_dir`, the first
     forecast step of every window is written as CSV (target / predict / absolute error / absolute percentage error).
     ignore_nan: NaN targets (missing readings) are left out of every metric; the CSV files keep them as NaN.
@@ -207,7 +207,11 @@ def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=
     calibrator (a fitted math_utils.ConformalCalibrator): the bands are calibrated, in the forecast's normalised units, ahead of
     those figures, and the uncalibrated ones are kept under ``interval_coverage_raw`` / ``interval_width_raw``; the point row and
     every point metric are untouched.  A math_utils.SeasonalConformalCalibrator also needs `origin`, the time index of every
-    window's step-0 target (an int: window i has origin + i; or an int64 tensor [count])."""
+    window's step-0 target (an int: window i has origin + i; or an int64 tensor [count]).
+    paths [count, S, horizon, N] (rolling_scenarios(..., return_paths=True)): the sampled trajectories are scored as an ensemble
+    (math_utils.EnsembleScores; `fair` is its flag): ``crps``, ``energy_score``, ``ensemble_rmse``, ``spread`` and
+    ``rank_histogram`` [S + 1], each also per step under ``*_step``, in raw units and, like the keys above, in normalised
+    units under ``*_norm`` (the histogram has no units).  Without paths= the result is what it was, key for key."""
     seasonal = getattr(calibrator, "kind", None) == "seasonal"
     if seasonal and origin is None:
         raise ValueError("score_forecast: a seasonal calibrator needs origin= (the time index of every window's first target)")
@@ -244,6 +248,14 @@ def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=
     normed = Scores(target, forecast, ignore_nan=ignore_nan).get() if mul is not None else (mape, mae, rmse)
     out.update(mape_norm=normed[0], mae_norm=normed[1], rmse_norm=normed[2])
     out.update(calibration)
+    if paths is not None:
+        ens = EnsembleScores(target, paths, mul, add, ignore_nan=ignore_nan, fair=fair)
+        ens_n = EnsembleScores(target, paths, ignore_nan=ignore_nan, fair=fair) if mul is not None else ens
+        for key, name in (("crps", "crps"), ("energy_score", "energy"), ("ensemble_rmse", "rmse"), ("spread", "spread")):
+            for suffix in ("", "_step"):
+                out[key + suffix] = getattr(ens, name + suffix)
+                out[key + suffix + "_norm"] = getattr(ens_n, name + suffix)
+        out.update(rank_histogram=ens.rank_histogram, rank_histogram_step=ens.rank_histogram_step)
     if dump_dir is not None:
         d = pathlib.Path(dump_dir)
         d.mkdir(parents=True, exist_ok=True)
