@@ -947,6 +947,54 @@ int stemgnn_scenario_roll(const float* inputs, const float* forecast, const floa
                           void* stream);
 int stemgnn_scenario_bands(const float* paths, int Bo, int S, int horizon, int N, int Q, const int* ranks, int step_from,
                            float* bands, void* stream);
+/* roll_given: stemgnn_scenario_roll with step 2 replaced by u = uniforms[b, s, j, n] (uniforms [Bo, S, L, N], fp32 and
+ * contiguous, on the device): the same kernel with a third source for u, so steps 1 and 3 to 5, the outputs and every refusal
+ * above hold as they stand (coupling, seed, offset and origin0 do not exist here; uniforms == NULL is refused too).  The 16-byte
+ * path also needs uniforms 16-byte aligned.  A value outside (0, 1) or a NaN follows from the arithmetic of steps 3 to 5;
+ * keeping u inside is the caller's contract (stemgnn_copula_uniforms does; antithetic or user-defined dependence may not). */
+int stemgnn_scenario_roll_given(const float* inputs, const float* forecast, const float* taus, const float* uniforms, int Bo,
+                                int S, int fan, int W, int L, int N, int Q, int step, int horizon, int tails, float* inputs_next,
+                                float* paths, float* bands, void* stream);
+
+/* ---- Gaussian-copula coupling of scenario paths (csrc/copula.hip) ---------------------------------------
+ * The marginals stay the model's quantile functions; the uniforms of one (path, step) row are u_n = Phi(z_n), z = L e with e
+ * i.i.d. N(0, 1) and L L^T = R a correlation matrix over the nodes, estimated from the normal scores of held-out targets.
+ * pit:      u[c, h, n] = F(target[c, h, n]), F the quantile function of stemgnn_scenario_roll's steps 1 and 3 to 5 read the other
+ *           way.  target [count, H, N], forecast [count, Q, H, N], u [count, H, N], fp32 and contiguous; taus = the Q levels as
+ *           fp32 in HOST memory.  With v_(0) <= .. <= v_(Q-1) the column in that order and y the target:
+ *             i  = the largest index in [0, Q - 2] with v_(i) <= y, 0 when there is none
+ *             d  = v_(i+1) - v_(i);  wt = (y - v_(i)) / d, fp32, a correctly rounded division;
+ *                  where d == 0: wt = 0.5 when y == v_(i), else +inf / -inf by the sign of y - v_(i)
+ *             tails == SG_SCENARIO_CLAMP clamps wt to [0, 1]
+ *             u  = taus[i] + (taus[i + 1] - taus[i]) * wt, the subtraction, the product and the sum rounded separately (no FMA),
+ *                  then clamped to [2^-24, 1 - 2^-24].
+ *           Both clamps are comparisons that keep a NaN.  A NaN target or a NaN anywhere in the column gives u = NaN (bits
+ *           0x7fc00000), "missing"; an infinite column value follows from the arithmetic.  One launch; 16-byte accesses when
+ *           N % 4 == 0 and target, forecast and u are 16-byte aligned, a scalar path otherwise.
+ * gram:     u [M, N] fp32 (M = count * H rows); z = normcdfinv((double)u) in fp64, a NaN z (a NaN u, a u outside [0, 1]) is
+ *           absent.  For every (i, j), over the rows where z_i and z_j are both present:
+ *             pairs[i, j] = their number (int64, exact)
+ *             sums[0][i, j] = sum z_i z_j    sums[1][i, j] = sum z_i    sums[2][i, j] = sum z_i^2     (fp64 [3][N][N])
+ *           Two launches: rows in chunks of 1024 added in row order, then the chunks in chunk order; no atomics, the same bits on
+ *           every run.  scratch: stemgnn_copula_scratch_doubles(M, N) doubles on the device (0 for a refused shape).
+ * uniforms: u [Bo, S, Lsteps, N] fp32.  factor_t [N, N] fp32, factor_t[k * N + n] = L[n][k], L lower triangular; the entries
+ *           with k > n are never used.  For path (b, s), step j < Lsteps and node k:
+ *             e_k = normcdfinvf(((w >> 9) + 0.5f) * 2^-23), w the Philox word of stemgnn_scenario_roll's step 2 under
+ *                   SG_SCENARIO_INDEPENDENT for (origin0 + b, s, step + j, k): a draw is named by global origin, path, step, node
+ *             z_n = sum_{k <= n} L[n][k] * e_k, fp32 FMAs with k ascending from 0 (the order depends on n alone)
+ *             u_n = normcdff(z_n) clamped to [2^-24, 1 - 2^-24].
+ *           One launch, no scratch.  N <= 2048 (the rows of e a workgroup holds: 16 up to N = 512, 4 beyond).
+ * No allocation, no host synchronisation, no atomics; capturable.
+ * SG_EINVAL (nothing launched): a NULL pointer; count, H, N, M, Bo, Lsteps <= 0; Q < 2 or Q > 32; levels not strictly increasing
+ * inside (0, 1); an unknown tails; S outside [1, 1024]; step outside [0, horizon); uniforms: N > 2048; pit: H * N, Q * H * N,
+ * count * H or the grid ceil(count * H * (N / VEC) / threads) >= 2^31; gram: M, N * N or the grid ceil(N / 16)^2 *
+ * ceil(M / 1024) >= 2^31; uniforms: Bo * S * Lsteps or S * horizon >= 2^31. */
+int stemgnn_copula_pit(const float* target, const float* forecast, const float* taus, long count, int H, int N, int Q, int tails,
+                       float* u, void* stream);
+size_t stemgnn_copula_scratch_doubles(long M, int N);
+int stemgnn_copula_gram(const float* u, long M, int N, double* scratch, long long* pairs, double* sums, void* stream);
+int stemgnn_copula_uniforms(const float* factor_t, int Bo, int S, int Lsteps, int N, int step, int horizon, long long origin0,
+                            unsigned long long seed, unsigned long long offset, float* u, void* stream);
 
 /* ---- ensemble scores of scenario paths: CRPS, energy score, rank histogram (csrc/ensemble.hip) --------
  * target [count, H, N] and paths [count, S, H, N] (stemgnn_scenario_roll's layout), fp32 and contiguous, 1 <= S <= 1024; optional

@@ -215,6 +215,13 @@ SIGNATURES = {
     "stemgnn_scenario_roll": (c_int, [_P, _P, POINTER(c_float), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_longlong, c_ulonglong, c_ulonglong, c_int, c_int, _P, _P, _P, _P]),
     "stemgnn_scenario_bands": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), c_int, _P, _P]),
+    "stemgnn_scenario_roll_given": (c_int, [_P, _P, POINTER(c_float), _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                            c_int, c_int, _P, _P, _P, _P]),
+    "stemgnn_copula_pit": (c_int, [_P, _P, POINTER(c_float), c_long, c_int, c_int, c_int, c_int, _P, _P]),
+    "stemgnn_copula_scratch_doubles": (c_size_t, [c_long, c_int]),
+    "stemgnn_copula_gram": (c_int, [_P, c_long, c_int, _P, _P, _P, _P]),
+    "stemgnn_copula_uniforms": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_longlong, c_ulonglong, c_ulonglong, _P,
+                                        _P]),
     "stemgnn_ensemble_scratch_doubles": (c_size_t, [c_long, c_int, c_int, c_int]),
     "stemgnn_ensemble_out_doubles": (c_size_t, [c_int]),
     "stemgnn_ensemble_scores": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),

@@ -1,5 +1,5 @@
 // Scenario forecasts: sampled rolling paths and their order statistics (include/stemgnn_hip.h: stemgnn_scenario_roll /
-// _bands / _rank).
+// _roll_given / _bands / _rank).
 //
 // roll: one round of the roll for Bo origins x S paths.  Path p = b * S + s reads source row p / fan of `inputs` and
 // `forecast` (fan == S: round 0, the model ran once per origin; fan == 1: a later round, once per path).  For step j < L and
@@ -7,6 +7,7 @@
 // forecast[src, :, j, n] in the order of quantile_serve.hip (fp32's with -0 == +0, NaN last, ties in row order), taken at the
 // uniform u of a Philox word: see sc_draw.  The draw goes to paths[b, s, step + j, n] and takes the place of the forecast row
 // in the window roll of sg_roll_window_kernel (data.hip); round 0 also files the model's own column in bands.
+// roll_given: the same kernel template with u read from uniforms[b, s, j, n] (copula.hip makes correlated ones).
 //
 // A workgroup owns one path; its threads walk the path's (row, node group) items, lanes along n, so every global access of a
 // wave is a coalesced run of one row.  The column of a draw item is held in the thread's own LDS words [Q][VEC][threads]
@@ -32,6 +33,7 @@
 #include "conformal_args.h"
 #include "conformal_select.h"
 #include "philox.h"
+#include "scenario_draw.h"
 #include "sg_host.h"
 
 namespace {
@@ -47,6 +49,7 @@ struct ScRollArgs {                         // travels by value in the kernel ar
   float* inputs_next;                       // [Bo * S, W, N] or NULL
   float* paths;                             // [Bo, S, horizon, N]
   float* bands;                             // [Bo, Q, horizon, N] or NULL
+  const float* uniforms;                    // [Bo, S, L, N]: the GIVEN kernels only
   unsigned long long origin0, seed, offset;
   int S, fan, W, L, N, Q, step, horizon, path_coupling, clamp;
   float tau[CF_MAX_Q];
@@ -58,12 +61,6 @@ struct ScBandArgs {
   int S, Q, HN, from, cols, C, tiles;       // from = step_from * N; cols = HN - from; tiles = ceil(cols / C) per origin
   int rank[CF_MAX_Q];                       // 1-based
 };
-
-// v before w in the order of quantile_serve.hip (qs_less), ties left to the caller
-__device__ inline bool sc_less(float v, float w) { return v < w || (v == v && w != w); }
-
-// the uniform of a Philox word: exact in fp32, strictly inside (0, 1)
-__device__ inline float sc_uniform(uint32_t w) { return __fmul_rn(__fadd_rn((float)(w >> 9), 0.5f), 1.1920928955078125e-07f); }
 
 // The draw at u from the thread's column col[q * stride], q < Q: segment i = the last level <= u within [0, Q - 2],
 // wt = (u - tau_i) / (tau_{i+1} - tau_i), y = v_(i) + (v_(i+1) - v_(i)) * wt on the ordered values, every operation rounded
@@ -100,7 +97,8 @@ __device__ inline float sc_draw(const ScRollArgs& a, const float* col, int strid
   return lo + m;
 }
 
-template <int VEC>
+// GIVEN: u is read from a.uniforms[b, s, j, n] instead of being made from a Philox word (stemgnn_scenario_roll_given)
+template <int VEC, bool GIVEN>
 __global__ __launch_bounds__(SC_THREADS) void sc_roll_kernel(const ScRollArgs a) {
   extern __shared__ float4 sc_lds[];
   const int T = blockDim.x, t = threadIdx.x, Q = a.Q, N = a.N, W = a.W, L = a.L;
@@ -134,14 +132,17 @@ __global__ __launch_bounds__(SC_THREADS) void sc_roll_kernel(const ScRollArgs a)
       for (int k = 0; k < VEC; ++k) col[(q * VEC + k) * T] = v[k];
       if (a.bands && s == 0 && j < take) cf_store<VEC>(a.bands + ((b * Q + q) * a.horizon + a.step + j) * N + n, v);
     }
-    uint32_t w[4];
-    sg_philox4(a.seed, a.offset, a.path_coupling ? row0 * nq : (row0 + j) * nq + (n >> 2), w);
-    float y[VEC];
+    float u[VEC], y[VEC];
+    if constexpr (GIVEN) {
+      cf_load<VEC>(a.uniforms + ((p * L + j) * N + n), u);
+    } else {
+      uint32_t w[4];
+      sg_philox4(a.seed, a.offset, a.path_coupling ? row0 * nq : (row0 + j) * nq + (n >> 2), w);
 #pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-      const uint32_t word = a.path_coupling ? w[0] : (VEC == 4 ? w[k] : w[n & 3]);
-      y[k] = sc_draw(a, col + k * T, VEC * T, sc_uniform(word));
+      for (int k = 0; k < VEC; ++k) u[k] = sc_uniform(a.path_coupling ? w[0] : (VEC == 4 ? w[k] : w[n & 3]));
     }
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) y[k] = sc_draw(a, col + k * T, VEC * T, u[k]);
     if (j < take) cf_store<VEC>(a.paths + (p * a.horizon + a.step + j) * N + n, y);
     if (a.inputs_next) cf_store<VEC>(a.inputs_next + (p * W + r) * N + n, y);
   }
@@ -190,21 +191,12 @@ __global__ __launch_bounds__(SC_THREADS) void sc_bands_kernel(const ScBandArgs a
 
 bool sc_fits_int(long long v) { return v > 0 && v < (1ll << 31); }
 
-}  // namespace
-
-extern "C" long stemgnn_scenario_rank(double tau, long S) {
-  if (S < 1) return 0;
-  if (!(tau > 0.0)) return 1;
-  const double t = tau * (double)S;
-  const double k = ceil(t * (1.0 - 1e-12));
-  return k < 1.0 ? 1 : (k > (double)S ? S : (long)k);
-}
-
-extern "C" int stemgnn_scenario_roll(const float* inputs, const float* forecast, const float* taus, int Bo, int S, int fan, int W,
-                                     int L, int N, int Q, int step, int horizon, long long origin0, unsigned long long seed,
-                                     unsigned long long offset, int coupling, int tails, float* inputs_next, float* paths,
-                                     float* bands, void* stream) {
-  if (!inputs || !forecast || !taus || !paths || inputs == inputs_next) return SG_EINVAL;
+// the checks and the launch of both roll entries; uniforms == NULL: the Philox draws of `coupling`
+template <bool GIVEN>
+int sc_roll(const float* inputs, const float* forecast, const float* taus, const float* uniforms, int Bo, int S, int fan, int W,
+            int L, int N, int Q, int step, int horizon, long long origin0, unsigned long long seed, unsigned long long offset,
+            int coupling, int tails, float* inputs_next, float* paths, float* bands, void* stream) {
+  if (!inputs || !forecast || !taus || !paths || inputs == inputs_next || (GIVEN && !uniforms)) return SG_EINVAL;
   if (Bo <= 0 || W <= 0 || N <= 0 || L <= 0 || L > W || step < 0 || step >= horizon) return SG_EINVAL;
   if (Q < 2 || Q > CF_MAX_Q || S < 1 || S > SC_MAX_S || (fan != 1 && fan != S)) return SG_EINVAL;
   if ((coupling != SG_SCENARIO_INDEPENDENT && coupling != SG_SCENARIO_PATH) ||
@@ -222,12 +214,14 @@ extern "C" int stemgnn_scenario_roll(const float* inputs, const float* forecast,
       !sc_fits_int((long long)Q * horizon * N) || !sc_fits_int((long long)S * horizon))
     return SG_EINVAL;
   a.inputs = inputs; a.forecast = forecast; a.inputs_next = inputs_next; a.paths = paths; a.bands = bands;
+  a.uniforms = uniforms;
   a.origin0 = (unsigned long long)origin0; a.seed = seed; a.offset = offset;
   a.S = S; a.fan = fan; a.W = W; a.L = L; a.N = N; a.Q = Q; a.step = step; a.horizon = horizon;
   a.path_coupling = coupling == SG_SCENARIO_PATH;
   a.clamp = tails == SG_SCENARIO_CLAMP;
   const bool vec = (N & 3) == 0 && sg_aligned16(inputs) && sg_aligned16(forecast) && sg_aligned16(paths) &&
-                   (!inputs_next || sg_aligned16(inputs_next)) && (!bands || sg_aligned16(bands));
+                   (!inputs_next || sg_aligned16(inputs_next)) && (!bands || sg_aligned16(bands)) &&
+                   (!GIVEN || sg_aligned16(uniforms));
   const int VEC = vec ? 4 : 1;
   const long long items = (long long)(inputs_next ? W : L) * (N / VEC);
   int T = SC_THREADS;
@@ -235,11 +229,36 @@ extern "C" int stemgnn_scenario_roll(const float* inputs, const float* forecast,
   const size_t lds = (size_t)T * Q * VEC * 4;                 // <= 32 KB: Q <= 32, VEC <= 4, T >= 64
   const dim3 grid((unsigned)(Bo * S));
   if (vec)
-    hipLaunchKernelGGL(sc_roll_kernel<4>, grid, dim3(T), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((sc_roll_kernel<4, GIVEN>), grid, dim3(T), lds, (hipStream_t)stream, a);
   else
-    hipLaunchKernelGGL(sc_roll_kernel<1>, grid, dim3(T), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((sc_roll_kernel<1, GIVEN>), grid, dim3(T), lds, (hipStream_t)stream, a);
   SG_TRY(hipGetLastError());
   return 0;
+}
+
+}  // namespace
+
+extern "C" long stemgnn_scenario_rank(double tau, long S) {
+  if (S < 1) return 0;
+  if (!(tau > 0.0)) return 1;
+  const double t = tau * (double)S;
+  const double k = ceil(t * (1.0 - 1e-12));
+  return k < 1.0 ? 1 : (k > (double)S ? S : (long)k);
+}
+
+extern "C" int stemgnn_scenario_roll(const float* inputs, const float* forecast, const float* taus, int Bo, int S, int fan, int W,
+                                     int L, int N, int Q, int step, int horizon, long long origin0, unsigned long long seed,
+                                     unsigned long long offset, int coupling, int tails, float* inputs_next, float* paths,
+                                     float* bands, void* stream) {
+  return sc_roll<false>(inputs, forecast, taus, nullptr, Bo, S, fan, W, L, N, Q, step, horizon, origin0, seed, offset, coupling,
+                        tails, inputs_next, paths, bands, stream);
+}
+
+extern "C" int stemgnn_scenario_roll_given(const float* inputs, const float* forecast, const float* taus, const float* uniforms,
+                                           int Bo, int S, int fan, int W, int L, int N, int Q, int step, int horizon, int tails,
+                                           float* inputs_next, float* paths, float* bands, void* stream) {
+  return sc_roll<true>(inputs, forecast, taus, uniforms, Bo, S, fan, W, L, N, Q, step, horizon, 0, 0ull, 0ull,
+                       SG_SCENARIO_INDEPENDENT, tails, inputs_next, paths, bands, stream);
 }
 
 extern "C" int stemgnn_scenario_bands(const float* paths, int Bo, int S, int horizon, int N, int Q, const int* ranks,

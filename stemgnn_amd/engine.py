@@ -944,9 +944,19 @@ class QuantileForecastStep(ForecastStep):
 
 def scenario_rounds(model, window, horizon, paths, origin0, seed, coupling, tails, graph_kw):
     """The rounds of one batch of rolling_scenarios (LiveForecaster.scenarios runs the same on its head window):
-    window [Bo,W,N] -> (bands [Bo,Q,horizon,N], paths [Bo,S,horizon,N])."""
+    window [Bo,W,N] -> (bands [Bo,Q,horizon,N], paths [Bo,S,horizon,N]).  coupling: "independent", "path", or a fitted
+    math_utils.GaussianCopula, whose correlated uniforms (one ops.copula_uniforms launch per round) then drive the draws."""
     quantiles = model.quantiles
     Bo, _, N = window.shape
+    copula = None if isinstance(coupling, str) else coupling
+    if copula is not None:                                   # refused on the host, before the model is touched
+        if getattr(copula, "factor_t", None) is None:
+            raise ValueError("scenario_rounds: coupling must be 'independent', 'path' or a fitted GaussianCopula")
+        if copula.nodes != N:
+            raise ValueError(f"scenario_rounds: the copula was fitted on {copula.nodes} nodes, the window has {N}")
+        if copula.tails != tails:
+            raise ValueError(f"scenario_rounds: the copula's tails are {copula.tails!r}, the call's {tails!r}: the transform of "
+                             "the fit and the draw must be inverses")
     steps = torch.empty(Bo, paths, horizon, N, device=window.device)
     bands = torch.empty(Bo, len(quantiles), horizon, N, device=window.device)
     done, L = 0, None
@@ -955,8 +965,10 @@ def scenario_rounds(model, window, horizon, paths, origin0, seed, coupling, tail
         if out.shape[-2] == 0:
             raise Exception("Get blank inference result")
         L = out.shape[-2] if L is None else L
+        u = None if copula is None else copula.uniforms(Bo, paths, out.shape[-2], done, horizon, origin0, seed)
         window = ops.scenario_roll(window, out, quantiles, steps, done, origin0=origin0, seed=seed, coupling=coupling,
-                                   tails=tails, bands=bands if done == 0 else None, last=done + out.shape[-2] >= horizon)
+                                   tails=tails, bands=bands if done == 0 else None, last=done + out.shape[-2] >= horizon,
+                                   uniforms=u)
         done += min(horizon - done, out.shape[-2])
     ops.scenario_bands(steps, quantiles, min(L, horizon), bands)
     return bands, steps

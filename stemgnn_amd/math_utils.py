@@ -109,6 +109,146 @@ class EnsembleScores:
         self.rank_uniformity = np.float64(((self.rank_histogram - expect) ** 2).sum() / expect) if total else np.float64("nan")
 
 
+class GaussianCopula:
+    """The dependence BETWEEN NODES of sampled scenario paths: a Gaussian copula over the model's own marginals, on the device.
+
+    `coupling="independent"` and `coupling="path"` are the two ends of the range; a network's residuals are correlated in blocks.
+    Here the uniforms that drive the draws of one (path, step) row are u = Phi(L e), e i.i.d. standard normal and L L^T = R a
+    correlation matrix over the nodes, so every node keeps exactly the predicted quantile function as its marginal and only the
+    joint behaviour changes.  Pass the fitted object as `coupling=` to trainer.rolling_scenarios / LiveForecaster.scenarios;
+    `EnsembleScores.energy` is the score that ranks it against the two strings.
+
+    fit(y, y_hat): y [count, H, N] held-out ground truth, y_hat [count, Q, H, N], normalised units, as a validation pass leaves
+    them at the model's own horizon (`trainer.rolling_forecast(model, loader, model.horizon)`); all H steps are pooled.
+      u = pit(y, y_hat)                 the transform of each target under its forecast (`ops.copula_pit`), NaN = missing
+      pairs, sums = ops.copula_gram(u)  pairwise-complete moments of z = Phi^-1(u), fp64, m_ij = pairs
+      mean_i|j = a_ij / m_ij,  cov_ij = s_ij / m_ij - mean_i|j mean_j|i,  var_i|j = q_ij / m_ij - mean_i|j^2
+      R_ij = cov_ij / sqrt(var_i|j var_j|i), 0 where m_ij < min_pairs or a variance is not positive; unit diagonal; (R + R^T) / 2
+      correlation = (1 - shrinkage) R + shrinkage I
+    elementwise in fp64 on the device; the Cholesky factor of that one N x N matrix is taken on the host in fp64 (a ValueError
+    names the smallest eigenvalue when it fails: pairwise-complete estimates need not be positive definite, a larger shrinkage
+    makes them so), cast to fp32, transposed and copied to the device.
+    from_correlation(R, quantiles, tails): a prior matrix instead of a fit, validated once on the host.
+    pit(y, y_hat) -> u [count, H, N]: its histogram per node is a calibration diagnostic in its own right (flat when calibrated).
+    uniforms(Bo, S, L, step, horizon, origin0, seed, offset=0) -> u [Bo, S, L, N] (`ops.copula_uniforms`), what
+    `ops.scenario_roll(..., uniforms=u)` takes; a draw is named by global origin, path, step and node as for "independent".
+    tails must be the `tails=` of the scenario call: the transform of the fit and the draw are inverses only then.
+    Attributes: correlation (fp64 [N, N], device, the shrunk matrix), correlation_raw, pairs (int64 [N, N]; None from a prior),
+    factor_t (fp32 [N, N], factor_t[k, n] = L[n, k]), nodes."""
+
+    def __init__(self, quantiles, shrinkage=0.05, tails="linear", min_pairs=8):
+        q = tuple(float(t) for t in quantiles)
+        if len(q) < 2 or not all(0.0 < a < b < 1.0 for a, b in zip(q, q[1:])):
+            raise ValueError(f"GaussianCopula: at least two levels, strictly increasing inside (0, 1), are needed; got {q}")
+        if not 0.0 <= float(shrinkage) <= 1.0:
+            raise ValueError(f"GaussianCopula: shrinkage must be within [0, 1], got {shrinkage}")
+        if tails not in ("linear", "clamp"):
+            raise ValueError(f"GaussianCopula: tails must be 'linear' or 'clamp', got {tails!r}")
+        if int(min_pairs) < 2:
+            raise ValueError(f"GaussianCopula: min_pairs must be at least 2 (a variance needs two rows), got {min_pairs}")
+        self.quantiles, self.shrinkage, self.tails, self.min_pairs = q, float(shrinkage), tails, int(min_pairs)
+        self.correlation = self.correlation_raw = self.pairs = self.factor_t = self.nodes = None
+
+    def pit(self, y, y_hat):
+        y_hat = _as_f32(y_hat)
+        y = _as_f32(y, like=y_hat)
+        if y_hat.dim() != 4 or y_hat.shape[1] != len(self.quantiles):
+            raise ValueError(f"GaussianCopula.pit: y_hat must be [count, {len(self.quantiles)}, H, N], got {tuple(y_hat.shape)}")
+        return ops.copula_pit(y.contiguous(), y_hat.contiguous(), self.quantiles, self.tails)
+
+    def fit(self, y, y_hat):
+        pairs, (s, a, q) = ops.copula_gram(self.pit(y, y_hat))
+        m = pairs.double()
+        mean = a / m                                                    # mean_i|j; its transpose is mean_j|i (m is symmetric)
+        var = q / m - mean * mean
+        R = (s / m - mean * mean.T) / torch.sqrt(var * var.T)
+        R = torch.where((pairs < self.min_pairs) | ~(var > 0) | ~(var.T > 0), torch.zeros_like(R), R)
+        R.fill_diagonal_(1.0)
+        R = (R + R.T) / 2
+        eye = torch.eye(R.shape[0], dtype=R.dtype, device=R.device)
+        shrunk = (1.0 - self.shrinkage) * R + self.shrinkage * eye
+        factor = self._factor(shrunk.cpu().numpy(), "GaussianCopula.fit")
+        self._take(shrunk, R, pairs, factor, R.device)
+        return self
+
+    @staticmethod
+    def _factor(R, who):
+        """The lower Cholesky factor of the host matrix R in fp64, or the ValueError that says why there is none."""
+        if not np.isfinite(R).all():
+            raise ValueError(f"{who}: the correlation matrix has entries that are not finite")
+        try:
+            return np.linalg.cholesky(R)
+        except np.linalg.LinAlgError:
+            low = float(np.linalg.eigvalsh((R + R.T) / 2).min())
+            raise ValueError(f"{who}: the correlation matrix is not positive definite (smallest eigenvalue {low:.3e}); a larger "
+                             "shrinkage is needed") from None
+
+    def _take(self, correlation, raw, pairs, factor, device):
+        self.correlation, self.correlation_raw, self.pairs = correlation, raw, pairs
+        self.factor_t = torch.from_numpy(np.ascontiguousarray(factor.astype(np.float32).T)).to(device)
+        self.nodes = int(factor.shape[0])
+
+    @classmethod
+    def from_correlation(cls, R, quantiles, tails="linear", device=None):
+        """A copula from a prior correlation matrix (numpy or tensor): square, finite, symmetric and of unit diagonal to 1e-6,
+        positive definite.  device: where factor_t goes (default: R's when it is a device tensor, else the current HIP device)."""
+        if torch.is_tensor(R):
+            device = R.device if device is None and R.is_cuda else device
+            R = R.detach().cpu().numpy()
+        R = np.asarray(R, dtype=np.float64)
+        if R.ndim != 2 or R.shape[0] != R.shape[1] or R.shape[0] < 1:
+            raise ValueError(f"GaussianCopula.from_correlation: a square matrix is needed, got shape {R.shape}")
+        if not np.isfinite(R).all():
+            raise ValueError("GaussianCopula.from_correlation: the matrix has entries that are not finite")
+        if np.abs(R - R.T).max() > 1e-6:
+            raise ValueError(f"GaussianCopula.from_correlation: the matrix is not symmetric (max |R - R^T| = "
+                             f"{np.abs(R - R.T).max():.3e})")
+        if np.abs(np.diag(R) - 1.0).max() > 1e-6:
+            raise ValueError(f"GaussianCopula.from_correlation: the diagonal is not 1 (max |R_ii - 1| = "
+                             f"{np.abs(np.diag(R) - 1.0).max():.3e})")
+        self = cls(quantiles, shrinkage=0.0, tails=tails)
+        factor = cls._factor(R, "GaussianCopula.from_correlation")
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        dev_R = torch.from_numpy(R.copy()).to(device)
+        self._take(dev_R, dev_R.clone(), None, factor, device)
+        return self
+
+    def uniforms(self, Bo, S, L, step, horizon, origin0, seed, offset=0):
+        if self.factor_t is None:
+            raise ValueError("GaussianCopula.uniforms: not fitted (call fit, from_correlation or load_state_dict first)")
+        return ops.copula_uniforms(self.factor_t, Bo, S, L, step, horizon, origin0=origin0, seed=seed, offset=offset)
+
+    def state_dict(self):
+        return dict(quantiles=self.quantiles, shrinkage=self.shrinkage, tails=self.tails, min_pairs=self.min_pairs,
+                    nodes=self.nodes, correlation=self.correlation, correlation_raw=self.correlation_raw, pairs=self.pairs,
+                    factor_t=self.factor_t)
+
+    def load_state_dict(self, state, device=None):
+        q = tuple(float(t) for t in state["quantiles"])
+        if q != self.quantiles or state["tails"] != self.tails:
+            raise ValueError(f"GaussianCopula.load_state_dict: saved for levels {q}, tails={state['tails']!r}; this one has "
+                             f"{self.quantiles}, {self.tails!r}")
+        f = state["factor_t"]
+        if f is not None and (f.dim() != 2 or f.shape[0] != f.shape[1] or tuple(state["correlation"].shape) != tuple(f.shape)):
+            raise ValueError(f"GaussianCopula.load_state_dict: factor_t {tuple(f.shape)} / correlation "
+                             f"{tuple(state['correlation'].shape)} are not one square shape")
+
+        def put(t, dtype):
+            if t is None:
+                return None
+            return t.detach().to(device=t.device if device is None else device, dtype=dtype).contiguous().clone()
+
+        self.correlation, self.correlation_raw = put(state["correlation"], torch.float64), put(state["correlation_raw"], torch.float64)
+        self.pairs, self.factor_t = put(state["pairs"], torch.int64), put(f, torch.float32)
+        self.nodes = None if f is None else int(f.shape[0])
+        return self
+
+    @classmethod
+    def from_state_dict(cls, state, device=None):
+        return cls(state["quantiles"], state["shrinkage"], state["tails"], state["min_pairs"]).load_state_dict(state, device)
+
+
 class ConformalCalibrator:
     """Split-conformal calibration of the bands of a quantile forecast (conformalized quantile regression), on the device.
 

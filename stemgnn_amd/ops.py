@@ -1890,14 +1890,16 @@ def scenario_rank(tau, S):
 
 
 def scenario_roll(inputs, forecast, quantiles, paths, step, origin0=0, seed=0, offset=0, coupling="independent",
-                  tails="linear", bands=None, last=False):
+                  tails="linear", bands=None, last=False, uniforms=None):
     """One round of a sampled roll (``stemgnn_scenario_roll``): every path draws its next window rows from the quantile
     function through (quantiles, forecast column) -- the definition in include/stemgnn_hip.h -- instead of taking the point row.
     inputs [Bsrc,W,N], forecast [Bsrc,Q,L,N], paths [Bo,S,horizon,N] (rows step .. step + L - 1 are written).  Bsrc == Bo is
     round 0 (fan = S: every path of an origin reads the origin's one forecast) and takes bands [Bo,Q,horizon,N], which receives
     the model's own rows of those steps; Bsrc == Bo * S is a later round (fan = 1, no bands).  origin0: the global index of
-    the batch's first origin; seed / offset: the Philox key and the counter's high words.  Returns the next inputs
-    [Bo * S,W,N], or None with last=True (the round whose windows nobody reads)."""
+    the batch's first origin; seed / offset: the Philox key and the counter's high words.  uniforms: a float32 tensor
+    [Bo,S,L,N] whose values take the place of the Philox uniforms (``stemgnn_scenario_roll_given``; `copula_uniforms` makes
+    correlated ones); coupling, origin0, seed and offset are then ignored, and values inside (0, 1) are the caller's contract.
+    Returns the next inputs [Bo * S,W,N], or None with last=True (the round whose windows nobody reads)."""
     lib = _lib.load()
     _require_gpu(inputs, "inputs")
     _require_gpu(forecast, "forecast")
@@ -1926,11 +1928,22 @@ def scenario_roll(inputs, forecast, quantiles, paths, step, origin0=0, seed=0, o
         raise _lib.StemGNNHipError("scenario_roll: paths must be contiguous")
     if bands is not None and (tuple(bands.shape) != (Bo, Q, horizon, N) or not bands.is_contiguous()):
         raise _lib.StemGNNHipError(f"scenario_roll: bands must be a contiguous [Bo,Q,horizon,N] tensor, got {tuple(bands.shape)}")
-    if coupling not in _lib.SG_SCENARIO_COUPLING or tails not in _lib.SG_SCENARIO_TAILS:
+    if (uniforms is None and coupling not in _lib.SG_SCENARIO_COUPLING) or tails not in _lib.SG_SCENARIO_TAILS:
         raise ValueError(f"scenario_roll: coupling is one of {tuple(_lib.SG_SCENARIO_COUPLING)}, tails one of "
                          f"{tuple(_lib.SG_SCENARIO_TAILS)}, got {coupling!r}, {tails!r}")
     inputs, forecast = inputs.contiguous(), forecast.contiguous()
     nxt = None if last else torch.empty(Bo * S, W, N, device=inputs.device, dtype=torch.float32)
+    if uniforms is not None:
+        if tuple(uniforms.shape) != (Bo, S, L, N) or uniforms.dtype != torch.float32 or uniforms.device != inputs.device or \
+                not uniforms.is_contiguous():
+            raise _lib.StemGNNHipError(f"scenario_roll: uniforms must be a contiguous float32 {(Bo, S, L, N)} tensor on the "
+                                       f"inputs' device, got {uniforms.dtype} {tuple(uniforms.shape)} on {uniforms.device}")
+        _lib.check(lib.stemgnn_scenario_roll_given(inputs.data_ptr(), forecast.data_ptr(), _lib.host_floats(quantiles),
+                                                   uniforms.data_ptr(), Bo, S, fan, W, L, N, Q, int(step), horizon,
+                                                   _lib.SG_SCENARIO_TAILS[tails], None if nxt is None else nxt.data_ptr(),
+                                                   paths.data_ptr(), None if bands is None else bands.data_ptr(), _stream()),
+                   "scenario_roll")
+        return nxt
     mask = (1 << 64) - 1
     _lib.check(lib.stemgnn_scenario_roll(inputs.data_ptr(), forecast.data_ptr(), _lib.host_floats(quantiles), Bo, S, fan, W, L,
                                          N, Q, int(step), horizon, int(origin0), int(seed) & mask, int(offset) & mask,
@@ -1961,6 +1974,67 @@ def scenario_bands(paths, quantiles, step_from, bands):
     _lib.check(lib.stemgnn_scenario_bands(paths.data_ptr(), Bo, S, horizon, N, Q, ranks, int(step_from), bands.data_ptr(),
                                           _stream()), "scenario_bands")
     return bands
+
+
+def copula_pit(y, y_hat, quantiles, tails="linear"):
+    """The probability integral transform of y under the forecast's quantile function (``stemgnn_copula_pit``; the exact
+    inverse of scenario_roll's draw, defined in include/stemgnn_hip.h): y [count,H,N], y_hat [count,Q,H,N], contiguous float32
+    on one device -> u [count,H,N] in [2^-24, 1 - 2^-24]; NaN where y or a value of its column is NaN (missing)."""
+    lib = _lib.load()
+    _require_gpu(y, "y")
+    _require_gpu(y_hat, "y_hat")
+    if y.dim() != 3 or y_hat.dim() != 4 or (y_hat.shape[0],) + tuple(y_hat.shape[2:]) != tuple(y.shape) or \
+            y_hat.shape[1] != len(quantiles):
+        raise _lib.StemGNNHipError(f"copula_pit: y must be [count,H,N] and y_hat [count,{len(quantiles)},H,N], got "
+                                   f"{tuple(y.shape)} / {tuple(y_hat.shape)}")
+    if y.device != y_hat.device or not y.is_contiguous() or not y_hat.is_contiguous():
+        raise _lib.StemGNNHipError("copula_pit: y and y_hat must be contiguous tensors on one device")
+    if tails not in _lib.SG_SCENARIO_TAILS:
+        raise ValueError(f"copula_pit: tails is one of {tuple(_lib.SG_SCENARIO_TAILS)}, got {tails!r}")
+    C, Q, H, N = y_hat.shape
+    u = torch.empty_like(y)
+    _lib.check(lib.stemgnn_copula_pit(y.data_ptr(), y_hat.data_ptr(), _lib.host_floats(quantiles), C, H, N, Q,
+                                      _lib.SG_SCENARIO_TAILS[tails], u.data_ptr(), _stream()), "copula_pit")
+    return u
+
+
+def copula_gram(u):
+    """Pairwise-complete second moments of the normal scores z = normcdfinv(u) (``stemgnn_copula_gram``): u [M,N] (or
+    [count,H,N], pooled over its leading axes), contiguous float32, NaN = absent -> (pairs int64 [N,N], sums float64 [3,N,N] =
+    sum z_i z_j | sum z_i | sum z_i^2 over the rows where i and j are both present), on the device, no sync."""
+    lib = _lib.load()
+    _require_gpu(u, "u")
+    if u.dim() < 2 or not u.is_contiguous():
+        raise _lib.StemGNNHipError(f"copula_gram: u must be a contiguous [M,N] or [count,H,N] tensor, got {tuple(u.shape)}")
+    N = u.shape[-1]
+    M = u.numel() // max(N, 1)
+    words = lib.stemgnn_copula_scratch_doubles(M, N)
+    if words == 0:
+        raise _lib.StemGNNHipError(f"copula_gram: {M} rows of {N} nodes are outside the entry's range (SG_EINVAL)")
+    scratch = torch.empty(words, device=u.device, dtype=torch.float64)
+    pairs = torch.empty(N, N, device=u.device, dtype=torch.int64)
+    sums = torch.empty(3, N, N, device=u.device, dtype=torch.float64)
+    _lib.check(lib.stemgnn_copula_gram(u.data_ptr(), M, N, scratch.data_ptr(), pairs.data_ptr(), sums.data_ptr(), _stream()),
+               "copula_gram")
+    return pairs, sums
+
+
+def copula_uniforms(factor_t, Bo, S, L, step, horizon, origin0=0, seed=0, offset=0):
+    """The correlated uniforms of one round (``stemgnn_copula_uniforms``): factor_t [N,N] float32 with factor_t[k, n] = L[n, k],
+    L the lower Cholesky factor of the nodes' correlation matrix (the entries with k > n are never read into the result) ->
+    u [Bo,S,L,N] = normcdf(L e) clamped to [2^-24, 1 - 2^-24], e the standard normal of the Philox word that
+    coupling="independent" takes for that (global origin, path, step, node)."""
+    lib = _lib.load()
+    _require_gpu(factor_t, "factor_t")
+    if factor_t.dim() != 2 or factor_t.shape[0] != factor_t.shape[1] or not factor_t.is_contiguous():
+        raise _lib.StemGNNHipError(f"copula_uniforms: factor_t must be a contiguous [N,N] tensor, got {tuple(factor_t.shape)}")
+    N = factor_t.shape[0]
+    u = torch.empty(int(Bo), int(S), int(L), N, device=factor_t.device, dtype=torch.float32)
+    mask = (1 << 64) - 1
+    _lib.check(lib.stemgnn_copula_uniforms(factor_t.data_ptr(), int(Bo), int(S), int(L), N, int(step), int(horizon),
+                                           int(origin0), int(seed) & mask, int(offset) & mask, u.data_ptr(), _stream()),
+               "copula_uniforms")
+    return u
 
 
 def ensemble_scores(y, paths, mul=None, add=None, ignore_nan=False, fair=False):
