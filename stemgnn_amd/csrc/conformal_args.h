@@ -1,6 +1,7 @@
 // The argument checks, the by-value row table with its band widening, and the grouping geometry shared by the conformal
-// entries (conformal.hip), the serving epilogue (quantile_serve.hip), the adaptive update (aci.hip) and the anomaly scores
-// (anomaly.hip): one definition of what a valid (shape, pairs) is, of what a calibrated row is, and of what a group is.
+// entries (conformal.hip, seasonal.hip), the fit and the column kernel they share (conformal_fit.h, quantile_column.h), the
+// serving epilogue (quantile_serve.hip), the adaptive update (aci.hip) and the anomaly scores (anomaly.hip): one definition of
+// what a valid (shape, pairs) is, of what a calibrated row is, and of what a group is.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -1,6 +1,7 @@
-// The device primitives of the serving kernels (conformal.hip, quantile_serve.hip, live.hip, aci.hip, anomaly.hip): the rank
-// formula, the order-preserving key and the wave pick of the radix select -- one definition of which score is "the k-th
-// smallest of m" -- the float4-or-scalar load / store behind every VEC template, and the special bit patterns.
+// The device primitives of the serving kernels (conformal_fit.h, quantile_column.h, conformal.hip, seasonal.hip, live.hip,
+// aci.hip, anomaly.hip): the rank formula, the order-preserving key and the wave pick of the radix select -- one definition of
+// which score is "the k-th smallest of m" -- the float4-or-scalar load / store behind every VEC template, and the special bit
+// patterns.  The select's kernels themselves are conformal_fit.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

@@ -4,7 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// v before w in the order of quantile_serve.hip (qs_less), ties left to the caller
+// v before w in the order of quantile_column.h (qc_less), ties left to the caller
 __device__ inline bool sc_less(float v, float w) { return v < w || (v == v && w != w); }
 
 // the uniform of a Philox word: exact in fp32, strictly inside (0, 1)

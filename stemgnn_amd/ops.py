@@ -1631,6 +1631,59 @@ def _conformal_pairs(pairs, Q):
     return len(pairs), lo, hi
 
 
+def _fit_inputs(what, target, forecast, pairs, coverage):
+    """The calibration set of a fit, checked: target [count,H,N] and forecast [count,Q,H,N] on one device, one coverage per
+    pair.  Returns (target, forecast), contiguous, and (P, lo, hi)."""
+    _require_gpu(target, "target")
+    _require_gpu(forecast, "forecast")
+    if target.dim() != 3 or forecast.dim() != 4 or (forecast.shape[0],) + tuple(forecast.shape[2:]) != tuple(target.shape):
+        raise _lib.StemGNNHipError(f"{what}: target must be [count,H,N] and forecast [count,Q,H,N], got "
+                                   f"{tuple(target.shape)} / {tuple(forecast.shape)}")
+    if target.device != forecast.device:
+        raise _lib.StemGNNHipError(f"{what}: target is on {target.device}, forecast on {forecast.device}")
+    P, lo, hi = _conformal_pairs(pairs, forecast.shape[1])
+    if len(coverage) != P:
+        raise ValueError(f"{what}: {P} pairs but {len(coverage)} coverages")
+    return target.contiguous(), forecast.contiguous(), P, lo, hi
+
+
+def _tables(lead, H, N, per_step, per_node):
+    """The shape of offsets / counts: the tables of `lead` = (P,) or (K, P) over the groups [Hg, Ng]."""
+    return tuple(lead) + (H if per_step else 1, N if per_node else 1)
+
+
+def _fit_outputs(nbytes, shape, device):
+    """(scratch, offsets, counts) of a fit whose tables have `shape`."""
+    return (torch.empty(max(nbytes, 16), device=device, dtype=torch.uint8),
+            torch.empty(shape, device=device, dtype=torch.float32), torch.empty(shape, device=device, dtype=torch.int64))
+
+
+def _offsets_ok(what, offsets, shape, device, float32=True, contiguous=False):
+    """offsets must be the tables `shape` on `device`; float32 / contiguous: whether the entry also insists on that.  Returns
+    them contiguous."""
+    if tuple(offsets.shape) != shape or offsets.device != device or (float32 and offsets.dtype != torch.float32) or \
+            (contiguous and not offsets.is_contiguous()):
+        want = ("contiguous " if contiguous else "") + ("float32 " if float32 else "")
+        got = f"{offsets.dtype} " if float32 else ""
+        raise _lib.StemGNNHipError(f"{what}: offsets must be {want}{shape} on {device}, got {got}{tuple(offsets.shape)} "
+                                   f"on {offsets.device}")
+    return offsets.contiguous()
+
+
+def _out_like(what, forecast, out, float32=True):
+    """out=None: a new tensor (and forecast made contiguous); otherwise forecast and out must be contiguous tensors of one
+    shape on one device already (float32: whether the entry also insists on out's dtype).  Returns (forecast, out)."""
+    if out is None:
+        forecast = forecast.contiguous()
+        return forecast, torch.empty_like(forecast)
+    _require_gpu(out, "out")
+    if not forecast.is_contiguous() or not out.is_contiguous() or out.shape != forecast.shape or \
+            out.device != forecast.device or (float32 and out.dtype != torch.float32):
+        raise _lib.StemGNNHipError(f"{what}: with out=, forecast and out must be contiguous {'float32 ' if float32 else ''}"
+                                   f"tensors of one shape on one device")
+    return forecast, out
+
+
 def conformal_fit(target, forecast, pairs, coverage, per_step=True, per_node=False, ignore_nan=False):
     """Split-conformal offsets of the quantile pairs (``stemgnn_conformal_fit``): target [count,H,N], forecast [count,Q,H,N] fp32,
     pairs = P (lo, hi) rows, coverage = their P nominal coverages.  Returns (offsets fp32, counts int64), both device tensors
@@ -1638,25 +1691,10 @@ def conformal_fit(target, forecast, pairs, coverage, per_step=True, per_node=Fal
     k = ceil((m + 1) coverage (1 - 1e-12)) of its m scores, +inf where k > m.  ignore_nan: NaN targets are left out (otherwise
     they count as +inf)."""
     lib = _lib.load()
-    _require_gpu(target, "target")
-    _require_gpu(forecast, "forecast")
-    if target.dim() != 3 or forecast.dim() != 4 or (forecast.shape[0],) + tuple(forecast.shape[2:]) != tuple(target.shape):
-        raise _lib.StemGNNHipError(f"conformal_fit: target must be [count,H,N] and forecast [count,Q,H,N], got "
-                                   f"{tuple(target.shape)} / {tuple(forecast.shape)}")
-    if target.device != forecast.device:
-        raise _lib.StemGNNHipError(f"conformal_fit: target is on {target.device}, forecast on {forecast.device}")
-    target, forecast = target.contiguous(), forecast.contiguous()
-    C, H, N = target.shape
-    Q = forecast.shape[1]
-    P, lo, hi = _conformal_pairs(pairs, Q)
-    if len(coverage) != P:
-        raise ValueError(f"conformal_fit: {P} pairs but {len(coverage)} coverages")
-    dev = target.device
-    shape = (P, H if per_step else 1, N if per_node else 1)
+    target, forecast, P, lo, hi = _fit_inputs("conformal_fit", target, forecast, pairs, coverage)
+    C, Q, H, N = forecast.shape
     nbytes = lib.stemgnn_conformal_scratch_bytes(C, H, N, P, int(bool(per_step)), int(bool(per_node)))
-    scratch = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
-    offsets = torch.empty(shape, device=dev, dtype=torch.float32)
-    counts = torch.empty(shape, device=dev, dtype=torch.int64)
+    scratch, offsets, counts = _fit_outputs(nbytes, _tables((P,), H, N, per_step, per_node), target.device)
     _lib.check(lib.stemgnn_conformal_fit(target.data_ptr(), forecast.data_ptr(), C, Q, H, N, P, lo, hi,
                                          _lib.host_floats(coverage, _lib.c_double), int(bool(per_step)), int(bool(per_node)),
                                          int(bool(ignore_nan)), scratch.data_ptr(), offsets.data_ptr(), counts.data_ptr(),
@@ -1675,20 +1713,9 @@ def conformal_apply(forecast, offsets, pairs, per_step=True, per_node=False, out
         raise _lib.StemGNNHipError(f"conformal_apply: forecast must be [count,Q,H,N], got {tuple(forecast.shape)}")
     C, Q, H, N = forecast.shape
     P, lo, hi = _conformal_pairs(pairs, Q)
-    shape = (P, H if per_step else 1, N if per_node else 1)
-    if tuple(offsets.shape) != shape or offsets.device != forecast.device:
-        raise _lib.StemGNNHipError(f"conformal_apply: offsets must be {shape} on {forecast.device}, got {tuple(offsets.shape)} "
-                                   f"on {offsets.device}")
-    if out is None:
-        forecast = forecast.contiguous()
-        out = torch.empty_like(forecast)
-    else:
-        _require_gpu(out, "out")
-        if not forecast.is_contiguous() or not out.is_contiguous() or out.shape != forecast.shape or \
-                out.device != forecast.device:
-            raise _lib.StemGNNHipError("conformal_apply: with out=, forecast and out must be contiguous tensors of one shape on "
-                                       "one device")
-    _lib.check(lib.stemgnn_conformal_apply(forecast.data_ptr(), offsets.contiguous().data_ptr(), C, Q, H, N, P, lo, hi,
+    offsets = _offsets_ok("conformal_apply", offsets, _tables((P,), H, N, per_step, per_node), forecast.device, float32=False)
+    forecast, out = _out_like("conformal_apply", forecast, out, float32=False)
+    _lib.check(lib.stemgnn_conformal_apply(forecast.data_ptr(), offsets.data_ptr(), C, Q, H, N, P, lo, hi,
                                            int(bool(per_step)), int(bool(per_node)), out.data_ptr(), _stream()),
                "conformal_apply")
     return out
@@ -1721,27 +1748,12 @@ def seasonal_fit(target, forecast, origin, pairs, coverage, season, per_step=Tru
     (period, K, phase).  Returns (offsets fp32, counts int64) [K, P, Hg, Ng]: slice s is conformal_fit over the bucket's
     elements (+inf / 0 for an empty bucket)."""
     lib = _lib.load()
-    _require_gpu(target, "target")
-    _require_gpu(forecast, "forecast")
-    if target.dim() != 3 or forecast.dim() != 4 or (forecast.shape[0],) + tuple(forecast.shape[2:]) != tuple(target.shape):
-        raise _lib.StemGNNHipError(f"seasonal_fit: target must be [count,H,N] and forecast [count,Q,H,N], got "
-                                   f"{tuple(target.shape)} / {tuple(forecast.shape)}")
-    if target.device != forecast.device:
-        raise _lib.StemGNNHipError(f"seasonal_fit: target is on {target.device}, forecast on {forecast.device}")
-    target, forecast = target.contiguous(), forecast.contiguous()
-    C, H, N = target.shape
-    Q = forecast.shape[1]
-    P, lo, hi = _conformal_pairs(pairs, Q)
-    if len(coverage) != P:
-        raise ValueError(f"seasonal_fit: {P} pairs but {len(coverage)} coverages")
+    target, forecast, P, lo, hi = _fit_inputs("seasonal_fit", target, forecast, pairs, coverage)
+    C, Q, H, N = forecast.shape
     period, K, phase = _season("seasonal_fit", season)
-    dev = target.device
-    optr, origin0, keep = _origins("seasonal_fit", origin, C, dev)
-    shape = (K, P, H if per_step else 1, N if per_node else 1)
+    optr, origin0, keep = _origins("seasonal_fit", origin, C, target.device)
     nbytes = lib.stemgnn_seasonal_scratch_bytes(C, H, N, P, K, int(bool(per_step)), int(bool(per_node)))
-    scratch = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
-    offsets = torch.empty(shape, device=dev, dtype=torch.float32)
-    counts = torch.empty(shape, device=dev, dtype=torch.int64)
+    scratch, offsets, counts = _fit_outputs(nbytes, _tables((K, P), H, N, per_step, per_node), target.device)
     _lib.check(lib.stemgnn_seasonal_fit(target.data_ptr(), forecast.data_ptr(), optr, origin0, C, Q, H, N, P, lo, hi,
                                         _lib.host_floats(coverage, _lib.c_double), int(bool(per_step)), int(bool(per_node)),
                                         int(bool(ignore_nan)), period, K, phase, scratch.data_ptr(), offsets.data_ptr(),
@@ -1763,21 +1775,10 @@ def seasonal_apply(forecast, offsets, origin, pairs, season, per_step=True, per_
     C, Q, H, N = forecast.shape
     P, lo, hi = _conformal_pairs(pairs, Q)
     period, K, phase = _season("seasonal_apply", season)
-    shape = (K, P, H if per_step else 1, N if per_node else 1)
-    if tuple(offsets.shape) != shape or offsets.device != forecast.device or offsets.dtype != torch.float32:
-        raise _lib.StemGNNHipError(f"seasonal_apply: offsets must be float32 {shape} on {forecast.device}, got {offsets.dtype} "
-                                   f"{tuple(offsets.shape)} on {offsets.device}")
-    if out is None:
-        forecast = forecast.contiguous()
-        out = torch.empty_like(forecast)
-    else:
-        _require_gpu(out, "out")
-        if not forecast.is_contiguous() or not out.is_contiguous() or out.shape != forecast.shape or \
-                out.device != forecast.device or out.dtype != torch.float32:
-            raise _lib.StemGNNHipError("seasonal_apply: with out=, forecast and out must be contiguous float32 tensors of one "
-                                       "shape on one device")
+    offsets = _offsets_ok("seasonal_apply", offsets, _tables((K, P), H, N, per_step, per_node), forecast.device)
+    forecast, out = _out_like("seasonal_apply", forecast, out)
     optr, origin0, keep = _origins("seasonal_apply", origin, C, forecast.device)
-    _lib.check(lib.stemgnn_seasonal_apply(forecast.data_ptr(), offsets.contiguous().data_ptr(), optr, origin0, C, Q, H, N,
+    _lib.check(lib.stemgnn_seasonal_apply(forecast.data_ptr(), offsets.data_ptr(), optr, origin0, C, Q, H, N,
                                           int(bool(rearrange)), P, lo, hi, int(bool(per_step)), int(bool(per_node)), period, K,
                                           phase, out.data_ptr(), _stream()), "seasonal_apply")
     return out
@@ -1793,11 +1794,7 @@ def _finish_stages(what, forecast, offsets, pairs, per_step, per_node):
         raise ValueError(f"{what}: offsets= needs pairs= (the (lo, hi) rows they belong to)")
     _, Q, H, N = forecast.shape
     P, lo, hi = _conformal_pairs(pairs, Q)
-    shape = (P, H if per_step else 1, N if per_node else 1)
-    if tuple(offsets.shape) != shape or offsets.device != forecast.device or offsets.dtype != torch.float32:
-        raise _lib.StemGNNHipError(f"{what}: offsets must be float32 {shape} on {forecast.device}, got {offsets.dtype} "
-                                   f"{tuple(offsets.shape)} on {offsets.device}")
-    offsets = offsets.contiguous()
+    offsets = _offsets_ok(what, offsets, _tables((P,), H, N, per_step, per_node), forecast.device)
     return offsets.data_ptr(), P, lo, hi, offsets
 
 
@@ -1812,15 +1809,7 @@ def quantile_finish(forecast, rearrange=False, offsets=None, pairs=None, per_ste
         raise _lib.StemGNNHipError(f"quantile_finish: forecast must be float32 [count,Q,H,N], got {forecast.dtype} "
                                    f"{tuple(forecast.shape)}")
     optr, P, lo, hi, keep = _finish_stages("quantile_finish", forecast, offsets, pairs, per_step, per_node)
-    if out is None:
-        forecast = forecast.contiguous()
-        out = torch.empty_like(forecast)
-    else:
-        _require_gpu(out, "out")
-        if not forecast.is_contiguous() or not out.is_contiguous() or out.shape != forecast.shape or \
-                out.device != forecast.device or out.dtype != torch.float32:
-            raise _lib.StemGNNHipError("quantile_finish: with out=, forecast and out must be contiguous float32 tensors of one "
-                                       "shape on one device")
+    forecast, out = _out_like("quantile_finish", forecast, out)
     C, Q, H, N = forecast.shape
     _lib.check(lib.stemgnn_quantile_finish(forecast.data_ptr(), C, Q, H, N, int(bool(rearrange)), optr, P, lo, hi,
                                            int(bool(per_step)), int(bool(per_node)), out.data_ptr(), _stream()),
@@ -1871,11 +1860,7 @@ def quantile_store_seasonal(steps, target, pos, out_forecast, out_target, rearra
     if t_dev is None or t_dev.dtype != torch.int64 or t_dev.device != steps.device or t_dev.numel() < 1:
         raise _lib.StemGNNHipError("quantile_store_seasonal: t_dev must be an int64 tensor on the steps' device")
     P, lo, hi = _conformal_pairs(pairs, Q)
-    shape = (K, P, H if per_step else 1, N if per_node else 1)
-    if tuple(offsets.shape) != shape or offsets.device != steps.device or offsets.dtype != torch.float32 or \
-            not offsets.is_contiguous():
-        raise _lib.StemGNNHipError(f"quantile_store_seasonal: offsets must be contiguous float32 {shape} on {steps.device}, "
-                                   f"got {offsets.dtype} {tuple(offsets.shape)} on {offsets.device}")
+    _offsets_ok("quantile_store_seasonal", offsets, _tables((K, P), H, N, per_step, per_node), steps.device, contiguous=True)
     _lib.check(lib.stemgnn_quantile_store_seasonal(steps.data_ptr(), target.data_ptr(), pos.data_ptr(), t_dev.data_ptr(),
                                                    B, Q, H, N, int(bool(rearrange)), offsets.data_ptr(), P, lo, hi,
                                                    int(bool(per_step)), int(bool(per_node)), period, K, phase,

@@ -310,3 +310,32 @@ def test_seasonal_store_entry_on_a_batch():
         want = cal.apply(torch.sort(steps, dim=1, stable=True).values, origin=-9 + T_OFFSET)
         assert same_bits(slab[2:4], want[:2])                     # the third row is beyond the capacity
         assert bool((slab[:2] == 0).all()) and bool((targets[2:4] == 1).all()) and bool((targets[:2] == 0).all())
+
+
+@pytest.mark.parametrize("N", (4, 5), ids=("float4", "scalar"))
+@pytest.mark.parametrize("Q", (3, 17, 32))
+@pytest.mark.parametrize("rearrange", (False, True), ids=("as-is", "rearrange"))
+def test_seasonal_store_column_kernel_paths(rearrange, Q, N):
+    """the seasonal store through every path of the shared column kernel, against numpy bit for bit: one LDS plane (as-is) and
+    two (rearrange); Q = 17 is the first value past the float4 form's limit of 16, Q = 32 shrinks the workgroup to 128 threads
+    whose two planes fill 32 KB exactly; N = 4 takes the float4 form, N = 5 the scalar one with a ragged last column block.
+    B = 3 rows at pos = 2 of capacity 4: the third row is dropped.  Season (7, 3, 2) with t_dev = -11: the stored rows' steps
+    fall in buckets (2, 2) and (2, 0)."""
+    from stemgnn_amd import ops
+    B, Hs, cap, season, t0 = 3, 2, 4, (7, 3, 2), -11
+    assert [[R.bucket(t0 + b + h, *season) for h in range(Hs)] for b in range(2)] == [[2, 2], [2, 0]]
+    rng = np.random.default_rng(SEED + 64 * Q + 2 * N + int(rearrange))
+    pairs = tuple((i, Q - 1 - i) for i in range(Q // 2))
+    steps = rng.normal(size=(B, Q, Hs, N)).astype(np.float32)
+    target = rng.normal(size=(B, Hs, N)).astype(np.float32)
+    offsets = np.abs(rng.normal(size=(season[1], len(pairs), Hs, N))).astype(np.float32)
+    slab, targets = torch.zeros(cap, Q, Hs, N, device=DEV), torch.zeros(cap, Hs, N, device=DEV)
+    ops.quantile_store_seasonal(torch.from_numpy(steps).to(DEV), torch.from_numpy(target).to(DEV),
+                                torch.tensor([2], dtype=torch.int64, device=DEV), slab, targets, rearrange=rearrange,
+                                offsets=torch.from_numpy(offsets).to(DEV), pairs=pairs, per_step=True, per_node=True,
+                                seasonal=season, t_dev=torch.tensor([t0], dtype=torch.int64, device=DEV))
+    ordered = np.sort(steps, axis=1, kind="stable") if rearrange else steps
+    want = R.apply_np(ordered, offsets, t0, pairs, season)
+    assert same_bits(slab[2:], torch.from_numpy(want[:2]))
+    assert same_bits(targets[2:], torch.from_numpy(target[:2]))
+    assert bool((slab[:2] == 0).all()) and bool((targets[:2] == 0).all())
