@@ -620,6 +620,43 @@ __device__ __forceinline__ float gru_matvec(const gru_f2 (&wr)[32], float hv, fl
   if constexpr ((KU & 3) != 0) a0 = __builtin_elementwise_fma(wr[(KU - 2) >> 1], bc.pair(KU - 2), a0);
   return (a0.x + a1.x) + (a0.y + a1.y);
 }
+// The same sums with the k range FOLDED over the two 32-lane halves of the wave (gru_cluster4.h, GRU_BWD_FOLD; slices of
+// U <= 64 units).  Lanes l and 32 + l both own the units j0 = 2 l and j1 = 2 l + 1; the lower half runs their a0 chains
+// (k pairs 4i, 4i+1: the even pairs of gru_matvec, the tail pair of KU % 4 == 2 among them), the upper half their a1 chains
+// (k pairs 4i+2, 4i+3).  w[t][i] = the weight pair of unit j_t for this half's i-th k pair.  A lane walks half of the k,
+// so it needs half of the broadcast values: NP ds_read_b64 of the wave's private row (the 32 lanes of a half read one
+// address) and no v_readlane, against 16 v_readlane + 11 ds_read_b128 at KU = 58.  Every chain keeps its k order; three
+// v_permlane32_swap + add rounds then form (a0.x + a1.x) + (a0.y + a1.y): the swap exchanges the upper half of its first
+// operand with the lower half of its second, so after swap(x chain, y chain) the lower half holds (a0.x, a1.x) and the upper
+// (a0.y, a1.y) of one unit, and after swap(sum of j0, sum of j1) lane l holds both halves of j0's sum and lane 32 + l of j1's.
+// The result is pv(2 l) in lane l and pv(2 l + 1) in lane 32 + l, bit-identical to gru_matvec's.
+// KU % 4 == 2: the upper half's last pair (k = KU, KU + 1) does not exist.  Its weights are -0 and its broadcast values
+// +0 (lanes >= kn polled nothing), and fma(-0, +0, a) == a for every a, the sign of a zero included.
+constexpr int gru_fold_pairs(int KU) { return (KU + 3) / 4; }
+constexpr int GRU_FOLD_PMAX = 16;
+template <int KU>
+__device__ __forceinline__ float gru_matvec_fold(const gru_f2 (&w)[2][GRU_FOLD_PMAX], float dv, float* lrow, int lane) {
+  static_assert(KU <= 64 && (KU & 1) == 0, "folded mat-vec: slices of at most 64 units");
+  constexpr int NP = gru_fold_pairs(KU);
+  lrow[lane] = dv;
+  asm volatile("" ::: "memory");                     // program order is enough: one wave's LDS operations complete in order
+  const float* lr = lrow + ((lane >> 5) << 1);
+  gru_f2 d[NP];
+#pragma unroll
+  for (int i = 0; i < NP; ++i) d[i] = *reinterpret_cast<const gru_f2*>(lr + 4 * i);
+  __builtin_amdgcn_sched_barrier(0);                 // all reads in flight before the first fma
+  gru_f2 c0 = {0.f, 0.f}, c1 = {0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    c0 = __builtin_elementwise_fma(w[0][i], d[i], c0);
+    c1 = __builtin_elementwise_fma(w[1][i], d[i], c1);
+  }
+  auto swap_add = [](float a, float b) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
+    return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
+  };
+  return swap_add(swap_add(c0.x, c0.y), swap_add(c1.x, c1.y));
+}
 __device__ __forceinline__ float gru_poll_lane(const gru_u64* g, unsigned tag, bool active, int* status) {
   float v = 0.f;
   if (active) v = gru_consume(g, tag, status);

@@ -10,6 +10,11 @@
 //     v_pk_fma); backward: 3P, (gate g, owner slice q) -- poll their slice's granules (the workgroup's own units included:
 //     every slice arrives through the exchange), multiply, leave a partial sum in LDS.  Nothing else: a global store or
 //     load issued ahead of a poll would hold the poll back (vmcnt retires in order).
+//     Lane maps of the multiply (the poll is always lane = k of the slice).  Forward, slices of 33..40 units: lane l of
+//     lane set t holds output 64 t + l = gate * U + unit, every k (GRU_FWD_PACK); otherwise lane = unit for three gates.
+//     Backward, one slice per wave and KU > 32: lanes l and 32 + l hold the units 2 l and 2 l + 1, the lower half of the
+//     wave the k pairs (4i, 4i+1), the upper half (4i+2, 4i+3); lane l ends with the sum of unit 2 l, lane 32 + l with
+//     that of 2 l + 1 (GRU_BWD_FOLD); KU = 32 and two slices per wave (P = 6): lane = unit, every k.
 //   * ONE GATE wave: barrier -> partial sums and inputs from LDS -> gate math -> granule stores -> results into an LDS
 //     stash.  No global loads, no global data stores, no mat-vec.
 //   * ONE CHORE wave: it fetches the next step's gate inputs from global memory into LDS (one step ahead), moves the
@@ -117,7 +122,7 @@ __device__ __forceinline__ void gru4_poll2(const gru_u64* g0, const gru_u64* g1,
   v[1] = act1 ? __uint_as_float((unsigned)x1) : 0.f;
 }
 // A/B hooks, default on; 0 restores the instruction streams they replaced (csrc/Makefile: libstemgnn_hip_gruref.so has
-// both off).  Neither changes a bit of the results (tests/test_hip_gru_packed.py).
+// all three off).  None changes a bit of the results (tests/test_hip_gru_packed.py, tests/test_hip_gru_bwd_fold.py).
 // GRU_FWD_PACK: forward mat-vec waves of the KU = 34 and 40 instantiations (slices of 33..40 units) hold lane -> (gate,
 //   unit) over two lane sets instead of lane -> unit for three gates: two v_pk_fma per k-pair instead of three
 //   (gru_matvec2).  KU = 32 (slices of <= 32 units: hidden <= 224, the small models) stays unpacked: nothing was measured
@@ -125,8 +130,19 @@ __device__ __forceinline__ void gru4_poll2(const gru_u64* g0, const gru_u64* g1,
 //   train step's overlapped-or-serialised schedule decision from run to run.
 // GRU_PART_VEC: the partial sums lie with the slice index contiguous per output, so the gate wave fetches them with
 //   ds_read_b128 (forward P = 7: six instead of 21 ds_read_b32; backward P = 4: three instead of 12).
+// GRU_BWD_FOLD: backward mat-vec waves of the OW = 1 instantiations (P = 1, 2, 4) with KU = 48, 58, 64 hold lane -> two
+//   units (2 l, 2 l + 1 in lanes l and 32 + l) and split the k pairs over the two lane halves instead of lane -> unit for
+//   every k (gru_matvec_fold): a lane needs half of the polled values, read from the wave's LDS row with ds_read_b64, and
+//   no v_readlane; three v_permlane32_swap + add rounds form each unit's sum in gru_matvec's association.  OW = 2 (P = 6)
+//   keeps the readlane mat-vec: folded, the two slices' 128 weight registers and 32 values in flight leave <6,64,2> at 168
+//   registers with 64 bytes of scratch (spills) under its 170-register bound.  KU = 32 (reached with P = 1 only: hidden
+//   <= 32, the small models) keeps it too, for the forward's reason: nothing to gain in those few-microsecond steps, and
+//   the folded kernel moved their timing enough to flip the train step's schedule decision.
 #ifndef GRU_FWD_PACK
 #define GRU_FWD_PACK 1
+#endif
+#ifndef GRU_BWD_FOLD
+#define GRU_BWD_FOLD 1
 #endif
 #ifndef GRU_PART_VEC
 #define GRU_PART_VEC 1
@@ -174,6 +190,7 @@ constexpr int gru4_static_lds_floats(int P, int nin, int nout) {
 // dynamic LDS the PACKED forward instantiations reserve without using it (see the launcher): what is left of 156 KiB
 // beside their static part[2][128 rows] + lrow + gin + stash; 0 = the instantiation does not pack
 constexpr bool gru4_fwd_packs(int KU) { return GRU_FWD_PACK != 0 && KU > 32 && KU <= 40; }
+constexpr bool gru4_bwd_folds(int KU, int OW) { return GRU_BWD_FOLD != 0 && OW == 1 && KU > 32; }
 constexpr size_t gru4_fwd_hog_bytes(int P, int KU) {
   return gru4_fwd_packs(KU)
              ? (size_t)156 * 1024 - sizeof(float) * (2 * 128 * (GRU_PART_VEC ? gru4_part_stride(P) : P) + P * 64 + 2 * 3 * 64 + 2 * 5 * 64)
@@ -202,8 +219,16 @@ constexpr int GRU4_WMAX = 16;            // window lengths up to this have dW_ih
 #ifndef GRU_SW_SLEEP
 #define GRU_SW_SLEEP 30                  // ... issued this long (x 64 clocks) behind the step's barrier: AFTER the gate wave's granule
 #endif                                   // stores (measured, backward recurrence at PEMS07: sleep 0 / 10: 304 / 300 us, 30: 268; plain stores 268, none 259)
+// x 64 cycles after the barrier (the backward gate phase takes ~450).  As in the forward, the chore wave is in the step's
+// barrier: behind the folded mat-vec its pause of 10 closed the step.  Backward in the step at PEMS07, pause 14 / 12 / 10 / 9 /
+// 8 / 7 / 6 / 5 / 4: 263 / 254 / 244 / 241 / 237 / 236 / 239 / 252 / 254 us (profiles/gru_bwd_fold_ab.txt): at 5 and below its
+// loads and stores get in front of the granule stores; 7 keeps two notches from that edge.  The instantiations that do not
+// fold (two slices per wave, KU = 32, or GRU_BWD_FOLD = 0) keep the 10 tuned for the readlane mat-vec (GRU_CHORE_SLEEP_B_RL).
 #ifndef GRU_CHORE_SLEEP_B
-#define GRU_CHORE_SLEEP_B 10
+#define GRU_CHORE_SLEEP_B 7
+#endif
+#ifndef GRU_CHORE_SLEEP_B_RL
+#define GRU_CHORE_SLEEP_B_RL 10
 #endif
 template <int P, int KU, bool RS = true>     // RS = false: no `reserve` stores (stemgnn_gru_fwd_infer)
 __global__ __launch_bounds__((P + 2) * 64) void gru_fwd_cluster4_kernel(const float* __restrict__ gi, const float* __restrict__ w_hh,
@@ -418,7 +443,8 @@ __global__ __launch_bounds__((3 * P / OW + 2 + (SW ? 1 : 0)) * 64) void gru_bwd_
   // written or read and the kernel that formed it leaves the backward's critical chain; `dout` is unused then
   static_assert(P % OW == 0 && (OW == 1 || OW == 2), "owner slices per wave");
   constexpr int NMV = 3 * P / OW;
-  typedef Gru4Part<64, NMV> Part;                        // row = lane (own unit), one partial sum per mat-vec wave
+  constexpr bool FOLD = gru4_bwd_folds(KU, OW);          // (else the readlane mat-vec: see GRU_BWD_FOLD)
+  typedef Gru4Part<64, NMV> Part;                        // row = unit, one partial sum per mat-vec wave
   __shared__ __attribute__((aligned(16))) float part[2][Part::FLOATS];
   __shared__ __attribute__((aligned(16))) float lrow[NMV][64];
   __shared__ float bin[2][6][64];                        // dh_out, r, z, n, W_hn h + b_hn, h_prev
@@ -440,21 +466,42 @@ __global__ __launch_bounds__((3 * P / OW + 2 + (SW ? 1 : 0)) * 64) void gru_bwd_
   if (wave < NMV) {
     // ---------------- mat-vec wave (gate g, owner slot q rotated by p): reduction slice j = g*Hd + units of that owner
     const int g = wave / (P / OW), q0 = (wave - g * (P / OW)) * OW;
-    gru_f2 wr[OW][32];
+    gru_f2 wr[OW][32];                                   // lane = unit, every k
+    gru_f2 wf[2][GRU_FOLD_PMAX];                         // FOLD: lane -> units 2 (lane & 31) + t, the k pairs of its half
     int kn[OW];
     const gru_u64* pollp[OW];                            // parity 0
 #pragma unroll
     for (int o = 0; o < OW; ++o) {
       const int k0 = ((q0 + o + p) % P) * U;
       kn[o] = max(0, min(Hd, k0 + U) - k0);
-      const float* wcol = w_hh + ((size_t)g * Hd + (kn[o] > 0 ? k0 : 0)) * Hd + gu;
+      if constexpr (FOLD) {
+        const int half = lane >> 5;
 #pragma unroll
-      for (int kk = 0; kk < KU; ++kk) {
-        const float v = wcol[(size_t)(kk < kn[o] ? kk : 0) * Hd];
-        wr[o][kk >> 1][kk & 1] = (lane_ok && kk < kn[o]) ? v : 0.f;
+        for (int t = 0; t < 2; ++t) {
+          const int j = 2 * (lane & 31) + t;
+          const bool live = j < un;
+          const float* wcol = w_hh + ((size_t)g * Hd + (kn[o] > 0 ? k0 : 0)) * Hd + u0 + (live ? j : 0);
+#pragma unroll
+          for (int i = 0; i < gru_fold_pairs(KU); ++i)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+              const int kk = 4 * i + 2 * half + c;
+              const float v = wcol[(size_t)(kk < kn[o] ? kk : 0) * Hd];
+              wf[t][i][c] = (live && kk < kn[o]) ? v : (kk < KU ? 0.f : -0.f);     // (kk >= KU: gru_matvec_fold)
+            }
+        }
+      } else {
+        const float* wcol = w_hh + ((size_t)g * Hd + (kn[o] > 0 ? k0 : 0)) * Hd + gu;
+#pragma unroll
+        for (int kk = 0; kk < KU; ++kk) {
+          const float v = wcol[(size_t)(kk < kn[o] ? kk : 0) * Hd];
+          wr[o][kk >> 1][kk & 1] = (lane_ok && kk < kn[o]) ? v : 0.f;
+        }
       }
       pollp[o] = xbuf + (size_t)b * H3 + (size_t)g * Hd + k0 + (lane < kn[o] ? lane : 0);
     }
+    // where this lane's partial sum goes: FOLD leaves pv(2 l) in lane l and pv(2 l + 1) in lane 32 + l
+    const int prow = FOLD ? 2 * (lane & 31) + (lane >> 5) : lane;
     const size_t par = (size_t)B * H3;
 #ifdef GRU_PROF
     long long c_a = 0, c_b = 0, c_c = 0;
@@ -466,7 +513,8 @@ __global__ __launch_bounds__((3 * P / OW + 2 + (SW ? 1 : 0)) * 64) void gru_bwd_
       float pv;
       if constexpr (OW == 1) {
         const float dv = gru4_poll<GRU_POLL_PRE_B>(pollp[0] + (tag & 1) * par, tag, lane < kn[0], status);
-        pv = gru_matvec<KU, (KU <= 58 ? GRU_NR4 : (GRU_NR4 > 24 ? GRU_NR4 : 24))>(wr[0], dv, lrow[wave], lane);
+        if constexpr (FOLD) pv = gru_matvec_fold<KU>(wf, dv, lrow[wave], lane);
+        else pv = gru_matvec<KU, (KU <= 58 ? GRU_NR4 : (GRU_NR4 > 24 ? GRU_NR4 : 24))>(wr[0], dv, lrow[wave], lane);
       } else {
         float dv[2];
         gru4_poll2<GRU_POLL_PRE_B>(pollp[0] + (tag & 1) * par, pollp[1] + (tag & 1) * par, tag, lane < kn[0], lane < kn[1],
@@ -474,7 +522,7 @@ __global__ __launch_bounds__((3 * P / OW + 2 + (SW ? 1 : 0)) * 64) void gru_bwd_
         pv = gru_matvec<KU, 64>(wr[0], dv[0], lrow[wave], lane);
         pv += gru_matvec<KU, 64>(wr[OW - 1], dv[1], lrow[wave], lane);
       }
-      part[tag & 1][Part::at(lane, wave)] = pv;
+      part[tag & 1][Part::at(prow, wave)] = pv;
       GRU_T(t2);
       GRU_ACC(c_b, t2, t0);                              // (poll + mat-vec together: the poll's end is inside the if constexpr)
       gru_lds_barrier();                                 // B_s
@@ -549,7 +597,7 @@ __global__ __launch_bounds__((3 * P / OW + 2 + (SW ? 1 : 0)) * 64) void gru_bwd_
       if (have) { dr = bout[(s + 1) & 1][0][lane]; dz = bout[(s + 1) & 1][1][lane]; dn = bout[(s + 1) & 1][2][lane]; dnr = bout[(s + 1) & 1][3][lane]; }
       float xv[GRU4_WMAX];
       if (have) wih_x(s + 1, xv);                        // scalar-cache loads: not in the vector memory pipeline's way
-      __builtin_amdgcn_s_sleep(GRU_CHORE_SLEEP_B);       // let the granule stores of gate(s) go first
+      __builtin_amdgcn_s_sleep(FOLD ? GRU_CHORE_SLEEP_B : GRU_CHORE_SLEEP_B_RL);      // the granule stores of gate(s) go first
       if (s >= 2) fetch(s - 2, val);
       if (have && lane_ok) put((size_t)(s + 1) * B + b, dr, dz, dn, dnr);
       if (have) wih(xv, dr, dz, dn);
