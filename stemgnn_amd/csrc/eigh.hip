@@ -526,6 +526,14 @@ __global__ __launch_bounds__(64) void eig_invit_kernel(const float* __restrict__
   double* DU2 = work + 3 * NN + j;
   double* X = work + 4 * NN + j;
   unsigned char* PV = reinterpret_cast<unsigned char*>(work + 5 * NN) + j;
+  if (aux[0] == 0.0) {
+    // T is identically zero (L = 0: a diagonal adjacency, self-loops only).  Every eigenvalue is 0 and any orthonormal basis
+    // serves; T - lam I has no entry above the denormals, 1 / pivot overflows and the solves below would return NaN.
+    // z_j = e_j; `work` stays unwritten and the cluster pass returns on the same test.
+    float* z = Z + (size_t)j * N;
+    for (int i = 0; i < N; ++i) z[i] = i == j ? 1.f : 0.f;
+    return;
+  }
   const double lam = lam64[j];
   const double eps3 = 2.3e-16 * fmax(aux[0], 1e-300);
   // pivoted LU of T - lam I (LAPACK gttrf): row i is finished when row i + 1 has been looked at
@@ -654,6 +662,7 @@ __global__ __launch_bounds__(64) void eig_cluster_fix_kernel(const double* __res
     lam64 += bz * (sscr / 2); aux += bz * (sscr / 2); work += bz * (sscr / 2); Z += bz * sscr;
   }
   const int j0 = blockIdx.x, lane = threadIdx.x;
+  if (aux[0] == 0.0) return;             // T == 0: eig_invit_kernel returned the unit vectors and left no LU in `work`
   const double tol = 1e-9 * fmax(aux[0], 1e-300);
   const bool prev_close = j0 > 0 && lam64[j0] - lam64[j0 - 1] < tol;
   const bool next_close = j0 + 1 < N && lam64[j0 + 1] - lam64[j0] < tol;

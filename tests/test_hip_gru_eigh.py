@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from oracle import stemgnn_oracle as O
+from tests.helpers.eigh_cases import oracle_laplacian as _laplacian
 from tests.util import relerr
 
 pytestmark = pytest.mark.gpu
@@ -237,14 +238,6 @@ def test_gru_hand_tuned_pauses_only_change_the_time():
     assert tuned["h"] == untuned["h"] and tuned["grads"] == untuned["grads"]
     # a mis-tuned pause may cost time, not correctness; the calibrated build must not be the slower one by a margin
     assert tuned["fwd_us"] + tuned["bwd_us"] < 1.3 * (untuned["fwd_us"] + untuned["bwd_us"])
-
-
-def _laplacian(N, B=6, seed=0):
-    sd = O.det_state_dict(N, 12, 5, 3, seed=seed)
-    torch.manual_seed(seed)
-    x = torch.randn(B, 12, N)
-    att = O.self_graph_attention(O.gru_front(x, sd), sd["weight_key"], sd["weight_query"])
-    return O.laplacian_from_attention(att)[0]
 
 
 @pytest.mark.parametrize("N,sweeps", [(228, 0), (33, 0), (64, 0), (140, 0), (5, 0), (321, 0), (1024, 0), (2048, 0),
