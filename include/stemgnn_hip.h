@@ -1030,6 +1030,34 @@ int stemgnn_ensemble_scores(const float* target, const float* paths, const doubl
 int stemgnn_ensemble_scores_masked(const float* target, const float* paths, const double* mul, const double* add, long count,
                                    int S, int H, int N, int fair, double* scratch, double* out, long long* hist, void* stream);
 
+/* ---- scenario events: aggregates over node sets and crossing counts of sampled paths (csrc/events.hip) --
+ * De-normalisation, both entries: v = (double)x * mul[j] + add[j] in fp64, the product and the sum rounded separately (as in
+ * stemgnn_ensemble_scores), j the node (aggregate) or the column (events); mul == add == NULL: v = (double)x.
+ * aggregate: x [rows, N] fp32 and contiguous (paths: rows = count * S * H; targets: rows = count * H), weights [R, N] fp64 on the
+ *            device, out [rows, R] fp32:
+ *              out[row, r] = (float) sum over the nodes n with weights[r, n] != 0 of weights[r, n] * v_n
+ *            accumulated in fp64 (fused multiply-adds) in an order that depends on N and R alone, never on the row or on rows: a
+ *            pass computed batch by batch is the whole pass bit for bit.  A node whose weight is exactly 0 is not part of the
+ *            sum (a NaN there does not reach the group); a NaN inside a group propagates.  16-byte loads when N % 4 == 0 and x is
+ *            16-byte aligned, a scalar path otherwise.  R <= 32, N <= 4096.
+ * events:    paths [count, S, H, M] fp32 and contiguous (M: the node axis or an aggregated group axis), thr [M] fp64 on the
+ *            device, counts int32 [count, 2 H + 1, M].  E(s, h) = v > thr[m] when above == 1, v < thr[m] when above == 0, strict
+ *            fp64 comparisons: a NaN value or threshold is never in the event.  For origin c and column m:
+ *              counts[c, h, m]      = #{s : E(s, h)}                                            h < H   ("step")
+ *              counts[c, H + h, m]  = #{s : E(s, h) and no E(s, h') for h' < h}                 h < H   ("first")
+ *              counts[c, 2 H, m]    = #{s : the longest run of consecutive steps with E is >= min_run}  ("run")
+ *            A NaN breaks a run and is not a crossing.  Integers only: exact.  1 <= S <= 1024, 1 <= H <= 256.
+ * One launch each; no allocation, no host synchronisation, no memset, no global atomics (integer LDS adds in events only): the
+ * same bits on every run, capturable.
+ * SG_EINVAL (nothing launched): a NULL pointer other than mul / add; mul without add (or add without mul);
+ * aggregate: rows, N or R <= 0, R > 32, N > 4096, rows * R >= 2^31 (the grid is min(ceil(rows / 4), 2048));
+ * events: count, S, H or M <= 0, S > 1024, H > 256, min_run outside [1, H], above not 0 / 1, S * H * M, (2 H + 1) * M or the
+ * grid count * ceil(M / C) >= 2^31 (C the column tile, 1 .. 64). */
+int stemgnn_scenario_aggregate(const float* x, const double* weights, const double* mul, const double* add, long long rows,
+                               int N, int R, float* out, void* stream);
+int stemgnn_scenario_events(const float* paths, const double* thr, const double* mul, const double* add, long count, int S,
+                            int H, int M, int above, int min_run, int* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1294,6 +1294,14 @@ class LiveForecaster:
                                            self.seed if seed is None else seed, coupling, tails, self.graph_kw)
         return (bands[0], steps[0]) if return_paths else bands[0]
 
+    def event_odds(self, spec, paths=64, horizon=None, seed=None, coupling="independent", tails="linear"):
+        """The odds of an event (a math_utils.EventSpec) over the steps ahead of the last row pushed: `scenarios(...,
+        return_paths=True)` from the ring's head window, then `spec.count` on its paths.  Returns a math_utils.ScenarioEvents
+        with count = 1 (p_any, p_run, p_by, p_step, duration: device tensors, no sync).  The arguments are scenarios'; the
+        captured graph, the history slab and every calibrator are left untouched."""
+        _, steps = self.scenarios(paths=paths, horizon=horizon, seed=seed, coupling=coupling, tails=tails, return_paths=True)
+        return spec.count(steps[None])
+
     # -- matured pairs ------------------------------------------------------------------------------------------
     def matured(self):
         """(forecasts [m,(Q,)horizon,N], targets [m,horizon,N], origins int64 [m] ascending) of the stored forecasts whose targets

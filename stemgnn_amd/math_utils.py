@@ -109,6 +109,223 @@ class EnsembleScores:
         self.rank_uniformity = np.float64(((self.rank_histogram - expect) ** 2).sum() / expect) if total else np.float64("nan")
 
 
+MAX_GROUPS = 32                              # R of stemgnn_scenario_aggregate
+
+
+def group_weights(groups, N, reduce="mean"):
+    """The [R, N] float64 weight matrix of node groups (host tensor; `ops.scenario_aggregate` takes it).  groups: a [R, N]
+    tensor / array, used as it is, or a sequence of index sequences: 1 / len(g) ("mean") or 1 ("sum") on the members of g, 0
+    elsewhere.  Validated on the host: indices within [0, N), no empty group, no index twice in a group, R <= 32."""
+    if reduce not in ("mean", "sum"):
+        raise ValueError(f"group_weights: reduce is 'mean' or 'sum', got {reduce!r}")
+    N = int(N)
+    if N < 1:
+        raise ValueError(f"group_weights: N must be at least 1, got {N}")
+    if torch.is_tensor(groups) or isinstance(groups, np.ndarray):
+        w = groups.detach().cpu() if torch.is_tensor(groups) else torch.as_tensor(groups)
+        if w.dim() != 2 or w.shape[1] != N or w.shape[0] < 1 or w.is_complex() or w.dtype == torch.bool:
+            raise ValueError(f"group_weights: a weight matrix must be real and [R, {N}], got {w.dtype} {tuple(w.shape)}")
+        if w.shape[0] > MAX_GROUPS:
+            raise ValueError(f"group_weights: at most {MAX_GROUPS} groups, got {w.shape[0]}")
+        return w.to(torch.float64).contiguous()
+    groups = [list(g) for g in groups]
+    if not 1 <= len(groups) <= MAX_GROUPS:
+        raise ValueError(f"group_weights: 1 to {MAX_GROUPS} groups, got {len(groups)}")
+    w = torch.zeros(len(groups), N, dtype=torch.float64)
+    for r, g in enumerate(groups):
+        if not g:
+            raise ValueError(f"group_weights: group {r} is empty")
+        idx = [int(i) for i in g]
+        if any(i != j for i, j in zip(idx, g)) or min(idx) < 0 or max(idx) >= N:
+            raise ValueError(f"group_weights: group {r} has an index outside [0, {N})")
+        if len(set(idx)) != len(idx):
+            raise ValueError(f"group_weights: group {r} names an index twice")
+        w[r, idx] = 1.0 / len(idx) if reduce == "mean" else 1.0
+    return w
+
+
+def _brier(table, S):
+    """(brier, base_rate, skill) of a reliability table [..., S + 1, 2] of (n_j, o_j), fp64 on the host"""
+    n, o = table[..., 0].astype(np.float64), table[..., 1].astype(np.float64)
+    p = np.arange(S + 1, dtype=np.float64) / S
+    with np.errstate(divide="ignore", invalid="ignore"):
+        V = n.sum(axis=-1)
+        brier = (o * (1.0 - p) ** 2 + (n - o) * p ** 2).sum(axis=-1) / V
+        base = o.sum(axis=-1) / V
+        skill = np.where((base > 0) & (base < 1), 1.0 - brier / (base * (1.0 - base)), np.nan)
+    return brier, base, skill
+
+
+class EventScores:
+    """Verification of event probabilities against what happened, from one integer table (`ScenarioEvents.score`).
+    A forecast probability is j / S, j the number of paths in the event.  For each of "any" (the event at some step), "run" (at
+    least min_run steps in a row) and every single step:
+      reliability        int64 [M, S + 1, 2] = (n_j, o_j): the valid (origin, column) pairs whose forecast count was j, and those
+                         of them where the event occurred            (reliability_run; reliability_step [H, M, S + 1, 2])
+      brier              (1 / V) sum_j [o_j (1 - j / S)^2 + (n_j - o_j) (j / S)^2], V = sum_j n_j
+      base_rate          sum_j o_j / V
+      skill              1 - brier / (base_rate (1 - base_rate)), NaN when the base rate is 0 or 1 (or nothing is valid)
+    each overall (brier, brier_run, brier_step [H]) and per column (brier_column [M], brier_run_column, brier_step_column
+    [H, M]), numpy float64 computed on the host from the table: exact functions of integers.  valid: V of "any"."""
+
+    def __init__(self, table, S):
+        table = np.asarray(table, dtype=np.int64)                                # [2 + H, M, S + 1, 2]
+        self.S = int(S)
+        self.reliability, self.reliability_run, self.reliability_step = table[0], table[1], table[2:]
+        for suffix, t in (("", table[0]), ("_run", table[1]), ("_step", table[2:])):
+            pooled = t.sum(axis=-3)
+            for column, tab in (("", pooled), ("_column", t)):
+                b, r, s = _brier(tab, self.S)
+                whole = suffix != "_step" and not column
+                setattr(self, "brier" + suffix + column, np.float64(b) if whole else b)
+                setattr(self, "base_rate" + suffix + column, np.float64(r) if whole else r)
+                setattr(self, "skill" + suffix + column, np.float64(s) if whole else s)
+        self.valid = int(table[0][..., 0].sum())
+
+
+class ScenarioEvents:
+    """The counts of `ops.scenario_events` (int32 [count, 2H + 1, M], device) of S paths, read as probabilities (float64 device
+    tensors, no sync):
+      p_step [count, H, M]  the event at step h              p_by [count, H, M]   the event at some step <= h (first passage)
+      p_any [count, M]      the event at some step           p_run [count, M]     at least min_run steps in a row
+      duration [count, M]   the expected number of steps in the event
+    cat(parts) joins batches along the origins.  score(realised, ignore_nan=False) -> EventScores: `realised` is
+    `EventSpec.realised(target)`, the same counts of the one path that happened (S = 1) with `missing` [count, H, M].
+    ignore_nan: an (origin, column) with a missing (NaN) target at ANY step is left out of "any" and "run", a missing step out of
+    that step alone; without it a NaN target is "not in the event" (the strict comparison's answer) and everything is valid."""
+
+    def __init__(self, counts, S, missing=None):
+        if counts.dim() != 3 or counts.shape[1] % 2 != 1 or counts.dtype != torch.int32:
+            raise ValueError(f"ScenarioEvents: counts must be int32 [count, 2H + 1, M], got {counts.dtype} {tuple(counts.shape)}")
+        self.counts, self.S, self.missing = counts, int(S), missing
+        self.count, self.H, self.M = int(counts.shape[0]), int(counts.shape[1]) // 2, int(counts.shape[2])
+
+    @property
+    def step(self):
+        return self.counts[:, :self.H]
+
+    @property
+    def first(self):
+        return self.counts[:, self.H:2 * self.H]
+
+    @property
+    def run(self):
+        return self.counts[:, 2 * self.H]
+
+    @property
+    def p_step(self):
+        return self.step.double() / self.S
+
+    @property
+    def p_by(self):
+        return self.first.cumsum(dim=1).double() / self.S
+
+    @property
+    def p_any(self):
+        return self.first.sum(dim=1).double() / self.S
+
+    @property
+    def p_run(self):
+        return self.run.double() / self.S
+
+    @property
+    def duration(self):
+        return self.step.sum(dim=1).double() / self.S
+
+    @staticmethod
+    def cat(parts):
+        parts = list(parts)
+        if not parts or any(p.S != parts[0].S or p.counts.shape[1:] != parts[0].counts.shape[1:] for p in parts):
+            raise ValueError("ScenarioEvents.cat: the parts must share S, H and M")
+        missing = None if parts[0].missing is None else torch.cat([p.missing for p in parts])
+        return ScenarioEvents(torch.cat([p.counts for p in parts]), parts[0].S, missing)
+
+    def score(self, realised, ignore_nan=False):
+        if not isinstance(realised, ScenarioEvents) or realised.S != 1 or realised.counts.shape != self.counts.shape:
+            raise ValueError("ScenarioEvents.score: realised must be EventSpec.realised(target) of the same origins, steps and "
+                             "columns")
+        H, M, S = self.H, self.M, self.S
+        # kinds: any | run | step 0 .. H - 1; forecast count j and occurrence o of every (kind, origin, column)
+        j = torch.cat([self.first.sum(dim=1, keepdim=True), self.run[:, None], self.step], dim=1).long()
+        o = torch.cat([realised.first.sum(dim=1, keepdim=True), realised.run[:, None], realised.step], dim=1).long()
+        kinds = H + 2
+        k = torch.arange(kinds, device=j.device)[None, :, None]
+        m = torch.arange(M, device=j.device)[None, None, :]
+        key = ((k * M + m) * (S + 1) + j) * 2 + o
+        bins = kinds * M * (S + 1) * 2
+        if ignore_nan and realised.missing is not None:
+            gone = realised.missing.any(dim=1, keepdim=True)
+            key = torch.where(torch.cat([gone, gone, realised.missing], dim=1), torch.full_like(key, bins), key)
+        table = torch.bincount(key.reshape(-1), minlength=bins + 1)[:bins].reshape(kinds, M, S + 1, 2).cpu().numpy()   # the sync
+        out = np.empty_like(table)
+        out[..., 0] = table.sum(axis=-1)
+        out[..., 1] = table[..., 1]
+        return EventScores(out, S)
+
+
+class EventSpec:
+    """The definition of an event on scenario paths: value > threshold (above=True) or value < threshold, for at least `min_run`
+    consecutive steps where a run is asked for, per node or per GROUP of nodes.
+    threshold: a scalar or one value per column (node, or group with groups=), in raw units when mul / add are given.
+    groups / reduce: `group_weights`' arguments: the event is about the mean (or sum) over each group's nodes -- the one
+    product where the `coupling=` of the paths changes the answer.  mul / add: per-node de-normalisation, fp64.
+      count(paths [count,S,H,N]) -> ScenarioEvents; with groups the paths are aggregated first (`ops.scenario_aggregate`, which
+                                  de-normalises), then counted with no further de-normalisation (`ops.scenario_events`)
+      aggregate(x [..., N])      -> [..., R] float32, the aggregated (de-normalised) paths or target: rolling_scenarios' layout
+                                  with N = R, so ops.scenario_bands, EnsembleScores and QuantileScores take it as it is
+      realised(target [count,H,N]) -> ScenarioEvents of the one path that happened (S = 1) with `missing` [count,H,M]: the
+                                  (aggregated) target is NaN there"""
+
+    def __init__(self, threshold, above=True, min_run=1, groups=None, reduce="mean", mul=None, add=None):
+        if isinstance(min_run, bool) or int(min_run) != min_run or int(min_run) < 1:
+            raise ValueError(f"EventSpec: min_run must be an integer of at least 1, got {min_run!r}")
+        if reduce not in ("mean", "sum"):
+            raise ValueError(f"EventSpec: reduce is 'mean' or 'sum', got {reduce!r}")
+        if (mul is None) != (add is None):
+            raise ValueError("EventSpec: mul and add go together")
+        if groups is not None and not (torch.is_tensor(groups) or isinstance(groups, np.ndarray)):
+            groups = [list(g) for g in groups]
+        self.threshold, self.above, self.min_run = threshold, bool(above), int(min_run)
+        self.groups, self.reduce, self.mul, self.add = groups, reduce, mul, add
+        self._weights = {}
+
+    def weights(self, N, device):
+        key = (int(N), str(device))
+        if key not in self._weights:
+            self._weights[key] = group_weights(self.groups, N, self.reduce).to(device)
+        return self._weights[key]
+
+    def aggregate(self, x):
+        if self.groups is None:
+            raise ValueError("EventSpec.aggregate: the spec has no groups=")
+        x = _as_f32(x)
+        return ops.scenario_aggregate(x, self.weights(x.shape[-1], x.device), self.mul, self.add)
+
+    def _count(self, paths):
+        paths = _as_f32(paths)
+        if paths.dim() != 4:
+            raise ops._lib.StemGNNHipError(f"EventSpec: paths must be [count,S,H,N], got {tuple(paths.shape)}")
+        if self.groups is not None:
+            return ops.scenario_events(self.aggregate(paths), self.threshold, self.above, self.min_run), paths.shape[1]
+        return ops.scenario_events(paths, self.threshold, self.above, self.min_run, self.mul, self.add), paths.shape[1]
+
+    def count(self, paths):
+        counts, S = self._count(paths)
+        return ScenarioEvents(counts, S)
+
+    def realised(self, target):
+        target = _as_f32(target)
+        if target.dim() != 3:
+            raise ops._lib.StemGNNHipError(f"EventSpec.realised: target must be [count,H,N], got {tuple(target.shape)}")
+        if self.groups is not None:
+            value = self.aggregate(target)
+            counts = ops.scenario_events(value[:, None], self.threshold, self.above, self.min_run)
+        else:
+            value = target
+            counts = ops.scenario_events(target[:, None], self.threshold, self.above, self.min_run, self.mul, self.add)
+        return ScenarioEvents(counts, 1, torch.isnan(value))
+
+
 class GaussianCopula:
     """The dependence BETWEEN NODES of sampled scenario paths: a Gaussian copula over the model's own marginals, on the device.
 

@@ -10,6 +10,7 @@ import ctypes
 import os
 import weakref
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -2058,6 +2059,94 @@ def ensemble_scores(y, paths, mul=None, add=None, ignore_nan=False, fair=False):
                      add.data_ptr() if add is not None else None, C, S, H, N, int(bool(fair)), scratch.data_ptr(),
                      out.data_ptr(), hist.data_ptr(), _stream()), "ensemble_scores")
     return out, hist
+
+
+def _per_column(what, name, v, n):
+    """a scalar or n values -> a float64 host-or-device tensor [n] (not yet moved); refuses any other shape"""
+    v = v.detach() if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, dtype=np.float64))
+    if v.dim() == 0:
+        v = v.reshape(1).expand(n)
+    if v.dim() != 1 or v.shape[0] != n or v.is_complex():
+        raise _lib.StemGNNHipError(f"{what}: {name} must be a scalar or {n} values, got shape {tuple(v.shape)}")
+    return v
+
+
+def _denorm_pair(what, mul, add, n):
+    if (mul is None) != (add is None):
+        raise _lib.StemGNNHipError(f"{what}: mul and add go together")
+    if mul is None:
+        return None, None
+    return _per_column(what, "mul", mul, n), _per_column(what, "add", add, n)
+
+
+def _f64_on(v, device):
+    return None if v is None else v.to(device=device, dtype=torch.float64).contiguous()
+
+
+def scenario_aggregate(x, weights, mul=None, add=None):
+    """Weighted aggregates over node sets (``stemgnn_scenario_aggregate``; the definition is in include/stemgnn_hip.h):
+    x [..., N] contiguous float32 on the device (paths [count,S,H,N], targets [count,H,N], ..), weights [R,N] (any real dtype,
+    used as float64; math_utils.group_weights makes them), R <= 32, N <= 4096 -> out [..., R] float32 with
+    out[.., r] = sum over the nodes with a non-zero weight of weights[r, n] * (x[.., n] * mul[n] + add[n]), in fp64.
+    A node of weight 0 is not read into the sum (its NaN stays out); the same bits however the leading axes are batched."""
+    what = "scenario_aggregate"
+    if not torch.is_tensor(x) or x.dim() < 1 or x.shape[-1] < 1 or x.numel() == 0:
+        raise _lib.StemGNNHipError(f"{what}: x must be a non-empty [..., N] tensor, got "
+                                   f"{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+    N = int(x.shape[-1])
+    if not torch.is_tensor(weights) or weights.dim() != 2 or weights.shape[1] != N or weights.shape[0] < 1 or \
+            weights.is_complex():
+        raise _lib.StemGNNHipError(f"{what}: weights must be a [R,{N}] tensor, got "
+                                   f"{tuple(weights.shape) if torch.is_tensor(weights) else type(weights).__name__}")
+    R = int(weights.shape[0])
+    if R > 32 or N > 4096:
+        raise _lib.StemGNNHipError(f"{what}: at most 32 groups over at most 4096 nodes, got R = {R}, N = {N}")
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise _lib.StemGNNHipError(f"{what}: x must be a contiguous float32 tensor, got {x.dtype}, strides {tuple(x.stride())}")
+    mul, add = _denorm_pair(what, mul, add, N)
+    rows = x.numel() // N
+    if rows * R >= 2 ** 31:
+        raise _lib.StemGNNHipError(f"{what}: {rows} rows x {R} groups do not fit the entry's range (2^31)")
+    _require_gpu(x, "x")
+    lib = _lib.load()
+    dev = x.device
+    weights, mul, add = _f64_on(weights.detach(), dev), _f64_on(mul, dev), _f64_on(add, dev)
+    out = torch.empty(tuple(x.shape[:-1]) + (R,), device=dev, dtype=torch.float32)
+    _lib.check(lib.stemgnn_scenario_aggregate(x.data_ptr(), weights.data_ptr(), None if mul is None else mul.data_ptr(),
+                                              None if add is None else add.data_ptr(), rows, N, R, out.data_ptr(), _stream()),
+               what)
+    return out
+
+
+def scenario_events(paths, threshold, above=True, min_run=1, mul=None, add=None):
+    """Crossing counts of sampled paths (``stemgnn_scenario_events``; the definition is in include/stemgnn_hip.h):
+    paths [count,S,H,M] contiguous float32 on the device (M: nodes, or the groups of scenario_aggregate), threshold a scalar or
+    M values (float64, in the units of paths * mul + add) -> counts int32 [count, 2H+1, M]: rows 0..H-1 the paths in the event
+    per step, rows H..2H-1 the paths whose FIRST step in the event it is, row 2H the paths with at least `min_run` consecutive
+    steps in it.  above: the event is value > threshold (True) or value < threshold (False), strict, never true of a NaN."""
+    what = "scenario_events"
+    if not torch.is_tensor(paths) or paths.dim() != 4 or paths.numel() == 0:
+        raise _lib.StemGNNHipError(f"{what}: paths must be a non-empty [count,S,H,M] tensor, got "
+                                   f"{tuple(paths.shape) if torch.is_tensor(paths) else type(paths).__name__}")
+    if paths.dtype != torch.float32 or not paths.is_contiguous():
+        raise _lib.StemGNNHipError(f"{what}: paths must be a contiguous float32 tensor, got {paths.dtype}, strides "
+                                   f"{tuple(paths.stride())}")
+    C, S, H, M = (int(v) for v in paths.shape)
+    if S > 1024 or H > 256:
+        raise _lib.StemGNNHipError(f"{what}: at most 1024 paths of at most 256 steps, got S = {S}, H = {H}")
+    if isinstance(min_run, bool) or int(min_run) != min_run or not 1 <= int(min_run) <= H:
+        raise _lib.StemGNNHipError(f"{what}: min_run must be an integer within [1, {H}], got {min_run!r}")
+    threshold = _per_column(what, "threshold", threshold, M)
+    mul, add = _denorm_pair(what, mul, add, M)
+    _require_gpu(paths, "paths")
+    lib = _lib.load()
+    dev = paths.device
+    threshold, mul, add = _f64_on(threshold, dev), _f64_on(mul, dev), _f64_on(add, dev)
+    counts = torch.empty(C, 2 * H + 1, M, device=dev, dtype=torch.int32)
+    _lib.check(lib.stemgnn_scenario_events(paths.data_ptr(), threshold.data_ptr(), None if mul is None else mul.data_ptr(),
+                                           None if add is None else add.data_ptr(), C, S, H, M, int(bool(above)), int(min_run),
+                                           counts.data_ptr(), _stream()), what)
+    return counts
 
 
 def _ring_ok(what, ring, t_dev):

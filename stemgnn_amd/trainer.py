@@ -28,7 +28,7 @@ from . import ops
 from .base_model import Model, check_quantiles, point_index
 from .engine import ForecastStep, QuantileForecastStep, TrainStep, scenario_rounds
 from .forecast_dataloader import ForecastDataset, WindowLoader, denorm_coefficients, mark_missing
-from .math_utils import ConformalCalibrator, EnsembleScores, QuantileScores, Scores
+from .math_utils import ConformalCalibrator, EnsembleScores, QuantileScores, ScenarioEvents, Scores
 from .optim import FusedAdam, FusedRMSprop
 
 BEST = "_stemgnn.pt"
@@ -116,7 +116,7 @@ def _check_scenarios(who, model, horizon, paths):
 
 
 def rolling_scenarios(model, loader, horizon, paths=64, seed=0, adjacency=None, coupling="independent", tails="linear",
-                      return_paths=False, origin=0):
+                      return_paths=False, origin=0, events=None):
     """Multi-step forecast of every window the loader yields from SAMPLED trajectories: where rolling_forecast feeds the point
     row back, each of `paths` trajectories per window draws its next rows from the predicted quantile function (the piecewise-
     linear one through the model's levels and rearranged rows: ops.scenario_roll) and the model runs on all of them as one
@@ -133,13 +133,16 @@ def rolling_scenarios(model, loader, horizon, paths=64, seed=0, adjacency=None, 
     Returns (bands [count, Q, horizon, N], target [count, horizon, N]) and, with return_paths, paths [count, S, horizon, N],
     float32 device tensors in the forecast's normalised units: ConformalCalibrator.fit and QuantileScores take them as they are.
     A calibrator fitted on point-path bands (rolling_forecast's) is not valid for these bands.  The model's training state is
-    restored on exit."""
+    restored on exit.
+    events (a math_utils.EventSpec): every loader batch's paths are counted as they are produced (`events.count`) and the joined
+    math_utils.ScenarioEvents is returned as the LAST element of the tuple -- a pass no longer has to keep its paths to ask
+    about them; return_paths is still honoured.  Without the keyword the function is call for call what it was."""
     _check_scenarios("rolling_scenarios", model, horizon, paths)
     horizon, paths = int(horizon), int(paths)
     graph_kw = {} if adjacency is None else dict(adjacency=adjacency)
     was_training = getattr(model, "training", False)
     model.eval()
-    bands, targets, trajectories = [], [], []
+    bands, targets, trajectories, counted = [], [], [], []
     count = int(origin)
     try:
         with torch.no_grad():
@@ -150,11 +153,12 @@ def rolling_scenarios(model, loader, horizon, paths=64, seed=0, adjacency=None, 
                 targets.append(target)
                 if return_paths:
                     trajectories.append(p)
+                if events is not None:
+                    counted.append(events.count(p))
     finally:
         model.train(was_training)
-    if return_paths:
-        return torch.cat(bands), torch.cat(targets), torch.cat(trajectories)
-    return torch.cat(bands), torch.cat(targets)
+    out = (torch.cat(bands), torch.cat(targets)) + ((torch.cat(trajectories),) if return_paths else ())
+    return out if events is None else out + (ScenarioEvents.cat(counted),)
 
 
 def rolling_forecast_graph(model, dataset, horizon, batch_size, adjacency=None):
@@ -196,7 +200,7 @@ def rolling_quantile_forecast_graph(model, dataset, horizon, batch_size, adjacen
 
 
 def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=None, ignore_nan=False, quantiles=None,
-                   calibrator=None, origin=None, paths=None, fair=False):
+                   calibrator=None, origin=None, paths=None, fair=False, events=None):
     """Metrics of a rolling forecast in raw units (and normalised units under ``*_norm``).  With `dump_dir`, the first
     forecast step of every window is written as CSV (target / predict / absolute error / absolute percentage error).
     ignore_nan: NaN targets (missing readings) are left out of every metric; the CSV files keep them as NaN.
@@ -211,7 +215,14 @@ def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=
     paths [count, S, horizon, N] (rolling_scenarios(..., return_paths=True)): the sampled trajectories are scored as an ensemble
     (math_utils.EnsembleScores; `fair` is its flag): ``crps``, ``energy_score``, ``ensemble_rmse``, ``spread`` and
     ``rank_histogram`` [S + 1], each also per step under ``*_step``, in raw units and, like the keys above, in normalised
-    units under ``*_norm`` (the histogram has no units).  Without paths= the result is what it was, key for key."""
+    units under ``*_norm`` (the histogram has no units).  Without paths= the result is what it was, key for key.
+    events (a math_utils.EventSpec; needs paths=): the event's odds read off the paths are verified against the target
+    (math_utils.EventScores; the spec's own threshold, groups and mul / add): ``event_brier``, ``event_brier_skill``,
+    ``event_base_rate`` and ``event_reliability`` [M, S + 1, 2] for "the event at some step", the same under ``*_run`` for "at
+    least min_run steps in a row" and under ``*_step`` ([horizon], the table [horizon, M, S + 1, 2]) for every single step;
+    ignore_nan leaves the (origin, column) pairs with a missing target out.  Without events= the keys are what they were."""
+    if events is not None and paths is None:
+        raise ValueError("score_forecast: events= goes with paths= (the sampled trajectories the odds are read from)")
     seasonal = getattr(calibrator, "kind", None) == "seasonal"
     if seasonal and origin is None:
         raise ValueError("score_forecast: a seasonal calibrator needs origin= (the time index of every window's first target)")
@@ -256,6 +267,13 @@ def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=
                 out[key + suffix] = getattr(ens, name + suffix)
                 out[key + suffix + "_norm"] = getattr(ens_n, name + suffix)
         out.update(rank_histogram=ens.rank_histogram, rank_histogram_step=ens.rank_histogram_step)
+    if events is not None:
+        sc = events.count(paths).score(events.realised(target), ignore_nan=ignore_nan)
+        for suffix in ("", "_run", "_step"):
+            out["event_brier" + suffix] = getattr(sc, "brier" + suffix)
+            out["event_brier_skill" + suffix] = getattr(sc, "skill" + suffix)
+            out["event_base_rate" + suffix] = getattr(sc, "base_rate" + suffix)
+            out["event_reliability" + suffix] = getattr(sc, "reliability" + suffix)
     if dump_dir is not None:
         d = pathlib.Path(dump_dir)
         d.mkdir(parents=True, exist_ok=True)
