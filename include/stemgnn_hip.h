@@ -1058,6 +1058,39 @@ int stemgnn_scenario_aggregate(const float* x, const double* weights, const doub
 int stemgnn_scenario_events(const float* paths, const double* thr, const double* mul, const double* add, long count, int S,
                             int H, int M, int above, int min_run, int* counts, void* stream);
 
+/* ---- scenario reduction: K representative paths with weights, by forward selection (csrc/reduce.hip) ---
+ * distances: paths [count, S, L] fp32 and contiguous, a path's trajectory flattened (L = H * M); scale [L] fp64 on the device or
+ *            NULL (all ones); D [count, S, S] fp64:
+ *              D[c, i, j] = sqrt( sum_l (((double)x_il - (double)x_jl) * scale_l)^2 ),  l = 0, 1, .. L - 1 in that order
+ *            each difference formed first, then multiplied by scale_l, then accumulated by one fp64 fused multiply-add; with
+ *            squared != 0 there is no square root.  The sum is over DIFFERENCES, never |x|^2 + |x'|^2 - 2 x.x': two coincident
+ *            paths are at exactly 0 (paths of coupling = "path" nearly coincide).  The upper triangle is computed and stored
+ *            twice: D[c, i, j] and D[c, j, i] are the same bits, and the diagonal of a finite path is +0.  Nothing is masked: a
+ *            NaN or an infinity in a path reaches its row and its column, the diagonal included, as the arithmetic gives it.
+ *            One launch, one workgroup per (origin, 32 x 32 tile of pairs on or above the diagonal).
+ * reduce:    D [count, S, S] fp64, from the entry above or any cost of the caller's: D[k, u] is the cost of moving path k onto
+ *            path u; symmetry is neither needed nor checked.  Per origin, with m_k = +inf, for pick i = 0 .. K - 1:
+ *              z_u         = sum_k min(m_k, D[k, u]),  k = 0, 1, .. S - 1 in that order, one fp64 add after the other
+ *              selected[i] = the u not yet selected with the smallest z_u, the lowest index among equals
+ *              cost[i]     = z_u / S: the Kantorovich distance between the uniform ensemble and the kept set with optimally
+ *                            redistributed weights
+ *              m_k         = min(m_k, D[k, selected[i]])
+ *            and after the last pick assign[k] = the position j in 0 .. K - 1 of the kept path nearest to k (D[k, selected[j]]
+ *            smallest; among equals the one selected earliest) and counts[j] = #{k : assign[k] = j}: the weights are
+ *            counts / S, and the counts add up to S.  selected, counts int32 [count, K]; assign int32 [count, S]; cost fp64
+ *            [count, K].  An origin whose D holds an entry that is not a finite number >= 0 is refused: its selected and assign
+ *            are -1, its counts 0, its cost NaN; the other origins of the call are not affected.
+ *            One launch, one workgroup per origin; D is held in LDS where S (S | 1) doubles fit 160 KiB (S <= 141).
+ * Both: no floating-point atomics, no allocation, no host synchronisation; the same bits on every run, and an origin's results do
+ * not depend on which other origins share the call.
+ * SG_EINVAL (nothing launched): a NULL pointer other than scale; count or S <= 0; S > 1024; count * S * S >= 2^31;
+ * distances: L <= 0, squared not 0 / 1, S * L or the grid count * T (T + 1) / 2 (T = ceil(S / 32)) >= 2^31;
+ * reduce: K < 1 or K > S. */
+int stemgnn_scenario_distances(const float* paths, const double* scale, long count, int S, int L, int squared, double* D,
+                               void* stream);
+int stemgnn_scenario_reduce(const double* D, long count, int S, int K, int* selected, int* counts, int* assign, double* cost,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

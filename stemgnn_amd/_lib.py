@@ -228,6 +228,8 @@ SIGNATURES = {
     "stemgnn_ensemble_scores_masked": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
     "stemgnn_scenario_aggregate": (c_int, [_P, _P, _P, _P, c_longlong, c_int, c_int, _P, _P]),
     "stemgnn_scenario_events": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "stemgnn_scenario_distances": (c_int, [_P, _P, c_long, c_int, c_int, c_int, _P, _P]),
+    "stemgnn_scenario_reduce": (c_int, [_P, c_long, c_int, c_int, _P, _P, _P, _P, _P]),
     "stemgnn_infer_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
     "stemgnn_infer_workspace_split_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "stemgnn_gru_fwd_infer": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),

@@ -1302,6 +1302,17 @@ class LiveForecaster:
         _, steps = self.scenarios(paths=paths, horizon=horizon, seed=seed, coupling=coupling, tails=tails, return_paths=True)
         return spec.count(steps[None])
 
+    def scenario_set(self, keep, paths=64, horizon=None, seed=None, coupling="independent", tails="linear", on=None, scale=None,
+                     squared=False):
+        """`keep` representative paths with probabilities for the steps ahead of the last row pushed: `scenarios(...,
+        return_paths=True)` from the ring's head window, then `math_utils.reduce_scenarios` on its paths.  Returns a
+        math_utils.ScenarioSet with count = 1 (paths [1,keep,horizon,N], weights [1,keep], cost: device tensors, no sync).
+        on / scale / squared are reduce_scenarios' (on: an EventSpec with groups=, or a [1,S,horizon,R] tensor); the other
+        arguments are scenarios'; the captured graph, the history slab and every calibrator are left untouched."""
+        from .math_utils import reduce_scenarios
+        _, steps = self.scenarios(paths=paths, horizon=horizon, seed=seed, coupling=coupling, tails=tails, return_paths=True)
+        return reduce_scenarios(steps[None], keep, on=on, scale=scale, squared=squared)
+
     # -- matured pairs ------------------------------------------------------------------------------------------
     def matured(self):
         """(forecasts [m,(Q,)horizon,N], targets [m,horizon,N], origins int64 [m] ascending) of the stored forecasts whose targets

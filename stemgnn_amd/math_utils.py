@@ -326,6 +326,135 @@ class EventSpec:
         return ScenarioEvents(counts, 1, torch.isnan(value))
 
 
+def _first_min(values):
+    """the lowest position of the minimum along the last axis (torch.argmin leaves the choice among equals open)"""
+    k = values.shape[-1]
+    pos = torch.arange(k, device=values.device).expand_as(values)
+    return torch.where(values == values.amin(dim=-1, keepdim=True), pos, torch.full_like(pos, k)).amin(dim=-1)
+
+
+class ScenarioSet:
+    """K representative paths per origin with weights: the result of `reduce_scenarios` (scenario reduction by forward
+    selection, `ops.scenario_reduce`).  Device tensors, no sync:
+      index   int64 [count, K]    the kept paths' indices among the S, in the order they were picked
+      counts  int32 [count, K]    the paths whose nearest kept path each is       weights  float64 [count, K] = counts / S
+      assign  int32 [count, S]    the position in 0 .. K-1 every path went to
+      cost    float64 [count, K]  the Kantorovich distance between the full ensemble and the first i + 1 picks with their
+                                  optimal weights: non-increasing in i, so K can be chosen by tolerance (keep_for)
+      paths   float32 [count, K, H, N]  the kept trajectories                      S  the size of the ensemble
+    A refused origin (a NaN or an infinity among its distances): index and assign -1, counts 0, cost NaN, and its `paths` rows and
+    `weights` are NaN, so nothing computed from them passes for a number.
+      expect(values [count, S, ...]) -> float64 [count, ...]: the weighted sum over the kept members of any functional
+                    evaluated on all S paths -- what the full ensemble's mean of it is replaced by
+      keep_for(tol) -> int64 [count]: the smallest number of members whose cost is at most tol * cost[:, 0]
+      head(k)       -> the ScenarioSet of the first k picks (forward selection is nested: they ARE the picks at keep = k); its
+                    counts and assign are re-derived from the distances, so the set must still hold `distances` [count, S, S]
+                    or `source` = (the [count, S, H, R] tensor the distances were taken on, scale, squared): reduce_scenarios
+                    keeps a reference to the latter, trainer.reduced_scenarios drops it with the batch's paths
+      cat(parts)    joins batches along the origins"""
+
+    def __init__(self, index, counts, assign, cost, S, paths, distances=None, source=None):
+        if index.dim() != 2 or index.dtype != torch.int64 or counts.dtype != torch.int32 or counts.shape != index.shape or \
+                cost.shape != index.shape or assign.dim() != 2 or assign.shape[0] != index.shape[0] or \
+                paths.dim() != 4 or paths.shape[:2] != index.shape:
+            raise ValueError(f"ScenarioSet: index must be int64 [count, K] with int32 counts, cost [count, K], assign [count, S] "
+                             f"and paths [count, K, H, N], got {index.dtype} {tuple(index.shape)}, {counts.dtype} "
+                             f"{tuple(counts.shape)}, {tuple(cost.shape)}, {tuple(assign.shape)}, {tuple(paths.shape)}")
+        self.index, self.counts, self.assign, self.cost, self.S, self.paths = index, counts, assign, cost, int(S), paths
+        self.distances, self.source = distances, source
+        self.count, self.K = int(index.shape[0]), int(index.shape[1])
+        self.H, self.N = int(paths.shape[2]), int(paths.shape[3])
+
+    @property
+    def weights(self):
+        w = self.counts.double() / self.S
+        return torch.where(self.index[:, :1] < 0, torch.full_like(w, float("nan")), w)
+
+    def expect(self, values):
+        if not torch.is_tensor(values) or values.dim() < 2 or tuple(values.shape[:2]) != (self.count, self.S):
+            raise ValueError(f"ScenarioSet.expect: values must be [count, S, ...] = [{self.count}, {self.S}, ...], got "
+                             f"{tuple(values.shape) if torch.is_tensor(values) else type(values).__name__}")
+        tail = values.shape[2:]
+        idx = self.index.clamp(min=0).reshape(self.count, self.K, *([1] * len(tail))).expand(self.count, self.K, *tail)
+        kept = torch.gather(values.double(), 1, idx)
+        return (kept * self.weights.reshape(self.count, self.K, *([1] * len(tail)))).sum(dim=1)
+
+    def keep_for(self, tol):
+        ok = self.cost <= float(tol) * self.cost[:, :1]
+        first = torch.arange(1, self.K + 1, device=ok.device).expand_as(ok)
+        return torch.where(ok, first, torch.full_like(first, self.K)).amin(dim=1)
+
+    def _distances(self, lo, hi):
+        if self.distances is not None:
+            return self.distances[lo:hi]
+        on, scale, squared = self.source
+        return ops.scenario_distances(on[lo:hi], scale, squared)
+
+    def head(self, k):
+        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= self.K:
+            raise ValueError(f"ScenarioSet.head: k must be an integer within [1, {self.K}], got {k!r}")
+        if self.distances is None and self.source is None:
+            raise ValueError("ScenarioSet.head: counts and assign of the first k picks are re-derived from the distances: the "
+                             "set needs `distances` ([count, S, S], ops.scenario_distances) or `source` (the full [count, S, H, R] "
+                             "paths the distances were taken on, with scale and squared), and holds neither")
+        k, S = int(k), self.S
+        index = self.index[:, :k]
+        refused = index[:, :1] < 0
+        assign = torch.empty_like(self.assign)
+        step = max(1, (256 << 20) // (S * S * 8))
+        for lo in range(0, self.count, step):
+            D = self._distances(lo, lo + step)                                   # [n, S, S]: D[k, u], path k onto path u
+            cols = index[lo:lo + step].clamp(min=0)[:, None, :].expand(-1, S, -1)
+            assign[lo:lo + step] = _first_min(torch.gather(D, 2, cols)).to(assign.dtype)
+        assign = torch.where(refused, torch.full_like(assign, -1), assign)
+        counts = (assign[:, :, None] == torch.arange(k, device=assign.device)).sum(dim=1).to(torch.int32)
+        return ScenarioSet(index.contiguous(), counts, assign, self.cost[:, :k].contiguous(), S, self.paths[:, :k].contiguous(),
+                           self.distances, self.source)
+
+    @staticmethod
+    def cat(parts):
+        parts = list(parts)
+        if not parts or any((p.S, p.K, p.H, p.N) != (parts[0].S, parts[0].K, parts[0].H, parts[0].N) for p in parts):
+            raise ValueError("ScenarioSet.cat: the parts must share S, K, H and N")
+        distances = torch.cat([p.distances for p in parts]) if all(p.distances is not None for p in parts) else None
+        return ScenarioSet(*(torch.cat([getattr(p, name) for p in parts]) for name in ("index", "counts", "assign", "cost")),
+                           parts[0].S, torch.cat([p.paths for p in parts]), distances)
+
+
+def reduce_scenarios(paths, keep, on=None, scale=None, squared=False):
+    """Scenario reduction: of the S sampled paths of every origin (paths [count, S, H, N] float32 on the device,
+    `trainer.rolling_scenarios(..., return_paths=True)`), the `keep` that represent the ensemble best, with probabilities -- what a
+    stochastic program or a dispatcher can take where they cannot take S equally likely paths.  Forward selection (Heitsch &
+    Roemisch 2003) on the Euclidean distance between whole trajectories (`ops.scenario_reduce`): each pick is the path that most
+    lowers the Kantorovich distance between the ensemble and the kept set, and every dropped path's probability 1 / S goes to its
+    nearest kept path, so the weights are integer counts over S.  Returns a ScenarioSet.
+    on: the [count, S, H, R] float32 tensor the distances are taken on instead of `paths` -- typically
+    `EventSpec.aggregate(paths)`, a reduction by corridor means whose kept members are still the full node paths; an EventSpec
+    with groups= stands for its `aggregate(paths)`.  scale (a scalar, [R] or [H, R]; R = N without on=): multiplies every
+    difference, e.g. 1 / std per column or a discount per step; squared: squared Euclidean distances."""
+    paths = _as_f32(paths)
+    if paths.dim() != 4:
+        raise ops._lib.StemGNNHipError(f"reduce_scenarios: paths must be [count,S,H,N], got {tuple(paths.shape)}")
+    if isinstance(on, EventSpec):
+        if on.groups is None:
+            raise ValueError("reduce_scenarios: on= an EventSpec stands for its aggregate(paths); the spec has no groups=")
+        on = on.aggregate(paths)
+    elif on is None:
+        on = paths
+    else:
+        on = _as_f32(on, like=paths)
+        if on.dim() != 4 or tuple(on.shape[:3]) != tuple(paths.shape[:3]):
+            raise ops._lib.StemGNNHipError(f"reduce_scenarios: on must be [count,S,H,R] with the paths' count, S and H "
+                                           f"{tuple(paths.shape[:3])}, got {tuple(on.shape)}")
+    on = on.contiguous()
+    selected, counts, assign, cost = ops.scenario_reduce(on, keep, scale, squared)
+    index = selected.long()
+    C, S, H, N = paths.shape
+    kept = torch.gather(paths, 1, index.clamp(min=0)[:, :, None, None].expand(-1, -1, H, N))
+    kept = torch.where((index < 0)[:, :, None, None], torch.full_like(kept, float("nan")), kept)
+    return ScenarioSet(index, counts, assign, cost, S, kept, source=(on, scale, bool(squared)))
+
+
 class GaussianCopula:
     """The dependence BETWEEN NODES of sampled scenario paths: a Gaussian copula over the model's own marginals, on the device.
 

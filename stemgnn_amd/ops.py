@@ -2149,6 +2149,135 @@ def scenario_events(paths, threshold, above=True, min_run=1, mul=None, add=None)
     return counts
 
 
+def _reduce_paths(what, paths):
+    """paths [count,S,H,M] contiguous float32 (checked on the host, the device last) -> (count, S, H, M)"""
+    if not torch.is_tensor(paths) or paths.dim() != 4 or paths.numel() == 0:
+        raise _lib.StemGNNHipError(f"{what}: paths must be a non-empty [count,S,H,M] tensor, got "
+                                   f"{tuple(paths.shape) if torch.is_tensor(paths) else type(paths).__name__}")
+    if paths.dtype != torch.float32 or not paths.is_contiguous():
+        raise _lib.StemGNNHipError(f"{what}: paths must be a contiguous float32 tensor, got {paths.dtype}, strides "
+                                   f"{tuple(paths.stride())}")
+    C, S, H, M = (int(v) for v in paths.shape)
+    if S > 1024:
+        raise _lib.StemGNNHipError(f"{what}: at most 1024 paths, got S = {S}")
+    if S * H * M >= 2 ** 31:
+        raise _lib.StemGNNHipError(f"{what}: {S} paths of {H} x {M} values do not fit the entry's range (2^31)")
+    return C, S, H, M
+
+
+def _reduce_scale(what, scale, H, M):
+    """scale: None, a scalar, [M] or [H,M] -> None or a float64 tensor [H * M] (not yet moved)"""
+    if scale is None:
+        return None
+    v = scale.detach() if torch.is_tensor(scale) else torch.as_tensor(np.asarray(scale, dtype=np.float64))
+    if v.is_complex() or v.dim() > 2 or (v.dim() == 1 and v.shape[0] != M) or (v.dim() == 2 and tuple(v.shape) != (H, M)):
+        raise _lib.StemGNNHipError(f"{what}: scale must be a scalar, [{M}] or [{H},{M}], got shape {tuple(v.shape)}")
+    return v.to(torch.float64).expand(H, M).reshape(H * M)
+
+
+def _reduce_flag(what, squared):
+    if not isinstance(squared, (bool, np.bool_, int)) or squared not in (0, 1):
+        raise _lib.StemGNNHipError(f"{what}: squared must be True or False, got {squared!r}")
+    return int(bool(squared))
+
+
+def _reduce_keep(what, keep, S):
+    if isinstance(keep, bool) or not isinstance(keep, (int, np.integer)) or not 1 <= int(keep) <= S:
+        raise _lib.StemGNNHipError(f"{what}: keep must be an integer within [1, {S}] (S = {S} paths), got {keep!r}")
+    return int(keep)
+
+
+def _reduce_batch(what, S, max_scratch_bytes):
+    """origins per call: D [batch,S,S] float64 within max_scratch_bytes and within the entries' range (2^31 elements)"""
+    if isinstance(max_scratch_bytes, bool) or int(max_scratch_bytes) != max_scratch_bytes or int(max_scratch_bytes) < S * S * 8:
+        raise _lib.StemGNNHipError(f"{what}: max_scratch_bytes must hold one origin's [S,S] float64 distances "
+                                   f"({S * S * 8} bytes), got {max_scratch_bytes!r}")
+    return max(1, min(int(max_scratch_bytes) // (S * S * 8), (2 ** 31 - 1) // (S * S)))
+
+
+def scenario_distances(paths, scale=None, squared=False):
+    """Pairwise distances of sampled paths (``stemgnn_scenario_distances``; the definition is in include/stemgnn_hip.h):
+    paths [count,S,H,M] contiguous float32 on the device (M: nodes, or the groups of scenario_aggregate) ->
+    D [count,S,S] float64, D[c,i,j] = sqrt(sum over (h, m) of ((x_i - x_j) * scale)^2) in fp64 from the differences; squared:
+    without the root.  scale: a scalar, [M] or [H,M] (any real dtype, used as float64), e.g. 1 / std per node or a discount per
+    step.  D equals its transpose bit for bit; coincident paths are at exactly 0; a NaN in a path reaches its row and column."""
+    what = "scenario_distances"
+    C, S, H, M = _reduce_paths(what, paths)
+    scale = _reduce_scale(what, scale, H, M)
+    squared = _reduce_flag(what, squared)
+    if C * S * S >= 2 ** 31:
+        raise _lib.StemGNNHipError(f"{what}: {C} origins x {S} x {S} distances do not fit the entry's range (2^31); "
+                                   "scenario_reduce walks the origins in batches")
+    _require_gpu(paths, "paths")
+    lib = _lib.load()
+    scale = _f64_on(scale, paths.device)
+    D = torch.empty(C, S, S, device=paths.device, dtype=torch.float64)
+    _lib.check(lib.stemgnn_scenario_distances(paths.data_ptr(), None if scale is None else scale.data_ptr(), C, S, H * M,
+                                              squared, D.data_ptr(), _stream()), what)
+    return D
+
+
+def scenario_reduce(paths, keep, scale=None, squared=False, distances=None, max_scratch_bytes=256 << 20):
+    """Scenario reduction by forward selection (``stemgnn_scenario_distances`` + ``stemgnn_scenario_reduce``; the definition is
+    in include/stemgnn_hip.h): of the S paths of every origin, `keep` representatives are picked greedily, each pick the one that
+    most lowers the Kantorovich distance between the uniform ensemble and the kept set, and every path is assigned to its nearest
+    kept one.  paths [count,S,H,M] contiguous float32 on the device; scale / squared: scenario_distances'.  Returns
+      selected int32 [count,keep]  path indices in the order they were picked       counts int32 [count,keep]  paths assigned to each
+      assign   int32 [count,S]     the position in 0 .. keep-1 every path went to   cost   float64 [count,keep]  the distance after
+                                                                                   every pick (non-increasing)
+    all on the device, no sync; the weights are counts / S.  An origin with a NaN or an infinity among its distances is refused:
+    -1 / 0 / -1 / NaN, the others are not affected.  The origins are walked in batches whose [batch,S,S] float64 distances stay
+    within max_scratch_bytes; the result is that of one call, bit for bit.
+    distances [count,S,S] float64 (contiguous, on the device): any cost of the caller's, D[k,u] = moving path k onto path u;
+    only the second entry runs, and paths may be None."""
+    what = "scenario_reduce"
+    if distances is None:
+        C, S, H, M = _reduce_paths(what, paths)
+        scale = _reduce_scale(what, scale, H, M)
+        squared = _reduce_flag(what, squared)
+        source = paths
+    else:
+        if not torch.is_tensor(distances) or distances.dim() != 3 or distances.shape[1] != distances.shape[2] or \
+                distances.numel() == 0:
+            raise _lib.StemGNNHipError(f"{what}: distances must be a non-empty [count,S,S] tensor, got "
+                                       f"{tuple(distances.shape) if torch.is_tensor(distances) else type(distances).__name__}")
+        if distances.dtype != torch.float64 or not distances.is_contiguous():
+            raise _lib.StemGNNHipError(f"{what}: distances must be a contiguous float64 tensor, got {distances.dtype}, strides "
+                                       f"{tuple(distances.stride())}")
+        C, S = int(distances.shape[0]), int(distances.shape[1])
+        if S > 1024:
+            raise _lib.StemGNNHipError(f"{what}: at most 1024 paths, got S = {S}")
+        if paths is not None and (not torch.is_tensor(paths) or paths.dim() != 4 or tuple(paths.shape[:2]) != (C, S)):
+            raise _lib.StemGNNHipError(f"{what}: paths must be [count,S,H,M] with the distances' count = {C} and S = {S}, got "
+                                       f"{tuple(paths.shape) if torch.is_tensor(paths) else type(paths).__name__}")
+        source = distances
+    K = _reduce_keep(what, keep, S)
+    batch = _reduce_batch(what, S, max_scratch_bytes)
+    if not source.is_cuda:
+        raise _lib.StemGNNHipError(f"{what}: {'paths' if distances is None else 'distances'} is on {source.device}: "
+                                   "stemgnn_amd runs only on a HIP device (no CPU fallback)")
+    lib = _lib.load()
+    dev = source.device
+    selected = torch.empty(C, K, device=dev, dtype=torch.int32)
+    counts = torch.empty(C, K, device=dev, dtype=torch.int32)
+    assign = torch.empty(C, S, device=dev, dtype=torch.int32)
+    cost = torch.empty(C, K, device=dev, dtype=torch.float64)
+    if distances is None:
+        scale = _f64_on(scale, dev)
+        D = torch.empty(min(batch, C), S, S, device=dev, dtype=torch.float64)
+    for lo in range(0, C, batch):
+        n = min(batch, C - lo)
+        if distances is None:
+            _lib.check(lib.stemgnn_scenario_distances(paths[lo:lo + n].data_ptr(), None if scale is None else scale.data_ptr(),
+                                                      n, S, H * M, squared, D.data_ptr(), _stream()), "scenario_distances")
+            d_ptr = D.data_ptr()
+        else:
+            d_ptr = distances[lo:lo + n].data_ptr()
+        _lib.check(lib.stemgnn_scenario_reduce(d_ptr, n, S, K, selected[lo:lo + n].data_ptr(), counts[lo:lo + n].data_ptr(),
+                                               assign[lo:lo + n].data_ptr(), cost[lo:lo + n].data_ptr(), _stream()), what)
+    return selected, counts, assign, cost
+
+
 def _ring_ok(what, ring, t_dev):
     _require_gpu(ring, "ring")
     if ring.dim() != 2 or ring.dtype != torch.float32 or not ring.is_contiguous():

@@ -28,7 +28,8 @@ from . import ops
 from .base_model import Model, check_quantiles, point_index
 from .engine import ForecastStep, QuantileForecastStep, TrainStep, scenario_rounds
 from .forecast_dataloader import ForecastDataset, WindowLoader, denorm_coefficients, mark_missing
-from .math_utils import ConformalCalibrator, EnsembleScores, QuantileScores, ScenarioEvents, Scores
+from .math_utils import (ConformalCalibrator, EnsembleScores, EventSpec, QuantileScores, ScenarioEvents, ScenarioSet, Scores,
+                         reduce_scenarios)
 from .optim import FusedAdam, FusedRMSprop
 
 BEST = "_stemgnn.pt"
@@ -138,27 +139,59 @@ def rolling_scenarios(model, loader, horizon, paths=64, seed=0, adjacency=None, 
     math_utils.ScenarioEvents is returned as the LAST element of the tuple -- a pass no longer has to keep its paths to ask
     about them; return_paths is still honoured.  Without the keyword the function is call for call what it was."""
     _check_scenarios("rolling_scenarios", model, horizon, paths)
+    bands, targets, trajectories, counted = [], [], [], []
+    for b, target, p in _scenario_batches(model, loader, horizon, paths, seed, adjacency, coupling, tails, origin):
+        bands.append(b)
+        targets.append(target)
+        if return_paths:
+            trajectories.append(p)
+        if events is not None:
+            counted.append(events.count(p))
+    out = (torch.cat(bands), torch.cat(targets)) + ((torch.cat(trajectories),) if return_paths else ())
+    return out if events is None else out + (ScenarioEvents.cat(counted),)
+
+
+def _scenario_batches(model, loader, horizon, paths, seed, adjacency, coupling, tails, origin):
+    """The batch loop of rolling_scenarios and reduced_scenarios: yields (bands [Bo,Q,horizon,N], target, paths [Bo,S,horizon,N])
+    per loader batch, the origin index running on over the batches; the model is in eval mode while the loop runs and gets its
+    training state back when it ends, however it ends."""
     horizon, paths = int(horizon), int(paths)
     graph_kw = {} if adjacency is None else dict(adjacency=adjacency)
     was_training = getattr(model, "training", False)
     model.eval()
-    bands, targets, trajectories, counted = [], [], [], []
     count = int(origin)
     try:
         with torch.no_grad():
             for window, target in loader:
                 b, p = scenario_rounds(model, window, horizon, paths, count, seed, coupling, tails, graph_kw)
                 count += window.shape[0]
-                bands.append(b)
-                targets.append(target)
-                if return_paths:
-                    trajectories.append(p)
-                if events is not None:
-                    counted.append(events.count(p))
+                yield b, target, p
     finally:
         model.train(was_training)
-    out = (torch.cat(bands), torch.cat(targets)) + ((torch.cat(trajectories),) if return_paths else ())
-    return out if events is None else out + (ScenarioEvents.cat(counted),)
+
+
+def reduced_scenarios(model, loader, horizon, keep, paths=64, seed=0, adjacency=None, coupling="independent", tails="linear",
+                      origin=0, on=None, scale=None, squared=False):
+    """rolling_scenarios handing on `keep` representative paths with probabilities per window instead of `paths` equally likely
+    ones: every loader batch's paths are reduced as they are produced (math_utils.reduce_scenarios: forward selection on the
+    distance between whole trajectories), so the pass keeps count * keep paths, not count * paths.  The arguments up to `origin`
+    are rolling_scenarios'; on / scale / squared are reduce_scenarios' (on: an EventSpec with groups=, whose aggregate of every
+    batch's paths the distances are taken on; a tensor cannot be named ahead of the paths).
+    Returns (bands, target, math_utils.ScenarioSet): the bands and the target are rolling_scenarios' own, and the set is
+    `reduce_scenarios(paths, keep, ...)` of rolling_scenarios(..., return_paths=True)'s paths, bit for bit, however the loader
+    batches the windows.  The set keeps neither the distances nor the full paths: its head(k) needs one of them put back."""
+    _check_scenarios("reduced_scenarios", model, horizon, paths)
+    if on is not None and not isinstance(on, EventSpec):
+        raise ValueError("reduced_scenarios: on= is an EventSpec with groups= (the aggregate of every batch's paths); a tensor "
+                         "goes to math_utils.reduce_scenarios with the paths it belongs to")
+    bands, targets, sets = [], [], []
+    for b, target, p in _scenario_batches(model, loader, horizon, paths, seed, adjacency, coupling, tails, origin):
+        bands.append(b)
+        targets.append(target)
+        kept = reduce_scenarios(p, keep, on=on, scale=scale, squared=squared)
+        kept.source = None                                   # the batch's paths go with the batch
+        sets.append(kept)
+    return torch.cat(bands), torch.cat(targets), ScenarioSet.cat(sets)
 
 
 def rolling_forecast_graph(model, dataset, horizon, batch_size, adjacency=None):
