@@ -638,14 +638,20 @@ int stemgnn_normalize_series(const double* raw, const double* sub, const double*
                              long T, int N, void* stream);
 /* ForecastDataset.__getitem__ + default collate (forecast_dataloader.py:56-63, models/handler.py:136-138,158-159):
  * x[b,w,:] = series[hi[b]-W+w,:], y[b,h,:] = series[hi[b]+h,:]; series [T,N] fp32 resident, hi [B] int64 (device).
- * A window outside [0,T] is written as zeros and sets bit 0 of *status (device int, may be NULL). */
+ * A window outside [0,T] is written as zeros and sets bit 0 of *status (device int, may be NULL); the other windows of the batch
+ * are gathered.  H = 0 is allowed (y is not touched).  B is a grid extent: B > 65535 returns SG_EINVAL, nothing launched (both
+ * gathers, their `_pair` forms, stemgnn_roll_window, stemgnn_roll_window_quantile and stemgnn_forecast_store). */
 int stemgnn_window_gather(const float* series, const long long* hi, float* x, float* y, int B, int W, int H, int N,
                           long T, int* status, void* stream);
 /* The same gather as an ITERATOR over one shuffled epoch (the DataLoader loop of models/handler.py:157-159): order [count]
  * int64 window-end rows (device), queue = device long long[4] {position, 0, count, wrap}, set by the caller when an epoch
  * is loaded (wrap != 0: a position from which no full batch is left goes back to 0 instead of running past the end --
  * start-up replays only).  Every call gathers windows order[position .. position+B) and advances position by B ON THE DEVICE, so a
- * captured hipGraph step needs no per-step index copy.  Past the end: zeros + bit 1 of *status. */
+ * captured hipGraph step needs no per-step index copy.  Row b of a call is window order[position + b] while 0 <= position and
+ * position + b < count; a row past the end (or at a negative position) is zeros and sets bit 1 of *status, so a ragged last batch
+ * holds its first count - position windows followed by zero rows.  A window of `order` outside [0,T] is zeros + bit 0, as above.
+ * The position always moves: to position + B, or with wrap to 0 when position + 2 B > count.  queue[1] is the call's own
+ * arrival counter and is 0 again after every call. */
 int stemgnn_window_gather_queue(const float* series, const long long* order, long long* queue, float* x, float* y, int B,
                                 int W, int H, int N, long T, int* status, void* stream);
 /* Both gathers with the y rows taken from a second series of the same shape (x from series_x, y from series_y): the
@@ -659,17 +665,18 @@ int stemgnn_window_gather_queue_pair(const float* series_x, const float* series_
  * a fixed-order two-stage reduction; bwd: dforecast = grad_loss[0] * 2 (forecast-target)/n. */
 size_t stemgnn_mse_scratch_floats(void);
 int stemgnn_mse_fwd(const float* forecast, const float* target, size_t n, float* scratch, float* loss,
-                    double* loss_accum, void* stream);   /* loss_accum (may be NULL): device double, += loss */
+                    double* loss_accum, void* stream);   /* loss_accum (may be NULL): device double, += (double)loss[0] */
 int stemgnn_mse_bwd(const float* forecast, const float* target, size_t n, const float* grad_loss, float* dforecast,
                     void* stream);
 /* one iteration of the rolling inference (models/handler.py:56-61), out of place: inputs_next = inputs shifted left
  * by L with forecast [B,L,N] appended; forecast_steps[b, step + j, :] = forecast[b,j,:] for j < min(horizon-step, L).
- * L > W (which the reference fails on with a shape error) returns SG_EINVAL. */
+ * Rows of forecast_steps outside [step, step + min(horizon-step, L)) are not written.  L > W (which the reference fails on with a
+ * shape error), step outside [0, horizon) or B > 65535 returns SG_EINVAL. */
 int stemgnn_roll_window(const float* inputs, const float* forecast, float* inputs_next, float* forecast_steps,
                         int B, int W, int L, int N, int step, int horizon, void* stream);
 /* engine.ForecastStep's result slabs: out_forecast / out_target [capacity, H, N] rows pos[0] + b := forecast / target [B, H, N]
  * row b, with pos (int64[1]) read on the device -- the window queue's position before the batch's gather; rows outside
- * [0, capacity) are dropped. */
+ * [0, capacity) are dropped and no other row of the slabs is written.  B > 65535 or H N > 2^30: SG_EINVAL. */
 int stemgnn_forecast_store(const float* forecast, const float* target, const long long* pos, float* out_forecast,
                            float* out_target, int B, int H, int N, long capacity, void* stream);
 /* evaluate() (utils/math_utils.py:24-74) with the optional de_normalized() (forecast_dataloader.py:25-38) in front:
@@ -686,6 +693,25 @@ int stemgnn_eval_metrics(const float* target, const float* forecast, const doubl
 size_t stemgnn_eval_scratch_doubles_masked(long count, int H, int N);
 int stemgnn_eval_metrics_masked(const float* target, const float* forecast, const double* mul, const double* add,
                                 long count, int H, int N, double* scratch, double* out, void* stream);
+/* stemgnn_data_plan: how one entry of csrc/data.hip launches for a shape, host only: it launches nothing and reads no buffer.
+ * Every launcher of that file takes its geometry from the static function this entry calls for it, so what it reports is what
+ * runs; tests use it to prove which thread counts, copy forms, grid-stride passes and chunk counts their cases reach
+ * (tests/test_data_cases.py).  `entry` is one of SG_DATA_* and a0..a4 are its shape (unused ones are ignored):
+ *   SG_DATA_NORMALIZE (T, N) | SG_DATA_GATHER, SG_DATA_GATHER_QUEUE (B, W, H, N) | SG_DATA_MSE_FWD, SG_DATA_MSE_BWD (n)
+ *   SG_DATA_ROLL (B, W, L, N) | SG_DATA_ROLL_QUANTILE (B, W, L, N, Q) | SG_DATA_FORECAST_STORE (B, H, N)
+ *   SG_DATA_EVAL (count, H, N; the masked entry launches the same) | SG_DATA_QUANTILE_METRICS (count, Q, H, N; likewise).
+ * out = SG_DATA_PLAN_WORDS ints, 0 where a word does not apply:
+ *   [0] [1] [2] the grid of the entry's first (or only) launch   [3] its threads per workgroup
+ *   [4] the gathers: 1 = float4 copies (N % 4 == 0), 0 = scalar   [5] queue gather: slab rows per workgroup
+ *   [6] MSE forward: 0 = one workgroup, 1 = two-stage (partial sums, then one workgroup over them)
+ *   [7] normalise, MSE (both), forecast store: trips of the busiest thread through its grid-stride loop
+ *   [8] eval and quantile metrics: row chunks of `count` (= grid.y).
+ * SG_EINVAL for an unknown entry, out == NULL, or a shape the entry itself refuses (its checks on sizes, not on pointers, T,
+ * step, horizon or point). */
+enum { SG_DATA_NORMALIZE = 0, SG_DATA_GATHER = 1, SG_DATA_GATHER_QUEUE = 2, SG_DATA_MSE_FWD = 3, SG_DATA_MSE_BWD = 4, SG_DATA_ROLL = 5,
+       SG_DATA_ROLL_QUANTILE = 6, SG_DATA_FORECAST_STORE = 7, SG_DATA_EVAL = 8, SG_DATA_QUANTILE_METRICS = 9 };
+enum { SG_DATA_PLAN_WORDS = 9 };
+int stemgnn_data_plan(int entry, long a0, long a1, long a2, long a3, long a4, int* out /* [SG_DATA_PLAN_WORDS] */);
 
 /* ---- quantile forecasts (a model with Q output rows per horizon step; csrc/data.hip) ---------------------------------
  * stemgnn_roll_window for a quantile forecast [B, Q, L, N]: inputs_next is built from the POINT row (forecast[b, point]) exactly

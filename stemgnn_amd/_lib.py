@@ -46,6 +46,23 @@ def fc_tail_plan(B, N, W, H):
     return {fam: {k: int(out[12 * f + i]) for k, i in SG_TAIL_WORD.items()} for f, fam in enumerate(("plain", "train"))}
 
 
+# entries and words of stemgnn_data_plan (SG_DATA_* in include/stemgnn_hip.h)
+SG_DATA_ENTRY = {"normalize": 0, "gather": 1, "gather_queue": 2, "mse_fwd": 3, "mse_bwd": 4, "roll": 5, "roll_quantile": 6,
+                 "forecast_store": 7, "eval": 8, "quantile_metrics": 9}
+SG_DATA_PLAN_WORDS = 9
+SG_DATA_WORD = {"grid_x": 0, "grid_y": 1, "grid_z": 2, "threads": 3, "vec": 4, "rows_per_wg": 5, "form": 6, "passes": 7,
+                "nchunk": 8}
+
+
+def data_plan(entry, *shape):
+    """stemgnn_data_plan as a dict of SG_DATA_WORD names; `entry` a key of SG_DATA_ENTRY, `shape` as the header lists it for that
+    entry; raises on SG_EINVAL."""
+    out = (c_int * SG_DATA_PLAN_WORDS)()
+    args = list(shape) + [0] * (5 - len(shape))
+    check(load().stemgnn_data_plan(SG_DATA_ENTRY[entry], *args, out), f"stemgnn_data_plan({entry}, {shape})")
+    return {k: int(out[i]) for k, i in SG_DATA_WORD.items()}
+
+
 _P = c_void_p          # device pointer
 _PP = POINTER(c_void_p)  # host array of device pointers
 
@@ -141,6 +158,7 @@ SIGNATURES = {
     "stemgnn_eval_metrics": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, _P, _P, _P]),
     "stemgnn_eval_scratch_doubles_masked": (c_size_t, [c_long, c_int, c_int]),
     "stemgnn_eval_metrics_masked": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, _P, _P, _P]),
+    "stemgnn_data_plan": (c_int, [c_int, c_long, c_long, c_long, c_long, c_long, POINTER(c_int)]),
     "stemgnn_block_pack": (c_int, [_PP, _P, _P, c_int, c_int, _P]),
     "stemgnn_block_pack_panels": (c_int, [_PP, _P, _P, c_int, c_int, _P]),
     "stemgnn_block_unpack_grads": (c_int, [_P, c_int, _P, _PP, c_int, c_int, c_int, _P]),

@@ -13,6 +13,31 @@
 #include "sg_host.h"
 
 // ---------------------------------------------------------------------------------------------------------------
+// Launch plans.  Every launcher below asks one of the static `*_plan` functions for its geometry and launches exactly that;
+// stemgnn_data_plan (the end of this file) hands the same answers to the tests, so a threshold or a cap lives in one place.
+// A plan function returns false for a shape its entry refuses.
+struct SgDataPlan {
+  unsigned gx = 1, gy = 1, gz = 1;                                // the (first) launch's grid
+  int threads = 0, vec = 0, rows_per_wg = 0, form = 0, passes = 0, nchunk = 0;
+};
+constexpr int SG_GRID_YZ_MAX = 65535;                             // HIP's limit on grid.y and grid.z
+constexpr int COPY_THREADS = 256;                                 // the flat grid-stride kernels (normalise, MSE backward, store)
+
+static inline int sg_passes(size_t total, size_t per_pass) {     // trips of thread 0 of workgroup 0 through `i < total; i += per_pass`
+  const size_t p = (total + per_pass - 1) / per_pass;
+  return p > (size_t)0x7fffffff ? 0x7fffffff : (int)p;
+}
+static inline bool flat_plan(size_t total, unsigned max_blocks, SgDataPlan* p) {
+  size_t blocks = (total + COPY_THREADS - 1) / COPY_THREADS;
+  if (blocks > max_blocks) blocks = max_blocks;
+  p->gx = (unsigned)blocks;
+  p->threads = COPY_THREADS;
+  p->passes = sg_passes(total, blocks * COPY_THREADS);
+  return true;
+}
+__host__ __device__ static inline bool sg_copy_vec(int N) { return (N & 3) == 0; }   // a row of N floats as float4s
+
+// ---------------------------------------------------------------------------------------------------------------
 // out[t,n] = float( clip01?( (raw[t,n] - sub[n]) / div[n] ) ) -- IEEE fp64 subtract and divide, as numpy does
 __global__ void sg_normalize_kernel(const double* __restrict__ raw, const double* __restrict__ sub,
                                     const double* __restrict__ div, int clip01, float* __restrict__ out, size_t total,
@@ -27,13 +52,17 @@ __global__ void sg_normalize_kernel(const double* __restrict__ raw, const double
   }
 }
 
+static bool normalize_plan(long T, int N, SgDataPlan* p) {
+  if (T <= 0 || N <= 0) return false;
+  return flat_plan((size_t)T * N, 4096, p);
+}
+
 extern "C" int stemgnn_normalize_series(const double* raw, const double* sub, const double* div, int clip01, float* out,
                                         long T, int N, void* stream) {
-  if (!raw || !sub || !div || !out || T <= 0 || N <= 0) return SG_EINVAL;
+  SgDataPlan p;
+  if (!raw || !sub || !div || !out || !normalize_plan(T, N, &p)) return SG_EINVAL;
   const size_t total = (size_t)T * N;
-  unsigned blocks = (unsigned)((total + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(sg_normalize_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, raw, sub, div, clip01, out,
+  hipLaunchKernelGGL(sg_normalize_kernel, dim3(p.gx), dim3(p.threads), 0, (hipStream_t)stream, raw, sub, div, clip01, out,
                      total, N);
   SG_TRY(hipGetLastError());
   return 0;
@@ -54,7 +83,7 @@ __global__ void sg_window_gather_kernel(const float* __restrict__ series, const 
   const bool ok = h0 - W >= 0 && h0 + H <= T;
   if (!ok && threadIdx.x == 0 && status) atomicOr(status, 1);
   const float* src = (r < W ? series : series_y) + (size_t)(ok ? t : 0) * N;
-  if ((N & 3) == 0) {
+  if (sg_copy_vec(N)) {
     const float4* s4 = reinterpret_cast<const float4*>(src);
     float4* d4 = reinterpret_cast<float4*>(dst);
     for (int i = threadIdx.x; i < N / 4; i += blockDim.x) d4[i] = ok ? s4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -63,12 +92,24 @@ __global__ void sg_window_gather_kernel(const float* __restrict__ series, const 
   }
 }
 
+// B is grid.y of both gathers, the window shifts and the store: above HIP's limit the launch itself would fail
+static inline bool gather_shape_ok(int B, int W, int H, int N) {
+  return B > 0 && B <= SG_GRID_YZ_MAX && W > 0 && H >= 0 && N > 0;
+}
+static bool gather_plan(int B, int W, int H, int N, SgDataPlan* p) {
+  if (!gather_shape_ok(B, W, H, N)) return false;
+  p->gx = (unsigned)(W + H), p->gy = (unsigned)B;
+  p->threads = N >= 1024 ? 256 : (N >= 256 ? 128 : 64);
+  p->vec = sg_copy_vec(N);
+  return true;
+}
+
 extern "C" int stemgnn_window_gather_pair(const float* series_x, const float* series_y, const long long* hi, float* x,
                                           float* y, int B, int W, int H, int N, long T, int* status, void* stream) {
-  if (!series_x || !series_y || !hi || !x || !y || B <= 0 || W <= 0 || H < 0 || N <= 0 || T < (long)W + H) return SG_EINVAL;
-  if ((N & 3) == 0 && ((((uintptr_t)series_x | (uintptr_t)series_y | (uintptr_t)x | (uintptr_t)y) & 15) != 0)) return SG_EINVAL;
-  const int threads = N >= 1024 ? 256 : (N >= 256 ? 128 : 64);
-  hipLaunchKernelGGL(sg_window_gather_kernel, dim3(W + H, B), dim3(threads), 0, (hipStream_t)stream, series_x, series_y, hi,
+  SgDataPlan p;
+  if (!series_x || !series_y || !hi || !x || !y || !gather_plan(B, W, H, N, &p) || T < (long)W + H) return SG_EINVAL;
+  if (p.vec && ((((uintptr_t)series_x | (uintptr_t)series_y | (uintptr_t)x | (uintptr_t)y) & 15) != 0)) return SG_EINVAL;
+  hipLaunchKernelGGL(sg_window_gather_kernel, dim3(p.gx, p.gy), dim3(p.threads), 0, (hipStream_t)stream, series_x, series_y, hi,
                      x, y, W, H, N, T, status);
   SG_TRY(hipGetLastError());
   return 0;
@@ -105,7 +146,7 @@ __global__ void sg_window_gather_queue_kernel(const float* __restrict__ series, 
   for (int r = r0; r < r1; ++r) {
     float* dst = r < W ? x + ((size_t)b * W + r) * N : y + ((size_t)b * H + (r - W)) * N;
     const float* src = (r < W ? series : series_y) + (size_t)(ok ? h0 - W + r : 0) * N;
-    if ((N & 3) == 0) {
+    if (sg_copy_vec(N)) {
       const float4* s4 = reinterpret_cast<const float4*>(src);
       float4* d4 = reinterpret_cast<float4*>(dst);
       for (int i = threadIdx.x; i < N / 4; i += blockDim.x) d4[i] = ok ? s4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -126,17 +167,27 @@ __global__ void sg_window_gather_queue_kernel(const float* __restrict__ series, 
   }
 }
 
+static bool gather_queue_plan(int B, int W, int H, int N, SgDataPlan* p) {
+  if (!gather_shape_ok(B, W, H, N)) return false;
+  constexpr int WGS = 64;                                         // about this many workgroups take a ticket
+  int rows_per_wg = ((W + H) * B + WGS - 1) / WGS;
+  if (rows_per_wg > W + H) rows_per_wg = W + H;
+  p->gx = (unsigned)((W + H + rows_per_wg - 1) / rows_per_wg), p->gy = (unsigned)B;
+  p->threads = N >= 512 ? 256 : (N >= 128 ? 128 : 64);            // fewer, longer-lived workgroups than the plain gather's
+  p->vec = sg_copy_vec(N);
+  p->rows_per_wg = rows_per_wg;
+  return true;
+}
+
 extern "C" int stemgnn_window_gather_queue_pair(const float* series_x, const float* series_y, const long long* order,
                                                 long long* queue, float* x, float* y, int B, int W, int H, int N, long T,
                                                 int* status, void* stream) {
-  if (!series_x || !series_y || !order || !queue || !x || !y || B <= 0 || W <= 0 || H < 0 || N <= 0 || T < (long)W + H)
+  SgDataPlan p;
+  if (!series_x || !series_y || !order || !queue || !x || !y || !gather_queue_plan(B, W, H, N, &p) || T < (long)W + H)
     return SG_EINVAL;
-  if ((N & 3) == 0 && ((((uintptr_t)series_x | (uintptr_t)series_y | (uintptr_t)x | (uintptr_t)y) & 15) != 0)) return SG_EINVAL;
-  const int threads = N >= 512 ? 256 : (N >= 128 ? 128 : 64);
-  int rows_per_wg = ((W + H) * B + 63) / 64;
-  if (rows_per_wg > W + H) rows_per_wg = W + H;
-  hipLaunchKernelGGL(sg_window_gather_queue_kernel, dim3((W + H + rows_per_wg - 1) / rows_per_wg, B), dim3(threads), 0,
-                     (hipStream_t)stream, series_x, series_y, order, queue, x, y, W, H, N, T, rows_per_wg, status);
+  if (p.vec && ((((uintptr_t)series_x | (uintptr_t)series_y | (uintptr_t)x | (uintptr_t)y) & 15) != 0)) return SG_EINVAL;
+  hipLaunchKernelGGL(sg_window_gather_queue_kernel, dim3(p.gx, p.gy), dim3(p.threads), 0, (hipStream_t)stream, series_x,
+                     series_y, order, queue, x, y, W, H, N, T, p.rows_per_wg, status);
   SG_TRY(hipGetLastError());
   return 0;
 }
@@ -149,6 +200,8 @@ extern "C" int stemgnn_window_gather_queue(const float* series, const long long*
 // MSE (nn.MSELoss(reduction='mean'), handler.py:140): loss = sum((f-y)^2)/n; two-stage fixed-order reduction.
 constexpr int MSE_BLOCKS = 128;
 constexpr int MSE_THREADS = 256;
+constexpr int MSE_SMALL_THREADS = 1024;                           // the one-workgroup form
+constexpr size_t MSE_SMALL_MAX = (size_t)1 << 16;                 // ... up to this many elements
 
 __device__ __forceinline__ float sg_block_sum(float v, float* sm) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
@@ -188,11 +241,12 @@ __global__ void sg_mse_final_kernel(const float* __restrict__ part, int nparts, 
 
 // small inputs (one training batch: B*H*N = 21,888 values at PEMS07): ONE workgroup, one launch -- the two-stage
 // reduction above costs a second kernel boundary on the critical path for nothing
-__global__ __launch_bounds__(1024) void sg_mse_small_kernel(const float* __restrict__ f, const float* __restrict__ y, size_t n,
-                                                            float* __restrict__ loss, double* __restrict__ accum) {
-  __shared__ float sm[16];
+__global__ __launch_bounds__(MSE_SMALL_THREADS) void sg_mse_small_kernel(const float* __restrict__ f,
+                                                                         const float* __restrict__ y, size_t n,
+                                                                         float* __restrict__ loss, double* __restrict__ accum) {
+  __shared__ float sm[MSE_SMALL_THREADS / 64];
   float acc = 0.f;
-  for (size_t i = threadIdx.x; i < n; i += 1024) {
+  for (size_t i = threadIdx.x; i < n; i += MSE_SMALL_THREADS) {
     const float d = f[i] - y[i];
     acc = fmaf(d, d, acc);
   }
@@ -213,16 +267,27 @@ __global__ void sg_mse_bwd_kernel(const float* __restrict__ f, const float* __re
 
 extern "C" size_t stemgnn_mse_scratch_floats(void) { return MSE_BLOCKS; }
 
+static bool mse_fwd_plan(size_t n, SgDataPlan* p) {
+  if (n == 0) return false;
+  p->form = n <= MSE_SMALL_MAX ? 0 : 1;
+  p->gx = p->form == 0 ? 1 : MSE_BLOCKS;
+  p->threads = p->form == 0 ? MSE_SMALL_THREADS : MSE_THREADS;
+  p->passes = sg_passes(n, (size_t)p->gx * p->threads);
+  return true;
+}
+static bool mse_bwd_plan(size_t n, SgDataPlan* p) { return n != 0 && flat_plan(n, 1024, p); }
+
 extern "C" int stemgnn_mse_fwd(const float* forecast, const float* target, size_t n, float* scratch, float* loss,
                                double* loss_accum, void* stream) {
-  if (!forecast || !target || !scratch || !loss || n == 0) return SG_EINVAL;
-  if (n <= (size_t)1 << 16) {
-    hipLaunchKernelGGL(sg_mse_small_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, forecast, target, n, loss, loss_accum);
+  SgDataPlan p;
+  if (!forecast || !target || !scratch || !loss || !mse_fwd_plan(n, &p)) return SG_EINVAL;
+  if (p.form == 0) {
+    hipLaunchKernelGGL(sg_mse_small_kernel, dim3(p.gx), dim3(p.threads), 0, (hipStream_t)stream, forecast, target, n, loss,
+                       loss_accum);
     SG_TRY(hipGetLastError());
     return 0;
   }
-  hipLaunchKernelGGL(sg_mse_partial_kernel, dim3(MSE_BLOCKS), dim3(MSE_THREADS), 0, (hipStream_t)stream, forecast,
-                     target, n, scratch);
+  hipLaunchKernelGGL(sg_mse_partial_kernel, dim3(p.gx), dim3(p.threads), 0, (hipStream_t)stream, forecast, target, n, scratch);
   SG_TRY(hipGetLastError());
   hipLaunchKernelGGL(sg_mse_final_kernel, dim3(1), dim3(MSE_BLOCKS), 0, (hipStream_t)stream, scratch, MSE_BLOCKS, n,
                      loss, loss_accum);
@@ -232,10 +297,9 @@ extern "C" int stemgnn_mse_fwd(const float* forecast, const float* target, size_
 
 extern "C" int stemgnn_mse_bwd(const float* forecast, const float* target, size_t n, const float* grad_loss,
                                float* dforecast, void* stream) {
-  if (!forecast || !target || !grad_loss || !dforecast || n == 0) return SG_EINVAL;
-  unsigned blocks = (unsigned)((n + 255) / 256);
-  if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(sg_mse_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, forecast, target, n, grad_loss,
+  SgDataPlan p;
+  if (!forecast || !target || !grad_loss || !dforecast || !mse_bwd_plan(n, &p)) return SG_EINVAL;
+  hipLaunchKernelGGL(sg_mse_bwd_kernel, dim3(p.gx), dim3(p.threads), 0, (hipStream_t)stream, forecast, target, n, grad_loss,
                      dforecast);
   SG_TRY(hipGetLastError());
   return 0;
@@ -263,13 +327,23 @@ __global__ void sg_roll_window_kernel(const float* __restrict__ inputs, const fl
   for (int i = threadIdx.x; i < N; i += blockDim.x) dst[i] = src[i];
 }
 
+// both window shifts: W window rows, then Q * L rows of forecast_steps (Q = 1: the point forecast's)
+static bool roll_plan(int B, int W, int L, int N, int Q, SgDataPlan* p) {
+  if (B <= 0 || B > SG_GRID_YZ_MAX || W <= 0 || N <= 0 || L <= 0 || L > W) return false;
+  if (Q <= 0 || (long long)Q * L > (1 << 20)) return false;
+  p->gx = (unsigned)(W + Q * L), p->gy = (unsigned)B;
+  p->threads = N >= 256 ? 256 : 64;
+  return true;
+}
+
 extern "C" int stemgnn_roll_window(const float* inputs, const float* forecast, float* inputs_next,
                                    float* forecast_steps, int B, int W, int L, int N, int step, int horizon,
                                    void* stream) {
+  SgDataPlan p;
   if (!inputs || !forecast || !inputs_next || !forecast_steps || inputs == inputs_next) return SG_EINVAL;
-  if (B <= 0 || W <= 0 || N <= 0 || L <= 0 || L > W || step < 0 || step >= horizon) return SG_EINVAL;
-  hipLaunchKernelGGL(sg_roll_window_kernel, dim3(W + L, B), dim3(N >= 256 ? 256 : 64), 0, (hipStream_t)stream, inputs,
-                     forecast, inputs_next, forecast_steps, W, L, N, step, horizon);
+  if (!roll_plan(B, W, L, N, 1, &p) || step < 0 || step >= horizon) return SG_EINVAL;
+  hipLaunchKernelGGL(sg_roll_window_kernel, dim3(p.gx, p.gy), dim3(p.threads), 0, (hipStream_t)stream, inputs, forecast,
+                     inputs_next, forecast_steps, W, L, N, step, horizon);
   SG_TRY(hipGetLastError());
   return 0;
 }
@@ -299,11 +373,11 @@ __global__ void sg_roll_window_quantile_kernel(const float* __restrict__ inputs,
 extern "C" int stemgnn_roll_window_quantile(const float* inputs, const float* forecast, float* inputs_next,
                                             float* forecast_steps, int B, int W, int L, int N, int Q, int point, int step,
                                             int horizon, void* stream) {
+  SgDataPlan p;
   if (!inputs || !forecast || !inputs_next || !forecast_steps || inputs == inputs_next) return SG_EINVAL;
-  if (B <= 0 || W <= 0 || N <= 0 || L <= 0 || L > W || step < 0 || step >= horizon) return SG_EINVAL;
-  if (Q <= 0 || point < 0 || point >= Q || B > 65535 || (long long)Q * L > (1 << 20)) return SG_EINVAL;
-  hipLaunchKernelGGL(sg_roll_window_quantile_kernel, dim3(W + Q * L, B), dim3(N >= 256 ? 256 : 64), 0, (hipStream_t)stream,
-                     inputs, forecast, inputs_next, forecast_steps, W, L, N, Q, point, step, horizon);
+  if (!roll_plan(B, W, L, N, Q, &p) || step < 0 || step >= horizon || point < 0 || point >= Q) return SG_EINVAL;
+  hipLaunchKernelGGL(sg_roll_window_quantile_kernel, dim3(p.gx, p.gy), dim3(p.threads), 0, (hipStream_t)stream, inputs,
+                     forecast, inputs_next, forecast_steps, W, L, N, Q, point, step, horizon);
   SG_TRY(hipGetLastError());
   return 0;
 }
@@ -323,14 +397,20 @@ __global__ void sg_forecast_store_kernel(const float* __restrict__ forecast, con
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < HN; i += gridDim.x * blockDim.x) dst[i] = src[i];
 }
 
+static bool store_plan(int B, int H, int N, SgDataPlan* p) {
+  if (B <= 0 || B > SG_GRID_YZ_MAX || H <= 0 || N <= 0 || (long long)H * N > (1 << 30)) return false;    // the kernel's int index
+  flat_plan((size_t)H * N, 64, p);                                // per slab row: at most 64 workgroups
+  p->gy = (unsigned)B, p->gz = 2;                                 // z: forecast | target
+  return true;
+}
+
 extern "C" int stemgnn_forecast_store(const float* forecast, const float* target, const long long* pos, float* out_forecast,
                                       float* out_target, int B, int H, int N, long capacity, void* stream) {
-  if (!forecast || !target || !pos || !out_forecast || !out_target || B <= 0 || H <= 0 || N <= 0 || capacity <= 0)
+  SgDataPlan p;
+  if (!forecast || !target || !pos || !out_forecast || !out_target || !store_plan(B, H, N, &p) || capacity <= 0)
     return SG_EINVAL;
-  const int HN = H * N;
-  const unsigned gx = (unsigned)((HN + 255) / 256 < 64 ? (HN + 255) / 256 : 64);
-  hipLaunchKernelGGL(sg_forecast_store_kernel, dim3(gx, B, 2), dim3(256), 0, (hipStream_t)stream, forecast, target, pos,
-                     out_forecast, out_target, HN, capacity);
+  hipLaunchKernelGGL(sg_forecast_store_kernel, dim3(p.gx, p.gy, p.gz), dim3(p.threads), 0, (hipStream_t)stream, forecast,
+                     target, pos, out_forecast, out_target, H * N, capacity);
   SG_TRY(hipGetLastError());
   return 0;
 }
@@ -344,13 +424,18 @@ extern "C" int stemgnn_forecast_store(const float* forecast, const float* target
 // MASKED (stemgnn_eval_metrics_masked): an element whose target is NaN is skipped, a fourth plane of `part` / `colsum` counts
 // the elements kept per column, and every mean divides by its slice's count (a slice with none: 0 / 0 = NaN).
 constexpr int EVAL_CHUNK_ROWS = 64;
+constexpr int METRIC_THREADS = 256;                               // both stages of both metric entries
 
 template <bool MASKED>
-__global__ __launch_bounds__(256) void sg_eval_partial_kernel(const float* __restrict__ target,
+__global__ __launch_bounds__(METRIC_THREADS) void sg_eval_partial_kernel(const float* __restrict__ target,
                                                               const float* __restrict__ forecast,
                                                               const double* __restrict__ mul,
                                                               const double* __restrict__ add, long count, int HN, int N,
                                                               double* __restrict__ part) {
+  // Plain operators under `fp contract(off)`: __dmul_rn / __dadd_rn are inline functions holding a plain operator each, compiled
+  // under the translation unit's contraction mode, so v * mul + add and s_se + d * d written with them fused into one FMA and
+  // the de-normalised values were not numpy's `data * std + mean`.  The pragma covers what is written in this body.
+#pragma clang fp contract(off)
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= HN) return;
   const long r0 = (long)blockIdx.y * EVAL_CHUNK_ROWS;
@@ -365,8 +450,8 @@ __global__ __launch_bounds__(256) void sg_eval_partial_kernel(const float* __res
       s_cnt += 1.0;                                               // a small integer: exact in fp64
     }
     if (mul) {
-      t = __dadd_rn(__dmul_rn(t, mu), ad);
-      f = __dadd_rn(__dmul_rn(f, mu), ad);
+      t = t * mu + ad;
+      f = f * mu + ad;
     }
     const double d = __dsub_rn(f, t);
     const double ae = fabs(d);
@@ -374,7 +459,7 @@ __global__ __launch_bounds__(256) void sg_eval_partial_kernel(const float* __res
     ape = ape > 5.0 ? 5.0 : ape;
     s_ape += ape;
     s_ae += ae;
-    s_se = __dadd_rn(s_se, __dmul_rn(d, d));
+    s_se += d * d;
   }
   const size_t nchunk = gridDim.y;
   part[((size_t)0 * nchunk + blockIdx.y) * HN + c] = s_ape;
@@ -386,7 +471,7 @@ __global__ __launch_bounds__(256) void sg_eval_partial_kernel(const float* __res
 // one workgroup; thread-per-column chunk sums -> by_step_node sums in LDS-free global scratch (`colsum`), then the
 // coarser variants by fixed-order loops (H*N is a few thousand at most: this is a microsecond-scale epilogue)
 template <bool MASKED>
-__global__ __launch_bounds__(256) void sg_eval_final_kernel(const double* __restrict__ part, int nchunk, long count,
+__global__ __launch_bounds__(METRIC_THREADS) void sg_eval_final_kernel(const double* __restrict__ part, int nchunk, long count,
                                                             int H, int N, double* __restrict__ colsum,
                                                             double* __restrict__ out) {
   const int HN = H * N;
@@ -446,6 +531,14 @@ __global__ __launch_bounds__(256) void sg_eval_final_kernel(const double* __rest
 }
 
 static inline int eval_nchunk(long count) { return (int)((count + EVAL_CHUNK_ROWS - 1) / EVAL_CHUNK_ROWS); }
+// stage 1 of both metric entries: thread = column (h, n), grid.y = row chunk, grid.z = `planes` (quantile metrics: what to sum)
+static bool metrics_plan(long count, int H, int N, int planes, SgDataPlan* p) {
+  if (count <= 0 || H <= 0 || N <= 0 || (count + EVAL_CHUNK_ROWS - 1) / EVAL_CHUNK_ROWS > SG_GRID_YZ_MAX) return false;
+  p->nchunk = eval_nchunk(count);
+  p->threads = METRIC_THREADS;
+  p->gx = (unsigned)((H * N + METRIC_THREADS - 1) / METRIC_THREADS), p->gy = (unsigned)p->nchunk, p->gz = (unsigned)planes;
+  return true;
+}
 
 extern "C" size_t stemgnn_eval_scratch_doubles(long count, int H, int N) {
   if (count <= 0 || H <= 0 || N <= 0) return 0;
@@ -464,17 +557,17 @@ extern "C" size_t stemgnn_eval_scratch_doubles_masked(long count, int H, int N) 
 template <bool MASKED>
 static int eval_metrics_impl(const float* target, const float* forecast, const double* mul, const double* add, long count,
                              int H, int N, double* scratch, double* out, void* stream) {
-  if (!target || !forecast || !scratch || !out || count <= 0 || H <= 0 || N <= 0) return SG_EINVAL;
+  SgDataPlan p;
+  if (!target || !forecast || !scratch || !out || !metrics_plan(count, H, N, 1, &p)) return SG_EINVAL;
   if ((mul == nullptr) != (add == nullptr)) return SG_EINVAL;
-  const int HN = H * N, nchunk = eval_nchunk(count);
-  if (nchunk > 65535) return SG_EINVAL;
+  const int HN = H * N, nchunk = p.nchunk;
   double* part = scratch;
   double* colsum = scratch + (size_t)(MASKED ? 4 : 3) * HN * nchunk;
-  hipLaunchKernelGGL(sg_eval_partial_kernel<MASKED>, dim3((HN + 255) / 256, nchunk), dim3(256), 0, (hipStream_t)stream,
-                     target, forecast, mul, add, count, HN, N, part);
+  hipLaunchKernelGGL(sg_eval_partial_kernel<MASKED>, dim3(p.gx, p.gy), dim3(p.threads), 0, (hipStream_t)stream, target,
+                     forecast, mul, add, count, HN, N, part);
   SG_TRY(hipGetLastError());
-  hipLaunchKernelGGL(sg_eval_final_kernel<MASKED>, dim3(1), dim3(256), 0, (hipStream_t)stream, part, nchunk, count, H, N,
-                     colsum, out);
+  hipLaunchKernelGGL(sg_eval_final_kernel<MASKED>, dim3(1), dim3(METRIC_THREADS), 0, (hipStream_t)stream, part, nchunk, count,
+                     H, N, colsum, out);
   SG_TRY(hipGetLastError());
   return 0;
 }
@@ -498,11 +591,13 @@ extern "C" int stemgnn_eval_metrics_masked(const float* target, const float* for
 struct SgTausD { double v[32]; };
 
 template <bool MASKED>
-__global__ __launch_bounds__(256) void sg_quantile_partial_kernel(const float* __restrict__ target,
+__global__ __launch_bounds__(METRIC_THREADS) void sg_quantile_partial_kernel(const float* __restrict__ target,
                                                                   const float* __restrict__ forecast, SgTausD taus,
                                                                   const double* __restrict__ mul,
                                                                   const double* __restrict__ add, long count, int Q, int HN,
                                                                   int N, double* __restrict__ part) {
+  // as in sg_eval_partial_kernel: every product and sum rounds on its own
+#pragma clang fp contract(off)
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= HN) return;
   const int P = Q / 2, z = blockIdx.z;
@@ -521,11 +616,11 @@ __global__ __launch_bounds__(256) void sg_quantile_partial_kernel(const float* _
       double t = (double)target[(size_t)r * HN + c], f = (double)forecast[((size_t)r * Q + z) * HN + c];
       if (MASKED && t != t) continue;
       if (dn) {
-        t = __dadd_rn(__dmul_rn(t, mu), ad);
-        f = __dadd_rn(__dmul_rn(f, mu), ad);
+        t = t * mu + ad;
+        f = f * mu + ad;
       }
       const double d = __dsub_rn(f, t);
-      s0 += d >= 0.0 ? __dmul_rn(1.0 - tau, d) : __dmul_rn(-tau, d);
+      s0 += d >= 0.0 ? (1.0 - tau) * d : -tau * d;
       s1 += t <= f ? 1.0 : 0.0;
     }
   } else if (z < Q + P) {
@@ -536,9 +631,9 @@ __global__ __launch_bounds__(256) void sg_quantile_partial_kernel(const float* _
       double lo = (double)forecast[((size_t)r * Q + i) * HN + c], hi = (double)forecast[((size_t)r * Q + j) * HN + c];
       if (MASKED && t != t) continue;
       if (dn) {
-        t = __dadd_rn(__dmul_rn(t, mu), ad);
-        lo = __dadd_rn(__dmul_rn(lo, mu), ad);
-        hi = __dadd_rn(__dmul_rn(hi, mu), ad);
+        t = t * mu + ad;
+        lo = lo * mu + ad;
+        hi = hi * mu + ad;
       }
       s0 += (lo <= t && t <= hi) ? 1.0 : 0.0;
       s1 += __dsub_rn(hi, lo);
@@ -552,7 +647,7 @@ __global__ __launch_bounds__(256) void sg_quantile_partial_kernel(const float* _
       double prev = 0.0;
       for (int q = 0; q < Q; ++q) {
         double f = (double)forecast[((size_t)r * Q + q) * HN + c];
-        if (dn) f = __dadd_rn(__dmul_rn(f, mu), ad);
+        if (dn) f = f * mu + ad;
         if (q > 0 && f < prev) cross = true;
         prev = f;
       }
@@ -564,7 +659,7 @@ __global__ __launch_bounds__(256) void sg_quantile_partial_kernel(const float* _
   part[((size_t)k1 * nchunk + blockIdx.y) * HN + c] = s1;
 }
 
-__global__ __launch_bounds__(256) void sg_quantile_final_kernel(const double* __restrict__ part, int nchunk, int K, int H, int N,
+__global__ __launch_bounds__(METRIC_THREADS) void sg_quantile_final_kernel(const double* __restrict__ part, int nchunk, int K, int H, int N,
                                                                 double* __restrict__ colsum, double* __restrict__ out) {
   const int HN = H * N, K1 = K + 1;                                // plane K: the kept counts
   double* stepsum = colsum + (size_t)K1 * HN;                      // [K1][H]
@@ -591,6 +686,11 @@ __global__ __launch_bounds__(256) void sg_quantile_final_kernel(const double* __
 }
 
 static inline int quantile_nstat(int Q) { return 2 * Q + 2 * (Q / 2) + 1; }
+static bool quantile_metrics_plan(long count, int Q, int H, int N, SgDataPlan* p) {
+  if (Q <= 0 || Q > 32 || H <= 0 || N <= 0) return false;
+  if ((long long)H * N > (1ll << 30) / (quantile_nstat(Q) + 1)) return false;           // the final kernel's int indices
+  return metrics_plan(count, H, N, Q + Q / 2 + 1, p);             // z: Q levels, Q / 2 pairs, crossing + kept counts
+}
 extern "C" size_t stemgnn_quantile_scratch_doubles(long count, int Q, int H, int N) {
   if (count <= 0 || Q <= 0 || Q > 32 || H <= 0 || N <= 0) return 0;
   const size_t K1 = (size_t)quantile_nstat(Q) + 1;
@@ -605,23 +705,23 @@ template <bool MASKED>
 static int quantile_metrics_impl(const float* target, const float* forecast, const double* taus, const double* mul,
                                  const double* add, long count, int Q, int H, int N, double* scratch, double* out,
                                  void* stream) {
-  if (!target || !forecast || !taus || !scratch || !out || count <= 0 || Q <= 0 || Q > 32 || H <= 0 || N <= 0) return SG_EINVAL;
+  SgDataPlan p;
+  if (!target || !forecast || !taus || !scratch || !out || !quantile_metrics_plan(count, Q, H, N, &p)) return SG_EINVAL;
   if ((mul == nullptr) != (add == nullptr)) return SG_EINVAL;
-  if ((long long)H * N > (1ll << 30) / (quantile_nstat(Q) + 1)) return SG_EINVAL;       // the final kernel's int indices
   SgTausD t;
   for (int q = 0; q < 32; ++q) t.v[q] = 0.5;
   for (int q = 0; q < Q; ++q) {
     if (!(taus[q] > 0.0 && taus[q] < 1.0)) return SG_EINVAL;        // NaN fails both
     t.v[q] = taus[q];
   }
-  const int HN = H * N, nchunk = eval_nchunk(count), K = quantile_nstat(Q);
-  if (nchunk > 65535) return SG_EINVAL;
+  const int HN = H * N, nchunk = p.nchunk, K = quantile_nstat(Q);
   double* part = scratch;
   double* colsum = scratch + (size_t)(K + 1) * HN * nchunk;
-  hipLaunchKernelGGL(sg_quantile_partial_kernel<MASKED>, dim3((HN + 255) / 256, nchunk, Q + Q / 2 + 1), dim3(256), 0,
-                     (hipStream_t)stream, target, forecast, t, mul, add, count, Q, HN, N, part);
+  hipLaunchKernelGGL(sg_quantile_partial_kernel<MASKED>, dim3(p.gx, p.gy, p.gz), dim3(p.threads), 0, (hipStream_t)stream,
+                     target, forecast, t, mul, add, count, Q, HN, N, part);
   SG_TRY(hipGetLastError());
-  hipLaunchKernelGGL(sg_quantile_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, part, nchunk, K, H, N, colsum, out);
+  hipLaunchKernelGGL(sg_quantile_final_kernel, dim3(1), dim3(METRIC_THREADS), 0, (hipStream_t)stream, part, nchunk, K, H, N,
+                     colsum, out);
   SG_TRY(hipGetLastError());
   return 0;
 }
@@ -634,4 +734,33 @@ extern "C" int stemgnn_quantile_metrics_masked(const float* target, const float*
                                                const double* add, long count, int Q, int H, int N, double* scratch, double* out,
                                                void* stream) {
   return quantile_metrics_impl<true>(target, forecast, taus, mul, add, count, Q, H, N, scratch, out, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// What the launchers above do for a shape (include/stemgnn_hip.h: stemgnn_data_plan): host only, nothing is launched or read.
+static inline bool fits_int(long v) { return v >= -0x7fffffffl - 1 && v <= 0x7fffffffl; }
+
+extern "C" int stemgnn_data_plan(int entry, long a0, long a1, long a2, long a3, long a4, int* out) {
+  if (!out) return SG_EINVAL;
+  const bool ints3 = fits_int(a0) && fits_int(a1) && fits_int(a2), ints = ints3 && fits_int(a3);   // a4: the quantile shift's Q alone
+  const int i0 = (int)a0, i1 = (int)a1, i2 = (int)a2, i3 = (int)a3, i4 = (int)a4;
+  SgDataPlan p;
+  bool ok = false;
+  switch (entry) {
+    case SG_DATA_NORMALIZE: ok = fits_int(a1) && normalize_plan(a0, i1, &p); break;
+    case SG_DATA_GATHER: ok = ints && gather_plan(i0, i1, i2, i3, &p); break;
+    case SG_DATA_GATHER_QUEUE: ok = ints && gather_queue_plan(i0, i1, i2, i3, &p); break;
+    case SG_DATA_MSE_FWD: ok = a0 > 0 && mse_fwd_plan((size_t)a0, &p); break;
+    case SG_DATA_MSE_BWD: ok = a0 > 0 && mse_bwd_plan((size_t)a0, &p); break;
+    case SG_DATA_ROLL: ok = ints && roll_plan(i0, i1, i2, i3, 1, &p); break;
+    case SG_DATA_ROLL_QUANTILE: ok = ints && fits_int(a4) && roll_plan(i0, i1, i2, i3, i4, &p); break;
+    case SG_DATA_FORECAST_STORE: ok = ints3 && store_plan(i0, i1, i2, &p); break;
+    case SG_DATA_EVAL: ok = fits_int(a1) && fits_int(a2) && metrics_plan(a0, i1, i2, 1, &p); break;
+    case SG_DATA_QUANTILE_METRICS: ok = fits_int(a1) && fits_int(a2) && fits_int(a3) && quantile_metrics_plan(a0, i1, i2, i3, &p); break;
+    default: break;
+  }
+  if (!ok) return SG_EINVAL;
+  const int words[SG_DATA_PLAN_WORDS] = {(int)p.gx, (int)p.gy, (int)p.gz, p.threads, p.vec, p.rows_per_wg, p.form, p.passes, p.nchunk};
+  for (int i = 0; i < SG_DATA_PLAN_WORDS; ++i) out[i] = words[i];
+  return 0;
 }

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.helpers.data_ref import masked_metrics_numpy
 from tests.util import synthetic_series
 
 pytestmark = pytest.mark.gpu
@@ -75,25 +76,6 @@ def test_forecast_dataset_missing_marks_targets_and_keeps_inputs_imputed(method)
     assert torch.equal(bits(y)[~miss], bits(y0)[~miss])               # bitwise equal elsewhere
     xi, yi = ds[3]
     assert torch.equal(xi, x[3]) and torch.equal(torch.isnan(yi), miss[3])
-
-
-def masked_metrics_numpy(t32, f32, mul=None, add=None):
-    """evaluate()'s formulas over the elements whose target is not NaN, fp64: dict axis-variant -> (mape, mae, rmse)."""
-    t, f = t32.astype(np.float64), f32.astype(np.float64)
-    if mul is not None:
-        t, f = t * mul + add, f * mul + add
-    valid = ~np.isnan(t)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        d = f - t
-        ape = np.abs(d) / np.abs(t) + 1e-5
-        ape = np.where(ape > 5, 5, ape)
-    out = {}
-    for name, axis in (("overall", None), ("by_node", (0, 1)), ("by_step", (0, 2)), ("by_step_node", 0)):
-        cnt = valid.sum(axis=axis).astype(np.float64)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            mean = [np.where(valid, v, 0.0).sum(axis=axis) / cnt for v in (ape, np.abs(d), d * d)]
-        out[name] = (mean[0], mean[1], np.sqrt(mean[2]))
-    return out
 
 
 @pytest.mark.parametrize("denorm", [False, True])

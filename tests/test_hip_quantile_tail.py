@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.helpers.data_ref import scores64
 from tests.test_hip_loss_tail import TOL, fc64
 from tests.test_hip_loss_tail import case as mae_case
 from tests.util import relerr
@@ -221,43 +222,6 @@ def test_roll_window_quantile_is_the_indexing_it_stands_for(B, W, L, N, Q, horiz
             torch.cuda.synchronize()
             assert torch.equal(nxt, want), (point, step)
             assert torch.equal(got_steps, want_steps), (point, step)
-
-
-def scores64(t, f, taus, mul, add, ignore_nan):
-    """numpy fp64 restatement of stemgnn_quantile_metrics: dict name -> (overall, per step [.., H])."""
-    t, f = t.astype(np.float64), f.astype(np.float64)
-    C, Q, H, N = f.shape
-    if mul is not None:
-        t, f = t * mul + add, f * mul + add
-    valid = ~np.isnan(t) if ignore_nan else np.ones_like(t, dtype=bool)
-    P = Q // 2
-
-    def mean(v, h):                                     # v [C,H,N] -> mean over the valid elements of step h (None: all steps)
-        sel = valid if h is None else valid[:, h]
-        vv = v if h is None else v[:, h]
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return np.float64(vv[sel].sum()) / np.float64(sel.sum())
-
-    def both(v):
-        return mean(v, None), np.array([mean(v, h) for h in range(H)])
-    out = {k: ([], []) for k in ("pinball", "coverage", "interval_coverage", "interval_width")}
-
-    def push(k, v):
-        o, s = both(v)
-        out[k][0].append(o)
-        out[k][1].append(s)
-    for q in range(Q):
-        d = f[:, q] - t
-        push("pinball", np.where(d >= 0, (1 - taus[q]) * d, -taus[q] * d))
-        push("coverage", (t <= f[:, q]).astype(np.float64))
-    for i in range(P):
-        lo, hi = f[:, i], f[:, Q - 1 - i]
-        push("interval_coverage", ((lo <= t) & (t <= hi)).astype(np.float64))
-        push("interval_width", hi - lo)
-    res = {k: (np.array(o), np.array(s).reshape(len(o), H)) for k, (o, s) in out.items()}
-    cross = (np.diff(f, axis=1) < 0).any(axis=1).astype(np.float64) if Q > 1 else np.zeros_like(t)
-    res["crossing"] = both(cross)
-    return res
 
 
 @functools.lru_cache(maxsize=None)

@@ -376,11 +376,9 @@ MSE_ONE_WORKGROUP = 1 << 16           # csrc/data.hip, stemgnn_mse_fwd: `n <= (s
 
 @pytest.mark.parametrize("n", (MSE_ONE_WORKGROUP - 1, MSE_ONE_WORKGROUP, MSE_ONE_WORKGROUP + 1, MSE_ONE_WORKGROUP + 4465))
 def test_mse_fwd_on_both_sides_of_its_one_workgroup_threshold(n):
-    import os
-    import re
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stemgnn_amd", "csrc", "data.hip")).read()
-    m = re.search(r"if \(n <= \(size_t\)1 << (\d+)\) \{\s*hipLaunchKernelGGL\(sg_mse_small_kernel", src)
-    assert m and 1 << int(m.group(1)) == MSE_ONE_WORKGROUP, "the threshold moved: move the sizes of this test with it"
+    from stemgnn_amd import _lib
+    forms = [_lib.data_plan("mse_fwd", MSE_ONE_WORKGROUP + k)["form"] for k in (0, 1)]     # what the launcher itself goes by
+    assert forms == [0, 1], "the threshold moved: move the sizes of this test with it"
     assert (MSE_ONE_WORKGROUP + 4465) % 256 != 0
     g = _gen("mse", n)
     f, y, gl = torch.randn(n, generator=g), torch.randn(n, generator=g), torch.tensor([-0.625])

@@ -111,6 +111,35 @@ class _Buf:
         return bool((self.full[self.n:] == SENTINEL).all())
 
 
+class _BufD(_Buf):
+    """_Buf of doubles"""
+
+    def __init__(self, n, fill=float("nan")):
+        self.n = int(n)
+        self.full = torch.full((self.n + GUARD,), fill, device=DEV, dtype=torch.float64)
+        self.full[self.n:] = SENTINEL
+        self.t = self.full[: self.n]
+
+
+POISON_I64 = -0x0DEAD0BAD0C0FFEE          # what an int64 / int32 buffer holds before a call: no position, count or status looks like it
+POISON_I32 = -0x0BADC0DE
+SENTINEL_I = -77772525
+
+
+class _BufI(_Buf):
+    """_Buf of int64 (or int32) words: a recognisable poison in place of NaN, an integer sentinel behind them"""
+
+    def __init__(self, n, fill=None, dtype=torch.int64):
+        self.n = int(n)
+        fill = (POISON_I64 if dtype == torch.int64 else POISON_I32) if fill is None else fill
+        self.full = torch.full((self.n + GUARD,), fill, device=DEV, dtype=dtype)
+        self.full[self.n:] = SENTINEL_I
+        self.t = self.full[: self.n]
+
+    def intact(self):
+        return bool((self.full[self.n:] == SENTINEL_I).all())
+
+
 # ---- csrc/layout.h in Python (tests/test_block_cases.py checks it against the stemgnn_*_floats functions) ----
 def dims(B, N, W, multi):
     c16 = lambda v: (v + 15) & ~15
