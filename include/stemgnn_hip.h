@@ -934,6 +934,35 @@ int stemgnn_anomaly_update(const float* slab, int S, int R, int lo_row, int hi_r
                            long long* counts, long long* alarm_sum, long long* judged_sum, float* log_p, int keep, int log_slot,
                            unsigned int* work, void* stream);
 
+/* stemgnn_serving_plan: how one of the four per-arrival serving entries above launches for a shape, host only: it launches
+ * nothing and reads no buffer.  The launchers take their geometry from the static functions this entry calls
+ * (csrc/serving_plan.h), so what it reports is what runs; tests use it to prove which forms, tiles, trips, parts and batches
+ * their cases reach (tests/test_serving_cases.py).  `entry` is one of SG_SERVING_* and a0..a5 are its shape (unused ones are
+ * ignored); `misaligned` has one bit per buffer whose address decides the form, set = NOT 16-byte aligned:
+ *   SG_SERVING_PUSH (K, N, C), no bits | SG_SERVING_GATHER (C, N, B, L), bit 0 ring, bit 1 out
+ *   SG_SERVING_ACI (H, N, P, M, per_step, per_node), bits 0..3 issued, raw, ring_y, scores
+ *   SG_SERVING_ANOMALY (H, N, M, per_step, per_node), bit 0 scores.
+ * out = SG_SERVING_PLAN_WORDS ints, 0 where a word does not apply:
+ *   [0] form: 0 = columns (and push, gather), 1 = stream, 2 = pooled   [1] [2] [3] the grid of the first (or only) launch
+ *   [4] its threads per workgroup   [5] VEC: 4 = 16-byte accesses, 1 = scalar, 0 = the form has no choice   [6] launches
+ *   push:    [7] k0, the first of the K rows that is stored (K - C when K > C)
+ *   gather:  [7] trips of a thread through the copy loop of one row
+ *   ACI:     [7] Cc [8] Hr [9] L [10] G (the grouping: columns and rows per slot of the column form, run length and runs of the
+ *            stream form)   [11] columns of the last tile   [12] stream: 1 = the window is kept in registers, 0 = streamed
+ *            [13] [14] rows one trip of a workgroup covers, on the fullest (first) and on the last tile (stream: elements)
+ *            [15] [16] trips of the first row lane through one histogram pass over the window, likewise
+ *            [17] [18] its trips through the scoring of the origin, likewise   [19] columns of a full tile (column form)
+ *   anomaly: [7] hspan [8] spans [9] rparts [10] node tiles   [11] trips of a row lane over the population's rows
+ *            [12] rparts before its clamps (192 / (tiles * spans))   [13] the most parts that still get rows   (both: spans > 1)
+ *            [14] pooled: parts   [15] batches of queries   [16] [17] the last batch's queries and their power of two
+ *            [18] L [19] G (pooled)   [20] nodes of a full tile   [21] row lanes of a workgroup (both: column form).
+ * SG_EINVAL for an unknown entry, out == NULL, a bit that names no buffer, or a shape the entry itself refuses (its checks on the
+ * sizes given here, not on pointers, C of the target ring, S, R, keep or the slots). */
+enum { SG_SERVING_PUSH = 0, SG_SERVING_GATHER = 1, SG_SERVING_ACI = 2, SG_SERVING_ANOMALY = 3 };
+enum { SG_SERVING_PLAN_WORDS = 22 };
+int stemgnn_serving_plan(int entry, long a0, long a1, long a2, long a3, long a4, long a5, int misaligned,
+                         int* out /* [SG_SERVING_PLAN_WORDS] */);
+
 /* ---- scenario forecasts: sampled rolling paths and their order statistics (csrc/scenario.hip) --------
  * roll:  one round of a roll that feeds SAMPLED rows back instead of the point row, for Bo origins x S paths.  inputs
  *        [Bsrc, W, N], forecast [Bsrc, Q, L, N], fp32 and contiguous; taus = the Q levels as fp32 in HOST memory, read by the call

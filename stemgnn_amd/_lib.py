@@ -63,6 +63,32 @@ def data_plan(entry, *shape):
     return {k: int(out[i]) for k, i in SG_DATA_WORD.items()}
 
 
+# entries and words of stemgnn_serving_plan (SG_SERVING_* in include/stemgnn_hip.h): the common words, then each entry's own
+SG_SERVING_ENTRY = {"push": 0, "gather": 1, "aci": 2, "anomaly": 3}
+SG_SERVING_FORM = {"columns": 0, "stream": 1, "pooled": 2}
+SG_SERVING_PLAN_WORDS = 22
+SG_SERVING_WORD = {"form": 0, "grid_x": 1, "grid_y": 2, "grid_z": 3, "threads": 4, "vec": 5, "launches": 6}
+SG_SERVING_ENTRY_WORD = {
+    "push": {"k0": 7},
+    "gather": {"trips": 7},
+    "aci": {"Cc": 7, "Hr": 8, "L": 9, "G": 10, "wd_last": 11, "keep": 12, "step_full": 13, "step_last": 14, "pass_trips_full": 15,
+            "pass_trips_last": 16, "origin_trips_full": 17, "origin_trips_last": 18, "tile": 19},
+    "anomaly": {"hspan": 7, "spans": 8, "rparts": 9, "tiles": 10, "pop_trips": 11, "want": 12, "most": 13, "parts": 14,
+                "batches": 15, "nb_last": 16, "p2_last": 17, "L": 18, "G": 19, "tile": 20,
+                "row_lanes": 21},
+}
+
+
+def serving_plan(entry, *shape, misaligned=0):
+    """stemgnn_serving_plan as a dict of SG_SERVING_WORD and the entry's SG_SERVING_ENTRY_WORD names; `entry` a key of
+    SG_SERVING_ENTRY, `shape` as the header lists it for that entry, `misaligned` its bit set; raises on SG_EINVAL."""
+    out = (c_int * SG_SERVING_PLAN_WORDS)()
+    args = [int(v) for v in shape] + [0] * (6 - len(shape))
+    check(load().stemgnn_serving_plan(SG_SERVING_ENTRY[entry], *args, int(misaligned), out),
+          f"stemgnn_serving_plan({entry}, {shape}, {misaligned})")
+    return {k: int(out[i]) for k, i in {**SG_SERVING_WORD, **SG_SERVING_ENTRY_WORD[entry]}.items()}
+
+
 _P = c_void_p          # device pointer
 _PP = POINTER(c_void_p)  # host array of device pointers
 
@@ -229,6 +255,7 @@ SIGNATURES = {
     "stemgnn_anomaly_update": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_longlong, _P, c_int, c_int, c_int, c_int, c_int,
                                        c_longlong, c_double, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P,
                                        _P]),
+    "stemgnn_serving_plan": (c_int, [c_int, c_long, c_long, c_long, c_long, c_long, c_long, c_int, POINTER(c_int)]),
     "stemgnn_scenario_rank": (c_long, [c_double, c_long]),
     "stemgnn_scenario_roll": (c_int, [_P, _P, POINTER(c_float), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_longlong, c_ulonglong, c_ulonglong, c_int, c_int, _P, _P, _P, _P]),

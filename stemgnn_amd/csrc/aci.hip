@@ -25,17 +25,16 @@
 #include "../../include/stemgnn_hip.h"
 #include "conformal_args.h"
 #include "conformal_select.h"
+#include "serving_plan.h"
 #include "sg_host.h"
 
 namespace {
 
-constexpr int ACI_THREADS = 1024;
-constexpr int ACI_WAVES = ACI_THREADS / 64;
-constexpr int ACI_TILE = 32;                  // columns per workgroup (column form)
+// (ACI_THREADS, ACI_WAVES, ACI_TILE = the columns per workgroup of the column form, ACI_KEEP = the loads of the window a thread
+// keeps in registers over the passes of the stream form: serving_plan.h, with the launch geometry)
 constexpr int ACI_PITCH = ACI_TILE + 1;       // LDS row pitch in words
 constexpr int ACI_SEGS = ACI_THREADS / ACI_TILE;   // 32 segments of 8 bins per column in the pick
 constexpr int ACI_COPIES = 16;                // histogram copies (stream form)
-constexpr int ACI_KEEP = 16;                  // loads of the window a thread keeps in registers over the passes (stream form)
 
 struct AciPairs {                             // travels by value in the kernel arguments
   int lo[CF_MAX_P], hi[CF_MAX_P];
@@ -332,15 +331,16 @@ extern "C" int stemgnn_aci_update(const float* issued, const float* raw, const f
   }
   const AciState st = {scores, alpha, offsets, counts, miss_sum, valid_sum};
   hipStream_t s = (hipStream_t)stream;
-  const CfGrouping gr = cf_grouping(per_step, per_node, H, N);
-  if (per_node) {
-    const dim3 grid((unsigned)sg_ceil_div(gr.Cc, ACI_TILE), (unsigned)P);
+  AciPlan pl;
+  aci_plan(H, N, P, M, per_step, per_node, sg_aligned16(issued) && sg_aligned16(raw) && sg_aligned16(ring_y) && sg_aligned16(scores),
+           &pl);
+  const CfGrouping gr = pl.gr;
+  const dim3 grid(pl.gx, pl.gy);
+  if (pl.form == 0) {
     hipLaunchKernelGGL(aci_columns, grid, dim3(ACI_THREADS), 0, s, issued, raw, ring_y, C, origin, H, N, P, pairs, gamma, M,
                        slot, min_scores, gr.Cc, gr.Hr, st);
   } else {
-    const dim3 grid((unsigned)gr.G, (unsigned)P);
-    const bool vec = (N & 3) == 0 && sg_aligned16(issued) && sg_aligned16(raw) && sg_aligned16(ring_y) && sg_aligned16(scores);
-    if (vec)
+    if (pl.vec == 4)
       hipLaunchKernelGGL(aci_stream<4>, grid, dim3(ACI_THREADS), 0, s, issued, raw, ring_y, C, origin, H, N, P, pairs, gamma,
                          M, slot, min_scores, gr.L, st);
     else

@@ -30,24 +30,15 @@
 #include <math.h>
 #include <stdint.h>
 
-#include <algorithm>
-
 #include "../../include/stemgnn_hip.h"
 #include "conformal_args.h"
 #include "conformal_select.h"
+#include "serving_plan.h"
 #include "sg_host.h"
 
 namespace {
 
-constexpr int AN_THREADS = 1024;
-constexpr int AN_TILE = 32;                       // nodes per workgroup (column form)
-constexpr int AN_ROWS = AN_THREADS / AN_TILE;     // row lanes per node
-constexpr int AN_QC = 4;                          // queries per node that share one pass over the population
-constexpr int AN_BATCH = 4096;                    // queries sorted at a time (pooled form)
-constexpr int AN_COL_BLOCKS = 192;                // workgroups the column form of a long horizon aims at
-constexpr int AN_MAX_RPARTS = 16;
-constexpr int AN_PART_KEYS = 8192;                // population keys per workgroup the pooled form aims at
-constexpr int AN_MAX_PARTS = 64;
+// (AN_THREADS, AN_TILE, AN_ROWS, AN_QC, AN_BATCH and the caps of the two spreads: serving_plan.h, with the launch geometry)
 
 struct AnIn {
   const float* slab;
@@ -352,35 +343,77 @@ extern "C" int stemgnn_anomaly_update(const float* slab, int S, int R, int lo_ro
   const AnIn in = {slab, origins, ring_y, S, R, lo_row, hi_row, C, H, N, row};
   const AnOut out = {scores, pvalues, node_p, alarm, counts, alarm_sum, judged_sum, log_p + (size_t)log_slot * N};
   hipStream_t s = (hipStream_t)stream;
-  if (per_node) {
-    const int hspan = H <= AN_QC ? H : (per_step ? 1 : AN_QC), spans = (H + hspan - 1) / hspan;
-    const int tiles = sg_ceil_div(N, AN_TILE);
-    if (spans > 65535) return SG_EINVAL;
-    int rparts = 1;
-    if (spans > 1) {                              // a long horizon: enough workgroups, none without rows
-      const long long rows = per_step ? M : (long long)M * H, most = (rows + AN_ROWS - 1) / AN_ROWS;
-      const long long want = AN_COL_BLOCKS / ((long long)tiles * spans);
-      rparts = (int)(want < 1 ? 1 : (want > AN_MAX_RPARTS ? AN_MAX_RPARTS : want));
-      if (rparts > most) rparts = (int)most;
-    }
-    hipLaunchKernelGGL(anomaly_columns, dim3((unsigned)tiles, (unsigned)spans, (unsigned)rparts), dim3(AN_THREADS), 0, s, in, M,
-                       slot, min_scores, alpha, per_step, hspan, work, out);
+  AnPlan pl;
+  if (!an_plan(H, N, M, per_step, per_node, sg_aligned16(scores), &pl)) return SG_EINVAL;
+  const dim3 grid(pl.gx, pl.gy, pl.gz);
+  if (pl.form == 0) {
+    hipLaunchKernelGGL(anomaly_columns, grid, dim3(AN_THREADS), 0, s, in, M, slot, min_scores, alpha, per_step, pl.hspan, work, out);
     SG_TRY(hipGetLastError());
-    if (spans > 1) {
+    if (pl.launches == 2) {
       hipLaunchKernelGGL(anomaly_finish, dim3(1), dim3(AN_THREADS), 0, s, H, N, slot, min_scores, alpha, per_step, 1, work, out);
       SG_TRY(hipGetLastError());
     }
     return 0;
   }
-  const CfGrouping gr = cf_grouping(per_step, 0, H, N);
-  const int L = gr.L, parts = std::min(sg_ceil_div((long long)M * L, AN_PART_KEYS), AN_MAX_PARTS);
-  const dim3 grid((unsigned)gr.G, (unsigned)parts);
-  if ((N & 3) == 0 && sg_aligned16(scores))
-    hipLaunchKernelGGL(anomaly_pooled<4>, grid, dim3(AN_THREADS), 0, s, in, M, slot, L, scores, work);
+  if (pl.vec == 4)
+    hipLaunchKernelGGL(anomaly_pooled<4>, grid, dim3(AN_THREADS), 0, s, in, M, slot, pl.L, scores, work);
   else
-    hipLaunchKernelGGL(anomaly_pooled<1>, grid, dim3(AN_THREADS), 0, s, in, M, slot, L, scores, work);
+    hipLaunchKernelGGL(anomaly_pooled<1>, grid, dim3(AN_THREADS), 0, s, in, M, slot, pl.L, scores, work);
   SG_TRY(hipGetLastError());
   hipLaunchKernelGGL(anomaly_finish, dim3(1), dim3(AN_THREADS), 0, s, H, N, slot, min_scores, alpha, per_step, 0, work, out);
   SG_TRY(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// What the serving launchers -- this file's, aci.hip's and live.hip's -- do for a shape (include/stemgnn_hip.h:
+// stemgnn_serving_plan): host only, nothing is launched or read.  Every number comes from the function of serving_plan.h the
+// launcher itself calls.
+static inline bool sv_int(long v) { return v >= -0x7fffffffl - 1 && v <= 0x7fffffffl; }
+
+extern "C" int stemgnn_serving_plan(int entry, long a0, long a1, long a2, long a3, long a4, long a5, int misaligned, int* out) {
+  if (!out || misaligned < 0) return SG_EINVAL;
+  int w[SG_SERVING_PLAN_WORDS] = {};
+  const int i0 = (int)a0, i1 = (int)a1, i2 = (int)a2, i3 = (int)a3;
+  switch (entry) {
+    case SG_SERVING_PUSH: {                       // (K, N, C)
+      LvPushPlan p;
+      if (!(sv_int(a0) && sv_int(a1) && sv_int(a2)) || misaligned || !lv_push_plan(i0, i1, i2, &p)) return SG_EINVAL;
+      w[1] = (int)p.blocks, w[2] = w[3] = 1, w[4] = p.threads, w[6] = 1, w[7] = p.k0;
+      break;
+    }
+    case SG_SERVING_GATHER: {                     // (C, N, B, L); misaligned: bit 0 ring, bit 1 out
+      LvGatherPlan p;
+      if (!(sv_int(a0) && sv_int(a1) && sv_int(a2) && sv_int(a3)) || misaligned > 3) return SG_EINVAL;
+      if (!lv_gather_plan(i0, i1, i2, i3, misaligned == 0, &p)) return SG_EINVAL;
+      w[1] = i3, w[2] = i2, w[3] = 1, w[4] = p.threads, w[5] = p.vec, w[6] = 1, w[7] = p.trips;
+      break;
+    }
+    case SG_SERVING_ACI: {                        // (H, N, P, M, per_step, per_node); misaligned: issued, raw, ring_y, scores
+      AciPlan p;
+      if (!(sv_int(a0) && sv_int(a1) && sv_int(a2) && sv_int(a3)) || misaligned > 15) return SG_EINVAL;
+      if (i3 <= 0 || !cf_shapes_ok(i3, 1, i0, i1, i2)) return SG_EINVAL;
+      aci_plan(i0, i1, i2, i3, a4 != 0, a5 != 0, misaligned == 0, &p);
+      w[0] = p.form, w[1] = (int)p.gx, w[2] = (int)p.gy, w[3] = 1, w[4] = ACI_THREADS, w[5] = p.vec, w[6] = 1;
+      w[7] = p.gr.Cc, w[8] = p.gr.Hr, w[9] = p.gr.L, w[10] = p.gr.G, w[11] = p.wd_last, w[12] = p.keep;
+      w[13] = p.step[0], w[14] = p.step[1], w[15] = p.pass_trips[0], w[16] = p.pass_trips[1];
+      w[17] = p.origin_trips[0], w[18] = p.origin_trips[1], w[19] = p.form == 0 ? ACI_TILE : 0;
+      break;
+    }
+    case SG_SERVING_ANOMALY: {                    // (H, N, M, per_step, per_node); misaligned: bit 0 scores
+      AnPlan p;
+      if (!(sv_int(a0) && sv_int(a1) && sv_int(a2)) || misaligned > 1) return SG_EINVAL;
+      if (i0 <= 0 || i1 <= 0 || i2 <= 0 || (long long)i0 * i1 >= (1ll << 31) || (long long)i2 * ((long long)i0 * i1) >= (1ll << 31))
+        return SG_EINVAL;
+      if (!an_plan(i0, i1, i2, a3 != 0, a4 != 0, misaligned == 0, &p)) return SG_EINVAL;
+      w[0] = p.form, w[1] = (int)p.gx, w[2] = (int)p.gy, w[3] = (int)p.gz, w[4] = AN_THREADS, w[5] = p.vec, w[6] = p.launches;
+      w[7] = p.hspan, w[8] = p.spans, w[9] = p.rparts, w[10] = p.tiles, w[11] = p.pop_trips, w[12] = (int)p.want;
+      w[13] = (int)p.most, w[14] = p.parts, w[15] = p.batches, w[16] = p.nb_last, w[17] = p.p2_last, w[18] = p.L, w[19] = p.G;
+      w[20] = p.form == 0 ? AN_TILE : 0, w[21] = p.form == 0 ? AN_ROWS : 0;
+      break;
+    }
+    default: return SG_EINVAL;
+  }
+  for (int i = 0; i < SG_SERVING_PLAN_WORDS; ++i) out[i] = w[i];
   return 0;
 }

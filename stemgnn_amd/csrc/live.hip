@@ -18,12 +18,12 @@
 
 #include "../../include/stemgnn_hip.h"
 #include "conformal_select.h"
+#include "serving_plan.h"
 #include "sg_host.h"
 
 namespace {
 
-constexpr int LV_PUSH_THREADS = 64;
-
+// (LV_PUSH_THREADS and the gather's thread classes: serving_plan.h)
 __global__ __launch_bounds__(LV_PUSH_THREADS) void lv_push_kernel(
     const double* __restrict__ raw, int K, int N, long long t0, const double* __restrict__ sub,
     const double* __restrict__ div, int clip01, double missing, int has_missing, double* __restrict__ last,
@@ -94,10 +94,9 @@ extern "C" int stemgnn_live_push(const double* raw, int K, int N, long long t0, 
                                  int clip01, double missing, int has_missing, double* last, float* ring_x, float* ring_y,
                                  int C, long long* t_dev, void* stream) {
   if (!raw || !sub || !div || !last || !ring_x || !ring_y || !t_dev) return SG_EINVAL;
-  if (K <= 0 || N <= 0 || C <= 0 || t0 < 0) return SG_EINVAL;
-  if ((long long)C * N >= (1ll << 31)) return SG_EINVAL;
-  const unsigned blocks = (unsigned)((N + LV_PUSH_THREADS - 1) / LV_PUSH_THREADS);
-  hipLaunchKernelGGL(lv_push_kernel, dim3(blocks), dim3(LV_PUSH_THREADS), 0, (hipStream_t)stream, raw, K, N, t0, sub, div,
+  LvPushPlan pl;
+  if (t0 < 0 || !lv_push_plan(K, N, C, &pl)) return SG_EINVAL;
+  hipLaunchKernelGGL(lv_push_kernel, dim3(pl.blocks), dim3(pl.threads), 0, (hipStream_t)stream, raw, K, N, t0, sub, div,
                      clip01, missing, has_missing, last, ring_x, ring_y, C, t_dev);
   SG_TRY(hipGetLastError());
   return 0;
@@ -106,12 +105,12 @@ extern "C" int stemgnn_live_push(const double* raw, int K, int N, long long t0, 
 extern "C" int stemgnn_ring_gather(const float* ring, int C, int N, const long long* starts, const long long* t_dev, int back,
                                    int B, int L, float* out, int* status, void* stream) {
   if (!ring || !t_dev || !out) return SG_EINVAL;
-  if (C <= 0 || N <= 0 || B <= 0 || L <= 0 || L > C || B > 65535 || back < 0 || back > C) return SG_EINVAL;
-  if (!starts && B != 1) return SG_EINVAL;
-  if ((long long)C * N >= (1ll << 31)) return SG_EINVAL;
-  const int threads = N >= 1024 ? 256 : (N >= 256 ? 128 : 64);
+  LvGatherPlan pl;
+  if (back < 0 || back > C || (!starts && B != 1)) return SG_EINVAL;
+  if (!lv_gather_plan(C, N, B, L, sg_aligned16(ring) && sg_aligned16(out), &pl)) return SG_EINVAL;
+  const int threads = pl.threads;
   const dim3 grid((unsigned)L, (unsigned)B);
-  if ((N & 3) == 0 && sg_aligned16(ring) && sg_aligned16(out))
+  if (pl.vec == 4)
     hipLaunchKernelGGL(lv_gather_kernel<true>, grid, dim3(threads), 0, (hipStream_t)stream, ring, C, N, starts, t_dev, back, L,
                        out, status);
   else

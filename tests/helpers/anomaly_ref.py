@@ -78,6 +78,56 @@ class AnomalyRef:
         return self.log_p[order].copy(), np.array([self.log_rows[s] for s in order], dtype=np.int64)
 
 
+class AnomalyRefFast(AnomalyRef):
+    """AnomalyRef with update() restated per GROUP instead of per element, for the wide cases of the serving stage suite
+    (tests/test_serving_cases.py proves it equal to the loop on the small cases): a group's population is sorted once and every
+    query of the group meets it through np.searchsorted -- `side="left"` counts the scores below the query in IEEE order
+    (-0 == +0, +inf largest), the rest are >= it.  The per-node combination is the same fp64 expression on whole rows."""
+
+    def update(self, y, f_lo, f_hi=None, present=None, row=None):
+        H, N, M = self.H, self.N, self.M
+        f_hi = f_lo if f_hi is None else f_hi
+        y = np.asarray(y, dtype=F32).reshape(N)
+        score = scores_of(y[None, :], np.asarray(f_lo, dtype=F32).reshape(H, N), np.asarray(f_hi, dtype=F32).reshape(H, N))
+        if present is not None:
+            score[~np.asarray(present, dtype=bool)] = F32(np.nan)
+        slot = self.n_done % M
+        others = np.delete(self.scores, slot, axis=0)                 # [M - 1, H, N]
+        Hg, Ng = self.counts.shape
+        # [Hg, Ng, population of the group] and [Hg, Ng, queries of the group], the queries with their (h, n)
+        pop = others.transpose(1, 2, 0) if self.per_step else others.transpose(2, 0, 1).reshape(1, N, -1)
+        pop = pop if self.per_node else pop.reshape(Hg, 1, -1)
+        hh, nn = np.meshgrid(np.arange(H), np.arange(N), indexing="ij")
+        p = np.full((H, N), np.nan, dtype=F32)
+        for hg in range(Hg):
+            for ng in range(Ng):
+                s = np.sort(pop[hg, ng])                              # NaN last
+                m = int(s.size - np.isnan(s).sum())
+                self.counts[hg, ng] = m
+                if m < self.min_scores:
+                    continue
+                sel = (hh == hg if self.per_step else np.ones((H, N), bool)) & (nn == ng if self.per_node else np.ones((H, N), bool))
+                q = score[sel]
+                ge = m - np.searchsorted(s[:m], q, side="left")
+                with np.errstate(invalid="ignore"):
+                    pv = (np.float64(1) + ge.astype(np.float64)) / np.float64(m + 1)
+                p[sel] = np.where(np.isnan(q), np.nan, pv).astype(F32)
+        self.scores[slot] = score
+        self.pvalues = p
+        ok = ~np.isnan(p)
+        v = ok.sum(axis=0)
+        pmin = np.where(ok, p, F32(np.inf)).min(axis=0).astype(np.float64)
+        with np.errstate(invalid="ignore"):                           # v = 0: 0 * inf, replaced below
+            node = np.minimum(np.float64(1.0), v.astype(np.float64) * pmin).astype(F32)
+        self.node_p = np.where(v > 0, node, F32(np.nan)).astype(F32)
+        self.alarm = ((v > 0) & (self.node_p.astype(np.float64) <= self.alpha)).astype(np.int32)
+        self.judged_sum += (v > 0)
+        self.alarm_sum += self.alarm
+        self.log_p[self.n_done % self.keep] = self.node_p
+        self.log_rows[self.n_done % self.keep] = self.n_done if row is None else int(row)
+        self.n_done += 1
+
+
 # ---- the validity / power stream of both test files ----------------------------------------------------------------------------
 VALID = dict(T=1500, N=8, H=2, window=64, min_scores=32, alpha=0.1, spikes=((700, 3), (701, 3), (1200, 5)), spike=8.0)
 
