@@ -1146,6 +1146,57 @@ int stemgnn_scenario_distances(const float* paths, const double* scale, long cou
 int stemgnn_scenario_reduce(const double* D, long count, int S, int K, int* selected, int* counts, int* assign, double* cost,
                             void* stream);
 
+/* ---- weighted scenario sets: bands, scores, event counts and a further reduction of kept paths (csrc/weighted.hip, DESIGN.md
+ * section 5t) ---------------------------------------------------------------------------------------------------------------
+ * A set is K members per origin with integer multiplicities mult int32 [count, K] (a ScenarioSet's counts): member k stands
+ * mult[c, k] times in an ensemble of W paths, 1 <= W <= 2^24, so every product w w' and W^2 is exact in fp64.  K <= 256 for
+ * bands, scores and events.  A member of multiplicity 0 is not read: a NaN there reaches nothing.  An origin is ABSENT when one
+ * of its multiplicities is negative or they do not add up to W (a refused origin of stemgnn_scenario_reduce has counts 0); an
+ * absent origin does not affect any other.
+ * bands:  paths [count, K, H, N], bands [count, Q, H, N] fp32; ranks = Q ints in HOST memory (stemgnn_scenario_rank(tau, W)),
+ *         passed on by value.  bands[c, q, h, n] = the first value, in the order of stemgnn_scenario_bands (-0 == +0, NaN last,
+ *         stable in k), whose cumulative multiplicity reaches ranks[q]: what stemgnn_scenario_bands returns for the W paths in
+ *         which member k stands mult[c, k] times in a row, bit for bit.  An absent origin is NaN (0x7fc00000) everywhere.  One
+ *         launch; 16-byte accesses when N % 4 == 0 and paths and bands are 16-byte aligned, a scalar path otherwise.
+ * scores: the definitions of stemgnn_ensemble_scores (`masked` != 0: of stemgnn_ensemble_scores_masked) with w_k = mult[c, k]:
+ *           crps = (1 / W) sum_k w_k |x_k - y| - (1 / (2 D)) sum_k sum_k' w_k w_k' |x_k - x_k'|,  D = W^2 or W (W - 1) with fair
+ *           mean = (1 / W) sum_k w_k x_k;  var = sum_k w_k (x_k - mean)^2 / (W - 1), NaN when W == 1
+ *           rank = sum{w_k : x_k < y} + (sum{w_k : x_k == y}) / 2 (integer division), on the raw fp32 values
+ *           energy: the same with Euclidean norms over the row's node set, formed from differences
+ *         out (fp64) = overall[7] | by_step[7][H]: slots 0 .. 5 as in stemgnn_ensemble_scores over the present origins, slot 6 the
+ *         number of absent origins (the same number in every by-step slot).  hist int64 [H][W + 1]; the call zeroes it itself.
+ *         De-normalisation, masking and NaN propagation as there.  Fixed-order two-level fp64 sums, integer atomics for hist
+ *         only (a row's ranks meet in LDS first where W + 1 <= 4096); three launches.  scratch: stemgnn_weighted_scratch_doubles doubles on the device.
+ * events: paths [count, K, H, M], counts int32 [count, 2 H + 1, M]: the three counts of stemgnn_scenario_events with every
+ *         member counted mult[c, k] times -- exact integers, equal to that entry's on the replicated ensemble.  An absent
+ *         origin is -1 everywhere.  One launch.  H <= 256.
+ * reduce_weighted: the forward selection of stemgnn_scenario_reduce on an ensemble of S members with probabilities
+ *         mult_in[c, k] / W (mult_in int32 [count, S], S <= 1024).  With p_k = (double)mult_in[c, k]:
+ *           z_u = sum_k p_k * min(m_k, D[k, u]) over the k with p_k > 0 in index order, the product and the add rounded
+ *                 separately (no FMA);  cost[i] = z_u / W;  counts[j] = the sum of mult_in[k] over the members assigned to j
+ *         A member of multiplicity 0 is no candidate, has assign = -1, and its row and column of D are not read.  Refused as
+ *         there (-1 / 0 / -1 / NaN), also when the origin is absent or K exceeds the number of members of positive multiplicity.
+ *         With mult_in all ones and W == S every output equals stemgnn_scenario_reduce's bit for bit.  One launch; D in LDS
+ *         where it fits (S <= 141).
+ * All: no allocation, no host synchronisation, no memset, no floating-point atomics; the same bits on every run, and an origin's
+ * results do not depend on which other origins share the call; capturable.
+ * SG_EINVAL (nothing launched): a NULL pointer other than mul / add; mul without add; count, K, S, H, N, M or Q <= 0; K > 256;
+ * Q > 32; S > 1024; W outside [1, 2^24]; a rank outside [1, W]; fair with W < 2; events: H > 256, min_run outside [1, H], above
+ * not 0 / 1; reduce_weighted: K outside [1, S]; an int product >= 2^31: count, count * H, H * N, K * H * N (K * H * M), Q * H * N,
+ * (2 H + 1) * M, H * (W + 1), count * S * S, or a grid (bands: count * ceil(H N / C); scores: count * H * T (T + 1) / 2,
+ * T = ceil(K / 32); events: count * ceil(M / C)); the size entries return 0 for such shapes. */
+int stemgnn_weighted_bands(const float* paths, const int* mult, long count, int K, int H, int N, int W, int Q, const int* ranks,
+                           float* bands, void* stream);
+size_t stemgnn_weighted_scratch_doubles(long count, int K, int H, int N);
+size_t stemgnn_weighted_out_doubles(int H);
+int stemgnn_weighted_scores(const float* target, const float* paths, const int* mult, const double* mul, const double* add,
+                            long count, int K, int H, int N, int W, int fair, int masked, double* scratch, double* out,
+                            long long* hist, void* stream);
+int stemgnn_weighted_events(const float* paths, const int* mult, const double* thr, const double* mul, const double* add,
+                            long count, int K, int H, int M, int W, int above, int min_run, int* counts, void* stream);
+int stemgnn_scenario_reduce_weighted(const double* D, const int* mult_in, long count, int S, int K, int W, int* selected,
+                                     int* counts, int* assign, double* cost, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,23 @@ class EnsembleScores:
         paths = _as_f32(paths)
         y = _as_f32(y, like=paths)
         out, hist = ops.ensemble_scores(y, paths, mul, add, ignore_nan=bool(ignore_nan), fair=bool(fair))
+        self._fill(out, hist, 6)
+
+    @classmethod
+    def _weighted(cls, y, paths, mult, total, mul=None, add=None, ignore_nan=False, fair=False):
+        """The scores of a weighted set (`stemgnn_weighted_scores`, through `ScenarioSet.scores`): the same attributes, the
+        histograms over total + 1 bins, and `absent`, the number of origins left out (refused by the reduction, or with
+        multiplicities that do not sum to total).  One host sync."""
+        paths = _as_f32(paths)
+        y = _as_f32(y, like=paths)
+        self = cls.__new__(cls)
+        out, hist = ops.weighted_scores(y, paths, mult, total, mul, add, ignore_nan=bool(ignore_nan), fair=bool(fair))
+        v = self._fill(out, hist, 7)
+        self.absent = int(v[6])
+        return self
+
+    def _fill(self, out, hist, K):
+        """the attributes from out [K * (1 + H)] and hist [H, S + 1] (device): the one sync"""
         H, S = int(hist.shape[0]), int(hist.shape[1]) - 1
         flat = torch.cat([out, hist.reshape(-1).double()]).cpu().numpy()         # (counts below 2^53: exact as doubles)
         v, h = flat[:out.numel()], flat[out.numel():].astype(np.int64).reshape(H, S + 1)
@@ -100,13 +117,14 @@ class EnsembleScores:
         for k, name in enumerate(names):
             kind = np.float64 if k < 4 else np.int64                         # the two counts are integers
             setattr(self, name, kind(v[k]))
-            setattr(self, name + "_step", v[6 + k * H:6 + (k + 1) * H].astype(kind))
+            setattr(self, name + "_step", v[K + k * H:K + (k + 1) * H].astype(kind))
         self.rank_histogram_step = h.copy()
         self.rank_histogram = h.sum(axis=0)
         total = int(self.rank_histogram.sum())
         expect = total / (S + 1.0)
         self.rank_uniformity_dof = S
         self.rank_uniformity = np.float64(((self.rank_histogram - expect) ** 2).sum() / expect) if total else np.float64("nan")
+        return v
 
 
 MAX_GROUPS = 32                              # R of stemgnn_scenario_aggregate
@@ -212,25 +230,30 @@ class ScenarioEvents:
     def run(self):
         return self.counts[:, 2 * self.H]
 
+    def _p(self, n):
+        """n / S; NaN where the counts are negative (an absent origin of a weighted set: `ops.weighted_events` files -1)"""
+        p = n.double() / self.S
+        return torch.where(n < 0, torch.full_like(p, float("nan")), p)
+
     @property
     def p_step(self):
-        return self.step.double() / self.S
+        return self._p(self.step)
 
     @property
     def p_by(self):
-        return self.first.cumsum(dim=1).double() / self.S
+        return self._p(self.first.cumsum(dim=1))
 
     @property
     def p_any(self):
-        return self.first.sum(dim=1).double() / self.S
+        return self._p(self.first.sum(dim=1))
 
     @property
     def p_run(self):
-        return self.run.double() / self.S
+        return self._p(self.run)
 
     @property
     def duration(self):
-        return self.step.sum(dim=1).double() / self.S
+        return self._p(self.step.sum(dim=1))
 
     @staticmethod
     def cat(parts):
@@ -253,6 +276,7 @@ class ScenarioEvents:
         m = torch.arange(M, device=j.device)[None, None, :]
         key = ((k * M + m) * (S + 1) + j) * 2 + o
         bins = kinds * M * (S + 1) * 2
+        key = torch.where(j < 0, torch.full_like(key, bins), key)               # an absent origin of a weighted set is left out
         if ignore_nan and realised.missing is not None:
             gone = realised.missing.any(dim=1, keepdim=True)
             key = torch.where(torch.cat([gone, gone, realised.missing], dim=1), torch.full_like(key, bins), key)
@@ -271,6 +295,8 @@ class EventSpec:
     product where the `coupling=` of the paths changes the answer.  mul / add: per-node de-normalisation, fp64.
       count(paths [count,S,H,N]) -> ScenarioEvents; with groups the paths are aggregated first (`ops.scenario_aggregate`, which
                                   de-normalises), then counted with no further de-normalisation (`ops.scenario_events`)
+                                  paths a ScenarioSet: its kept paths, every member counted with its multiplicity
+                                  (`ops.weighted_events`) -> ScenarioEvents(counts, set.total); an absent origin is -1 / NaN
       aggregate(x [..., N])      -> [..., R] float32, the aggregated (de-normalised) paths or target: rolling_scenarios' layout
                                   with N = R, so ops.scenario_bands, EnsembleScores and QuantileScores take it as it is
       realised(target [count,H,N]) -> ScenarioEvents of the one path that happened (S = 1) with `missing` [count,H,M]: the
@@ -310,6 +336,15 @@ class EventSpec:
         return ops.scenario_events(paths, self.threshold, self.above, self.min_run, self.mul, self.add), paths.shape[1]
 
     def count(self, paths):
+        if isinstance(paths, ScenarioSet):                                       # the kept paths, counted with their multiplicities
+            kept = paths.paths
+            if self.groups is not None:
+                counts = ops.weighted_events(self.aggregate(kept), paths.counts, paths.total, self.threshold, self.above,
+                                             self.min_run)
+            else:
+                counts = ops.weighted_events(kept, paths.counts, paths.total, self.threshold, self.above, self.min_run,
+                                             self.mul, self.add)
+            return ScenarioEvents(counts, paths.total)
         counts, S = self._count(paths)
         return ScenarioEvents(counts, S)
 
@@ -351,9 +386,26 @@ class ScenarioSet:
                     counts and assign are re-derived from the distances, so the set must still hold `distances` [count, S, S]
                     or `source` = (the [count, S, H, R] tensor the distances were taken on, scale, squared): reduce_scenarios
                     keeps a reference to the latter, trainer.reduced_scenarios drops it with the batch's paths
-      cat(parts)    joins batches along the origins"""
+      cat(parts)    joins batches along the origins
+    The set as a weighted ensemble: member k stands counts[c, k] times among `total` paths (total = S
+    unless the set was reduced again, merged or made from_weights; weights = counts / total).  An origin is ABSENT when a count
+    is negative or the counts do not sum to total (a refused origin's are 0): NaN bands, NaN probabilities, left out of scores.
+      bands(quantiles, out=None) -> float32 [count, Q, H, N], `ops.scenario_bands` of the replicated ensemble, bit for bit
+      scores(y, mul=None, add=None, ignore_nan=False, fair=False) -> EnsembleScores with rank histograms over total + 1 bins
+                    and `absent`, the number of absent origins; one host sync
+      events(spec)  -> spec.count(self): ScenarioEvents(counts, total)
+      reduce(keep, on=None, scale=None, squared=False) -> the ScenarioSet of `keep` of the K members, by forward selection with
+                    the counts as input probabilities (`ops.scenario_reduce_weighted`) on the distances between the kept paths,
+                    or between their on= aggregates (reduce_scenarios' on / scale / squared); its S is this set's K, its index
+                    and assign are positions among this set's members, its total this set's total
+      merge(parts)  (static) the members of several sets of the same origins side by side, the totals added: two seeds, two
+                    models, or chunks of an ensemble too large to hold -- merge(chunks).reduce(8) is a two-stage reduction;
+                    cost NaN, no distances
+      from_weights(paths, weights, total=65536)  (static, pure torch) user-supplied probabilities rounded to multiplicities
+                    that sum to total by largest remainders (the lower index first among equal remainders); a row that is
+                    negative, non-finite or all zero becomes an absent origin"""
 
-    def __init__(self, index, counts, assign, cost, S, paths, distances=None, source=None):
+    def __init__(self, index, counts, assign, cost, S, paths, distances=None, source=None, total=None):
         if index.dim() != 2 or index.dtype != torch.int64 or counts.dtype != torch.int32 or counts.shape != index.shape or \
                 cost.shape != index.shape or assign.dim() != 2 or assign.shape[0] != index.shape[0] or \
                 paths.dim() != 4 or paths.shape[:2] != index.shape:
@@ -364,11 +416,95 @@ class ScenarioSet:
         self.distances, self.source = distances, source
         self.count, self.K = int(index.shape[0]), int(index.shape[1])
         self.H, self.N = int(paths.shape[2]), int(paths.shape[3])
+        if total is not None and (isinstance(total, bool) or int(total) != total or not 1 <= int(total) <= 2 ** 24):
+            raise ValueError(f"ScenarioSet: total must be an integer within [1, 2^24], got {total!r}")
+        self.total = self.S if total is None else int(total)
+        self._parent = None                                                      # the set this one was reduced from (reduce)
 
     @property
     def weights(self):
-        w = self.counts.double() / self.S
+        w = self.counts.double() / self.total
         return torch.where(self.index[:, :1] < 0, torch.full_like(w, float("nan")), w)
+
+    def bands(self, quantiles, out=None):
+        return ops.weighted_bands(self.paths, self.counts, self.total, quantiles, out)
+
+    def scores(self, y, mul=None, add=None, ignore_nan=False, fair=False):
+        return EnsembleScores._weighted(y, self.paths, self.counts, self.total, mul, add, ignore_nan=ignore_nan, fair=fair)
+
+    def events(self, spec):
+        if not isinstance(spec, EventSpec):
+            raise ValueError(f"ScenarioSet.events: spec must be an EventSpec, got {type(spec).__name__}")
+        return spec.count(self)
+
+    def reduce(self, keep, on=None, scale=None, squared=False):
+        if isinstance(on, EventSpec):
+            if on.groups is None:
+                raise ValueError("ScenarioSet.reduce: on= an EventSpec stands for its aggregate(paths); the spec has no groups=")
+            on = on.aggregate(self.paths)
+        elif on is None:
+            on = self.paths
+        else:
+            on = _as_f32(on, like=self.paths)
+            if on.dim() != 4 or tuple(on.shape[:3]) != (self.count, self.K, self.H):
+                raise ops._lib.StemGNNHipError(f"ScenarioSet.reduce: on must be [count,K,H,R] with the set's count, K and H "
+                                               f"{(self.count, self.K, self.H)}, got {tuple(on.shape)}")
+        keep = ops._reduce_keep("ScenarioSet.reduce", keep, self.K)
+        D = ops.scenario_distances(on.contiguous(), scale, squared)
+        selected, counts, assign, cost = ops.scenario_reduce_weighted(D, self.counts, self.total, keep)
+        index = selected.long()
+        kept = torch.gather(self.paths, 1, index.clamp(min=0)[:, :, None, None].expand(-1, -1, self.H, self.N))
+        kept = torch.where((index < 0)[:, :, None, None], torch.full_like(kept, float("nan")), kept)
+        out = ScenarioSet(index, counts, assign, cost, self.K, kept, total=self.total)
+        out._parent = self
+        return out
+
+    @staticmethod
+    def merge(parts):
+        parts = list(parts)
+        if not parts or any(not isinstance(p, ScenarioSet) or (p.count, p.H, p.N) != (parts[0].count, parts[0].H, parts[0].N)
+                            for p in parts):
+            raise ValueError("ScenarioSet.merge: the parts must be ScenarioSets of the same origins: one count, H and N")
+        total = sum(p.total for p in parts)
+        if total > 2 ** 24:
+            raise ValueError(f"ScenarioSet.merge: the totals add up to {total}, beyond 2^24")
+        index, assign, s0, k0 = [], [], 0, 0
+        for p in parts:                                                          # indices among the joined S, positions among the joined K
+            index.append(torch.where(p.index < 0, p.index, p.index + s0))
+            assign.append(torch.where(p.assign < 0, p.assign, p.assign + k0))
+            s0, k0 = s0 + p.S, k0 + p.K
+        counts = torch.cat([p.counts for p in parts], dim=1)
+        cost = torch.full(counts.shape, float("nan"), dtype=torch.float64, device=counts.device)
+        return ScenarioSet(torch.cat(index, dim=1), counts, torch.cat(assign, dim=1), cost, s0,
+                           torch.cat([p.paths for p in parts], dim=1), total=total)
+
+    @staticmethod
+    def from_weights(paths, weights, total=65536):
+        paths = _as_f32(paths)
+        if paths.dim() != 4:
+            raise ValueError(f"ScenarioSet.from_weights: paths must be [count,K,H,N], got {tuple(paths.shape)}")
+        if isinstance(total, bool) or int(total) != total or not 1 <= int(total) <= 2 ** 24:
+            raise ValueError(f"ScenarioSet.from_weights: total must be an integer within [1, 2^24], got {total!r}")
+        total = int(total)
+        count, K = int(paths.shape[0]), int(paths.shape[1])
+        w = weights if torch.is_tensor(weights) else torch.as_tensor(np.asarray(weights, dtype=np.float64))
+        if tuple(w.shape) != (count, K) or w.is_complex():
+            raise ValueError(f"ScenarioSet.from_weights: weights must be real and [count, K] = [{count}, {K}], got "
+                             f"{tuple(w.shape)}")
+        w = w.detach().to(device=paths.device, dtype=torch.float64)
+        good = (torch.isfinite(w) & (w >= 0)).all(dim=1) & (w.sum(dim=1) > 0) & torch.isfinite(w.sum(dim=1))
+        w = torch.where(good[:, None], w, torch.ones_like(w))
+        q = w / w.sum(dim=1, keepdim=True) * total
+        base = torch.floor(q)
+        short = total - base.sum(dim=1, keepdim=True)                            # how many members are rounded up
+        order = torch.sort(q - base, dim=1, descending=True, stable=True).indices   # the lower index first among equals
+        place = torch.empty_like(order).scatter_(1, order, torch.arange(K, device=w.device).expand(count, K))
+        counts = (base + (place < short).double()).to(torch.int32)
+        counts = torch.where(good[:, None], counts, torch.zeros_like(counts))
+        each = torch.arange(K, device=paths.device).expand(count, K)
+        cost = torch.full((count, K), float("nan"), dtype=torch.float64, device=paths.device)
+        return ScenarioSet(each.contiguous(), counts.contiguous(), each.to(torch.int32).contiguous(), cost, K, paths.contiguous(),
+                           total=total)
 
     def expect(self, values):
         if not torch.is_tensor(values) or values.dim() < 2 or tuple(values.shape[:2]) != (self.count, self.S):
@@ -393,6 +529,9 @@ class ScenarioSet:
     def head(self, k):
         if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= self.K:
             raise ValueError(f"ScenarioSet.head: k must be an integer within [1, {self.K}], got {k!r}")
+        if self._parent is not None:
+            raise ValueError("ScenarioSet.head: this set was reduced from a weighted set, whose counts a head cannot re-derive; "
+                             "forward selection is nested, so parent.reduce(k) is the same set")
         if self.distances is None and self.source is None:
             raise ValueError("ScenarioSet.head: counts and assign of the first k picks are re-derived from the distances: the "
                              "set needs `distances` ([count, S, S], ops.scenario_distances) or `source` (the full [count, S, H, R] "
@@ -409,16 +548,18 @@ class ScenarioSet:
         assign = torch.where(refused, torch.full_like(assign, -1), assign)
         counts = (assign[:, :, None] == torch.arange(k, device=assign.device)).sum(dim=1).to(torch.int32)
         return ScenarioSet(index.contiguous(), counts, assign, self.cost[:, :k].contiguous(), S, self.paths[:, :k].contiguous(),
-                           self.distances, self.source)
+                           self.distances, self.source, total=self.total)
 
     @staticmethod
     def cat(parts):
         parts = list(parts)
         if not parts or any((p.S, p.K, p.H, p.N) != (parts[0].S, parts[0].K, parts[0].H, parts[0].N) for p in parts):
             raise ValueError("ScenarioSet.cat: the parts must share S, K, H and N")
+        if any(p.total != parts[0].total for p in parts):
+            raise ValueError("ScenarioSet.cat: the parts must share total")
         distances = torch.cat([p.distances for p in parts]) if all(p.distances is not None for p in parts) else None
         return ScenarioSet(*(torch.cat([getattr(p, name) for p in parts]) for name in ("index", "counts", "assign", "cost")),
-                           parts[0].S, torch.cat([p.paths for p in parts]), distances)
+                           parts[0].S, torch.cat([p.paths for p in parts]), distances, total=parts[0].total)
 
 
 def reduce_scenarios(paths, keep, on=None, scale=None, squared=False):

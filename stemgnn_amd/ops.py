@@ -2278,6 +2278,155 @@ def scenario_reduce(paths, keep, scale=None, squared=False, distances=None, max_
     return selected, counts, assign, cost
 
 
+def _weighted_set(what, paths, mult, total, most=256):
+    """paths [count,K,H,M] contiguous float32, mult int32 [count,K] contiguous, total the common sum W in [1, 2^24] (checked on
+    the host, the device last) -> (count, K, H, M, W)"""
+    if not torch.is_tensor(paths) or paths.dim() != 4 or paths.numel() == 0:
+        raise _lib.StemGNNHipError(f"{what}: paths must be a non-empty [count,K,H,N] tensor, got "
+                                   f"{tuple(paths.shape) if torch.is_tensor(paths) else type(paths).__name__}")
+    if paths.dtype != torch.float32 or not paths.is_contiguous():
+        raise _lib.StemGNNHipError(f"{what}: paths must be a contiguous float32 tensor, got {paths.dtype}, strides "
+                                   f"{tuple(paths.stride())}")
+    C, K, H, M = (int(v) for v in paths.shape)
+    if K > most:
+        raise _lib.StemGNNHipError(f"{what}: at most {most} weighted members, got K = {K}")
+    if K * H * M >= 2 ** 31:
+        raise _lib.StemGNNHipError(f"{what}: {K} members of {H} x {M} values do not fit the entry's range (2^31)")
+    W = _weighted_mult(what, mult, total, C, K)
+    if mult.device != paths.device:
+        raise _lib.StemGNNHipError(f"{what}: paths is on {paths.device}, mult on {mult.device}")
+    return C, K, H, M, W
+
+
+def _weighted_mult(what, mult, total, C, K):
+    if not torch.is_tensor(mult) or tuple(mult.shape) != (C, K) or mult.dtype != torch.int32 or not mult.is_contiguous():
+        raise _lib.StemGNNHipError(f"{what}: mult must be a contiguous int32 [{C},{K}] tensor of multiplicities, got "
+                                   f"{(str(mult.dtype) + ' ' + str(tuple(mult.shape))) if torch.is_tensor(mult) else type(mult).__name__}")
+    if isinstance(total, bool) or not isinstance(total, (int, np.integer)) or not 1 <= int(total) <= 2 ** 24:
+        raise _lib.StemGNNHipError(f"{what}: total must be an integer within [1, 2^24] (the multiplicities' common sum), got "
+                                   f"{total!r}")
+    return int(total)
+
+
+def weighted_bands(paths, mult, total, quantiles, out=None):
+    """The bands of a weighted scenario set (``stemgnn_weighted_bands``; the definition is in include/stemgnn_hip.h): paths
+    [count,K,H,N] contiguous float32 on the device, mult int32 [count,K] the members' multiplicities with common sum `total` ->
+    bands [count,Q,H,N] float32: bands[c,q,h,n] = the scenario_rank(quantiles[q], total)-th smallest of the ensemble in which member
+    k stands mult[c,k] times -- `scenario_bands` of the replicated ensemble, bit for bit, without forming it.  A member of
+    multiplicity 0 is not read; an origin whose multiplicities are negative or do not sum to total is NaN.  K <= 256."""
+    what = "weighted_bands"
+    C, K, H, N, W = _weighted_set(what, paths, mult, total)
+    quantiles = [float(t) for t in quantiles]
+    Q = len(quantiles)
+    if not 1 <= Q <= 32:
+        raise _lib.StemGNNHipError(f"{what}: 1 to 32 levels, got {Q}")
+    if out is not None and (not torch.is_tensor(out) or tuple(out.shape) != (C, Q, H, N) or out.dtype != torch.float32 or
+                            not out.is_contiguous() or out.device != paths.device):
+        raise _lib.StemGNNHipError(f"{what}: out must be a contiguous float32 {(C, Q, H, N)} tensor on the paths' device")
+    _require_gpu(paths, "paths")
+    lib = _lib.load()
+    bands = torch.empty(C, Q, H, N, device=paths.device, dtype=torch.float32) if out is None else out
+    ranks = (ctypes.c_int * Q)(*[scenario_rank(t, W) for t in quantiles])
+    _lib.check(lib.stemgnn_weighted_bands(paths.data_ptr(), mult.data_ptr(), C, K, H, N, W, Q, ranks, bands.data_ptr(), _stream()),
+               what)
+    return bands
+
+
+def weighted_scores(y, paths, mult, total, mul=None, add=None, ignore_nan=False, fair=False):
+    """Scores of a weighted scenario set against what happened (``stemgnn_weighted_scores``; the definitions are in
+    include/stemgnn_hip.h): y [count,H,N], paths [count,K,H,N], mult int32 [count,K] with common sum `total` ->
+    (out float64 [7 * (1 + H)] = overall | by_step[7][H]: the six statistics of `ensemble_scores` with every member weighted by
+    its multiplicity, then the number of absent origins; hist int64 [H, total + 1]), both on the device, no sync.
+    mul / add, ignore_nan, fair: `ensemble_scores`' (fair needs total >= 2)."""
+    what = "weighted_scores"
+    C, K, H, N, W = _weighted_set(what, paths, mult, total)
+    if not torch.is_tensor(y) or tuple(y.shape) != (C, H, N) or y.dtype != torch.float32 or not y.is_contiguous():
+        raise _lib.StemGNNHipError(f"{what}: y must be a contiguous float32 [count,H,N] = {(C, H, N)} tensor, got "
+                                   f"{(str(y.dtype) + ' ' + str(tuple(y.shape))) if torch.is_tensor(y) else type(y).__name__}")
+    mul, add = _denorm_pair(what, mul, add, N)
+    if fair and W < 2:
+        raise _lib.StemGNNHipError(f"{what}: fair=True needs total >= 2, got {W}")
+    if H * (W + 1) >= 2 ** 31:
+        raise _lib.StemGNNHipError(f"{what}: a histogram of {H} x {W + 1} bins does not fit the entry's range (2^31)")
+    _require_gpu(paths, "paths")
+    _require_gpu(y, "y")
+    if y.device != paths.device:
+        raise _lib.StemGNNHipError(f"{what}: y is on {y.device}, paths on {paths.device}")
+    lib = _lib.load()
+    dev = paths.device
+    mul, add = _f64_on(mul, dev), _f64_on(add, dev)
+    scratch = torch.empty(lib.stemgnn_weighted_scratch_doubles(C, K, H, N), device=dev, dtype=torch.float64)
+    out = torch.empty(lib.stemgnn_weighted_out_doubles(H), device=dev, dtype=torch.float64)
+    hist = torch.empty(H, W + 1, device=dev, dtype=torch.int64)
+    _lib.check(lib.stemgnn_weighted_scores(y.data_ptr(), paths.data_ptr(), mult.data_ptr(),
+                                           None if mul is None else mul.data_ptr(), None if add is None else add.data_ptr(),
+                                           C, K, H, N, W, int(bool(fair)), int(bool(ignore_nan)), scratch.data_ptr(),
+                                           out.data_ptr(), hist.data_ptr(), _stream()), what)
+    return out, hist
+
+
+def weighted_events(paths, mult, total, threshold, above=True, min_run=1, mul=None, add=None):
+    """Crossing counts of a weighted scenario set (``stemgnn_weighted_events``): `scenario_events` with every member counted
+    mult[c,k] times -- the counts of the replicated ensemble of `total` paths, exactly.  paths [count,K,H,M], mult int32
+    [count,K] -> counts int32 [count, 2H+1, M]; an origin whose multiplicities are negative or do not sum to total is -1."""
+    what = "weighted_events"
+    C, K, H, M, W = _weighted_set(what, paths, mult, total)
+    if H > 256:
+        raise _lib.StemGNNHipError(f"{what}: at most 256 steps, got H = {H}")
+    if isinstance(min_run, bool) or int(min_run) != min_run or not 1 <= int(min_run) <= H:
+        raise _lib.StemGNNHipError(f"{what}: min_run must be an integer within [1, {H}], got {min_run!r}")
+    threshold = _per_column(what, "threshold", threshold, M)
+    mul, add = _denorm_pair(what, mul, add, M)
+    _require_gpu(paths, "paths")
+    lib = _lib.load()
+    dev = paths.device
+    threshold, mul, add = _f64_on(threshold, dev), _f64_on(mul, dev), _f64_on(add, dev)
+    counts = torch.empty(C, 2 * H + 1, M, device=dev, dtype=torch.int32)
+    _lib.check(lib.stemgnn_weighted_events(paths.data_ptr(), mult.data_ptr(), threshold.data_ptr(),
+                                           None if mul is None else mul.data_ptr(), None if add is None else add.data_ptr(),
+                                           C, K, H, M, W, int(bool(above)), int(min_run), counts.data_ptr(), _stream()), what)
+    return counts
+
+
+def scenario_reduce_weighted(distances, mult, total, keep):
+    """Forward selection on an ensemble with probabilities mult / total (``stemgnn_scenario_reduce_weighted``; the definition is
+    in include/stemgnn_hip.h): distances float64 [count,S,S] contiguous on the device (`scenario_distances`, or any cost
+    D[k,u] of moving member k onto member u), mult int32 [count,S] with common sum `total` -> (selected int32 [count,keep],
+    counts int32 [count,keep] = the multiplicities gathered by each kept member, assign int32 [count,S], cost float64
+    [count,keep]), on the device, no sync.  A member of multiplicity 0 is no candidate and its distances are not read.  Refused
+    origins (-1 / 0 / -1 / NaN): a distance that is not a finite number >= 0, multiplicities that are negative or do not sum
+    to total, fewer than `keep` members of positive multiplicity.  All-ones mult and total = S: `scenario_reduce`, bit for bit."""
+    what = "scenario_reduce_weighted"
+    if not torch.is_tensor(distances) or distances.dim() != 3 or distances.shape[1] != distances.shape[2] or \
+            distances.numel() == 0:
+        raise _lib.StemGNNHipError(f"{what}: distances must be a non-empty [count,S,S] tensor, got "
+                                   f"{tuple(distances.shape) if torch.is_tensor(distances) else type(distances).__name__}")
+    if distances.dtype != torch.float64 or not distances.is_contiguous():
+        raise _lib.StemGNNHipError(f"{what}: distances must be a contiguous float64 tensor, got {distances.dtype}, strides "
+                                   f"{tuple(distances.stride())}")
+    C, S = int(distances.shape[0]), int(distances.shape[1])
+    if S > 1024:
+        raise _lib.StemGNNHipError(f"{what}: at most 1024 members, got S = {S}")
+    if C * S * S >= 2 ** 31:
+        raise _lib.StemGNNHipError(f"{what}: {C} origins x {S} x {S} distances do not fit the entry's range (2^31)")
+    W = _weighted_mult(what, mult, total, C, S)
+    K = _reduce_keep(what, keep, S)
+    if not distances.is_cuda:
+        raise _lib.StemGNNHipError(f"{what}: distances is on {distances.device}: stemgnn_amd runs only on a HIP device "
+                                   "(no CPU fallback)")
+    if mult.device != distances.device:
+        raise _lib.StemGNNHipError(f"{what}: distances is on {distances.device}, mult on {mult.device}")
+    lib = _lib.load()
+    dev = distances.device
+    selected = torch.empty(C, K, device=dev, dtype=torch.int32)
+    counts = torch.empty(C, K, device=dev, dtype=torch.int32)
+    assign = torch.empty(C, S, device=dev, dtype=torch.int32)
+    cost = torch.empty(C, K, device=dev, dtype=torch.float64)
+    _lib.check(lib.stemgnn_scenario_reduce_weighted(distances.data_ptr(), mult.data_ptr(), C, S, K, W, selected.data_ptr(),
+                                                    counts.data_ptr(), assign.data_ptr(), cost.data_ptr(), _stream()), what)
+    return selected, counts, assign, cost
+
+
 def _ring_ok(what, ring, t_dev):
     _require_gpu(ring, "ring")
     if ring.dim() != 2 or ring.dtype != torch.float32 or not ring.is_contiguous():

@@ -249,6 +249,8 @@ def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=
     (math_utils.EnsembleScores; `fair` is its flag): ``crps``, ``energy_score``, ``ensemble_rmse``, ``spread`` and
     ``rank_histogram`` [S + 1], each also per step under ``*_step``, in raw units and, like the keys above, in normalised
     units under ``*_norm`` (the histogram has no units).  Without paths= the result is what it was, key for key.
+    paths a math_utils.ScenarioSet (reduced_scenarios' third result): its kept paths are scored with their weights
+    (ScenarioSet.scores; the histogram has total + 1 bins), and events= counts them with their weights.
     events (a math_utils.EventSpec; needs paths=): the event's odds read off the paths are verified against the target
     (math_utils.EventScores; the spec's own threshold, groups and mul / add): ``event_brier``, ``event_brier_skill``,
     ``event_base_rate`` and ``event_reliability`` [M, S + 1, 2] for "the event at some step", the same under ``*_run`` for "at
@@ -293,8 +295,12 @@ def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=
     out.update(mape_norm=normed[0], mae_norm=normed[1], rmse_norm=normed[2])
     out.update(calibration)
     if paths is not None:
-        ens = EnsembleScores(target, paths, mul, add, ignore_nan=ignore_nan, fair=fair)
-        ens_n = EnsembleScores(target, paths, ignore_nan=ignore_nan, fair=fair) if mul is not None else ens
+        if isinstance(paths, ScenarioSet):                   # the kept paths with their weights: the same keys, total + 1 bins
+            ens = paths.scores(target, mul, add, ignore_nan=ignore_nan, fair=fair)
+            ens_n = paths.scores(target, ignore_nan=ignore_nan, fair=fair) if mul is not None else ens
+        else:
+            ens = EnsembleScores(target, paths, mul, add, ignore_nan=ignore_nan, fair=fair)
+            ens_n = EnsembleScores(target, paths, ignore_nan=ignore_nan, fair=fair) if mul is not None else ens
         for key, name in (("crps", "crps"), ("energy_score", "energy"), ("ensemble_rmse", "rmse"), ("spread", "spread")):
             for suffix in ("", "_step"):
                 out[key + suffix] = getattr(ens, name + suffix)
