@@ -1197,6 +1197,61 @@ int stemgnn_weighted_events(const float* paths, const int* mult, const double* t
 int stemgnn_scenario_reduce_weighted(const double* D, const int* mult_in, long count, int S, int K, int W, int* selected,
                                      int* counts, int* assign, double* cost, void* stream);
 
+/* ---- scenario trees: staged forward selection of sampled paths (csrc/tree.hip) -----------------------
+ * Paths x [count, S, H, M] fp32 and contiguous.  bounds = T ints in HOST memory, 0 < b_1 < b_2 < .. < b_T = H, passed on by
+ * value: stage t = 1 .. T owns the steps [b_{t-1}, b_t), b_0 = 0.  nodes = T ints in HOST memory, 1 <= n_1 <= .. <= n_T <= S,
+ * passed on by value.  mult_in int32 [count, S] with common total W, or NULL: all ones and W = S; the conventions are those
+ * of the weighted sets above (1 <= W <= 2^24; an origin with a negative multiplicity or a wrong sum is absent).  T <= 16.
+ * stage_distances: D [count, T, S, S] fp64, prefix form.  With scale [H * M] fp64 on the device or NULL (all ones):
+ *              Q_t[i, j] = sum over the columns (h, m) of stage t, in order, of (((double)x_i - (double)x_j) * scale)^2
+ *            the difference formed first, then multiplied by the scale, then accumulated by one fp64 fused multiply-add;
+ *              D_t^2 = ((Q_1 + Q_2) + ..) + Q_t, summed in stage order;   D_t = sqrt(D_t^2), or D_t^2 itself with squared != 0
+ *            DIFFERENCES, never the Gram expansion: D_t[i, j] and D_t[j, i] are the same bits, a finite path is at exactly +0
+ *            from itself, and a NaN or an infinity reaches its row and its column from its stage on and not before.  A
+ *            stage's own sum is kept as four partial sums: the stage's columns are walked in chunks of 64 counted from the
+ *            stage's first column, chunk c adding into sum c % 4, joined as ((s0 + s1) + s2) + s3 -- a function of M and the
+ *            bounds alone.  One launch that reads the paths once and stores all T tiles; one workgroup per (origin, 32 x 32
+ *            tile of pairs on or above the diagonal), of 256 threads or, where the grid leaves compute units idle, of 1024 (a
+ *            wave group per partial sum): the same bits either way.
+ * tree:      D [count, T, S, S] fp64, from the entry above or any cost of the caller's (D_t[k, u]: moving member k onto member
+ *            u in the metric of stage t; symmetry is neither needed nor checked).  Per origin, with p_k = (double)mult_in[k];
+ *            a member with p_k = 0 is never a candidate, is never read and keeps assign = -1 (the LIVE members are the others):
+ *              par_0(k) = 0 for all k.  For stage t = 1 .. T: m_k = +inf, then n_t picks, node i of the stage the i-th pick:
+ *              phase A, i = 0 .. n_{t-1} - 1 (n_0 = 1), one child for every parent in parent order: the candidates are the
+ *                unselected u with par_{t-1}(u) = i;  z_u = sum over the k with par_{t-1}(k) = i, in index order, of
+ *                p_k * D_t[k, u], the product and the add rounded separately (no FMA); the pick u* is the smallest z_u, the
+ *                lowest index among equals; then m_k = D_t[k, u*] for the k of that parent.  A parent without members (its
+ *                representative coincides with an earlier pick's, which took every member) has no candidate: that child is
+ *                EMPTY, node_path = -1, node_parent = i, node_count = 0, and nothing else changes.
+ *              phase B, i = n_{t-1} .. n_t - 1: the candidates are every unselected live u;  z_u = sum over all live k, in
+ *                index order, of p_k * min(m_k, E[k, u]),  E[k, u] = D_t[k, u] where par_{t-1}(k) = par_{t-1}(u), +inf
+ *                elsewhere (a path is only ever moved onto a path of its own parent); pick and ties as in phase A; then
+ *                m_k = min(m_k, D_t[k, u*]) for the k of u*'s parent.
+ *              after the stage's last pick: assign_t[k] = the node of stage t whose representative is nearest to k among the
+ *                nodes with k's parent, among equals the earliest pick;  par_t = assign_t;  node_path[t, i] = the pick;
+ *                node_parent[t, i] = par_{t-1}(pick), so node_parent[t, i] = i for i < n_{t-1};  node_count[t, i] = the sum of
+ *                mult_in over the members assigned to i;  cost[t] = (sum over live k, in index order, of p_k * m_k) / W, the
+ *                product and the add rounded separately: the Kantorovich distance, in the stage's prefix metric, between the
+ *                ensemble and the stage's nodes under the tree constraint.
+ *            With T = 1 every output equals stemgnn_scenario_reduce_weighted's bit for bit (node_path = selected, node_count =
+ *            counts, assign, cost[0] = its cost[K - 1]); with mult_in = NULL, stemgnn_scenario_reduce's.
+ *            Refused origin (node_path = node_parent = -1, node_count = 0, assign = -1, cost = NaN, ALL stages): the origin is
+ *            absent; n_T exceeds the members of positive multiplicity; an entry of any stage between two live members is not a
+ *            finite number >= 0.  The other origins of the call are not affected.
+ *            Outputs, padded to n_T per stage: node_path, node_parent, node_count int32 [count, T, n_T] with -1 / -1 / 0 beyond
+ *            n_t; assign int32 [count, T, S]; cost fp64 [count, T].  One launch, one workgroup per origin; a stage's D_t is held
+ *            in LDS where it fits (S <= 141), beyond that rows are read from memory.
+ * Both: no allocation, no host synchronisation, no memset, no floating-point atomics; the same bits on every run, and an
+ * origin's results do not depend on which other origins share the call; capturable.
+ * SG_EINVAL (nothing launched): a NULL pointer other than scale / mult_in; count, S, H, M or T <= 0; S > 1024; T > 16; bounds
+ * not strictly increasing from above 0 or not ending at H; nodes decreasing or outside [1, S]; W outside [1, 2^24], or W != S
+ * with mult_in NULL; squared not 0 / 1; count, count * T * S * S, S * H * M or the grid count * P (P + 1) / 2 (P = ceil(S / 32))
+ * >= 2^31. */
+int stemgnn_scenario_stage_distances(const float* paths, const double* scale, long count, int S, int H, int M, int T,
+                                     const int* bounds, int squared, double* D, void* stream);
+int stemgnn_scenario_tree(const double* D, const int* mult_in, long count, int S, int T, const int* nodes, int W, int* node_path,
+                          int* node_parent, int* node_count, int* assign, double* cost, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,10 +8,11 @@ fallback: calling the model without the HIP library or on a non-GPU tensor raise
 from .base_model import GLU, Model, StockBlockLayer  # noqa: F401
 from .graph import LatentGraph  # noqa: F401
 
-from .math_utils import EventScores, EventSpec, ScenarioEvents, ScenarioSet, group_weights, reduce_scenarios  # noqa: F401
+from .math_utils import (EventScores, EventSpec, ScenarioEvents, ScenarioSet, ScenarioTree, group_weights,  # noqa: F401
+                         reduce_scenarios, scenario_tree)
 
 __all__ = ["Model", "StockBlockLayer", "GLU", "LatentGraph", "LiveForecaster", "EventSpec", "ScenarioEvents", "EventScores",
-           "group_weights", "ScenarioSet", "reduce_scenarios"]
+           "group_weights", "ScenarioSet", "reduce_scenarios", "ScenarioTree", "scenario_tree"]
 __version__ = "0.1.0"
 
 

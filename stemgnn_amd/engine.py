@@ -1313,6 +1313,17 @@ class LiveForecaster:
         _, steps = self.scenarios(paths=paths, horizon=horizon, seed=seed, coupling=coupling, tails=tails, return_paths=True)
         return reduce_scenarios(steps[None], keep, on=on, scale=scale, squared=squared)
 
+    def scenario_tree(self, stages, nodes, paths=64, horizon=None, seed=None, coupling="independent", tails="linear", on=None,
+                      scale=None, squared=False):
+        """A scenario tree for the steps ahead of the last row pushed: `scenarios(..., return_paths=True)` from the ring's head
+        window, then `math_utils.scenario_tree` on its paths.  Returns a math_utils.ScenarioTree with count = 1 (device
+        tensors, no sync).  stages / nodes / on / scale / squared are scenario_tree's (on: an EventSpec with groups=, or a
+        [1,S,horizon,R] tensor); the other arguments are scenarios'; the captured graph, the history slab and every calibrator
+        are left untouched."""
+        from .math_utils import scenario_tree
+        _, steps = self.scenarios(paths=paths, horizon=horizon, seed=seed, coupling=coupling, tails=tails, return_paths=True)
+        return scenario_tree(steps[None], stages, nodes, on=on, scale=scale, squared=squared)
+
     # -- matured pairs ------------------------------------------------------------------------------------------
     def matured(self):
         """(forecasts [m,(Q,)horizon,N], targets [m,horizon,N], origins int64 [m] ascending) of the stored forecasts whose targets

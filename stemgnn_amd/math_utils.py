@@ -401,6 +401,9 @@ class ScenarioSet:
       merge(parts)  (static) the members of several sets of the same origins side by side, the totals added: two seeds, two
                     models, or chunks of an ensemble too large to hold -- merge(chunks).reduce(8) is a two-stage reduction;
                     cost NaN, no distances
+      tree(stages, nodes, on=None, scale=None, squared=False) -> the ScenarioTree of the set's K members with the counts as
+                    input probabilities (`scenario_tree`'s arguments): merge(chunks).tree(..) builds a
+                    tree from an ensemble too large to hold; its S is this set's K, its total this set's
       from_weights(paths, weights, total=65536)  (static, pure torch) user-supplied probabilities rounded to multiplicities
                     that sum to total by largest remainders (the lower index first among equal remainders); a row that is
                     negative, non-finite or all zero becomes an absent origin"""
@@ -458,6 +461,12 @@ class ScenarioSet:
         out = ScenarioSet(index, counts, assign, cost, self.K, kept, total=self.total)
         out._parent = self
         return out
+
+    def tree(self, stages, nodes, on=None, scale=None, squared=False):
+        on = _on_paths("ScenarioSet.tree", self.paths, on).contiguous()
+        out = ops.scenario_tree(on, stages, nodes, scale, squared, mult=self.counts, total=self.total)
+        return ScenarioTree._build(self.paths, ops._tree_stages("ScenarioSet.tree", stages, self.H),
+                                   ops._tree_nodes("ScenarioSet.tree", nodes, len(tuple(stages)), self.K), out, self.total)
 
     @staticmethod
     def merge(parts):
@@ -576,24 +585,177 @@ def reduce_scenarios(paths, keep, on=None, scale=None, squared=False):
     paths = _as_f32(paths)
     if paths.dim() != 4:
         raise ops._lib.StemGNNHipError(f"reduce_scenarios: paths must be [count,S,H,N], got {tuple(paths.shape)}")
-    if isinstance(on, EventSpec):
-        if on.groups is None:
-            raise ValueError("reduce_scenarios: on= an EventSpec stands for its aggregate(paths); the spec has no groups=")
-        on = on.aggregate(paths)
-    elif on is None:
-        on = paths
-    else:
-        on = _as_f32(on, like=paths)
-        if on.dim() != 4 or tuple(on.shape[:3]) != tuple(paths.shape[:3]):
-            raise ops._lib.StemGNNHipError(f"reduce_scenarios: on must be [count,S,H,R] with the paths' count, S and H "
-                                           f"{tuple(paths.shape[:3])}, got {tuple(on.shape)}")
-    on = on.contiguous()
+    on = _on_paths("reduce_scenarios", paths, on).contiguous()
     selected, counts, assign, cost = ops.scenario_reduce(on, keep, scale, squared)
     index = selected.long()
     C, S, H, N = paths.shape
     kept = torch.gather(paths, 1, index.clamp(min=0)[:, :, None, None].expand(-1, -1, H, N))
     kept = torch.where((index < 0)[:, :, None, None], torch.full_like(kept, float("nan")), kept)
     return ScenarioSet(index, counts, assign, cost, S, kept, source=(on, scale, bool(squared)))
+
+
+def _take_paths(paths, index, lo, hi):
+    """paths [count, S, H, N], index int64 [count, n] -> [count, n, hi - lo, N]: the steps [lo, hi) of the indexed paths, NaN
+    where the index is negative"""
+    n, N = index.shape[1], paths.shape[3]
+    got = torch.gather(paths[:, :, lo:hi], 1, index.clamp(min=0)[:, :, None, None].expand(-1, n, hi - lo, N))
+    return torch.where((index < 0)[:, :, None, None], torch.full_like(got, float("nan")), got)
+
+
+class ScenarioTree:
+    """A scenario tree per origin: the result of `scenario_tree` (staged forward selection, `ops.scenario_tree`; DESIGN.md
+    section 5u).  Stage t = 0 .. T - 1 owns the steps [stages[t - 1], stages[t]) (from 0 for t = 0) and has nodes[t] nodes;
+    every node is a sampled path's steps of that stage, a child of one node of the stage before, with an integer count.  The
+    members of a node share its ancestors' steps: what a multi-stage program needs (non-anticipativity).  Device tensors, no
+    sync, the node axis padded to n = nodes[-1]:
+      node_index int64 [count, T, n]  the path each node is represented by (-1: padding, a refused origin, an empty node)
+      parent     int32 [count, T, n]  the node's parent among the nodes of stage t - 1 (0 at t = 0; -1: padding, refused)
+      counts     int32 [count, T, n]  the multiplicities the node gathers; at every stage they add up to `total`
+      assign     int32 [count, T, S]  the node of stage t every path went to        cost  float64 [count, T]  the Kantorovich
+                                      distance between the ensemble and the stage's nodes, in the stage's prefix metric
+      paths      float32 [count, n, H, N]  the LEAVES' trajectories: leaf j's steps of stage t are those of the representative of
+                                      its ancestor at that stage      S, total  the ensemble's size and the multiplicities' sum
+    A refused origin: -1 / -1 / 0 / -1 / NaN and NaN trajectories.
+      scenarios()      -> the ScenarioSet of the leaves with counts[:, T - 1] and total: bands, scores, events,
+                          EventSpec.count and trainer.score_forecast(paths=) take a tree through it
+      values(t)        -> float32 [count, nodes[t], stages[t] - stages[t - 1], N], the nodes' own steps
+      probabilities(t) -> float64 [count, nodes[t]] = counts / total      conditional(t) -> counts / the parent's count
+      expect(values [count, S, ...]) -> float64 [count, ...], the leaf-weighted mean, as ScenarioSet.expect
+      cat(parts)       joins batches along the origins
+      export(c)        -> one origin on the host as a plain dict: stages, nodes, total, and per stage the lists parent,
+                          probability, conditional, values (numpy arrays): the node list tree-based solvers read; one sync"""
+
+    def __init__(self, stages, nodes, node_index, parent, counts, assign, cost, S, total, stage_values, paths):
+        stages, nodes = tuple(int(v) for v in stages), tuple(int(v) for v in nodes)
+        T, n = len(stages), nodes[-1]
+        if len(nodes) != T or node_index.dtype != torch.int64 or node_index.dim() != 3 or \
+                tuple(node_index.shape[1:]) != (T, n) or parent.shape != node_index.shape or counts.shape != node_index.shape or \
+                counts.dtype != torch.int32 or assign.dim() != 3 or tuple(assign.shape[:2]) != tuple(node_index.shape[:2]) or \
+                tuple(cost.shape) != tuple(node_index.shape[:2]) or len(stage_values) != T or paths.dim() != 4 or \
+                tuple(paths.shape[:3]) != (node_index.shape[0], n, stages[-1]):
+            raise ValueError(f"ScenarioTree: node_index must be int64 [count, T, n_T] with int32 parent and counts, assign "
+                             f"[count, T, S], cost [count, T], T stage values and paths [count, n_T, H, N]; got "
+                             f"{node_index.dtype} {tuple(node_index.shape)}, {tuple(parent.shape)}, {counts.dtype} "
+                             f"{tuple(counts.shape)}, {tuple(assign.shape)}, {tuple(cost.shape)}, {len(stage_values)}, "
+                             f"{tuple(paths.shape)} at stages {stages}, nodes {nodes}")
+        self.stages, self.nodes, self.T = stages, nodes, T
+        self.node_index, self.parent, self.counts, self.assign, self.cost = node_index, parent, counts, assign, cost
+        self.S, self.total, self.paths = int(S), int(total), paths
+        self._values = list(stage_values)
+        self.count, self.H, self.N = int(node_index.shape[0]), stages[-1], int(paths.shape[3])
+
+    @staticmethod
+    def _build(paths, stages, nodes, out, total):
+        """the tree of ops.scenario_tree's outputs `out` on paths [count, S, H, N]: gathers, no kernel"""
+        node_path, node_parent, node_count, assign, cost = out
+        T, S = len(stages), int(paths.shape[1])
+        index = node_path.long()
+        lo = (0,) + tuple(stages[:-1])
+        values = [_take_paths(paths, index[:, t, :nodes[t]], lo[t], stages[t]) for t in range(T)]
+        leaf = index[:, T - 1]                                                   # [count, n]
+        parts = []
+        for t in range(T):                                                       # the ancestor of every leaf at stage t, its path
+            anc = torch.gather(assign[:, t].long(), 1, leaf.clamp(min=0))
+            rep = torch.gather(index[:, t], 1, anc.clamp(min=0))
+            rep = torch.where((leaf < 0) | (anc < 0), torch.full_like(rep, -1), rep)
+            parts.append(_take_paths(paths, rep, lo[t], stages[t]))
+        return ScenarioTree(stages, nodes, index, node_parent, node_count, assign, cost, S, total, values,
+                            torch.cat(parts, dim=2).contiguous())
+
+    def _stage(self, who, t):
+        if isinstance(t, bool) or int(t) != t or not 0 <= int(t) < self.T:
+            raise ValueError(f"ScenarioTree.{who}: t must be a stage within [0, {self.T - 1}], got {t!r}")
+        return int(t)
+
+    def scenarios(self):
+        last = self.T - 1
+        cost = torch.full((self.count, self.nodes[-1]), float("nan"), dtype=torch.float64, device=self.cost.device)
+        cost[:, -1] = self.cost[:, last]
+        return ScenarioSet(self.node_index[:, last].contiguous(), self.counts[:, last].contiguous(),
+                           self.assign[:, last].contiguous(), cost, self.S, self.paths, total=self.total)
+
+    def values(self, t):
+        return self._values[self._stage("values", t)]
+
+    def probabilities(self, t):
+        t = self._stage("probabilities", t)
+        p = self.counts[:, t, :self.nodes[t]].double() / self.total
+        return torch.where(self.parent[:, t, :1] < 0, torch.full_like(p, float("nan")), p)
+
+    def conditional(self, t):
+        t = self._stage("conditional", t)
+        own = self.counts[:, t, :self.nodes[t]].double()
+        if t == 0:
+            above = torch.full_like(own, float(self.total))
+        else:
+            above = torch.gather(self.counts[:, t - 1].double(), 1, self.parent[:, t, :self.nodes[t]].long().clamp(min=0))
+        return torch.where(self.parent[:, t, :1] < 0, torch.full_like(own, float("nan")), own / above)
+
+    def expect(self, values):
+        return self.scenarios().expect(values)
+
+    @staticmethod
+    def cat(parts):
+        parts = list(parts)
+        if not parts or any(not isinstance(p, ScenarioTree) or
+                            (p.stages, p.nodes, p.S, p.total, p.N) != (parts[0].stages, parts[0].nodes, parts[0].S,
+                                                                       parts[0].total, parts[0].N) for p in parts):
+            raise ValueError("ScenarioTree.cat: the parts must be ScenarioTrees that share stages, nodes, S, total and N")
+        a = parts[0]
+        return ScenarioTree(a.stages, a.nodes,
+                            *(torch.cat([getattr(p, name) for p in parts]) for name in ("node_index", "parent", "counts",
+                                                                                        "assign", "cost")),
+                            a.S, a.total, [torch.cat([p._values[t] for p in parts]) for t in range(a.T)],
+                            torch.cat([p.paths for p in parts]))
+
+    def export(self, c):
+        if isinstance(c, bool) or int(c) != c or not 0 <= int(c) < self.count:
+            raise ValueError(f"ScenarioTree.export: c must be an origin within [0, {self.count - 1}], got {c!r}")
+        c = int(c)
+        out = dict(stages=self.stages, nodes=self.nodes, total=self.total, parent=[], probability=[], conditional=[], values=[])
+        for t in range(self.T):
+            out["parent"].append(self.parent[c, t, :self.nodes[t]].cpu().numpy())
+            out["probability"].append(self.probabilities(t)[c].cpu().numpy())
+            out["conditional"].append(self.conditional(t)[c].cpu().numpy())
+            out["values"].append(self._values[t][c].cpu().numpy())
+        return out
+
+
+def _on_paths(who, paths, on):
+    """the tensor the distances are taken on (on= of reduce_scenarios and scenario_tree): the paths, a [count,S,H,R] tensor, or
+    an EventSpec with groups= standing for its aggregate of the paths"""
+    if isinstance(on, EventSpec):
+        if on.groups is None:
+            raise ValueError(f"{who}: on= an EventSpec stands for its aggregate(paths); the spec has no groups=")
+        return on.aggregate(paths)
+    if on is None:
+        return paths
+    on = _as_f32(on, like=paths)
+    if on.dim() != 4 or tuple(on.shape[:3]) != tuple(paths.shape[:3]):
+        raise ops._lib.StemGNNHipError(f"{who}: on must be [count,S,H,R] with the paths' count, S and H "
+                                       f"{tuple(paths.shape[:3])}, got {tuple(on.shape)}")
+    return on
+
+
+def scenario_tree(paths, stages, nodes, on=None, scale=None, squared=False):
+    """A scenario tree of the S sampled paths of every origin (paths [count, S, H, N] float32 on the device): where
+    `reduce_scenarios` returns a fan -- K members that differ from the first step on, valid for two-stage decisions only --
+    the tree's members share their history up to a stage and branch afterwards, with conditional probabilities on the
+    branches: what dispatch, signal plans and rerouting, which decide again every few steps, need.  Forward tree construction
+    (Heitsch & Roemisch 2009; `ops.scenario_tree`): stage t, the steps [stages[t - 1], stages[t]), keeps nodes[t] paths; first
+    one child for every node of the stage before, then the rest where they most lower the Kantorovich distance in the metric of
+    the steps before stages[t]; a path only ever moves to a node of its own parent.  stages: strictly increasing step bounds
+    that end at H; nodes: non-decreasing counts within [1, S].  on / scale / squared: reduce_scenarios'.  Returns a
+    ScenarioTree; with one stage its leaves are `reduce_scenarios(paths, nodes[0])`."""
+    paths = _as_f32(paths)
+    if paths.dim() != 4:
+        raise ops._lib.StemGNNHipError(f"scenario_tree: paths must be [count,S,H,N], got {tuple(paths.shape)}")
+    on = _on_paths("scenario_tree", paths, on).contiguous()
+    out = ops.scenario_tree(on, stages, nodes, scale, squared)
+    return ScenarioTree._build(paths, ops._tree_stages("scenario_tree", stages, int(paths.shape[2])),
+                               ops._tree_nodes("scenario_tree", nodes, len(tuple(stages)), int(paths.shape[1])), out,
+                               int(paths.shape[1]))
+
 
 
 class GaussianCopula:

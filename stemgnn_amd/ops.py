@@ -2427,6 +2427,146 @@ def scenario_reduce_weighted(distances, mult, total, keep):
     return selected, counts, assign, cost
 
 
+def _tree_stages(what, stages, H):
+    """stage bounds 0 < b_1 < .. < b_T = H (T <= 16) -> a tuple of ints"""
+    try:
+        b = tuple(stages)
+    except TypeError:
+        b = None
+    if not b or len(b) > 16 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in b) or \
+            any(int(v) <= int(u) for u, v in zip((0,) + b[:-1], b)) or int(b[-1]) != H:
+        raise _lib.StemGNNHipError(f"{what}: stages must be 1 to 16 strictly increasing step bounds that end at H = {H} "
+                                   f"(stage t owns the steps [b_(t-1), b_t)), got {stages!r}")
+    return tuple(int(v) for v in b)
+
+
+def _tree_nodes(what, nodes, T, S):
+    """node counts 1 <= n_1 <= .. <= n_T <= S, one per stage -> a tuple of ints"""
+    try:
+        n = tuple(nodes)
+    except TypeError:
+        n = None
+    if not n or len(n) != T or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in n) or \
+            any(int(v) < int(u) for u, v in zip((1,) + n[:-1], n)) or int(n[-1]) > S:
+        raise _lib.StemGNNHipError(f"{what}: nodes must be {T} non-decreasing node counts within [1, {S}], one per stage "
+                                   f"(S = {S} paths), got {nodes!r}")
+    return tuple(int(v) for v in n)
+
+
+def scenario_stage_distances(paths, stages, scale=None, squared=False):
+    """Prefix distances of sampled paths at every stage boundary (``stemgnn_scenario_stage_distances``; the definition is in
+    include/stemgnn_hip.h): paths [count,S,H,M] contiguous float32 on the device, stages = the bounds 0 < b_1 < .. < b_T = H ->
+    D [count,T,S,S] float64, D[c,t,i,j] = sqrt(sum over the steps before b_t and all m of ((x_i - x_j) * scale)^2) in fp64 from
+    the differences, the stages' sums added in stage order; squared: without the root.  scale: scenario_distances'.  One
+    launch reads the paths once for all T tiles.  Every D[c,t] equals its transpose bit for bit; a NaN in a path reaches its row
+    and column from its stage on."""
+    what = "scenario_stage_distances"
+    C, S, H, M = _reduce_paths(what, paths)
+    bounds = _tree_stages(what, stages, H)
+    scale = _reduce_scale(what, scale, H, M)
+    squared = _reduce_flag(what, squared)
+    T = len(bounds)
+    if C * T * S * S >= 2 ** 31:
+        raise _lib.StemGNNHipError(f"{what}: {C} origins x {T} x {S} x {S} distances do not fit the entry's range (2^31); "
+                                   "scenario_tree walks the origins in batches")
+    _require_gpu(paths, "paths")
+    lib = _lib.load()
+    scale = _f64_on(scale, paths.device)
+    D = torch.empty(C, T, S, S, device=paths.device, dtype=torch.float64)
+    _lib.check(lib.stemgnn_scenario_stage_distances(paths.data_ptr(), None if scale is None else scale.data_ptr(), C, S, H, M, T,
+                                                    (ctypes.c_int * T)(*bounds), squared, D.data_ptr(), _stream()), what)
+    return D
+
+
+def scenario_tree(paths, stages, nodes, scale=None, squared=False, distances=None, mult=None, total=None,
+                  max_scratch_bytes=256 << 20):
+    """A scenario tree by staged forward selection (``stemgnn_scenario_stage_distances`` + ``stemgnn_scenario_tree``; the
+    definition is in include/stemgnn_hip.h): per origin, stage t keeps nodes[t] representative paths, every node a child of
+    one node of the stage before (the members of a node share their representative up to the stage's bound), every path
+    assigned to the nearest node among its parent's children in the prefix metric of the stage.  paths [count,S,H,M]
+    contiguous float32 on the device; stages / scale / squared: scenario_stage_distances'; nodes: 1 <= n_1 <= .. <= n_T <= S.
+    mult int32 [count,S] with common sum `total`: the paths' multiplicities (None: one each).  Returns
+      node_path   int32 [count,T,n_T]  the path each node is represented by      node_parent int32 [count,T,n_T]  its parent node
+      node_count  int32 [count,T,n_T]  the multiplicities it gathers              assign      int32 [count,T,S]    every path's node
+      cost        float64 [count,T]    the Kantorovich distance of the stage, in its prefix metric
+    on the device, no sync; beyond n_t the node entries are -1 / -1 / 0.  A refused origin (absent, n_T above its members of
+    positive multiplicity, or a distance between two such members that is not a finite number >= 0) is -1 / -1 / 0 / -1 / NaN at
+    every stage; the others are not affected.  The origins are walked in batches whose [batch,T,S,S] float64 distances stay
+    within max_scratch_bytes; the result is that of one call, bit for bit.
+    distances [count,T,S,S] float64 (contiguous, on the device): any cost of the caller's, D[t,k,u] = moving path k onto path u
+    in stage t; only the second entry runs, paths may be None, and `stages` is only checked for its length."""
+    what = "scenario_tree"
+    if distances is None:
+        C, S, H, M = _reduce_paths(what, paths)
+        bounds = _tree_stages(what, stages, H)
+        T = len(bounds)
+        scale = _reduce_scale(what, scale, H, M)
+        squared = _reduce_flag(what, squared)
+        source = paths
+    else:
+        if not torch.is_tensor(distances) or distances.dim() != 4 or distances.shape[2] != distances.shape[3] or \
+                distances.numel() == 0:
+            raise _lib.StemGNNHipError(f"{what}: distances must be a non-empty [count,T,S,S] tensor, got "
+                                       f"{tuple(distances.shape) if torch.is_tensor(distances) else type(distances).__name__}")
+        if distances.dtype != torch.float64 or not distances.is_contiguous():
+            raise _lib.StemGNNHipError(f"{what}: distances must be a contiguous float64 tensor, got {distances.dtype}, strides "
+                                       f"{tuple(distances.stride())}")
+        C, T, S = (int(v) for v in distances.shape[:3])
+        if S > 1024 or T > 16:
+            raise _lib.StemGNNHipError(f"{what}: at most 1024 paths and 16 stages, got S = {S}, T = {T}")
+        if paths is not None and (not torch.is_tensor(paths) or paths.dim() != 4 or tuple(paths.shape[:2]) != (C, S)):
+            raise _lib.StemGNNHipError(f"{what}: paths must be [count,S,H,M] with the distances' count = {C} and S = {S}, got "
+                                       f"{tuple(paths.shape) if torch.is_tensor(paths) else type(paths).__name__}")
+        if stages is not None and len(tuple(stages)) != T:
+            raise _lib.StemGNNHipError(f"{what}: {len(tuple(stages))} stages, but the distances hold T = {T}")
+        source = distances
+    n = _tree_nodes(what, nodes, T, S)
+    if mult is None:
+        if total is not None and total != S:
+            raise _lib.StemGNNHipError(f"{what}: without mult every path counts once and total is S = {S}, got {total!r}")
+        W = S
+    else:
+        W = _weighted_mult(what, mult, total, C, S)
+        if mult.device != source.device:
+            raise _lib.StemGNNHipError(f"{what}: mult is on {mult.device}, the {'paths' if distances is None else 'distances'} "
+                                       f"on {source.device}")
+    one = T * S * S * 8
+    if isinstance(max_scratch_bytes, bool) or int(max_scratch_bytes) != max_scratch_bytes or int(max_scratch_bytes) < one:
+        raise _lib.StemGNNHipError(f"{what}: max_scratch_bytes must hold one origin's [T,S,S] float64 distances ({one} bytes), "
+                                   f"got {max_scratch_bytes!r}")
+    batch = max(1, min(int(max_scratch_bytes) // one, (2 ** 31 - 1) // (T * S * S)))
+    if not source.is_cuda:
+        raise _lib.StemGNNHipError(f"{what}: {'paths' if distances is None else 'distances'} is on {source.device}: "
+                                   "stemgnn_amd runs only on a HIP device (no CPU fallback)")
+    lib = _lib.load()
+    dev = source.device
+    nT = n[-1]
+    node_path = torch.empty(C, T, nT, device=dev, dtype=torch.int32)
+    node_parent = torch.empty(C, T, nT, device=dev, dtype=torch.int32)
+    node_count = torch.empty(C, T, nT, device=dev, dtype=torch.int32)
+    assign = torch.empty(C, T, S, device=dev, dtype=torch.int32)
+    cost = torch.empty(C, T, device=dev, dtype=torch.float64)
+    n_host = (ctypes.c_int * T)(*n)
+    if distances is None:
+        scale = _f64_on(scale, dev)
+        b_host = (ctypes.c_int * T)(*bounds)
+        D = torch.empty(min(batch, C), T, S, S, device=dev, dtype=torch.float64)
+    for lo in range(0, C, batch):
+        k = min(batch, C - lo)
+        if distances is None:
+            _lib.check(lib.stemgnn_scenario_stage_distances(paths[lo:lo + k].data_ptr(),
+                                                            None if scale is None else scale.data_ptr(), k, S, H, M, T, b_host,
+                                                            squared, D.data_ptr(), _stream()), "scenario_stage_distances")
+            d_ptr = D.data_ptr()
+        else:
+            d_ptr = distances[lo:lo + k].data_ptr()
+        _lib.check(lib.stemgnn_scenario_tree(d_ptr, None if mult is None else mult[lo:lo + k].data_ptr(), k, S, T, n_host, W,
+                                             node_path[lo:lo + k].data_ptr(), node_parent[lo:lo + k].data_ptr(),
+                                             node_count[lo:lo + k].data_ptr(), assign[lo:lo + k].data_ptr(),
+                                             cost[lo:lo + k].data_ptr(), _stream()), what)
+    return node_path, node_parent, node_count, assign, cost
+
+
 def _ring_ok(what, ring, t_dev):
     _require_gpu(ring, "ring")
     if ring.dim() != 2 or ring.dtype != torch.float32 or not ring.is_contiguous():

@@ -28,8 +28,8 @@ from . import ops
 from .base_model import Model, check_quantiles, point_index
 from .engine import ForecastStep, QuantileForecastStep, TrainStep, scenario_rounds
 from .forecast_dataloader import ForecastDataset, WindowLoader, denorm_coefficients, mark_missing
-from .math_utils import (ConformalCalibrator, EnsembleScores, EventSpec, QuantileScores, ScenarioEvents, ScenarioSet, Scores,
-                         reduce_scenarios)
+from .math_utils import (ConformalCalibrator, EnsembleScores, EventSpec, QuantileScores, ScenarioEvents, ScenarioSet,
+                         ScenarioTree, Scores, reduce_scenarios, scenario_tree)
 from .optim import FusedAdam, FusedRMSprop
 
 BEST = "_stemgnn.pt"
@@ -192,6 +192,27 @@ def reduced_scenarios(model, loader, horizon, keep, paths=64, seed=0, adjacency=
         kept.source = None                                   # the batch's paths go with the batch
         sets.append(kept)
     return torch.cat(bands), torch.cat(targets), ScenarioSet.cat(sets)
+
+
+def scenario_trees(model, loader, horizon, stages, nodes, paths=64, seed=0, adjacency=None, coupling="independent",
+                   tails="linear", origin=0, on=None, scale=None, squared=False):
+    """rolling_scenarios handing on a scenario tree per window instead of `paths` equally likely ones: every loader batch's
+    paths become a tree as they are produced (math_utils.scenario_tree: staged forward selection, the members of a node
+    sharing their history up to the stage's bound), and the batch's paths are dropped.  The arguments up to `origin` are
+    rolling_scenarios'; stages / nodes / on / scale / squared are scenario_tree's (on: an EventSpec with groups=).
+    Returns (bands, target, math_utils.ScenarioTree): the bands and the target are rolling_scenarios' own, and the tree is
+    `scenario_tree(paths, stages, nodes, ...)` of rolling_scenarios(..., return_paths=True)'s paths, bit for bit, however the
+    loader batches the windows."""
+    _check_scenarios("scenario_trees", model, horizon, paths)
+    if on is not None and not isinstance(on, EventSpec):
+        raise ValueError("scenario_trees: on= is an EventSpec with groups= (the aggregate of every batch's paths); a tensor "
+                         "goes to math_utils.scenario_tree with the paths it belongs to")
+    bands, targets, trees = [], [], []
+    for b, target, p in _scenario_batches(model, loader, horizon, paths, seed, adjacency, coupling, tails, origin):
+        bands.append(b)
+        targets.append(target)
+        trees.append(scenario_tree(p, stages, nodes, on=on, scale=scale, squared=squared))
+    return torch.cat(bands), torch.cat(targets), ScenarioTree.cat(trees)
 
 
 def rolling_forecast_graph(model, dataset, horizon, batch_size, adjacency=None):
