@@ -258,15 +258,13 @@ __global__ __launch_bounds__(CP_THREADS) void cp_uniforms_kernel(const CpUniArgs
   }
 }
 
-bool cp_fits_int(long long v) { return v > 0 && v < (1ll << 31); }
-
 // the launch shape of gram; false where the entries answer SG_EINVAL
 bool cp_gram_plan(long M, int N, CpGramArgs* a) {
-  if (M <= 0 || N <= 0 || !cp_fits_int(M) || !cp_fits_int((long long)N * N)) return false;
+  if (M <= 0 || N <= 0 || !sg_fits_int(M) || !sg_fits_int((long long)N * N)) return false;
   a->M = M; a->N = N;
   a->tiles = sg_ceil_div(N, CP_TILE);
   a->chunks = sg_ceil_div(M, CP_CHUNK);
-  return cp_fits_int((long long)a->tiles * a->tiles * a->chunks);
+  return sg_fits_int((long long)a->tiles * a->tiles * a->chunks);
 }
 
 }  // namespace
@@ -283,7 +281,7 @@ extern "C" int stemgnn_copula_pit(const float* target, const float* forecast, co
     a.tau[q] = taus[q];
   }
   // what an int carries in the kernel: a row's nodes, a column's row stride, the rows and the grid
-  if (!cp_fits_int((long long)H * N) || !cp_fits_int((long long)Q * H * N) || !cp_fits_int((long long)count * H))
+  if (!sg_fits_int((long long)H * N) || !sg_fits_int((long long)Q * H * N) || !sg_fits_int((long long)count * H))
     return SG_EINVAL;
   const bool vec = (N & 3) == 0 && sg_aligned16(target) && sg_aligned16(forecast) && sg_aligned16(u);
   const int VEC = vec ? 4 : 1;
@@ -295,7 +293,7 @@ extern "C" int stemgnn_copula_pit(const float* target, const float* forecast, co
   while (T > 64 && ((size_t)T * Q * VEC * 4 > (size_t)CP_LDS_BYTES || T - 64 >= a.items)) T -= 64;
   const size_t lds = (size_t)T * Q * VEC * 4;                 // <= 32 KB: Q <= 32, VEC <= 4, T >= 64
   const long long grid = (a.items + T - 1) / T;
-  if (!cp_fits_int(grid)) return SG_EINVAL;
+  if (!sg_fits_int(grid)) return SG_EINVAL;
   if (vec)
     hipLaunchKernelGGL(cp_pit_kernel<4>, dim3((unsigned)grid), dim3(T), lds, (hipStream_t)stream, a);
   else
@@ -331,7 +329,7 @@ extern "C" int stemgnn_copula_uniforms(const float* factor_t, int Bo, int S, int
   if (Bo <= 0 || Lsteps <= 0 || N <= 0 || N > CP_MAX_N || S < 1 || S > CP_MAX_S || step < 0 || step >= horizon)
     return SG_EINVAL;
   // what an int carries in the kernel: the rows (the grid is at most that), a path's steps
-  if (!cp_fits_int((long long)Bo * S * Lsteps) || !cp_fits_int((long long)S * horizon)) return SG_EINVAL;
+  if (!sg_fits_int((long long)Bo * S * Lsteps) || !sg_fits_int((long long)S * horizon)) return SG_EINVAL;
   CpUniArgs a = {};
   a.factor_t = factor_t; a.u = u;
   a.origin0 = (unsigned long long)origin0; a.seed = seed; a.offset = offset;

@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "../../include/stemgnn_hip.h"
+#include "scenario_math.h"
 #include "sg_host.h"
 
 namespace {
@@ -56,23 +57,6 @@ struct EnArgs {
   long long rows, count;                    // rows = count * H
   int S, H, N, C, tn, nt, pairs, fair;
 };
-
-__device__ inline double en_dn(float v, bool dn, double mu, double ad) {
-  return dn ? __dadd_rn(__dmul_rn((double)v, mu), ad) : (double)v;
-}
-
-// v summed over the workgroup in a fixed order (a tree inside each wave, the waves in index order); every thread gets the sum
-__device__ inline double en_block_sum(double v, double* sh) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-  const int nw = blockDim.x >> 6;
-  __syncthreads();                                             // (sh may still be read from the previous sum)
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < nw; ++w) s += sh[w];
-  return s;
-}
 
 template <bool MASKED>
 __global__ __launch_bounds__(EN_THREADS) void en_energy_kernel(const EnArgs a) {
@@ -111,10 +95,10 @@ __global__ __launch_bounds__(EN_THREADS) void en_energy_kernel(const EnArgs a) {
     __syncthreads();                                           // the previous chunk has been read
     for (int r = lr; r < EN_PT; r += EN_THREADS / EN_NC) {
       const int si = I * EN_PT + r, sj = J * EN_PT + r;
-      pa[r * EN_LD + ln] = (valid && si < S) ? en_dn(px[(size_t)si * HN + n], dn, mu, ad) : 0.0;
-      if (!diag) pb_own[r * EN_LD + ln] = (valid && sj < S) ? en_dn(px[(size_t)sj * HN + n], dn, mu, ad) : 0.0;
+      pa[r * EN_LD + ln] = (valid && si < S) ? sg_dn(px[(size_t)si * HN + n], dn, mu, ad) : 0.0;
+      if (!diag) pb_own[r * EN_LD + ln] = (valid && sj < S) ? sg_dn(px[(size_t)sj * HN + n], dn, mu, ad) : 0.0;
     }
-    if (t < EN_NC) ys[t] = valid ? en_dn(y, dn, mu, ad) : 0.0;
+    if (t < EN_NC) ys[t] = valid ? sg_dn(y, dn, mu, ad) : 0.0;
     __syncthreads();
     const int lim = min(EN_NC, N - n0);
     const double* ra = pa + (2 * ti) * EN_LD;
@@ -154,8 +138,8 @@ __global__ __launch_bounds__(EN_THREADS) void en_energy_kernel(const EnArgs a) {
     if (si < S) e += sqrt(e0);
     if (si + 1 < S) e += sqrt(e1);
   }
-  p = en_block_sum(p, red);
-  e = en_block_sum(e, red);
+  p = sg_block_sum(p, red);
+  e = sg_block_sum(e, red);
   const int has = __syncthreads_or(any);
   if (t == 0) {
     const size_t np = (size_t)a.rows * a.pairs, r = (size_t)h * a.count + b;
@@ -188,13 +172,13 @@ __global__ __launch_bounds__(EN_THREADS) void en_marginal_kernel(const EnArgs a)
   const float y = live ? a.target[row * N + n] : 0.f;
   const bool valid = live && (!MASKED || y == y);
   const double mu = (dn && live) ? a.mul[n] : 1.0, ad = (dn && live) ? a.add[n] : 0.0;
-  const double yd = en_dn(y, dn, mu, ad);
+  const double yd = sg_dn(y, dn, mu, ad);
   const float* src = a.paths + (b * S * a.H + h) * (size_t)N + n;
   int lt = 0, eq = 0;
   double sa = 0.0, sx = 0.0;
   for (int i = g; i < S; i += G) {
     const float x = live ? src[(size_t)i * HN] : 0.f;
-    const double xd = en_dn(x, dn, mu, ad);
+    const double xd = sg_dn(x, dn, mu, ad);
     tile[i * C + c] = xd;
     lt += x < y ? 1 : 0;
     eq += x == y ? 1 : 0;
@@ -298,7 +282,7 @@ __global__ __launch_bounds__(EN_FIN_THREADS) void en_finish_kernel(const EnArgs 
       for (size_t i = t; i < (size_t)count; i += EN_FIN_THREADS) s[7] += a.epart[2 * np + (size_t)h * count + i];
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        v[k] = en_block_sum(s[k], red);
+        v[k] = sg_block_sum(s[k], red);
         all[k] += v[k];
       }
     } else {
@@ -318,11 +302,9 @@ __global__ __launch_bounds__(EN_FIN_THREADS) void en_finish_kernel(const EnArgs 
   }
 }
 
-bool en_fits_int(long long v) { return v > 0 && v < (1ll << 31); }
-
 // the launch shape of (count, S, H, N); false where the entries answer SG_EINVAL
 bool en_plan(long count, int S, int H, int N, EnArgs* a) {
-  if (count <= 0 || S <= 0 || H <= 0 || N <= 0 || S > EN_MAX_S || !en_fits_int(count)) return false;
+  if (count <= 0 || S <= 0 || H <= 0 || N <= 0 || S > EN_MAX_S || !sg_fits_int(count)) return false;
   int C = 4;
   while (C < 64 && C < N) C <<= 1;
   while (C > 4 && (size_t)S * C * 8 > (size_t)EN_TILE_BYTES) C >>= 1;
@@ -332,12 +314,12 @@ bool en_plan(long count, int S, int H, int N, EnArgs* a) {
   a->nt = nt;
   a->pairs = nt * (nt + 1) / 2;
   // what an int carries in the kernels: the grids, a row's nodes, the histogram's bins, one origin's path values
-  if (!en_fits_int((long long)count * H) || !en_fits_int((long long)H * N) || !en_fits_int((long long)H * (S + 1)) ||
-      !en_fits_int((long long)S * H * N))
+  if (!sg_fits_int((long long)count * H) || !sg_fits_int((long long)H * N) || !sg_fits_int((long long)H * (S + 1)) ||
+      !sg_fits_int((long long)S * H * N))
     return false;
   a->rows = (long long)count * H;
   a->count = count;
-  return en_fits_int(a->rows * a->tn) && en_fits_int(a->rows * a->pairs);
+  return sg_fits_int(a->rows * a->tn) && sg_fits_int(a->rows * a->pairs);
 }
 
 size_t en_scratch(const EnArgs& a) { return (size_t)a.rows * (5 * (size_t)a.tn + 2 * (size_t)a.pairs + 1); }

@@ -17,17 +17,15 @@
 //            more than one partial is left a lane keeps one half of its partials and hands the other to the lane `mask` away
 //            (masks 32, 16, ..), then the lanes that hold the same r add up over the remaining masks.  RB - 1 + 6 - log2(RB)
 //            exchanges instead of 6 RB; the order is a function of N and R alone.
-// events:    paths [count, S, H, M] fp32 -> counts int32 [count, 2 H + 1, M].  One workgroup per (origin, tile of C columns);
-//            C = 64 .. 1, a power of two: the smallest that covers M, halved until the tile's (2 H + 1) x C counters are within
-//            32 KB.  Thread (g, c) = (t / C, t % C) owns the paths g, g + G, .. of column c (G = 256 / C; lanes along m:
-//            coalesced) and walks h in order with "crossed yet", the current run and the longest run in registers; every
-//            count is an integer add into the LDS tile, and the workgroup writes its tile's 2 H + 1 rows itself.
+// events:    the kernel of path_events.h (ev_kernel<false>: every path counts once), shared with weighted.hip.
 // One launch each, no allocation, no memset, no global atomics, nothing floating-point that depends on arrival order: the same
 // bits on every run, capturable.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/stemgnn_hip.h"
+#include "path_events.h"
+#include "scenario_math.h"
 #include "sg_host.h"
 
 namespace {
@@ -38,10 +36,7 @@ constexpr int AG_MAX_R = 32;
 constexpr int AG_MAX_N = 4096;
 constexpr int AG_LDS_BYTES = 64 * 1024;     // the table of weights, mul and add; beyond it they are read from global memory
 constexpr int AG_MAX_BLOCKS = 2048;         // 256 CUs x 8 workgroups: the rows beyond are walked
-constexpr int EV_THREADS = 256;
 constexpr int EV_MAX_S = 1024;
-constexpr int EV_MAX_H = 256;
-constexpr int EV_LDS_BYTES = 32 * 1024;     // the tile of (2 H + 1) x C counters
 
 struct AgArgs {
   const float* x;                           // [rows, N]
@@ -52,19 +47,6 @@ struct AgArgs {
   long long rows;
   int N, R, Np;
 };
-
-struct EvArgs {
-  const float* paths;                       // [count, S, H, M]
-  const double* thr;                        // [M]
-  const double* mul;                        // [M] or NULL
-  const double* add;
-  int* counts;                              // [count, 2 H + 1, M]
-  int S, H, M, C, tiles, above, min_run;
-};
-
-__device__ inline double ev_dn(float v, bool dn, double mu, double ad) {
-  return dn ? __dadd_rn(__dmul_rn((double)v, mu), ad) : (double)v;
-}
 
 template <int VEC>
 struct AgVec {
@@ -165,7 +147,7 @@ __global__ __launch_bounds__(AG_THREADS) void ag_kernel(const AgArgs a) {
         } else {
           mu = dn ? a.mul[n0 + k] : 1.0; ad = dn ? a.add[n0 + k] : 0.0;
         }
-        v[k] = ev_dn(xv.v[k], dn, mu, ad);
+        v[k] = sg_dn(xv.v[k], dn, mu, ad);
         finite = finite && fabs(v[k]) < __builtin_inf();       // false for a NaN too
       }
       // A weight of exactly 0 leaves its node out.  Where every value of the wave's pass is finite the plain FMA does that by
@@ -205,48 +187,6 @@ __global__ __launch_bounds__(AG_THREADS) void ag_kernel(const AgArgs a) {
   }
 }
 
-__global__ __launch_bounds__(EV_THREADS) void ev_kernel(const EvArgs a) {
-  extern __shared__ int ev_lds[];                              // [2 H + 1][C]: step | first | run
-  const int S = a.S, H = a.H, M = a.M, C = a.C, t = threadIdx.x;
-  const int G = EV_THREADS / C, g = t / C, c = t - g * C, K = 2 * H + 1;
-  for (int i = t; i < K * C; i += EV_THREADS) ev_lds[i] = 0;
-  __syncthreads();
-  const size_t o = blockIdx.x / (unsigned)a.tiles;
-  const int tl = (int)(blockIdx.x - o * (unsigned)a.tiles);
-  const int m = tl * C + c;
-  if (m < M) {
-    const bool dn = a.mul != nullptr, above = a.above != 0;
-    const double mu = dn ? a.mul[m] : 1.0, ad = dn ? a.add[m] : 0.0, th = a.thr[m];
-    const size_t HM = (size_t)H * M;
-    const float* src = a.paths + o * S * HM + m;
-    for (int s = g; s < S; s += G) {
-      const float* p = src + (size_t)s * HM;
-      int crossed = 0, cur = 0, best = 0;
-#pragma unroll 4
-      for (int h = 0; h < H; ++h) {
-        const double v = ev_dn(p[(size_t)h * M], dn, mu, ad);
-        const bool e = above ? v > th : v < th;                // strict, so a NaN on either side is never in the event
-        if (e) {
-          atomicAdd(&ev_lds[h * C + c], 1);
-          if (!crossed) atomicAdd(&ev_lds[(H + h) * C + c], 1);
-        }
-        crossed |= e ? 1 : 0;
-        cur = e ? cur + 1 : 0;
-        best = max(best, cur);
-      }
-      if (best >= a.min_run) atomicAdd(&ev_lds[2 * H * C + c], 1);
-    }
-  }
-  __syncthreads();
-  int* dst = a.counts + o * K * M + (size_t)tl * C;
-  for (int i = t; i < K * C; i += EV_THREADS) {
-    const int k = i / C, cc = i - k * C;
-    if (tl * C + cc < M) dst[(size_t)k * M + cc] = ev_lds[i];
-  }
-}
-
-bool ev_fits_int(long long v) { return v > 0 && v < (1ll << 31); }
-
 template <int RB>
 int ag_launch(const AgArgs& a, int grid, bool vec, hipStream_t st) {
   const size_t lds = (size_t)(RB + 2) * a.Np * sizeof(double);
@@ -270,7 +210,7 @@ extern "C" int stemgnn_scenario_aggregate(const float* x, const double* weights,
   if (!x || !weights || !out) return SG_EINVAL;
   if ((mul == nullptr) != (add == nullptr)) return SG_EINVAL;
   if (rows <= 0 || N <= 0 || R <= 0 || R > AG_MAX_R || N > AG_MAX_N) return SG_EINVAL;
-  if (rows >= (1ll << 31) || !ev_fits_int(rows * R)) return SG_EINVAL;
+  if (rows >= (1ll << 31) || !sg_fits_int(rows * R)) return SG_EINVAL;
   AgArgs a = {};
   a.x = x; a.w = weights; a.mul = mul; a.add = add; a.out = out;
   a.rows = rows; a.N = N; a.R = R; a.Np = (N + 3) & ~3;
@@ -290,19 +230,9 @@ extern "C" int stemgnn_scenario_events(const float* paths, const double* thr, co
                                        int S, int H, int M, int above, int min_run, int* counts, void* stream) {
   if (!paths || !thr || !counts) return SG_EINVAL;
   if ((mul == nullptr) != (add == nullptr)) return SG_EINVAL;
-  if (count <= 0 || S <= 0 || H <= 0 || M <= 0 || S > EV_MAX_S || H > EV_MAX_H) return SG_EINVAL;
-  if (min_run < 1 || min_run > H || (above != 0 && above != 1)) return SG_EINVAL;
-  if (!ev_fits_int((long long)count) || !ev_fits_int((long long)S * H * M) || !ev_fits_int((2ll * H + 1) * M)) return SG_EINVAL;
-  int C = 1;
-  while (C < 64 && C < M) C <<= 1;
-  while (C > 1 && (size_t)(2 * H + 1) * C * sizeof(int) > (size_t)EV_LDS_BYTES) C >>= 1;
+  if (count <= 0 || S <= 0 || H <= 0 || M <= 0 || S > EV_MAX_S) return SG_EINVAL;
   EvArgs a = {};
   a.paths = paths; a.thr = thr; a.mul = mul; a.add = add; a.counts = counts;
-  a.S = S; a.H = H; a.M = M; a.C = C; a.above = above; a.min_run = min_run;
-  a.tiles = sg_ceil_div(M, C);
-  if (!ev_fits_int((long long)count * a.tiles)) return SG_EINVAL;
-  const size_t lds = (size_t)(2 * H + 1) * C * sizeof(int);
-  hipLaunchKernelGGL(ev_kernel, dim3((unsigned)(count * a.tiles)), dim3(EV_THREADS), lds, (hipStream_t)stream, a);
-  SG_TRY(hipGetLastError());
-  return 0;
+  a.S = S; a.H = H; a.M = M; a.above = above; a.min_run = min_run;
+  return ev_launch<false>(a, count, (hipStream_t)stream);
 }

@@ -189,8 +189,6 @@ __global__ __launch_bounds__(SC_THREADS) void sc_bands_kernel(const ScBandArgs a
   }
 }
 
-bool sc_fits_int(long long v) { return v > 0 && v < (1ll << 31); }
-
 // the checks and the launch of both roll entries; uniforms == NULL: the Philox draws of `coupling`
 template <bool GIVEN>
 int sc_roll(const float* inputs, const float* forecast, const float* taus, const float* uniforms, int Bo, int S, int fan, int W,
@@ -210,8 +208,8 @@ int sc_roll(const float* inputs, const float* forecast, const float* taus, const
     a.tau[q] = taus[q];
   }
   // what an int carries in the kernel: the path count (grid.x), the items of a path, a column's row stride
-  if (!sc_fits_int((long long)Bo * S) || !sc_fits_int((long long)W * N) || !sc_fits_int((long long)Q * L * N) ||
-      !sc_fits_int((long long)Q * horizon * N) || !sc_fits_int((long long)S * horizon))
+  if (!sg_fits_int((long long)Bo * S) || !sg_fits_int((long long)W * N) || !sg_fits_int((long long)Q * L * N) ||
+      !sg_fits_int((long long)Q * horizon * N) || !sg_fits_int((long long)S * horizon))
     return SG_EINVAL;
   a.inputs = inputs; a.forecast = forecast; a.inputs_next = inputs_next; a.paths = paths; a.bands = bands;
   a.uniforms = uniforms;
@@ -266,7 +264,7 @@ extern "C" int stemgnn_scenario_bands(const float* paths, int Bo, int S, int hor
   if (!paths || !ranks || !bands || paths == bands) return SG_EINVAL;
   if (Bo <= 0 || horizon <= 0 || N <= 0 || Q < 1 || Q > CF_MAX_Q || S < 1 || S > SC_MAX_S) return SG_EINVAL;
   if (step_from < 0 || step_from > horizon) return SG_EINVAL;
-  if (!sc_fits_int((long long)horizon * N) || !sc_fits_int((long long)Bo * S)) return SG_EINVAL;
+  if (!sg_fits_int((long long)horizon * N) || !sg_fits_int((long long)Bo * S)) return SG_EINVAL;
   ScBandArgs a = {};
   for (int q = 0; q < Q; ++q) {
     if (ranks[q] < 1 || ranks[q] > S) return SG_EINVAL;
@@ -281,7 +279,7 @@ extern "C" int stemgnn_scenario_bands(const float* paths, int Bo, int S, int hor
   while (C > 8 && (size_t)S * C * 4 > (size_t)SC_LDS_BYTES) C >>= 1;
   a.C = C;
   a.tiles = sg_ceil_div(a.cols, C);
-  if (!sc_fits_int((long long)Bo * a.tiles)) return SG_EINVAL;
+  if (!sg_fits_int((long long)Bo * a.tiles)) return SG_EINVAL;
   hipLaunchKernelGGL(sc_bands_kernel, dim3((unsigned)(Bo * a.tiles)), dim3(SC_THREADS), (size_t)S * C * 4, (hipStream_t)stream,
                      a);
   SG_TRY(hipGetLastError());

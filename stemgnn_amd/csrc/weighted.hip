@@ -10,7 +10,7 @@
 //          Thread (g, c) owns members g, g + G, .. of column c: `before` = the multiplicities of the values ahead of its own in
 //          the order of sc_less (-0 == +0, NaN last, the member index breaking ties); the member answers every rank in
 //          (before, before + w].  The answers meet in an LDS tile [Q][C] that the workgroup stores (NaN for an absent origin).
-// events:  the kernel of events.hip with `+= w` for `+= 1`; an absent origin's tile is -1.
+// events:  the kernel of path_events.h (ev_kernel<true>): `+= w` for `+= 1`; an absent origin's tile is -1.
 // scores:  the three launches of ensemble.hip on the live members (those of positive multiplicity, compacted in index order):
 //          the pair tiles of the energy score weigh a pair distance by w w' and a target distance by w; the marginal launch,
 //          one workgroup per row (c, h) walking the row's node tiles in order, weighs |x - y| and x by w, |x - x'| by w w'
@@ -18,16 +18,18 @@
 //          with one 64-bit integer add per non-empty bin (beyond: one add per element); the finish, one workgroup per step and one for the
 //          overall statistics, adds the partials in index order.  An absent origin contributes zeros and
 //          is counted in slot 6.
-// reduce:  the pick kernel of reduce.hip with z_u = sum_k p_k min(m_k, D[k, u]), the product and the sum rounded separately;
-//          a member of multiplicity 0 is no candidate and its row and column of D are not read.
+// reduce:  the pick of forward_select.h (fs_pick, WEIGHTED): z_u = sum_k p_k min(m_k, D[k, u]), the product and the sum rounded
+//          separately; a member of multiplicity 0 is no candidate and its row and column of D are not read.
 // No floating-point atomics, no allocation, no memset, no host synchronisation: the same bits on every run, origin by origin.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/stemgnn_hip.h"
-#include "devattr.h"
+#include "forward_select.h"
+#include "path_events.h"
 #include "scenario_draw.h"
+#include "scenario_math.h"
 #include "sg_host.h"
 
 namespace {
@@ -36,10 +38,7 @@ constexpr int WT_THREADS = 256;
 constexpr int WT_MAX_K = 256;               // bands, scores, events: members of a set
 constexpr int WT_MAX_Q = 32;
 constexpr int WT_MAX_W = 1 << 24;           // w w' and W^2 are exact in fp64
-constexpr int WT_MAX_H = 256;               // events
-constexpr int WT_MAX_S = 1024;              // reduce
-constexpr int WT_TILE_BYTES = 32 * 1024;    // bands, events, marginal: the LDS tile
-constexpr size_t WT_LDS_BYTES = 160 * 1024; // reduce: LDS of one workgroup on gfx950
+constexpr int WT_TILE_BYTES = 32 * 1024;    // bands, marginal: the LDS tile
 constexpr int WT_PT = 32;                   // energy: members per panel
 constexpr int WT_NC = 64;                   // energy: nodes per chunk
 constexpr int WT_LD = WT_NC + 1;            // energy: doubles between panel rows
@@ -47,26 +46,8 @@ constexpr int WT_FIN_THREADS = 1024;
 constexpr int WT_OUT_K = 7;
 constexpr int WT_HIST_BINS = 4096;          // marginal: a row's ranks meet in LDS where W + 1 bins are within 16 KB
 
-__device__ inline double wt_dn(float v, bool dn, double mu, double ad) {
-  return dn ? __dadd_rn(__dmul_rn((double)v, mu), ad) : (double)v;
-}
-
-// The origin's K multiplicities go to wm (LDS); true when the origin is present.  Every thread calls it (one barrier).
-__device__ inline bool wt_present(const int* mult, int K, int W, int* wm) {
-  for (int k = threadIdx.x; k < K; k += blockDim.x) wm[k] = mult[k];
-  __syncthreads();
-  long long sum = 0;
-  int neg = 0;
-  for (int k = 0; k < K; ++k) {
-    const int w = wm[k];
-    neg |= w < 0 ? 1 : 0;
-    sum += w;
-  }
-  return !neg && sum == (long long)W;
-}
-
-// wt_present, and the members of positive multiplicity compacted in index order: idx[i] the member, wl[i] its multiplicity,
-// i < *n.  K <= blockDim.x.  Two barriers.
+// wt_present (scenario_math.h), and the members of positive multiplicity compacted in index order: idx[i] the member, wl[i]
+// its multiplicity, i < *n.  K <= blockDim.x.  Two barriers.
 __device__ inline bool wt_live(const int* mult, int K, int W, int* wm, int* idx, int* wl, int* n) {
   const int t = threadIdx.x;
   const bool ok = wt_present(mult, K, W, wm);
@@ -164,60 +145,6 @@ __global__ __launch_bounds__(WT_THREADS) void wt_bands_kernel(const WtBandArgs a
   }
 }
 
-// ---- events --------------------------------------------------------------------------------------------------------------------
-struct WtEventArgs {
-  const float* paths;                       // [count, K, H, M]
-  const int* mult;
-  const double* thr;                        // [M]
-  const double* mul;                        // [M] or NULL
-  const double* add;
-  int* counts;                              // [count, 2 H + 1, M]
-  int K, H, M, C, tiles, above, min_run, W;
-};
-
-__global__ __launch_bounds__(WT_THREADS) void wt_events_kernel(const WtEventArgs a) {
-  extern __shared__ int wt_ev_lds[];                            // [2 H + 1][C]: step | first | run; then the multiplicities [K]
-  const int K = a.K, H = a.H, M = a.M, C = a.C, t = threadIdx.x;
-  const int G = WT_THREADS / C, g = t / C, c = t - g * C, R = 2 * H + 1;
-  int* wm = wt_ev_lds + R * C;
-  const size_t o = blockIdx.x / (unsigned)a.tiles;
-  const int tl = (int)(blockIdx.x - o * (unsigned)a.tiles);
-  for (int i = t; i < R * C; i += WT_THREADS) wt_ev_lds[i] = 0;
-  const bool ok = wt_present(a.mult + o * K, K, a.W, wm);       // (its barrier also settles the zeroes)
-  const int m = tl * C + c;
-  if (ok && m < M) {
-    const bool dn = a.mul != nullptr, above = a.above != 0;
-    const double mu = dn ? a.mul[m] : 1.0, ad = dn ? a.add[m] : 0.0, th = a.thr[m];
-    const size_t HM = (size_t)H * M;
-    const float* src = a.paths + o * K * HM + m;
-    for (int s = g; s < K; s += G) {
-      const int w = wm[s];
-      if (w <= 0) continue;
-      const float* p = src + (size_t)s * HM;
-      int crossed = 0, cur = 0, best = 0;
-#pragma unroll 4
-      for (int h = 0; h < H; ++h) {
-        const double v = wt_dn(p[(size_t)h * M], dn, mu, ad);
-        const bool e = above ? v > th : v < th;                 // strict, so a NaN on either side is never in the event
-        if (e) {
-          atomicAdd(&wt_ev_lds[h * C + c], w);
-          if (!crossed) atomicAdd(&wt_ev_lds[(H + h) * C + c], w);
-        }
-        crossed |= e ? 1 : 0;
-        cur = e ? cur + 1 : 0;
-        best = max(best, cur);
-      }
-      if (best >= a.min_run) atomicAdd(&wt_ev_lds[2 * H * C + c], w);
-    }
-  }
-  __syncthreads();
-  int* dst = a.counts + o * R * M + (size_t)tl * C;
-  for (int i = t; i < R * C; i += WT_THREADS) {
-    const int k = i / C, cc = i - k * C;
-    if (tl * C + cc < M) dst[(size_t)k * M + cc] = ok ? wt_ev_lds[i] : -1;
-  }
-}
-
 // ---- scores --------------------------------------------------------------------------------------------------------------------
 struct WtScoreArgs {
   const float* target;                      // [count, H, N]
@@ -234,19 +161,6 @@ struct WtScoreArgs {
   long long rows, count;                    // rows = count * H
   int K, H, N, C, tn, nt, pairs, fair, W, lds_hist;
 };
-
-// v summed over the workgroup in a fixed order (a tree inside each wave, the waves in index order); every thread gets the sum
-__device__ inline double wt_block_sum(double v, double* sh) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-  const int nw = blockDim.x >> 6;
-  __syncthreads();                                              // (sh may still be read from the previous sum)
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < nw; ++w) s += sh[w];
-  return s;
-}
 
 template <bool MASKED>
 __global__ __launch_bounds__(WT_THREADS) void wt_energy_kernel(const WtScoreArgs a) {
@@ -292,15 +206,15 @@ __global__ __launch_bounds__(WT_THREADS) void wt_energy_kernel(const WtScoreArgs
       __syncthreads();                                          // the previous chunk has been read
       for (int r = lr; r < nra; r += WT_THREADS / WT_NC) {
         const int si = I * WT_PT + r;
-        pa[r * WT_LD + ln] = (valid && si < kk) ? wt_dn(px[(size_t)idx[si] * HN + n], dn, mu, ad) : 0.0;
+        pa[r * WT_LD + ln] = (valid && si < kk) ? sg_dn(px[(size_t)idx[si] * HN + n], dn, mu, ad) : 0.0;
       }
       if (!diag) {
         for (int r = lr; r < nrb; r += WT_THREADS / WT_NC) {
           const int sj = J * WT_PT + r;
-          pb_own[r * WT_LD + ln] = (valid && sj < kk) ? wt_dn(px[(size_t)idx[sj] * HN + n], dn, mu, ad) : 0.0;
+          pb_own[r * WT_LD + ln] = (valid && sj < kk) ? sg_dn(px[(size_t)idx[sj] * HN + n], dn, mu, ad) : 0.0;
         }
       }
-      if (t < WT_NC) ys[t] = valid ? wt_dn(y, dn, mu, ad) : 0.0;
+      if (t < WT_NC) ys[t] = valid ? sg_dn(y, dn, mu, ad) : 0.0;
       __syncthreads();
       const int lim = min(WT_NC, N - n0);
       const double* ra = pa + (2 * ti) * WT_LD;
@@ -330,8 +244,8 @@ __global__ __launch_bounds__(WT_THREADS) void wt_energy_kernel(const WtScoreArgs
     if (si < kk) e += (double)wl[si] * sqrt(e0);
     if (si + 1 < kk) e += (double)wl[si + 1] * sqrt(e1);
   }
-  p = wt_block_sum(p, red);
-  e = wt_block_sum(e, red);
+  p = sg_block_sum(p, red);
+  e = sg_block_sum(e, red);
   const int has = __syncthreads_or(any);
   if (t == 0) {
     const size_t np = (size_t)a.rows * a.pairs, r = (size_t)h * a.count + b;
@@ -373,14 +287,14 @@ __global__ __launch_bounds__(WT_THREADS) void wt_marginal_kernel(const WtScoreAr
     const float y = live ? a.target[row * N + n] : 0.f;
     const bool valid = ok && live && (!MASKED || y == y);
     const double mu = (dn && live) ? a.mul[n] : 1.0, ad = (dn && live) ? a.add[n] : 0.0;
-    const double yd = wt_dn(y, dn, mu, ad);
+    const double yd = sg_dn(y, dn, mu, ad);
     const float* src = a.paths + (b * K * a.H + h) * (size_t)N + n;
     int lt = 0, eq = 0;
     double sa = 0.0, sx = 0.0;
     __syncthreads();                                            // the previous tile has been read
     for (int i = g; i < kk; i += G) {
       const float x = live ? src[(size_t)idx[i] * HN] : 0.f;
-      const double xd = wt_dn(x, dn, mu, ad), w = (double)wl[i];
+      const double xd = sg_dn(x, dn, mu, ad), w = (double)wl[i];
       tile[i * C + c] = xd;
       lt += x < y ? wl[i] : 0;
       eq += x == y ? wl[i] : 0;
@@ -470,7 +384,7 @@ __global__ __launch_bounds__(WT_FIN_THREADS) void wt_finish_kernel(const WtScore
   }
   for (size_t i = t; i < (size_t)count; i += WT_FIN_THREADS) s[8] += a.epart[2 * np + (size_t)a.rows + i];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) v[k] = wt_block_sum(s[k], red);
+  for (int k = 0; k < 9; ++k) v[k] = sg_block_sum(s[k], red);
   if (t == 0) {
     double* o = hb < H ? a.out + WT_OUT_K + hb : a.out;         // statistic k of step h: out[7 + k * H + h]
     const size_t ld = hb < H ? (size_t)H : 1;
@@ -485,140 +399,16 @@ __global__ __launch_bounds__(WT_FIN_THREADS) void wt_finish_kernel(const WtScore
 }
 
 // ---- reduce --------------------------------------------------------------------------------------------------------------------
-struct WtPickArgs {
-  const double* D;                          // [count, S, S]
-  const int* mult;                          // [count, S]
-  int* selected;                            // [count, K]
-  int* counts;                              // [count, K]
-  int* assign;                              // [count, S]
-  double* cost;                             // [count, K]
-  int S, K, ld, W;                          // ld: doubles between rows of the LDS copy
-};
-
-// the smaller of two (taken, value, index) candidates: an untaken one first, then the smaller value, then the lower index
-__device__ inline void wt_take_min(double& v, int& i, double ov, int oi) {
-  const bool ours_taken = i >= WT_MAX_S, theirs_taken = oi >= WT_MAX_S;
-  const bool better = ours_taken != theirs_taken ? ours_taken : (ov < v || (ov == v && oi < i));
-  if (better) {
-    v = ov;
-    i = oi;
-  }
-}
-
-// z + p * d with the product and the sum rounded separately: plain operators under `fp contract(off)` (the __dmul_rn / __dadd_rn
-// of this toolchain's headers are `x * y` / `x + y` under the default contraction, which fuses them once inlined)
-__device__ inline double wt_add_product(double z, double p, double d) {
-#pragma clang fp contract(off)
-  const double term = p * d;
-  return z + term;
-}
-
 template <bool IN_LDS>
-__global__ __launch_bounds__(1024) void wt_pick_kernel(const WtPickArgs a) {
-  extern __shared__ double wt_pick_mem[];
-  const int S = a.S, K = a.K, t = threadIdx.x, nthr = blockDim.x, nw = nthr >> 6;
-  double* m = wt_pick_mem;                                      // [S]
-  double* wv = m + S;                                           // [16]: the waves' candidates
-  int* wi = reinterpret_cast<int*>(wv + 16);                    // [16]
-  int* near = wi + 16;                                          // [S]
-  int* pick = near + S;                                         // [2]
-  int* mu = pick + 2;                                           // [S]: the multiplicities
-  double* Dl = reinterpret_cast<double*>(mu + S);               // [S][ld], IN_LDS only (16 + 2 + 2 S ints: 8-byte aligned)
-  const size_t c = blockIdx.x;
-  const double* Dg = a.D + c * (size_t)S * S;
-  const int ld = IN_LDS ? a.ld : S;
-  const double* Dr = IN_LDS ? Dl : Dg;                          // what the picks read
-  for (int k = t; k < S; k += nthr) {
-    mu[k] = a.mult[c * S + k];
-    m[k] = INFINITY;
-    near[k] = -1;
-  }
-  __syncthreads();
-  long long sum = 0;
-  int neg = 0, pos = 0;
-  for (int k = 0; k < S; ++k) {
-    const int w = mu[k];
-    neg |= w < 0 ? 1 : 0;
-    pos += w > 0 ? 1 : 0;
-    sum += w;
-  }
-  int bad = (neg || sum != (long long)a.W || K > pos) ? 1 : 0;  // (the same in every thread)
-  if (!bad) {
-    for (int i = t; i < S * S; i += nthr) {
-      const int k = i / S, u = i - k * S;
-      if (mu[k] <= 0 || mu[u] <= 0) continue;                   // a row or column of multiplicity 0 is not read
-      const double d = Dg[i];
-      bad |= (d >= 0.0 && d < INFINITY) ? 0 : 1;                // a NaN fails both comparisons
-      if (IN_LDS) Dl[k * ld + u] = d;
-    }
-  }
-  if (__syncthreads_or(bad)) {                                  // refused: this origin alone
-    for (int j = t; j < K; j += nthr) {
-      a.selected[c * K + j] = -1;
-      a.counts[c * K + j] = 0;
-      a.cost[c * K + j] = NAN;
-    }
-    for (int k = t; k < S; k += nthr) a.assign[c * S + k] = -1;
-    return;
-  }
-  const bool candidate = t < S && mu[t] > 0;
-  bool taken = !candidate;
-  for (int p = 0; p < K; ++p) {
-    double z = 0.0;
-    if (candidate) {
-      const double* col = Dr + t;
-      for (int k = 0; k < S; ++k) {
-        const int w = mu[k];
-        if (w > 0) z = wt_add_product(z, (double)w, fmin(m[k], col[(size_t)k * ld]));
-      }
-    }
-    double v = z;
-    int idx = taken ? WT_MAX_S + t : t;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const double ov = __shfl_down(v, off);
-      const int oi = __shfl_down(idx, off);
-      wt_take_min(v, idx, ov, oi);
-    }
-    if ((t & 63) == 0) {
-      wv[t >> 6] = v;
-      wi[t >> 6] = idx;
-    }
-    __syncthreads();
-    if (t == 0) {
-      for (int w = 1; w < nw; ++w) wt_take_min(v, idx, wv[w], wi[w]);
-      pick[0] = idx;
-      a.selected[c * K + p] = idx;
-      a.cost[c * K + p] = v / (double)a.W;
-    }
-    __syncthreads();
-    const int sel = pick[0];
-    taken = taken || t == sel;
-    for (int k = t; k < S; k += nthr) {
-      if (mu[k] <= 0) continue;
-      const double d = Dr[(size_t)k * ld + sel];
-      if (d < m[k]) {
-        m[k] = d;
-        near[k] = p;
-      }
-    }
-    __syncthreads();                                            // m, near and pick are settled for the next pick
-  }
-  for (int k = t; k < S; k += nthr) a.assign[c * S + k] = near[k];
-  for (int j = t; j < K; j += nthr) {
-    int n = 0;
-    for (int k = 0; k < S; ++k) n += near[k] == j ? mu[k] : 0;
-    a.counts[c * K + j] = n;
-  }
+__global__ __launch_bounds__(1024) void wt_pick_kernel(const FsPickArgs a) {
+  fs_pick<true, IN_LDS>(a);
 }
-
-bool wt_fits_int(long long v) { return v > 0 && v < (1ll << 31); }
 
 bool wt_sizes_ok(long count, int K, int W) { return count > 0 && K > 0 && K <= WT_MAX_K && W >= 1 && W <= WT_MAX_W; }
 
 // the launch shape of the scores at (count, K, H, N); false where the entries answer SG_EINVAL
 bool wt_plan(long count, int K, int H, int N, WtScoreArgs* a) {
-  if (count <= 0 || K <= 0 || H <= 0 || N <= 0 || K > WT_MAX_K || !wt_fits_int(count)) return false;
+  if (count <= 0 || K <= 0 || H <= 0 || N <= 0 || K > WT_MAX_K || !sg_fits_int(count)) return false;
   int C = 4;
   while (C < 64 && C < N) C <<= 1;
   while (C > 4 && (size_t)K * C * 8 > (size_t)WT_TILE_BYTES) C >>= 1;
@@ -627,27 +417,19 @@ bool wt_plan(long count, int K, int H, int N, WtScoreArgs* a) {
   a->tn = sg_ceil_div(N, C);
   a->nt = nt;
   a->pairs = nt * (nt + 1) / 2;
-  if (!wt_fits_int((long long)count * H) || !wt_fits_int((long long)H * N) || !wt_fits_int((long long)K * H * N)) return false;
+  if (!sg_fits_int((long long)count * H) || !sg_fits_int((long long)H * N) || !sg_fits_int((long long)K * H * N)) return false;
   a->rows = (long long)count * H;
   a->count = count;
-  return wt_fits_int(a->rows * a->pairs);
+  return sg_fits_int(a->rows * a->pairs);
 }
-
-size_t wt_pick_lds(int S, int ld, bool in_lds) {
-  // m [S] and the waves' 16 values as doubles; 16 + S + 2 + S ints; the copy of D
-  return ((size_t)S + 16) * 8 + (size_t)(16 + 2 * S + 2) * 4 + (in_lds ? (size_t)S * ld * 8 : 0);
-}
-
-SgDynLds wt_pick_guard;
-
 }  // namespace
 
 extern "C" int stemgnn_weighted_bands(const float* paths, const int* mult, long count, int K, int H, int N, int W, int Q,
                                       const int* ranks, float* bands, void* stream) {
   if (!paths || !mult || !ranks || !bands || paths == bands) return SG_EINVAL;
   if (!wt_sizes_ok(count, K, W) || H <= 0 || N <= 0 || Q < 1 || Q > WT_MAX_Q) return SG_EINVAL;
-  if (!wt_fits_int(count) || !wt_fits_int((long long)H * N) || !wt_fits_int((long long)K * H * N) ||
-      !wt_fits_int((long long)Q * H * N))
+  if (!sg_fits_int(count) || !sg_fits_int((long long)H * N) || !sg_fits_int((long long)K * H * N) ||
+      !sg_fits_int((long long)Q * H * N))
     return SG_EINVAL;
   WtBandArgs a = {};
   for (int q = 0; q < Q; ++q) {
@@ -660,7 +442,7 @@ extern "C" int stemgnn_weighted_bands(const float* paths, const int* mult, long 
   while (C > 8 && (size_t)K * C * 4 > (size_t)WT_TILE_BYTES) C >>= 1;
   a.C = C;
   a.tiles = sg_ceil_div(a.HN, C);
-  if (!wt_fits_int((long long)count * a.tiles)) return SG_EINVAL;
+  if (!sg_fits_int((long long)count * a.tiles)) return SG_EINVAL;
   const size_t lds = ((size_t)K * C + (size_t)Q * C + (size_t)K) * 4;
   const dim3 grid((unsigned)(count * a.tiles));
   const bool vec = N % 4 == 0 && sg_aligned16(paths) && sg_aligned16(bands);
@@ -687,7 +469,7 @@ extern "C" int stemgnn_weighted_scores(const float* target, const float* paths, 
   if ((mul == nullptr) != (add == nullptr)) return SG_EINVAL;
   WtScoreArgs a = {};
   if (!wt_plan(count, K, H, N, &a) || W < 1 || W > WT_MAX_W || (fair && W < 2)) return SG_EINVAL;
-  if (!wt_fits_int((long long)H * ((long long)W + 1))) return SG_EINVAL;
+  if (!sg_fits_int((long long)H * ((long long)W + 1))) return SG_EINVAL;
   a.target = target; a.paths = paths; a.mult = mult; a.mul = mul; a.add = add; a.out = out;
   a.hist = reinterpret_cast<unsigned long long*>(hist);
   a.fair = fair ? 1 : 0;
@@ -718,43 +500,20 @@ extern "C" int stemgnn_weighted_events(const float* paths, const int* mult, cons
                                        int* counts, void* stream) {
   if (!paths || !mult || !thr || !counts) return SG_EINVAL;
   if ((mul == nullptr) != (add == nullptr)) return SG_EINVAL;
-  if (!wt_sizes_ok(count, K, W) || H <= 0 || M <= 0 || H > WT_MAX_H) return SG_EINVAL;
-  if (min_run < 1 || min_run > H || (above != 0 && above != 1)) return SG_EINVAL;
-  if (!wt_fits_int(count) || !wt_fits_int((long long)K * H * M) || !wt_fits_int((2ll * H + 1) * M)) return SG_EINVAL;
-  int C = 1;
-  while (C < 64 && C < M) C <<= 1;
-  while (C > 1 && (size_t)(2 * H + 1) * C * sizeof(int) > (size_t)WT_TILE_BYTES) C >>= 1;
-  WtEventArgs a = {};
+  if (!wt_sizes_ok(count, K, W) || H <= 0 || M <= 0) return SG_EINVAL;
+  EvArgs a = {};
   a.paths = paths; a.mult = mult; a.thr = thr; a.mul = mul; a.add = add; a.counts = counts;
-  a.K = K; a.H = H; a.M = M; a.C = C; a.above = above; a.min_run = min_run; a.W = W;
-  a.tiles = sg_ceil_div(M, C);
-  if (!wt_fits_int((long long)count * a.tiles)) return SG_EINVAL;
-  const size_t lds = ((size_t)(2 * H + 1) * C + (size_t)K) * sizeof(int);
-  hipLaunchKernelGGL(wt_events_kernel, dim3((unsigned)(count * a.tiles)), dim3(WT_THREADS), lds, (hipStream_t)stream, a);
-  SG_TRY(hipGetLastError());
-  return 0;
+  a.S = K; a.H = H; a.M = M; a.above = above; a.min_run = min_run; a.W = W;
+  return ev_launch<true>(a, count, (hipStream_t)stream);
 }
 
 extern "C" int stemgnn_scenario_reduce_weighted(const double* D, const int* mult_in, long count, int S, int K, int W,
                                                 int* selected, int* counts, int* assign, double* cost, void* stream) {
   if (!D || !mult_in || !selected || !counts || !assign || !cost) return SG_EINVAL;
-  if (count <= 0 || S <= 0 || S > WT_MAX_S || K < 1 || K > S || W < 1 || W > WT_MAX_W) return SG_EINVAL;
-  if (!wt_fits_int(count) || !wt_fits_int((long long)count * S * S)) return SG_EINVAL;
-  WtPickArgs a = {};
+  if (count <= 0 || S <= 0 || S > FS_MAX_S || K < 1 || K > S || W < 1 || W > WT_MAX_W) return SG_EINVAL;
+  if (!sg_fits_int(count) || !sg_fits_int((long long)count * S * S)) return SG_EINVAL;
+  FsPickArgs a = {};
   a.D = D; a.mult = mult_in; a.selected = selected; a.counts = counts; a.assign = assign; a.cost = cost;
   a.S = S; a.K = K; a.W = W;
-  a.ld = S | 1;                             // an odd number of doubles: a column read meets every bank pair once
-  const bool in_lds = wt_pick_lds(S, a.ld, true) <= WT_LDS_BYTES;
-  const size_t lds = wt_pick_lds(S, a.ld, in_lds);
-  int threads = (S + 63) & ~63;             // a thread per candidate; at least four waves to bring D in
-  if (threads < WT_THREADS) threads = WT_THREADS;
-  hipStream_t st = (hipStream_t)stream;
-  if (in_lds) {
-    SG_TRY(sg_ensure_dyn_lds((const void*)wt_pick_kernel<true>, lds, wt_pick_guard));
-    hipLaunchKernelGGL(wt_pick_kernel<true>, dim3((unsigned)count), dim3(threads), lds, st, a);
-  } else {
-    hipLaunchKernelGGL(wt_pick_kernel<false>, dim3((unsigned)count), dim3(threads), lds, st, a);
-  }
-  SG_TRY(hipGetLastError());
-  return 0;
+  return fs_launch<wt_pick_kernel<true>, wt_pick_kernel<false>>(a, 2, count, (hipStream_t)stream);
 }

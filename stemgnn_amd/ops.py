@@ -2195,6 +2195,25 @@ def _reduce_batch(what, S, max_scratch_bytes):
     return max(1, min(int(max_scratch_bytes) // (S * S * 8), (2 ** 31 - 1) // (S * S)))
 
 
+def _reduce_distances(what, distances, staged=False):
+    """a caller's distances: a non-empty contiguous float64 [count,S,S] (staged: [count,T,S,S]) -> (count, S) ((count, T, S))"""
+    dims, layout = (4, "[count,T,S,S]") if staged else (3, "[count,S,S]")
+    if not torch.is_tensor(distances) or distances.dim() != dims or distances.shape[-2] != distances.shape[-1] or \
+            distances.numel() == 0:
+        raise _lib.StemGNNHipError(f"{what}: distances must be a non-empty {layout} tensor, got "
+                                   f"{tuple(distances.shape) if torch.is_tensor(distances) else type(distances).__name__}")
+    if distances.dtype != torch.float64 or not distances.is_contiguous():
+        raise _lib.StemGNNHipError(f"{what}: distances must be a contiguous float64 tensor, got {distances.dtype}, strides "
+                                   f"{tuple(distances.stride())}")
+    return tuple(int(v) for v in distances.shape[:-1])
+
+
+def _reduce_outputs(C, S, K, dev):
+    """selected [C,K], counts [C,K], assign [C,S] int32 and cost [C,K] float64, uninitialised on dev"""
+    return (torch.empty(C, K, device=dev, dtype=torch.int32), torch.empty(C, K, device=dev, dtype=torch.int32),
+            torch.empty(C, S, device=dev, dtype=torch.int32), torch.empty(C, K, device=dev, dtype=torch.float64))
+
+
 def scenario_distances(paths, scale=None, squared=False):
     """Pairwise distances of sampled paths (``stemgnn_scenario_distances``; the definition is in include/stemgnn_hip.h):
     paths [count,S,H,M] contiguous float32 on the device (M: nodes, or the groups of scenario_aggregate) ->
@@ -2237,14 +2256,7 @@ def scenario_reduce(paths, keep, scale=None, squared=False, distances=None, max_
         squared = _reduce_flag(what, squared)
         source = paths
     else:
-        if not torch.is_tensor(distances) or distances.dim() != 3 or distances.shape[1] != distances.shape[2] or \
-                distances.numel() == 0:
-            raise _lib.StemGNNHipError(f"{what}: distances must be a non-empty [count,S,S] tensor, got "
-                                       f"{tuple(distances.shape) if torch.is_tensor(distances) else type(distances).__name__}")
-        if distances.dtype != torch.float64 or not distances.is_contiguous():
-            raise _lib.StemGNNHipError(f"{what}: distances must be a contiguous float64 tensor, got {distances.dtype}, strides "
-                                       f"{tuple(distances.stride())}")
-        C, S = int(distances.shape[0]), int(distances.shape[1])
+        C, S = _reduce_distances(what, distances)
         if S > 1024:
             raise _lib.StemGNNHipError(f"{what}: at most 1024 paths, got S = {S}")
         if paths is not None and (not torch.is_tensor(paths) or paths.dim() != 4 or tuple(paths.shape[:2]) != (C, S)):
@@ -2258,10 +2270,7 @@ def scenario_reduce(paths, keep, scale=None, squared=False, distances=None, max_
                                    "stemgnn_amd runs only on a HIP device (no CPU fallback)")
     lib = _lib.load()
     dev = source.device
-    selected = torch.empty(C, K, device=dev, dtype=torch.int32)
-    counts = torch.empty(C, K, device=dev, dtype=torch.int32)
-    assign = torch.empty(C, S, device=dev, dtype=torch.int32)
-    cost = torch.empty(C, K, device=dev, dtype=torch.float64)
+    selected, counts, assign, cost = _reduce_outputs(C, S, K, dev)
     if distances is None:
         scale = _f64_on(scale, dev)
         D = torch.empty(min(batch, C), S, S, device=dev, dtype=torch.float64)
@@ -2397,14 +2406,7 @@ def scenario_reduce_weighted(distances, mult, total, keep):
     origins (-1 / 0 / -1 / NaN): a distance that is not a finite number >= 0, multiplicities that are negative or do not sum
     to total, fewer than `keep` members of positive multiplicity.  All-ones mult and total = S: `scenario_reduce`, bit for bit."""
     what = "scenario_reduce_weighted"
-    if not torch.is_tensor(distances) or distances.dim() != 3 or distances.shape[1] != distances.shape[2] or \
-            distances.numel() == 0:
-        raise _lib.StemGNNHipError(f"{what}: distances must be a non-empty [count,S,S] tensor, got "
-                                   f"{tuple(distances.shape) if torch.is_tensor(distances) else type(distances).__name__}")
-    if distances.dtype != torch.float64 or not distances.is_contiguous():
-        raise _lib.StemGNNHipError(f"{what}: distances must be a contiguous float64 tensor, got {distances.dtype}, strides "
-                                   f"{tuple(distances.stride())}")
-    C, S = int(distances.shape[0]), int(distances.shape[1])
+    C, S = _reduce_distances(what, distances)
     if S > 1024:
         raise _lib.StemGNNHipError(f"{what}: at most 1024 members, got S = {S}")
     if C * S * S >= 2 ** 31:
@@ -2417,11 +2419,7 @@ def scenario_reduce_weighted(distances, mult, total, keep):
     if mult.device != distances.device:
         raise _lib.StemGNNHipError(f"{what}: distances is on {distances.device}, mult on {mult.device}")
     lib = _lib.load()
-    dev = distances.device
-    selected = torch.empty(C, K, device=dev, dtype=torch.int32)
-    counts = torch.empty(C, K, device=dev, dtype=torch.int32)
-    assign = torch.empty(C, S, device=dev, dtype=torch.int32)
-    cost = torch.empty(C, K, device=dev, dtype=torch.float64)
+    selected, counts, assign, cost = _reduce_outputs(C, S, K, distances.device)
     _lib.check(lib.stemgnn_scenario_reduce_weighted(distances.data_ptr(), mult.data_ptr(), C, S, K, W, selected.data_ptr(),
                                                     counts.data_ptr(), assign.data_ptr(), cost.data_ptr(), _stream()), what)
     return selected, counts, assign, cost
@@ -2504,14 +2502,7 @@ def scenario_tree(paths, stages, nodes, scale=None, squared=False, distances=Non
         squared = _reduce_flag(what, squared)
         source = paths
     else:
-        if not torch.is_tensor(distances) or distances.dim() != 4 or distances.shape[2] != distances.shape[3] or \
-                distances.numel() == 0:
-            raise _lib.StemGNNHipError(f"{what}: distances must be a non-empty [count,T,S,S] tensor, got "
-                                       f"{tuple(distances.shape) if torch.is_tensor(distances) else type(distances).__name__}")
-        if distances.dtype != torch.float64 or not distances.is_contiguous():
-            raise _lib.StemGNNHipError(f"{what}: distances must be a contiguous float64 tensor, got {distances.dtype}, strides "
-                                       f"{tuple(distances.stride())}")
-        C, T, S = (int(v) for v in distances.shape[:3])
+        C, T, S = _reduce_distances(what, distances, staged=True)
         if S > 1024 or T > 16:
             raise _lib.StemGNNHipError(f"{what}: at most 1024 paths and 16 stages, got S = {S}, T = {T}")
         if paths is not None and (not torch.is_tensor(paths) or paths.dim() != 4 or tuple(paths.shape[:2]) != (C, S)):

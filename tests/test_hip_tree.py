@@ -126,11 +126,14 @@ def test_stage_distances_on_more_workgroups_than_compute_units():
     print(f"count = 300: worst error / bound {worst:.4f}")
 
 
-@pytest.mark.parametrize("S,H,M", [(33, 5, 13), (8, 2, 200), (65, 3, 64)])
-def test_one_stage_is_the_distance_entry(S, H, M):
-    """T = 1 against ops.scenario_distances within the same bound (and both against the longdouble restatement)"""
+@pytest.mark.parametrize("count,S,H,M", [pytest.param(2, 33, 5, 13, id="33-5-13"), pytest.param(2, 8, 2, 200, id="8-2-200"),
+                                         pytest.param(2, 65, 3, 64, id="65-3-64"), pytest.param(300, 5, 3, 110, id="300-5-3-110")])
+def test_one_stage_is_the_distance_entry(count, S, H, M):
+    """T = 1 against ops.scenario_distances: the same bits (one tile body behind both entries), and both within the bound of the
+    longdouble restatement.  300 origins are more workgroups than compute units: the 256-thread form, six chunks, the four
+    partial sums getting 2, 2, 1, 1; the other cases take the wide form"""
     from stemgnn_amd import ops
-    x = paths_case(np.random.default_rng(SEED + S), 2, S, H, M)
+    x = paths_case(np.random.default_rng(SEED + S), count, S, H, M)
     d_x = torch.from_numpy(x).to(DEV)
     L = H * M
     for squared in (False, True):
@@ -140,7 +143,7 @@ def test_one_stage_is_the_distance_entry(S, H, M):
         other = ops.scenario_distances(d_x, squared=squared).cpu().numpy()
         assert (np.abs(got.astype(np.longdouble) - ref) <= bound).all()
         assert (np.abs(got.astype(np.longdouble) - other.astype(np.longdouble)) <= bound).all()
-        print(f"{(S, H, M)} squared={squared}: the same bits as scenario_distances: {np.array_equal(bits64(got), bits64(other))}")
+        assert np.array_equal(bits64(got), bits64(other))
 
 
 def test_a_nan_reaches_its_row_and_column_from_its_stage_on():
