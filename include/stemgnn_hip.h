@@ -1252,6 +1252,39 @@ int stemgnn_scenario_stage_distances(const float* paths, const double* scale, lo
 int stemgnn_scenario_tree(const double* D, const int* mult_in, long count, int S, int T, const int* nodes, int W, int* node_path,
                           int* node_parent, int* node_count, int* assign, double* cost, void* stream);
 
+/* ---- simultaneous scenario bands: the studentised sup-norm envelope of sampled paths (csrc/envelope.hip, DESIGN.md section
+ * 5v) --------------------------------------------------------------------------------------------------------------------------
+ * paths [count, S, H, C] fp32 and contiguous (C: nodes, or the groups of stemgnn_scenario_aggregate).  mult int32 [count, S]
+ * with common sum `total`, or NULL: all ones (total is then not looked at).  The conventions are those of the weighted sets
+ * above: w_s = mult[c, s], T = total (without mult: w_s = 1, T = S); a member of weight 0 is never read.  Per (origin c, column
+ * n), all in fp64, every sum over s ascending, every product and every sum rounded on its own (no FMA):
+ *   centre   m_h = (sum_s w_s x[s, h]) / T
+ *   scale    s_h = sqrt((sum_s w_s (x[s, h] - m_h)^2) / T): the square rounded, then its product with w_s, then the add; the
+ *            division and the root correctly rounded.      moments[c, 0, h, n] = m_h, moments[c, 1, h, n] = s_h
+ *   depth    d_s = max_h |x[s, h] - m_h| / s_h, a step with s_h == 0 contributing 0;  depth[c, s, n] = d_s, NaN for a member
+ *            of weight 0 (depth may be NULL)
+ *   chosen   with k = the rank of stemgnn_conformal_rank(T, coverage): the smallest d_s whose members j with d_j <= d_s carry
+ *            weight at least k; +inf when k > T.  It is the multiplier that holds `coverage` of the ensemble's own paths.
+ *   q        chosen[c, n] when multiplier is NULL, else multiplier[multiplier_n == 1 ? 0 : n] (fp64, on the device)
+ *   bands    bands[c, 0, h, n] = (float)(m_h - q s_h), bands[c, 1, h, n] = (float)(m_h + q s_h); q = +inf: -inf / +inf
+ *            whatever s_h is
+ *   truth    with target [count, H, C] fp32: truth[c, n] = max_h |y_h - m_h| / s_h; where s_h == 0 the term is 0 if y_h == m_h
+ *            and +inf otherwise.  ignore_nan != 0: NaN steps of the target are skipped, NaN when every step is NaN;
+ *            ignore_nan == 0: NaN when any step is.  The band with multiplier q holds the whole target exactly when
+ *            truth <= q.  target and truth are both given or both NULL.
+ * ABSENT: a column with a non-finite value in a path of positive weight; every column of an origin whose weights are negative
+ * or do not sum to total.  An absent column is NaN in every output; no other column is affected.
+ * One launch, one workgroup per (origin, tile of 32 .. 4 columns); the tile's S * H values are held in LDS where they fit (64 KB
+ * with the depths and moments), so `paths` is read once, else read from memory by every phase; 16-byte loads when C % 4 == 0 and
+ * paths is 16-byte aligned, scalar ones otherwise.  No allocation, no host synchronisation, no memset, no atomics; the same
+ * bits on every run, and an origin's results do not depend on which other origins share the call; capturable.
+ * SG_EINVAL (nothing launched): paths, moments, chosen or bands NULL; one of target / truth without the other; S outside
+ * [1, 1024]; H outside [1, 256]; count or C <= 0; coverage not inside (0, 1) (NaN included); multiplier given with multiplier_n
+ * neither 1 nor C; mult given with total outside [1, 2^24]; count * S * C, count * H * C or S * H * C >= 2^31. */
+int stemgnn_scenario_envelope(const float* paths, const int* mult, int total, const float* target, int ignore_nan,
+                              const double* multiplier, int multiplier_n, int count, int S, int H, int C, double coverage,
+                              double* moments, double* depth, double* chosen, double* truth, float* bands, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

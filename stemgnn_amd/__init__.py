@@ -8,11 +8,13 @@ fallback: calling the model without the HIP library or on a non-GPU tensor raise
 from .base_model import GLU, Model, StockBlockLayer  # noqa: F401
 from .graph import LatentGraph  # noqa: F401
 
-from .math_utils import (EventScores, EventSpec, ScenarioEvents, ScenarioSet, ScenarioTree, group_weights,  # noqa: F401
-                         reduce_scenarios, scenario_tree)
+from .math_utils import (EnvelopeCalibrator, EventScores, EventSpec, PathEnvelope, ScenarioEvents,  # noqa: F401
+                         ScenarioSet, ScenarioTree, group_weights, joint_coverage, reduce_scenarios, scenario_tree,
+                         simultaneous_bands)
 
 __all__ = ["Model", "StockBlockLayer", "GLU", "LatentGraph", "LiveForecaster", "EventSpec", "ScenarioEvents", "EventScores",
-           "group_weights", "ScenarioSet", "reduce_scenarios", "ScenarioTree", "scenario_tree"]
+           "group_weights", "ScenarioSet", "reduce_scenarios", "ScenarioTree", "scenario_tree", "PathEnvelope",
+           "EnvelopeCalibrator", "simultaneous_bands", "joint_coverage"]
 __version__ = "0.1.0"
 
 

@@ -283,6 +283,8 @@ SIGNATURES = {
     "stemgnn_scenario_reduce_weighted": (c_int, [_P, _P, c_long, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "stemgnn_scenario_stage_distances": (c_int, [_P, _P, c_long, c_int, c_int, c_int, c_int, POINTER(c_int), c_int, _P, _P]),
     "stemgnn_scenario_tree": (c_int, [_P, _P, c_long, c_int, c_int, POINTER(c_int), c_int, _P, _P, _P, _P, _P, _P]),
+    "stemgnn_scenario_envelope": (c_int, [_P, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_double, _P, _P, _P,
+                                          _P, _P, _P]),
     "stemgnn_infer_workspace_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
     "stemgnn_infer_workspace_split_floats": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "stemgnn_gru_fwd_infer": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),

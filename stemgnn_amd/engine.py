@@ -1324,6 +1324,19 @@ class LiveForecaster:
         _, steps = self.scenarios(paths=paths, horizon=horizon, seed=seed, coupling=coupling, tails=tails, return_paths=True)
         return scenario_tree(steps[None], stages, nodes, on=on, scale=scale, squared=squared)
 
+    def envelope(self, coverage=0.9, paths=64, horizon=None, seed=None, coupling="independent", tails="linear", on=None,
+                 calibrator=None):
+        """The simultaneous band for the steps ahead of the last row pushed -- the one whose WHOLE trajectory, not each step on
+        its own, is covered: `scenarios(..., return_paths=True)` from the ring's head window, then
+        `math_utils.simultaneous_bands` on its paths.  Returns a math_utils.PathEnvelope with count = 1 (bands
+        [1,2,horizon,N], center, scale, chosen: device tensors in normalised units, no sync; no truth: nothing has happened
+        yet).  coverage / on / calibrator are simultaneous_bands' (on: an EventSpec with groups=, or a [1,S,horizon,R] tensor;
+        calibrator: a fitted math_utils.EnvelopeCalibrator, whose multiplier replaces the ensemble's own); the other arguments
+        are scenarios'; the captured graph, the history slab and every calibrator are left untouched."""
+        from .math_utils import simultaneous_bands
+        _, steps = self.scenarios(paths=paths, horizon=horizon, seed=seed, coupling=coupling, tails=tails, return_paths=True)
+        return simultaneous_bands(steps[None], coverage, on=on, calibrator=calibrator)
+
     # -- matured pairs ------------------------------------------------------------------------------------------
     def matured(self):
         """(forecasts [m,(Q,)horizon,N], targets [m,horizon,N], origins int64 [m] ascending) of the stored forecasts whose targets

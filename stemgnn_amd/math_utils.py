@@ -404,6 +404,8 @@ class ScenarioSet:
       tree(stages, nodes, on=None, scale=None, squared=False) -> the ScenarioTree of the set's K members with the counts as
                     input probabilities (`scenario_tree`'s arguments): merge(chunks).tree(..) builds a
                     tree from an ensemble too large to hold; its S is this set's K, its total this set's
+      envelope(coverage=0.9, on=None, target=None, calibrator=None, ignore_nan=False, return_depth=False) ->
+                    `simultaneous_bands` of the set: the PathEnvelope of the kept paths with their counts as weights
       from_weights(paths, weights, total=65536)  (static, pure torch) user-supplied probabilities rounded to multiplicities
                     that sum to total by largest remainders (the lower index first among equal remainders); a row that is
                     negative, non-finite or all zero becomes an absent origin"""
@@ -439,6 +441,10 @@ class ScenarioSet:
         if not isinstance(spec, EventSpec):
             raise ValueError(f"ScenarioSet.events: spec must be an EventSpec, got {type(spec).__name__}")
         return spec.count(self)
+
+    def envelope(self, coverage=0.9, on=None, target=None, calibrator=None, ignore_nan=False, return_depth=False):
+        return simultaneous_bands(self, coverage, on=on, target=target, calibrator=calibrator, ignore_nan=ignore_nan,
+                                  return_depth=return_depth)
 
     def reduce(self, keep, on=None, scale=None, squared=False):
         if isinstance(on, EventSpec):
@@ -756,6 +762,188 @@ def scenario_tree(paths, stages, nodes, on=None, scale=None, squared=False):
                                ops._tree_nodes("scenario_tree", nodes, len(tuple(stages)), int(paths.shape[1])), out,
                                int(paths.shape[1]))
 
+
+class PathEnvelope:
+    """A simultaneous band of sampled paths: the result of `simultaneous_bands` (`ops.scenario_envelope`).
+    Where every other band of the library covers the target step by step, this one is sized so that the WHOLE trajectory of a
+    column stays inside it.  Device tensors, no sync:
+      bands      float32 [count, 2, H, C]  lower and upper: center -+ multiplier * scale
+      center     float64 [count, H, C]     the paths' (weighted) mean per step      scale  float64 [count, H, C] their deviation
+      chosen     float64 [count, C]        the multiplier that holds `coverage` of the ensemble's own whole paths
+      multiplier float64                   the one in use: `chosen`, or a calibrator's [1] or [C]
+      truth      float64 [count, C]        the target's depth max_h |y - center| / scale, or None without a target
+      depth      float64 [count, S, C]     every path's depth, on request, else None
+      inside     bool [count, C]           truth <= multiplier: the band holds the whole target; False where absent (NaN)
+    joint_coverage() -> (overall, per column [C]) over the pairs with a truth, one sync;  width() -> float64 [H] on the
+    device, the mean upper - lower per step;  cat(parts) joins batches along the origins."""
+
+    def __init__(self, bands, moments, chosen, multiplier, truth=None, depth=None, coverage=None):
+        if bands.dim() != 4 or bands.shape[1] != 2 or moments.shape != bands.shape or \
+                tuple(chosen.shape) != (bands.shape[0], bands.shape[3]):
+            raise ValueError(f"PathEnvelope: bands and moments must be [count, 2, H, C] with chosen [count, C], got "
+                             f"{tuple(bands.shape)}, {tuple(moments.shape)}, {tuple(chosen.shape)}")
+        self.bands, self.moments, self.chosen, self.multiplier = bands, moments, chosen, multiplier
+        self.truth, self.depth, self.coverage = truth, depth, coverage
+        self.count, self.H, self.C = int(bands.shape[0]), int(bands.shape[2]), int(bands.shape[3])
+
+    @property
+    def center(self):
+        return self.moments[:, 0]
+
+    @property
+    def scale(self):
+        return self.moments[:, 1]
+
+    @property
+    def inside(self):
+        if self.truth is None:
+            raise ValueError("PathEnvelope.inside: the envelope was made without a target")
+        return self.truth <= self.multiplier
+
+    def joint_coverage(self):
+        inside = self.inside
+        valid = ~torch.isnan(self.truth)
+        hit = (inside & valid).sum(dim=0).double()
+        n = valid.sum(dim=0).double()
+        both = torch.stack([hit, n]).cpu().numpy()                               # the one sync
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return float(both[0].sum() / both[1].sum()), both[0] / both[1]
+
+    def width(self):
+        w = self.bands[:, 1].double() - self.bands[:, 0].double()
+        return torch.nanmean(w.transpose(0, 1).reshape(self.H, -1), dim=1)
+
+    @staticmethod
+    def cat(parts):
+        parts = list(parts)
+        if not parts or any(not isinstance(p, PathEnvelope) or (p.H, p.C) != (parts[0].H, parts[0].C) for p in parts):
+            raise ValueError("PathEnvelope.cat: the parts must be PathEnvelopes that share H and C")
+        first = parts[0]
+        if any((p.truth is None) != (first.truth is None) or (p.depth is None) != (first.depth is None) or
+               p.multiplier.dim() != first.multiplier.dim() for p in parts):
+            raise ValueError("PathEnvelope.cat: the parts must all have, or all lack, truth, depth and a calibrator's multiplier")
+        if first.depth is not None and any(p.depth.shape[1] != first.depth.shape[1] for p in parts):
+            raise ValueError("PathEnvelope.cat: the parts must share S")
+
+        def join(name):
+            return None if getattr(first, name) is None else torch.cat([getattr(p, name) for p in parts])
+
+        multiplier = join("multiplier") if first.multiplier.dim() == 2 else first.multiplier
+        return PathEnvelope(join("bands"), join("moments"), join("chosen"), multiplier, join("truth"), join("depth"),
+                            first.coverage)
+
+
+class EnvelopeCalibrator:
+    """Split-conformal calibration of the simultaneous band's multiplier: what gives "the whole trajectory stays inside with
+    probability `coverage`" its guarantee (the ensemble's own multiplier only holds that share of its own paths).
+    fit(envelope_or_truth, ignore_nan=True): the held-out truth depths (a PathEnvelope made with target=, or its `truth`
+    [count, C]), pooled or, with per_column, column by column; the multiplier is the k-th smallest of the m depths that are not
+    NaN, k = ceil((m + 1) coverage (1 - 1e-12)), +inf when k > m.  ignore_nan=False: a NaN depth makes its group's multiplier
+    NaN.  torch.sort on the tensor's own device, no sync.  multiplier: float64 [1] or [C]; counts: int64, the m of every group.
+    Passed as calibrator= to simultaneous_bands (ScenarioSet.envelope, trainer.scenario_envelopes, LiveForecaster.envelope),
+    its multiplier replaces the ensemble's own.  On exchangeable fresh origins the band then holds the whole trajectory with
+    probability at least `coverage`."""
+
+    def __init__(self, coverage=0.9, per_column=False):
+        if isinstance(coverage, bool) or not isinstance(coverage, (int, float, np.floating)) or not 0.0 < float(coverage) < 1.0:
+            raise ValueError(f"EnvelopeCalibrator: coverage must be a number inside (0, 1), got {coverage!r}")
+        self.coverage, self.per_column = float(coverage), bool(per_column)
+        self.multiplier = self.counts = None
+
+    def fit(self, envelope_or_truth, ignore_nan=True):
+        truth = envelope_or_truth.truth if isinstance(envelope_or_truth, PathEnvelope) else envelope_or_truth
+        if not torch.is_tensor(truth) or truth.dim() != 2:
+            raise ValueError("EnvelopeCalibrator.fit: a PathEnvelope made with target=, or its truth [count, C], is needed, got "
+                             f"{tuple(truth.shape) if torch.is_tensor(truth) else type(truth).__name__}")
+        d = truth.detach().double()
+        d = d.transpose(0, 1) if self.per_column else d.reshape(1, -1)           # [groups, n]
+        nan = torch.isnan(d)
+        m = (~nan).sum(dim=1)
+        n = d.shape[1]
+        if n == 0:
+            q = torch.full((d.shape[0],), float("inf"), dtype=torch.float64, device=d.device)
+        else:
+            ordered = torch.sort(d, dim=1).values                                # NaN last
+            k = torch.ceil(((m + 1).double() * self.coverage) * (1.0 - 1e-12)).clamp(min=1.0).long()
+            q = torch.gather(ordered, 1, (k - 1).clamp(max=n - 1)[:, None])[:, 0]
+            q = torch.where(k > m, torch.full_like(q, float("inf")), q)
+            if not ignore_nan:
+                q = torch.where(nan.any(dim=1), torch.full_like(q, float("nan")), q)
+        self.multiplier, self.counts = q.contiguous(), m
+        return self
+
+    def state_dict(self):
+        return dict(coverage=self.coverage, per_column=self.per_column, multiplier=self.multiplier, counts=self.counts)
+
+    def load_state_dict(self, state, device=None):
+        if float(state["coverage"]) != self.coverage or bool(state["per_column"]) != self.per_column:
+            raise ValueError(f"EnvelopeCalibrator.load_state_dict: saved for coverage {state['coverage']}, "
+                             f"per_column={state['per_column']}; this one has {self.coverage}, {self.per_column}")
+        multiplier, counts = state["multiplier"], state["counts"]
+        if multiplier is not None:
+            if multiplier.dim() != 1 or counts.shape != multiplier.shape or (not self.per_column and multiplier.shape[0] != 1):
+                raise ValueError(f"EnvelopeCalibrator.load_state_dict: multiplier {tuple(multiplier.shape)} / counts "
+                                 f"{tuple(counts.shape)} do not fit per_column={self.per_column}")
+            if device is not None:
+                multiplier, counts = multiplier.to(device), counts.to(device)
+            multiplier, counts = multiplier.double().contiguous(), counts.long().contiguous()
+        self.multiplier, self.counts = multiplier, counts
+        return self
+
+    @classmethod
+    def from_state_dict(cls, state, device=None):
+        return cls(state["coverage"], state["per_column"]).load_state_dict(state, device)
+
+
+def simultaneous_bands(paths, coverage=0.9, on=None, target=None, calibrator=None, ignore_nan=False, return_depth=False):
+    """The band that holds whole trajectories (`ops.scenario_envelope`): per origin and column, the
+    paths' mean and deviation per step and ONE multiplier for all steps, center -+ multiplier * scale.  Returns a PathEnvelope.
+    paths: [count, S, H, N] float32 on the device (rolling_scenarios(..., return_paths=True)), or a ScenarioSet, whose kept
+    paths enter with their counts as weights.  coverage: the share of the ensemble's own whole paths the band holds (`chosen`).
+    target [count, H, N]: what happened; the envelope's `truth` and `inside` say whether the band held it, and `truth` is what
+    EnvelopeCalibrator.fit takes.  calibrator (a fitted EnvelopeCalibrator): its multiplier is used instead of the ensemble's.
+    on: an EventSpec with groups=, whose aggregate of the paths AND of the target the band is made for (corridor means), or a
+    [count, S, H, R] tensor standing for the paths (the target is then [count, H, R])."""
+    mult = total = None
+    if isinstance(paths, ScenarioSet):
+        mult, total, paths = paths.counts, paths.total, paths.paths
+    paths = _as_f32(paths)
+    if paths.dim() != 4:
+        raise ops._lib.StemGNNHipError(f"simultaneous_bands: paths must be [count,S,H,N], got {tuple(paths.shape)}")
+    if target is not None:
+        target = _as_f32(target, like=paths)
+        if isinstance(on, EventSpec) and on.groups is not None:
+            target = on.aggregate(target)
+    on = _on_paths("simultaneous_bands", paths, on).contiguous()
+    multiplier = None
+    if calibrator is not None:
+        if not isinstance(calibrator, EnvelopeCalibrator) or calibrator.multiplier is None:
+            raise ValueError("simultaneous_bands: calibrator= takes a fitted EnvelopeCalibrator")
+        if calibrator.per_column and calibrator.multiplier.shape[0] != on.shape[3]:
+            raise ValueError(f"simultaneous_bands: the calibrator was fitted per column on {calibrator.multiplier.shape[0]} "
+                             f"columns, the paths have {on.shape[3]}")
+        multiplier = calibrator.multiplier
+    out = ops.scenario_envelope(on, coverage, None if target is None else target.contiguous(), mult, total, multiplier,
+                                ignore_nan, return_depth)
+    in_use = out["chosen"] if multiplier is None else multiplier.to(device=on.device, dtype=torch.float64)
+    return PathEnvelope(out["bands"], out["moments"], out["chosen"], in_use, out["truth"], out["depth"], float(coverage))
+
+
+def joint_coverage(y, lo, hi, ignore_nan=False):
+    """The share of (origin, column) pairs whose whole trajectory y [count, H, N] lies inside the band lo .. hi (both
+    [count, H, N]): what any band, pointwise ones included, is worth to a plan that assumes all steps hold at once.  A torch
+    composition; returns a float (one sync).  ignore_nan: NaN steps of y are skipped and a pair without a step is left out;
+    otherwise a NaN step counts as outside."""
+    y = y.double()
+    held = (y >= lo.double()) & (y <= hi.double())
+    if ignore_nan:
+        missing = torch.isnan(y)
+        held, valid = (held | missing).all(dim=1), ~missing.all(dim=1)
+    else:
+        held = held.all(dim=1)
+        valid = torch.ones_like(held)
+    both = torch.stack([(held & valid).sum(), valid.sum()]).cpu()
+    return float(both[0]) / float(both[1]) if int(both[1]) else float("nan")
 
 
 class GaussianCopula:

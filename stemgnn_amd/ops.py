@@ -2425,6 +2425,81 @@ def scenario_reduce_weighted(distances, mult, total, keep):
     return selected, counts, assign, cost
 
 
+def _envelope_coverage(what, coverage):
+    if isinstance(coverage, bool) or not isinstance(coverage, (int, float, np.floating)) or not 0.0 < float(coverage) < 1.0:
+        raise _lib.StemGNNHipError(f"{what}: coverage must be a number inside (0, 1), got {coverage!r}")
+    return float(coverage)
+
+
+def scenario_envelope(paths, coverage, target=None, mult=None, total=None, multiplier=None, ignore_nan=False,
+                      return_depth=False):
+    """The simultaneous band of sampled paths (``stemgnn_scenario_envelope``; the definition is in include/stemgnn_hip.h): per
+    (origin, column) a centre and a scale per step from the S paths, every path's depth max_h |x - centre| / scale, the
+    multiplier `chosen` that holds `coverage` of the ensemble's own whole paths, and the band centre -+ q * scale with
+    q = chosen, or q = `multiplier` (a scalar or C values, fp64: an EnvelopeCalibrator's) when one is given.
+    paths [count,S,H,C] contiguous float32 on the device; mult int32 [count,S] with common sum `total`: a weighted set's
+    multiplicities; target [count,H,C] float32: what happened, whose depth `truth` the band with multiplier q holds exactly when
+    truth <= q (ignore_nan: NaN steps are skipped).  Returns a dict of device tensors, no sync:
+      bands float32 [count,2,H,C], moments float64 [count,2,H,C] (centre, scale), chosen float64 [count,C],
+      truth float64 [count,C] or None, depth float64 [count,S,C] or None (return_depth).
+    A column with a non-finite path value, and every column of an origin whose multiplicities are negative or do not sum to
+    total, is NaN everywhere.  S <= 1024, H <= 256.  One launch."""
+    what = "scenario_envelope"
+    if not torch.is_tensor(paths) or paths.dim() != 4 or paths.numel() == 0:
+        raise _lib.StemGNNHipError(f"{what}: paths must be a non-empty [count,S,H,C] tensor, got "
+                                   f"{tuple(paths.shape) if torch.is_tensor(paths) else type(paths).__name__}")
+    if paths.dtype != torch.float32 or not paths.is_contiguous():
+        raise _lib.StemGNNHipError(f"{what}: paths must be a contiguous float32 tensor, got {paths.dtype}, strides "
+                                   f"{tuple(paths.stride())}")
+    count, S, H, C = (int(v) for v in paths.shape)
+    if S > 1024 or H > 256:
+        raise _lib.StemGNNHipError(f"{what}: at most 1024 paths of at most 256 steps, got S = {S}, H = {H}")
+    if max(count * S * C, count * H * C, S * H * C) >= 2 ** 31:
+        raise _lib.StemGNNHipError(f"{what}: {count} origins of {S} paths of {H} x {C} values do not fit the entry's range "
+                                   "(2^31); walk the origins in batches")
+    coverage = _envelope_coverage(what, coverage)
+    if (mult is None) != (total is None):
+        raise _lib.StemGNNHipError(f"{what}: mult and total go together")
+    W = 0 if mult is None else _weighted_mult(what, mult, total, count, S)
+    if mult is not None and mult.device != paths.device:
+        raise _lib.StemGNNHipError(f"{what}: paths is on {paths.device}, mult on {mult.device}")
+    if target is not None and (not torch.is_tensor(target) or tuple(target.shape) != (count, H, C) or
+                               target.dtype != torch.float32 or not target.is_contiguous()):
+        raise _lib.StemGNNHipError(
+            f"{what}: target must be a contiguous float32 [count,H,C] = {(count, H, C)} tensor, got "
+            f"{(str(target.dtype) + ' ' + str(tuple(target.shape))) if torch.is_tensor(target) else type(target).__name__}")
+    if multiplier is not None:
+        multiplier = multiplier.detach() if torch.is_tensor(multiplier) else \
+            torch.as_tensor(np.asarray(multiplier, dtype=np.float64))
+        if multiplier.dim() == 0:
+            multiplier = multiplier.reshape(1)
+        if multiplier.dim() != 1 or multiplier.shape[0] not in (1, C) or multiplier.is_complex():
+            raise _lib.StemGNNHipError(f"{what}: multiplier must be a scalar, [1] or [{C}] (one per column), got shape "
+                                       f"{tuple(multiplier.shape)}")
+    _require_gpu(paths, "paths")
+    if target is not None:
+        _require_gpu(target, "target")
+        if target.device != paths.device:
+            raise _lib.StemGNNHipError(f"{what}: target is on {target.device}, paths on {paths.device}")
+    lib = _lib.load()
+    dev = paths.device
+    multiplier = _f64_on(multiplier, dev)
+    f64 = dict(device=dev, dtype=torch.float64)
+    moments, chosen = torch.empty(count, 2, H, C, **f64), torch.empty(count, C, **f64)
+    truth = None if target is None else torch.empty(count, C, **f64)
+    depth = torch.empty(count, S, C, **f64) if return_depth else None
+    bands = torch.empty(count, 2, H, C, device=dev, dtype=torch.float32)
+
+    def ptr(v):
+        return None if v is None else v.data_ptr()
+
+    _lib.check(lib.stemgnn_scenario_envelope(paths.data_ptr(), ptr(mult), W, ptr(target), int(bool(ignore_nan)), ptr(multiplier),
+                                             0 if multiplier is None else int(multiplier.shape[0]), count, S, H, C, coverage,
+                                             moments.data_ptr(), ptr(depth), chosen.data_ptr(), ptr(truth), bands.data_ptr(),
+                                             _stream()), what)
+    return dict(bands=bands, moments=moments, chosen=chosen, truth=truth, depth=depth)
+
+
 def _tree_stages(what, stages, H):
     """stage bounds 0 < b_1 < .. < b_T = H (T <= 16) -> a tuple of ints"""
     try:

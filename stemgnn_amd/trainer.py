@@ -28,8 +28,8 @@ from . import ops
 from .base_model import Model, check_quantiles, point_index
 from .engine import ForecastStep, QuantileForecastStep, TrainStep, scenario_rounds
 from .forecast_dataloader import ForecastDataset, WindowLoader, denorm_coefficients, mark_missing
-from .math_utils import (ConformalCalibrator, EnsembleScores, EventSpec, QuantileScores, ScenarioEvents, ScenarioSet,
-                         ScenarioTree, Scores, reduce_scenarios, scenario_tree)
+from .math_utils import (ConformalCalibrator, EnsembleScores, EnvelopeCalibrator, EventSpec, PathEnvelope, QuantileScores,
+                         ScenarioEvents, ScenarioSet, ScenarioTree, Scores, reduce_scenarios, scenario_tree, simultaneous_bands)
 from .optim import FusedAdam, FusedRMSprop
 
 BEST = "_stemgnn.pt"
@@ -215,6 +215,28 @@ def scenario_trees(model, loader, horizon, stages, nodes, paths=64, seed=0, adja
     return torch.cat(bands), torch.cat(targets), ScenarioTree.cat(trees)
 
 
+def scenario_envelopes(model, loader, horizon, coverage=0.9, paths=64, seed=0, adjacency=None, coupling="independent",
+                       tails="linear", origin=0, on=None, calibrator=None, ignore_nan=False):
+    """rolling_scenarios handing on the simultaneous band of every window instead of its `paths` trajectories: every loader
+    batch's paths are enveloped against that batch's target as they are produced (math_utils.simultaneous_bands: a centre and a
+    scale per step and one multiplier, so that the WHOLE trajectory stays inside), then dropped.  The arguments up to `origin`
+    are rolling_scenarios'; coverage / on / calibrator / ignore_nan are simultaneous_bands' (on: an EventSpec with groups=,
+    whose aggregate of every batch's paths and target the band is made for).
+    Returns (bands, target, math_utils.PathEnvelope): the bands and the target are rolling_scenarios' own, and the envelope is
+    `simultaneous_bands(paths, coverage, target=target, ...)` of rolling_scenarios(..., return_paths=True)'s paths, bit for
+    bit, however the loader batches the windows.  Its `truth` from a held-out pass is what EnvelopeCalibrator.fit takes."""
+    _check_scenarios("scenario_envelopes", model, horizon, paths)
+    if on is not None and not isinstance(on, EventSpec):
+        raise ValueError("scenario_envelopes: on= is an EventSpec with groups= (the aggregate of every batch's paths); a tensor "
+                         "goes to math_utils.simultaneous_bands with the paths it belongs to")
+    bands, targets, envelopes = [], [], []
+    for b, target, p in _scenario_batches(model, loader, horizon, paths, seed, adjacency, coupling, tails, origin):
+        bands.append(b)
+        targets.append(target)
+        envelopes.append(simultaneous_bands(p, coverage, on=on, target=target, calibrator=calibrator, ignore_nan=ignore_nan))
+    return torch.cat(bands), torch.cat(targets), PathEnvelope.cat(envelopes)
+
+
 def rolling_forecast_graph(model, dataset, horizon, batch_size, adjacency=None):
     """rolling_forecast(model, WindowLoader(dataset, batch_size), horizon) on engine.ForecastStep: each full batch is one
     hipGraph replay of window gather -> Model.predict -> roll_window rounds -> result slabs; the ragged last batch runs
@@ -254,7 +276,7 @@ def rolling_quantile_forecast_graph(model, dataset, horizon, batch_size, adjacen
 
 
 def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=None, ignore_nan=False, quantiles=None,
-                   calibrator=None, origin=None, paths=None, fair=False, events=None):
+                   calibrator=None, origin=None, paths=None, fair=False, envelope=None, events=None):
     """Metrics of a rolling forecast in raw units (and normalised units under ``*_norm``).  With `dump_dir`, the first
     forecast step of every window is written as CSV (target / predict / absolute error / absolute percentage error).
     ignore_nan: NaN targets (missing readings) are left out of every metric; the CSV files keep them as NaN.
@@ -276,9 +298,19 @@ def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=
     (math_utils.EventScores; the spec's own threshold, groups and mul / add): ``event_brier``, ``event_brier_skill``,
     ``event_base_rate`` and ``event_reliability`` [M, S + 1, 2] for "the event at some step", the same under ``*_run`` for "at
     least min_run steps in a row" and under ``*_step`` ([horizon], the table [horizon, M, S + 1, 2]) for every single step;
-    ignore_nan leaves the (origin, column) pairs with a missing target out.  Without events= the keys are what they were."""
+    ignore_nan leaves the (origin, column) pairs with a missing target out.  Without events= the keys are what they were.
+    envelope (a coverage inside (0, 1), or a fitted math_utils.EnvelopeCalibrator; needs paths= and a quantile forecast): the
+    simultaneous band of the paths (math_utils.simultaneous_bands) is verified against the target: ``joint_coverage``, the share
+    of (window, node) pairs whose whole trajectory the band holds; ``joint_coverage_pointwise``, the same share for the outer
+    pair of the forecast's own (calibrated) bands; ``envelope_width`` [horizon], the band's mean width per step in raw units.
+    Both shares are taken over the same pairs, those with a truth depth: a pair with a NaN target step is left out of both
+    (with ignore_nan only its NaN steps are, and a pair without any step), and so is an absent column of the envelope.
+    Without envelope= the keys are what they were."""
     if events is not None and paths is None:
         raise ValueError("score_forecast: events= goes with paths= (the sampled trajectories the odds are read from)")
+    if envelope is not None and (paths is None or forecast.dim() != 4):
+        raise ValueError("score_forecast: envelope= goes with paths= (the sampled trajectories the band is made from) and a "
+                         "[count, Q, horizon, N] forecast")
     seasonal = getattr(calibrator, "kind", None) == "seasonal"
     if seasonal and origin is None:
         raise ValueError("score_forecast: a seasonal calibrator needs origin= (the time index of every window's first target)")
@@ -304,6 +336,7 @@ def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=
         calibration = dict(pinball=float(qs.pinball.mean()), pinball_q=qs.pinball, coverage_q=qs.coverage,
                            interval_coverage=qs.interval_coverage, interval_width=qs.interval_width,
                            interval_nominal=qs.interval_nominal, crossing=float(qs.crossing), **raw_bands)
+        outer = (forecast[:, 0], forecast[:, -1])
         forecast = point_row if calibrator is not None else forecast[:, point_index(quantiles)].contiguous()
     elif quantiles is not None:
         raise ValueError("score_forecast: quantiles= goes with a [count, Q, horizon, N] forecast")
@@ -334,6 +367,20 @@ def score_forecast(forecast, target, norm_method=None, statistic=None, dump_dir=
             out["event_brier_skill" + suffix] = getattr(sc, "skill" + suffix)
             out["event_base_rate" + suffix] = getattr(sc, "base_rate" + suffix)
             out["event_reliability" + suffix] = getattr(sc, "reliability" + suffix)
+    if envelope is not None:
+        fitted = envelope if isinstance(envelope, EnvelopeCalibrator) else None
+        env = simultaneous_bands(paths, fitted.coverage if fitted is not None else envelope, target=target, calibrator=fitted,
+                                 ignore_nan=ignore_nan)
+        width = env.bands[:, 1].double() - env.bands[:, 0].double()
+        if mul is not None:
+            width = width * mul
+        y = target.double()                                  # the pointwise band over the pairs the envelope is judged on
+        judged = ~torch.isnan(env.truth)
+        held = (((y >= outer[0].double()) & (y <= outer[1].double())) | torch.isnan(y)).all(dim=1) & judged
+        both = torch.stack([held.sum(), judged.sum()]).cpu()
+        out.update(joint_coverage=env.joint_coverage()[0],
+                   joint_coverage_pointwise=float(both[0]) / float(both[1]) if int(both[1]) else float("nan"),
+                   envelope_width=torch.nanmean(width.transpose(0, 1).reshape(width.shape[1], -1), dim=1).cpu().numpy())
     if dump_dir is not None:
         d = pathlib.Path(dump_dir)
         d.mkdir(parents=True, exist_ok=True)
