@@ -963,6 +963,58 @@ enum { SG_SERVING_PLAN_WORDS = 22 };
 int stemgnn_serving_plan(int entry, long a0, long a1, long a2, long a3, long a4, long a5, int misaligned,
                          int* out /* [SG_SERVING_PLAN_WORDS] */);
 
+/* stemgnn_calibration_plan: how the batch side of the conformal family launches for a shape -- stemgnn_conformal_fit / _apply,
+ * stemgnn_seasonal_fit / _apply and the column kernel behind stemgnn_quantile_finish / _store, stemgnn_seasonal_apply with
+ * rearrange and stemgnn_quantile_store_seasonal -- host only: it launches nothing and reads no buffer.  The launchers take their
+ * geometry from the static functions this entry calls (csrc/calibration_plan.h) with the compute-unit count this entry reports,
+ * so what it reports is what runs; tests use it to prove which forms, tiles, chunks, trips, thread counts and column blocks their
+ * cases reach (tests/test_calibration_cases.py).  `entry` is one of SG_CALIBRATION_*, `shape` its nshape values in HOST memory
+ * (nshape must be the entry's own number); `misaligned` has one bit per buffer whose address decides a form, set = NOT 16-byte
+ * aligned:
+ *   SG_CALIBRATION_FIT            (count, H, N, P, per_step, per_node), no bits
+ *   SG_CALIBRATION_SEASONAL_FIT   (count, H, N, P, per_step, per_node, period, K, has_origins), no bits; has_origins != 0: the
+ *                                 origins are a tensor, not origin0 + i
+ *   SG_CALIBRATION_APPLY          (count, Q, H, N), bit 0 forecast, bit 1 out
+ *   SG_CALIBRATION_SEASONAL_APPLY (count, Q, H, N), the same bits; rearrange == 0 (with rearrange: SG_CALIBRATION_COLUMN)
+ *   SG_CALIBRATION_COLUMN         (count or B, Q, H, N, rearrange, store), bit 0 src (forecast / steps), bit 1 dst (out /
+ *                                 out_forecast) and, store != 0 only, bit 2 target, bit 3 out_target.
+ * out = SG_CALIBRATION_PLAN_WORDS ints, 0 where a word does not apply:
+ *   [0] form: 0 = columns (and the applies, the column kernel), 1 = stream   [1] [2] [3] the grid of the first launch (the fit:
+ *   of a histogram launch)   [4] its threads per workgroup   [5] VEC: 4 = 16-byte accesses, 1 = scalar, 0 = no choice
+ *   [6] the compute units the caps below were worked out with (stemgnn_num_cus())
+ *   fit, seasonal fit:
+ *     [7] KP, the tables (P, or K * P)   [8] groups of a table   [9] Cc [10] Hr [11] L [12] G (the grouping: columns and rows per
+ *     window of the column form, run length and runs of the stream form)
+ *     [13] column tiles   [14] columns of the last tile   [15] [16] rows a wave covers per trip (rpw = 64 / width) on the first
+ *     and on the last tile   [17] columns of a full tile   ([13] .. [17]: column form)
+ *     [18] chunks chosen   [19] rows (stream: elements) per chunk   [20] what set [18]: 0 = the blocks wanted ([22]), 1 = the
+ *     rows / elements ([23]), 2 = the 65535 of grid.y; the first of them in this order that gives the minimum
+ *     [21] trips of the first row lane of the first tile (stream: of thread 0) through chunk 0
+ *     [22] ceil([24] / (tiles * KP)) (stream: / (KP * groups))   [23] ceil([27] / 64) (stream: / 1024)
+ *     [24] histogram workgroups aimed at: 4 per compute unit   [25] workgroups of the pick launch, a wave per (table, group)
+ *     [26] waves of the last pick workgroup that have none   [27] the rows (stream: elements) [23] divides: count * Hr
+ *     (count * L), or with DIRECT the virtual rows of the longest bucket in place of count
+ *     [28] seasonal: 1 = DIRECT (a bucket's rows are enumerated), 0 = skipping   [29] why: 0 = DIRECT, 1 = an origins tensor,
+ *     2 = K == 1, 3 = 2 * walk > count; -1 without a season   [30] runs = count / period + 2   [31] walk = runs * ceil(period / K)
+ *   apply, seasonal apply:
+ *     [7] workgroups that give every item a thread (seasonal: every (window, step) segment a wave) of its own
+ *     [8] the cap, 8 per compute unit   [9] 1 = the cap set the grid   [10] trips of thread 0 over the items (seasonal: of wave 0
+ *     over the segments)   [11] seasonal: trips of lane 0 over a segment's items   [12] seasonal: those items, Q * N / VEC
+ *   column kernel ([4] = T):
+ *     [7] LDS bytes   [8] planes (2 with rearrange)   [9] cpb [10] wpb: a workgroup holds wpb windows of cpb column groups
+ *     [11] threads with neither, T - cpb * wpb   [12] column blocks   [13] columns of the last column block
+ *     [14] window blocks   [15] 1 = their cap (16 per compute unit / [12]) set [14]   [16] trips of a workgroup's first window
+ *     lane over the windows   [17] store: 4 = the target is copied by float4, 1 = by scalar; 0 = not a store
+ *     [18] store: trips of target workgroup 0 over the batch's windows   [19] column groups (of VEC columns) per window.
+ * SG_EINVAL for an unknown entry, out == NULL, shape == NULL, an nshape that is not the entry's, a negative value, a bit that
+ * names no buffer of the entry, or a shape the entry itself refuses (its checks on the sizes given here, not on pointers, pairs,
+ * coverages, phase or capacity; the column kernel: those of stemgnn_quantile_finish without offsets). */
+enum { SG_CALIBRATION_FIT = 0, SG_CALIBRATION_SEASONAL_FIT = 1, SG_CALIBRATION_APPLY = 2, SG_CALIBRATION_SEASONAL_APPLY = 3,
+       SG_CALIBRATION_COLUMN = 4 };
+enum { SG_CALIBRATION_PLAN_WORDS = 32 };
+int stemgnn_calibration_plan(int entry, const long* shape, int nshape, int misaligned,
+                             int* out /* [SG_CALIBRATION_PLAN_WORDS] */);
+
 /* ---- scenario forecasts: sampled rolling paths and their order statistics (csrc/scenario.hip) --------
  * roll:  one round of a roll that feeds SAMPLED rows back instead of the point row, for Bo origins x S paths.  inputs
  *        [Bsrc, W, N], forecast [Bsrc, Q, L, N], fp32 and contiguous; taus = the Q levels as fp32 in HOST memory, read by the call

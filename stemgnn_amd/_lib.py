@@ -89,6 +89,35 @@ def serving_plan(entry, *shape, misaligned=0):
     return {k: int(out[i]) for k, i in {**SG_SERVING_WORD, **SG_SERVING_ENTRY_WORD[entry]}.items()}
 
 
+# entries and words of stemgnn_calibration_plan (SG_CALIBRATION_* in include/stemgnn_hip.h): the common words, then each entry's own
+SG_CALIBRATION_ENTRY = {"fit": 0, "seasonal_fit": 1, "apply": 2, "seasonal_apply": 3, "column": 4}
+SG_CALIBRATION_NSHAPE = {"fit": 6, "seasonal_fit": 9, "apply": 4, "seasonal_apply": 4, "column": 6}
+SG_CALIBRATION_FORM = {"columns": 0, "stream": 1}
+SG_CALIBRATION_BOUND = {"wanted": 0, "size": 1, "grid": 2}
+SG_CALIBRATION_WALK = {"direct": 0, "origins": 1, "one_bucket": 2, "long": 3}
+SG_CALIBRATION_PLAN_WORDS = 32
+SG_CALIBRATION_WORD = {"form": 0, "grid_x": 1, "grid_y": 2, "grid_z": 3, "threads": 4, "vec": 5, "cus": 6}
+_FIT_WORDS = {"KP": 7, "groups": 8, "Cc": 9, "Hr": 10, "L": 11, "G": 12, "tiles": 13, "wd_last": 14, "rpw_full": 15, "rpw_last": 16,
+              "tile": 17, "chunks": 18, "per_chunk": 19, "bound": 20, "trips": 21, "want": 22, "by_size": 23, "blocks_wanted": 24,
+              "pick_blocks": 25, "pick_idle": 26, "rows": 27, "direct": 28, "why": 29, "runs": 30, "walk": 31}
+_APPLY_WORDS = {"needed": 7, "cap": 8, "capped": 9, "trips": 10, "lane_trips": 11, "items": 12}
+SG_CALIBRATION_ENTRY_WORD = {
+    "fit": _FIT_WORDS, "seasonal_fit": _FIT_WORDS, "apply": _APPLY_WORDS, "seasonal_apply": _APPLY_WORDS,
+    "column": {"lds": 7, "planes": 8, "cpb": 9, "wpb": 10, "idle": 11, "col_blocks": 12, "cols_last": 13, "win_blocks": 14,
+               "capped": 15, "win_trips": 16, "tvec": 17, "target_trips": 18, "per": 19},
+}
+
+
+def calibration_plan(entry, *shape, misaligned=0):
+    """stemgnn_calibration_plan as a dict of SG_CALIBRATION_WORD and the entry's SG_CALIBRATION_ENTRY_WORD names; `entry` a key of
+    SG_CALIBRATION_ENTRY, `shape` as the header lists it for that entry, `misaligned` its bit set; raises on SG_EINVAL."""
+    out = (c_int * SG_CALIBRATION_PLAN_WORDS)()
+    args = (c_long * len(shape))(*[int(v) for v in shape])
+    check(load().stemgnn_calibration_plan(SG_CALIBRATION_ENTRY[entry], args, len(shape), int(misaligned), out),
+          f"stemgnn_calibration_plan({entry}, {shape}, {misaligned})")
+    return {k: int(out[i]) for k, i in {**SG_CALIBRATION_WORD, **SG_CALIBRATION_ENTRY_WORD[entry]}.items()}
+
+
 _P = c_void_p          # device pointer
 _PP = POINTER(c_void_p)  # host array of device pointers
 
@@ -256,6 +285,7 @@ SIGNATURES = {
                                        c_longlong, c_double, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P,
                                        _P]),
     "stemgnn_serving_plan": (c_int, [c_int, c_long, c_long, c_long, c_long, c_long, c_long, c_int, POINTER(c_int)]),
+    "stemgnn_calibration_plan": (c_int, [c_int, POINTER(c_long), c_int, c_int, POINTER(c_int)]),
     "stemgnn_scenario_rank": (c_long, [c_double, c_long]),
     "stemgnn_scenario_roll": (c_int, [_P, _P, POINTER(c_float), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_longlong, c_ulonglong, c_ulonglong, c_int, c_int, _P, _P, _P, _P]),

@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "../../include/stemgnn_hip.h"
+#include "calibration_plan.h"
 #include "conformal_args.h"
 #include "conformal_fit.h"
 #include "conformal_select.h"
@@ -75,11 +76,10 @@ extern "C" int stemgnn_conformal_apply(const float* forecast, const float* offse
   if (!cf_shapes_ok(count, Q, H, N, P) || !cf_pairs_ok(Q, P, lo_rows, hi_rows, &roles)) return SG_EINVAL;
   const size_t total = (size_t)count * Q * H * N;
   const CfGrouping gr = cf_grouping(per_step, per_node, H, N);
-  const bool vec = (N & 3) == 0 && sg_aligned16(forecast) && sg_aligned16(out);
-  const size_t items = vec ? total / 4 : total;
-  const size_t cap = (size_t)sg_num_cus() * 8;
-  const unsigned blocks = (unsigned)std::max<size_t>(1, std::min(cap, (items + CF_THREADS - 1) / CF_THREADS));
-  if (vec)
+  CfApplyPlan pl;                                   // VEC, the grid and its cap: calibration_plan.h
+  cf_apply_plan(count, Q, H, N, sg_aligned16(forecast) && sg_aligned16(out), sg_num_cus(), &pl);
+  const unsigned blocks = pl.blocks;
+  if (pl.vec == 4)
     hipLaunchKernelGGL(cf_apply<4>, dim3(blocks), dim3(CF_THREADS), 0, (hipStream_t)stream, forecast, offsets, total, Q, H, N,
                        roles, gr.Hg, gr.Ng, out);
   else

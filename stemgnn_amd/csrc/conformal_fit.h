@@ -33,6 +33,7 @@
 
 #include <algorithm>
 
+#include "calibration_plan.h"
 #include "conformal_args.h"
 #include "conformal_select.h"
 #include "devattr.h"
@@ -40,10 +41,7 @@
 
 namespace {
 
-constexpr int CF_TILE = 32;                 // columns per workgroup (column form)
-constexpr int CF_PITCH = CF_TILE + 1;       // LDS row pitch in words
-constexpr int CF_COPIES = 16;               // histogram copies per workgroup (stream form)
-constexpr int CF_THREADS = 256;
+// CF_TILE, CF_PITCH, CF_COPIES, CF_THREADS and the chunk arithmetic of the host loop: calibration_plan.h
 
 struct CfPairs {                            // travels by value in the kernel arguments
   int lo[CF_MAX_P], hi[CF_MAX_P];
@@ -231,31 +229,25 @@ int cf_fit_run(const float* target, const float* forecast, long count, long long
   uint32_t* prefix = hist + (size_t)PG * 256;
   uint32_t* krem = prefix + PG;
   SG_TRY(sg_zero_async(hist, (size_t)PG * 256 * sizeof(uint32_t), st));
-  const int blocks_wanted = 4 * sg_num_cus();
+  CfFitPlan pl;
+  cf_fit_plan(rows, KP, gr, per_node, sg_num_cus(), &pl);
   for (int d = 0; d < 4; ++d) {
     if (per_node) {
-      const int C = gr.Cc, Hr = gr.Hr, R = (int)(count * Hr), Rw = (int)(rows * Hr);
-      const int tiles = sg_ceil_div(C, CF_TILE);
-      int chunks = sg_ceil_div(blocks_wanted, (long long)tiles * KP);
-      chunks = std::max(1, std::min(std::min(chunks, sg_ceil_div(Rw, 64)), 65535));
-      const int rows_per_chunk = sg_ceil_div(Rw, chunks);
-      const dim3 grid((unsigned)tiles, (unsigned)sg_ceil_div(Rw, rows_per_chunk), (unsigned)KP);
+      const int C = gr.Cc, Hr = gr.Hr, R = (int)(count * Hr);
+      const dim3 grid((unsigned)pl.tiles, (unsigned)pl.launched, (unsigned)KP);
       auto kernel = masked ? cf_hist_columns<true, Season> : cf_hist_columns<false, Season>;
       hipLaunchKernelGGL(kernel, grid, dim3(CF_THREADS), 0, st, target, forecast, R, C, Hr, Q, HN, pairs, d, prefix, krem, hist,
-                         rows_per_chunk, sn);
+                         pl.per_chunk, sn);
     } else {
       const int L = gr.L;
-      const int M = (int)(count * L), Mw = (int)(rows * L);
-      int chunks = sg_ceil_div(blocks_wanted, PG);
-      chunks = std::max(1, std::min(chunks, sg_ceil_div(Mw, 4 * CF_THREADS)));
-      const int per_chunk = sg_ceil_div(Mw, chunks);
-      const dim3 grid((unsigned)sg_ceil_div(Mw, per_chunk), (unsigned)G, (unsigned)KP);
+      const int M = (int)(count * L);
+      const dim3 grid((unsigned)pl.launched, (unsigned)G, (unsigned)KP);
       auto kernel = masked ? cf_hist_stream<true, Season> : cf_hist_stream<false, Season>;
       hipLaunchKernelGGL(kernel, grid, dim3(CF_THREADS), 0, st, target, forecast, M, L, G, Q, HN, pairs, d, prefix, krem, hist,
-                         per_chunk, sn);
+                         pl.per_chunk, sn);
     }
     SG_TRY(hipGetLastError());
-    hipLaunchKernelGGL(cf_pick, dim3((unsigned)sg_ceil_div(PG, CF_THREADS / 64)), dim3(CF_THREADS), 0, st, hist, prefix, krem,
+    hipLaunchKernelGGL(cf_pick, dim3(pl.pick_blocks), dim3(CF_THREADS), 0, st, hist, prefix, krem,
                        (int)PG, G, pairs, d, offsets, counts, P);
     SG_TRY(hipGetLastError());
   }

@@ -30,6 +30,7 @@
 
 #include <algorithm>
 
+#include "calibration_plan.h"
 #include "conformal_args.h"
 #include "conformal_select.h"
 #include "devattr.h"
@@ -37,10 +38,7 @@
 
 namespace {
 
-constexpr int QC_THREADS = 256;             // the most; fewer (a multiple of 64) when Q is large: see qc_launch
-constexpr int QC_CHUNK = 4;                 // rows whose global loads are in flight together
-constexpr int QC_LDS_BYTES = 32 * 1024;     // per workgroup, both planes
-constexpr int QC_VEC_MAX_Q = 16;
+// QC_THREADS, QC_CHUNK, QC_LDS_BYTES, QC_VEC_MAX_Q and the workgroup geometry of qc_launch: calibration_plan.h
 
 struct QcArgs {                             // travels by value in the kernel arguments
   const float* src;                         // [count or B, Q, H, N]
@@ -149,7 +147,7 @@ __global__ __launch_bounds__(QC_THREADS) void qc_kernel(const QcArgs a, const Se
 
 // the vector form needs N % 4 == 0, Q <= 16 and both buffers 16-byte aligned
 inline bool qc_vec_ok(int N, int Q, const void* src, const void* dst) {
-  return (N & 3) == 0 && Q <= QC_VEC_MAX_Q && sg_aligned16(src) && sg_aligned16(dst);
+  return qc_vec_shape_ok(N, Q) && sg_aligned16(src) && sg_aligned16(dst);
 }
 
 // the two stages of a column: fills offsets and Q .. Ng of `a`; the roles are the caller's (cf_pairs_ok)
@@ -169,28 +167,22 @@ inline void qc_store_to(QcArgs* a, const float* target, const long long* pos, fl
   a->out_target = out_target;
   a->pos = pos;
   a->capacity = capacity;
-  a->tvec = (a->HN & 3) == 0 && sg_aligned16(target) && sg_aligned16(out_target);
+  a->tvec = qc_tvec_shape_ok(a->HN) && sg_aligned16(target) && sg_aligned16(out_target);
 }
 
 // fills the workgroup geometry of `a` and launches; `a` is a store when it has pos
 template <class Season>
 int qc_launch(QcArgs& a, long count, bool vec, const Season& sn, hipStream_t st) {
-  const bool store = a.pos != nullptr;
-  const int VEC = vec ? 4 : 1, planes = a.rearrange ? 2 : 1;
-  int T = QC_THREADS;
-  while (T > 64 && (size_t)T * a.Q * VEC * 4 * planes > (size_t)QC_LDS_BYTES) T -= 64;
-  const size_t lds = (size_t)T * a.Q * VEC * 4 * planes;                 // <= 32 KB: Q <= 32 (VEC 1), Q <= 16 (VEC 4)
-  const int per = a.HN / VEC;                                            // column groups per window
+  QcPlan pl;                                        // threads, LDS, the workgroup's shape and the grid: calibration_plan.h
+  qc_plan(count, a.Q, a.HN, a.rearrange != 0, vec, a.pos != nullptr, sg_num_cus(), &pl);
   a.count = count;
-  a.cpb = std::min(per, T);
-  a.wpb = T / a.cpb;
-  a.col_blocks = sg_ceil_div(per, a.cpb);
-  const long long wins = ((long long)count + a.wpb - 1) / a.wpb;
-  const long long cap = (long long)sg_num_cus() * 16;
-  a.win_blocks = (int)std::max<long long>(1, std::min(wins, cap / a.col_blocks));
-  const dim3 grid((unsigned)a.col_blocks * (unsigned)a.win_blocks, store ? 2 : 1);
+  a.cpb = pl.cpb;
+  a.wpb = pl.wpb;
+  a.col_blocks = pl.col_blocks;
+  a.win_blocks = pl.win_blocks;
+  const dim3 grid(pl.gx, pl.gy);
   auto kernel = vec ? qc_kernel<4, Season> : qc_kernel<1, Season>;
-  hipLaunchKernelGGL(kernel, grid, dim3(T), lds, st, a, sn);
+  hipLaunchKernelGGL(kernel, grid, dim3(pl.T), pl.lds, st, a, sn);
   SG_TRY(hipGetLastError());
   return 0;
 }

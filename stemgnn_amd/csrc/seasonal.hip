@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "../../include/stemgnn_hip.h"
+#include "calibration_plan.h"
 #include "conformal_args.h"
 #include "conformal_fit.h"
 #include "conformal_select.h"
@@ -35,7 +36,7 @@
 
 namespace {
 
-constexpr int SS_THREADS = 256;
+// SS_THREADS, the choice between the two walks of the fit and the grids of the applies: calibration_plan.h
 
 // where a row's origin comes from, and the season; by value.  origin0 has been reduced into [0, period) by the host (the bucket
 // depends on t mod period only), so origin0 + i + h stays far from any overflow.
@@ -208,12 +209,11 @@ extern "C" int stemgnn_seasonal_fit(const float* target, const float* forecast, 
   const CfGrouping gr = cf_grouping(per_step, per_node, H, N);
   if (!per_node && gr.groups() > 65535) return SG_EINVAL;              // grid.y of the stream form
   const SsTime tm = ss_time(origins, nullptr, origin0, period, K, phase);
-  // consecutive origins: a bucket's rows are enumerated when that walks fewer rows than skipping through all of them does
-  // (runs * the longest bucket against count; measured in DESIGN 5n), otherwise -- and always for an origins tensor -- skipped
-  const SsDirect dr = {(int)count, (int)(count / period) + 2};
-  const long long walk = (long long)dr.runs * ((period + K - 1) / K);    // virtual rows of the longest bucket
-  if (!origins && K >= 2 && 2 * walk <= (long long)count)
-    return cf_fit_run(target, forecast, count, walk, Q, H, N, P, K * P, pairs, gr, per_node != 0, masked != 0,
+  // DIRECT (a bucket's rows enumerated) or skipping through all of them: ss_fit_walk of calibration_plan.h
+  const SsFitWalk wk = ss_fit_walk(count, period, K, origins != nullptr);
+  const SsDirect dr = {(int)count, wk.runs};
+  if (wk.direct)
+    return cf_fit_run(target, forecast, count, wk.walk, Q, H, N, P, K * P, pairs, gr, per_node != 0, masked != 0,
                       SsWalk<true>{N, P, tm, dr}, scratch, offsets, counts, (hipStream_t)stream);
   return cf_fit_run(target, forecast, count, count, Q, H, N, P, K * P, pairs, gr, per_node != 0, masked != 0,
                     SsWalk<false>{N, P, tm, dr}, scratch, offsets, counts, (hipStream_t)stream);
@@ -233,11 +233,11 @@ extern "C" int stemgnn_seasonal_apply(const float* forecast, const float* offset
     a.dst = out;
     return qc_launch(a, count, qc_vec_ok(N, Q, forecast, out), SsSlice{tm, (size_t)P * a.Hg * a.Ng}, (hipStream_t)stream);
   }
-  const bool aligned = (N & 3) == 0 && sg_aligned16(forecast) && sg_aligned16(out);
+  CfApplyPlan pl;                                   // VEC, the grid and its cap: calibration_plan.h
+  ss_apply_plan(count, Q, H, N, sg_aligned16(forecast) && sg_aligned16(out), sg_num_cus(), &pl);
   const long long segments = (long long)count * H;
-  const long long cap = (long long)sg_num_cus() * 8;
-  const unsigned blocks = (unsigned)std::max<long long>(1, std::min(cap, (segments + SS_THREADS / 64 - 1) / (SS_THREADS / 64)));
-  if (aligned)
+  const unsigned blocks = pl.blocks;
+  if (pl.vec == 4)
     hipLaunchKernelGGL(ss_apply<4>, dim3(blocks), dim3(SS_THREADS), 0, (hipStream_t)stream, forecast, offsets, segments, Q, H, N,
                        a.roles, P, a.Hg, a.Ng, tm, out);
   else
@@ -262,4 +262,81 @@ extern "C" int stemgnn_quantile_store_seasonal(const float* steps, const float* 
   qc_store_to(&a, target, pos, out_target, capacity);
   const SsSlice sn = {ss_time(nullptr, t_dev, 0, period, K, phase), (size_t)P * a.Hg * a.Ng};
   return qc_launch(a, B, qc_vec_ok(N, Q, steps, out_forecast), sn, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// What the launchers of the batch side -- this file's, conformal.hip's and quantile_serve.hip's -- do for a shape
+// (include/stemgnn_hip.h: stemgnn_calibration_plan): host only, nothing is launched or read.  Every number comes from the
+// function of calibration_plan.h the launcher itself calls, with the compute-unit count the launcher itself asks for.
+static inline bool cp_int(long v) { return v >= 0 && v <= 0x7fffffffl; }
+
+extern "C" int stemgnn_calibration_plan(int entry, const long* shape, int nshape, int misaligned, int* out) {
+  static const int want[] = {6, 9, 4, 4, 6};
+  if (!out || !shape || misaligned < 0 || entry < 0 || entry > SG_CALIBRATION_COLUMN || nshape != want[entry]) return SG_EINVAL;
+  for (int i = 1; i < nshape; ++i)
+    if (!(cp_int(shape[i]) || (entry == SG_CALIBRATION_SEASONAL_FIT && i == 6))) return SG_EINVAL;
+  int w[SG_CALIBRATION_PLAN_WORDS] = {};
+  const long count = shape[0];
+  const int i1 = (int)shape[1], i2 = (int)shape[2], i3 = (int)shape[3];
+  const int cus = sg_num_cus();
+  w[6] = cus;
+  switch (entry) {
+    case SG_CALIBRATION_FIT:
+    case SG_CALIBRATION_SEASONAL_FIT: {             // (count, H, N, P, per_step, per_node [, period, K, has_origins])
+      const int H = i1, N = i2, P = i3, per_step = shape[4] != 0, per_node = shape[5] != 0;
+      if (misaligned || !cf_shapes_ok(count, 1, H, N, P)) return SG_EINVAL;
+      const CfGrouping gr = cf_grouping(per_step, per_node, H, N);
+      if (!per_node && gr.groups() > 65535) return SG_EINVAL;
+      int KP = P;
+      long long walked = count;
+      if (entry == SG_CALIBRATION_FIT) {
+        if ((long long)P * (long long)gr.groups() >= (1ll << 31) / 4) return SG_EINVAL;
+        w[28] = 0, w[29] = -1;
+      } else {
+        const long long period = shape[6];
+        const int K = (int)shape[7];
+        if (!ss_season_ok(period, K, 0) || !ss_sizes_ok(H, N, P, K, per_step, per_node)) return SG_EINVAL;
+        const SsFitWalk wk = ss_fit_walk(count, period, K, shape[8] != 0);
+        KP = K * P, walked = wk.walked;
+        w[28] = wk.direct, w[29] = wk.why, w[30] = wk.runs, w[31] = (int)std::min<long long>(wk.walk, 0x7fffffff);
+      }
+      CfFitPlan p;
+      cf_fit_plan(walked, KP, gr, per_node != 0, cus, &p);
+      w[0] = p.form, w[4] = CF_THREADS, w[3] = KP;
+      if (p.form == 0) w[1] = p.tiles, w[2] = p.launched;
+      else w[1] = p.launched, w[2] = p.G;
+      w[7] = KP, w[8] = p.G, w[9] = gr.Cc, w[10] = gr.Hr, w[11] = gr.L, w[12] = gr.G;
+      w[13] = p.tiles, w[14] = p.wd_last, w[15] = p.rpw_full, w[16] = p.rpw_last, w[17] = p.form == 0 ? CF_TILE : 0;
+      w[18] = p.chunks, w[19] = p.per_chunk, w[20] = p.bound, w[21] = p.trips, w[22] = p.want, w[23] = p.by_size;
+      w[24] = p.blocks_wanted, w[25] = (int)p.pick_blocks, w[26] = p.pick_idle, w[27] = p.rows;
+      break;
+    }
+    case SG_CALIBRATION_APPLY:
+    case SG_CALIBRATION_SEASONAL_APPLY: {           // (count, Q, H, N); misaligned: bit 0 forecast, bit 1 out
+      if (misaligned > 3 || !cf_shapes_ok(count, i1, i2, i3, 1)) return SG_EINVAL;
+      CfApplyPlan p;
+      if (entry == SG_CALIBRATION_APPLY) cf_apply_plan(count, i1, i2, i3, misaligned == 0, cus, &p);
+      else ss_apply_plan(count, i1, i2, i3, misaligned == 0, cus, &p);
+      w[1] = (int)p.blocks, w[2] = w[3] = 1, w[4] = entry == SG_CALIBRATION_APPLY ? CF_THREADS : SS_THREADS, w[5] = p.vec;
+      w[7] = (int)std::min<long long>(p.needed, 0x7fffffff), w[8] = (int)p.cap, w[9] = p.capped;
+      w[10] = (int)std::min<long long>(p.trips, 0x7fffffff), w[11] = p.lane_trips, w[12] = p.items;
+      break;
+    }
+    case SG_CALIBRATION_COLUMN: {                   // (count, Q, H, N, rearrange, store); misaligned: src, dst, target, out_target
+      const int Q = i1, H = i2, N = i3, store = shape[5] != 0;
+      if (count <= 0 || !cp_int(count) || Q <= 0 || H <= 0 || N <= 0 || Q > CF_MAX_Q || (long long)H * N >= (1ll << 31)) return SG_EINVAL;
+      if (misaligned > (store ? 15 : 3)) return SG_EINVAL;
+      QcPlan p;
+      qc_plan(count, Q, H * N, shape[4] != 0, qc_vec_shape_ok(N, Q) && (misaligned & 3) == 0, store, cus, &p);
+      w[1] = (int)p.gx, w[2] = (int)p.gy, w[3] = 1, w[4] = p.T, w[5] = p.vec;
+      w[7] = (int)p.lds, w[8] = p.planes, w[9] = p.cpb, w[10] = p.wpb, w[11] = p.idle, w[12] = p.col_blocks, w[13] = p.cols_last;
+      w[14] = p.win_blocks, w[15] = p.capped, w[16] = (int)std::min<long long>(p.win_trips, 0x7fffffff);
+      w[17] = store ? ((qc_tvec_shape_ok(H * N) && (misaligned & 12) == 0) ? 4 : 1) : 0;
+      w[18] = (int)std::min<long long>(p.target_trips, 0x7fffffff), w[19] = p.per;
+      break;
+    }
+    default: return SG_EINVAL;
+  }
+  for (int i = 0; i < SG_CALIBRATION_PLAN_WORDS; ++i) out[i] = w[i];
+  return 0;
 }

@@ -1,13 +1,15 @@
 """GPU: conformal calibration of quantile bands (csrc/conformal.hip, math_utils.ConformalCalibrator, the trainer plumbing)
-against the numpy restatement of its definition below.  The offset is a k-th smallest fp32 value, so every offset comparison
-is equality as numbers (np.array_equal: inf == inf, -0 == +0) and the counts are equal -- no tolerance anywhere."""
+against the numpy restatement of its definition (tests/helpers/conformal_ref.py).  The offset is a k-th smallest fp32 value, so
+every offset comparison is equality as numbers (np.array_equal: inf == inf, -0 == +0) and the counts are equal -- no tolerance
+anywhere."""
 import ctypes
-import math
 import types
 
 import numpy as np
 import pytest
 import torch
+
+from tests.helpers.conformal_ref import apply_np, fit_np, rank, scores_np  # the definition, in numpy
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -16,54 +18,10 @@ GROUPINGS = ((True, False), (False, False), (True, True), (False, True))        
 LEVELS = {2: (0.1, 0.9), 3: (0.1, 0.5, 0.9), 5: (0.05, 0.25, 0.5, 0.75, 0.95)}
 
 
-# ---- the definition, in numpy ---------------------------------------------------------------------------------------------
 def pairs_of(quantiles):
     Q = len(quantiles)
     pairs = tuple((i, Q - 1 - i) for i in range(Q // 2))
     return pairs, [float(quantiles[hi]) - float(quantiles[lo]) for lo, hi in pairs]
-
-
-def rank(m, c):
-    t = (m + 1) * c
-    return math.ceil(t * (1 - 1e-12))
-
-
-def scores_np(y, f, lo, hi):
-    """fp32: two rounded subtractions and a max; a NaN score counts as +inf"""
-    with np.errstate(invalid="ignore", over="ignore"):
-        s = np.maximum(f[:, lo] - y, y - f[:, hi])               # np.maximum propagates NaN
-    assert s.dtype == np.float32
-    return np.where(np.isnan(s), INF, s)
-
-
-def fit_np(y, f, pairs, coverage, per_step, per_node, masked):
-    C, H, N = y.shape
-    Hg, Ng = (H if per_step else 1), (N if per_node else 1)
-    offsets = np.empty((len(pairs), Hg, Ng), np.float32)
-    counts = np.empty((len(pairs), Hg, Ng), np.int64)
-    keep = ~np.isnan(y) if masked else np.ones(y.shape, bool)
-    for p, (lo, hi) in enumerate(pairs):
-        s = scores_np(y, f, lo, hi)
-        for hg in range(Hg):
-            hs = slice(hg, hg + 1) if per_step else slice(None)
-            for ng in range(Ng):
-                ns = slice(ng, ng + 1) if per_node else slice(None)
-                v = np.sort(s[:, hs, ns][keep[:, hs, ns]])
-                k = rank(v.size, coverage[p])
-                counts[p, hg, ng] = v.size
-                offsets[p, hg, ng] = INF if k > v.size else v[k - 1]
-    return offsets, counts
-
-
-def apply_np(f, offsets, pairs, per_step, per_node):
-    out = f.copy()
-    with np.errstate(invalid="ignore", over="ignore"):
-        for p, (lo, hi) in enumerate(pairs):
-            off = offsets[p][None]                                # [1, Hg, Ng] broadcasts over the pooled axes
-            out[:, lo] = f[:, lo] - off
-            out[:, hi] = f[:, hi] + off
-    assert out.dtype == np.float32
-    return out
 
 
 # ---- helpers ----------------------------------------------------------------------------------------------------------------
