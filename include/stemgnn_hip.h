@@ -1102,6 +1102,20 @@ size_t stemgnn_copula_scratch_doubles(long M, int N);
 int stemgnn_copula_gram(const float* u, long M, int N, double* scratch, long long* pairs, double* sums, void* stream);
 int stemgnn_copula_uniforms(const float* factor_t, int Bo, int S, int Lsteps, int N, int step, int horizon, long long origin0,
                             unsigned long long seed, unsigned long long offset, float* u, void* stream);
+/* uniforms_steps: the same with the steps of one round coupled as well, a separable Gaussian copula
+ * over (step, node): the normal scores of a path's round have correlation T[j][j'] * R[n][n'].  step_factor [Lsteps, Lsteps]
+ * fp32 row-major, step_factor[j * Lsteps + i] = A[j][i], A the lower Cholesky factor of T; the entries with i > j are never
+ * read.  For path (b, s):
+ *   e[j][k] = the e_k of stemgnn_copula_uniforms for (origin0 + b, s, step + j, k): the same Philox word, the same counter map
+ *   g[j][k] = sum_{i <= j} A[j][i] * e[i][k], fp32 FMAs with i ascending from 0, the sum starting at 0.f
+ *   z[j][n] = sum_{k <= n} L[n][k] * g[j][k], in stemgnn_copula_uniforms' order
+ *   u[b, s, j, n] = normcdff(z[j][n]) clamped to [2^-24, 1 - 2^-24].
+ * With A the identity the result is stemgnn_copula_uniforms', bit for bit.  A workgroup owns whole paths: Lsteps <= 16 for
+ * N <= 512 and Lsteps <= 4 for 512 < N <= 2048; anything else, a NULL step_factor and whatever stemgnn_copula_uniforms refuses
+ * is SG_EINVAL with nothing launched.  One launch, no scratch, no atomics; capturable. */
+int stemgnn_copula_uniforms_steps(const float* factor_t, const float* step_factor, int Bo, int S, int Lsteps, int N, int step,
+                                  int horizon, long long origin0, unsigned long long seed, unsigned long long offset, float* u,
+                                  void* stream);
 
 /* ---- ensemble scores of scenario paths: CRPS, energy score, rank histogram (csrc/ensemble.hip) --------
  * target [count, H, N] and paths [count, S, H, N] (stemgnn_scenario_roll's layout), fp32 and contiguous, 1 <= S <= 1024; optional

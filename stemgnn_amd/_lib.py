@@ -297,6 +297,8 @@ SIGNATURES = {
     "stemgnn_copula_gram": (c_int, [_P, c_long, c_int, _P, _P, _P, _P]),
     "stemgnn_copula_uniforms": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_longlong, c_ulonglong, c_ulonglong, _P,
                                         _P]),
+    "stemgnn_copula_uniforms_steps": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_longlong, c_ulonglong,
+                                              c_ulonglong, _P, _P]),
     "stemgnn_ensemble_scratch_doubles": (c_size_t, [c_long, c_int, c_int, c_int]),
     "stemgnn_ensemble_out_doubles": (c_size_t, [c_int]),
     "stemgnn_ensemble_scores": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),

@@ -14,6 +14,9 @@
 //           thread e_k of four rows); threads run along n with the rows' sums in registers and read row k of factor_t as a
 //           coalesced run (eight rows requested ahead), k ascending from 0: the order of a sum depends on n alone.  Entries
 //           with k > n are never used (a select after the load, not a product with 0).
+// uniforms_steps: the same kernel body with the steps of a path coupled too.  A tile then holds whole
+//           paths, floor(RT / Lsteps) of them, and between the fill and the node sum one thread per (k, path) replaces the path's
+//           Lsteps words of LDS row k by A times them, in place.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -63,6 +66,8 @@ struct CpUniArgs {
   unsigned long long origin0, seed, offset;
   long long rows;                           // Bo * S * Lsteps
   int S, Lsteps, N, step, horizon;
+  const float* step_factor;                 // [Lsteps, Lsteps], step_factor[j * Lsteps + i] = A[j][i]; the STEPS kernels only
+  int tile_rows;                            // (RT / Lsteps) * Lsteps: the rows of a tile that whole paths fill; STEPS only
 };
 
 // keeps a NaN, unlike fminf / fmaxf
@@ -193,19 +198,23 @@ __global__ __launch_bounds__(CP_THREADS) void cp_gram_finish_kernel(const CpGram
 }
 
 // RT rows per workgroup (a multiple of 4: e is read four rows at a time); a thread owns the nodes t, t + 256, ..
-template <int RT>
+// STEPS: a tile holds whole paths, a.tile_rows = (RT / Lsteps) * Lsteps live rows (the rest is padding, neither drawn nor stored),
+// and the steps of a path are mixed on e in LDS between the fill and the node sum: e[j] <- sum_{i <= j} A[j][i] e[i], i ascending,
+// walking j downwards, so that every e[i] a row still needs is the drawn one.
+template <int RT, bool STEPS>
 __global__ __launch_bounds__(CP_THREADS) void cp_uniforms_kernel(const CpUniArgs a) {
   static_assert(RT % 4 == 0, "e is read as float4 over the rows");
   extern __shared__ float4 cp_lds[];
   float* e = reinterpret_cast<float*>(cp_lds);                // [N][RT]
   const int t = threadIdx.x, N = a.N;
   const int nq = (N + 3) >> 2;                                // Philox calls of a row
-  const long long row0 = (long long)blockIdx.x * RT;
+  const int used = STEPS ? a.tile_rows : RT;                  // the tile's rows that stand for rows of u
+  const long long row0 = (long long)blockIdx.x * used;
   for (int it = t; it < RT * nq; it += CP_THREADS) {
     const int r = it / nq, g = it - r * nq;
     const long long row = row0 + r;
     float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (row < a.rows) {
+    if (r < used && row < a.rows) {
       const unsigned long long p = (unsigned long long)(row / a.Lsteps);        // the path b * S + s
       const unsigned long long j = (unsigned long long)(row - (long long)p * a.Lsteps);
       const unsigned long long b = p / (unsigned)a.S, s = p - b * (unsigned)a.S;
@@ -221,6 +230,22 @@ __global__ __launch_bounds__(CP_THREADS) void cp_uniforms_kernel(const CpUniArgs
       if (4 * g + k < N) e[(4 * g + k) * RT + r] = v[k];
   }
   __syncthreads();
+  if constexpr (STEPS) {
+    // one thread per (node, path of the tile): Lsteps words of one LDS row, in place.  step_factor is read at indices that
+    // do not depend on the thread, and only at i <= j.
+    const int Ls = a.Lsteps, PT = used / Ls;
+    for (int it = t; it < N * PT; it += CP_THREADS) {
+      const int k = it / PT, pl = it - k * PT;
+      float* ep = e + k * RT + pl * Ls;
+      for (int j = Ls - 1; j >= 0; --j) {
+        const float* aj = a.step_factor + j * Ls;
+        float g = 0.f;
+        for (int i = 0; i <= j; ++i) g = fmaf(aj[i], ep[i], g);
+        ep[j] = g;
+      }
+    }
+    __syncthreads();
+  }
   for (int n0 = 0; n0 < N; n0 += CP_THREADS) {
     const int n = n0 + t;
     const bool live = n < N;
@@ -254,7 +279,7 @@ __global__ __launch_bounds__(CP_THREADS) void cp_uniforms_kernel(const CpUniArgs
     if (!live) continue;
 #pragma unroll
     for (int r = 0; r < RT; ++r)
-      if (row0 + r < a.rows) a.u[(size_t)(row0 + r) * N + n] = cp_clamp(normcdff(z[r]), CP_U_LO, CP_U_HI);
+      if (r < used && row0 + r < a.rows) a.u[(size_t)(row0 + r) * N + n] = cp_clamp(normcdff(z[r]), CP_U_LO, CP_U_HI);
   }
 }
 
@@ -322,26 +347,50 @@ extern "C" int stemgnn_copula_gram(const float* u, long M, int N, double* scratc
   return 0;
 }
 
-extern "C" int stemgnn_copula_uniforms(const float* factor_t, int Bo, int S, int Lsteps, int N, int step, int horizon,
-                                       long long origin0, unsigned long long seed, unsigned long long offset, float* u,
-                                       void* stream) {
+namespace {
+
+// both uniforms entries: step_factor == nullptr is the entry without a step mix (rows fill the tiles; any Lsteps)
+int cp_uniforms(const float* factor_t, const float* step_factor, int Bo, int S, int Lsteps, int N, int step, int horizon,
+                long long origin0, unsigned long long seed, unsigned long long offset, float* u, void* stream) {
   if (!factor_t || !u) return SG_EINVAL;
   if (Bo <= 0 || Lsteps <= 0 || N <= 0 || N > CP_MAX_N || S < 1 || S > CP_MAX_S || step < 0 || step >= horizon)
     return SG_EINVAL;
   // what an int carries in the kernel: the rows (the grid is at most that), a path's steps
   if (!sg_fits_int((long long)Bo * S * Lsteps) || !sg_fits_int((long long)S * horizon)) return SG_EINVAL;
+  const int RT = N <= CP_WIDE_N ? 16 : 4;                     // N * RT * 4 <= 32 KB
+  if (step_factor && Lsteps > RT) return SG_EINVAL;           // a tile holds whole paths
   CpUniArgs a = {};
   a.factor_t = factor_t; a.u = u;
   a.origin0 = (unsigned long long)origin0; a.seed = seed; a.offset = offset;
   a.rows = (long long)Bo * S * Lsteps;
   a.S = S; a.Lsteps = Lsteps; a.N = N; a.step = step; a.horizon = horizon;
-  const int RT = N <= CP_WIDE_N ? 16 : 4;                     // N * RT * 4 <= 32 KB
-  const dim3 grid((unsigned)sg_ceil_div(a.rows, RT));
+  a.step_factor = step_factor;
+  a.tile_rows = step_factor ? (RT / Lsteps) * Lsteps : RT;
+  const dim3 grid((unsigned)sg_ceil_div(a.rows, a.tile_rows));
   const size_t lds = (size_t)N * RT * 4;
-  if (RT == 16)
-    hipLaunchKernelGGL(cp_uniforms_kernel<16>, grid, dim3(CP_THREADS), lds, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(cp_uniforms_kernel<4>, grid, dim3(CP_THREADS), lds, (hipStream_t)stream, a);
+  hipStream_t st = (hipStream_t)stream;
+  if (RT == 16) {
+    if (step_factor) hipLaunchKernelGGL((cp_uniforms_kernel<16, true>), grid, dim3(CP_THREADS), lds, st, a);
+    else hipLaunchKernelGGL((cp_uniforms_kernel<16, false>), grid, dim3(CP_THREADS), lds, st, a);
+  } else {
+    if (step_factor) hipLaunchKernelGGL((cp_uniforms_kernel<4, true>), grid, dim3(CP_THREADS), lds, st, a);
+    else hipLaunchKernelGGL((cp_uniforms_kernel<4, false>), grid, dim3(CP_THREADS), lds, st, a);
+  }
   SG_TRY(hipGetLastError());
   return 0;
+}
+
+}  // namespace
+
+extern "C" int stemgnn_copula_uniforms(const float* factor_t, int Bo, int S, int Lsteps, int N, int step, int horizon,
+                                       long long origin0, unsigned long long seed, unsigned long long offset, float* u,
+                                       void* stream) {
+  return cp_uniforms(factor_t, nullptr, Bo, S, Lsteps, N, step, horizon, origin0, seed, offset, u, stream);
+}
+
+extern "C" int stemgnn_copula_uniforms_steps(const float* factor_t, const float* step_factor, int Bo, int S, int Lsteps, int N,
+                                             int step, int horizon, long long origin0, unsigned long long seed,
+                                             unsigned long long offset, float* u, void* stream) {
+  if (!step_factor) return SG_EINVAL;
+  return cp_uniforms(factor_t, step_factor, Bo, S, Lsteps, N, step, horizon, origin0, seed, offset, u, stream);
 }

@@ -945,7 +945,8 @@ class QuantileForecastStep(ForecastStep):
 def scenario_rounds(model, window, horizon, paths, origin0, seed, coupling, tails, graph_kw):
     """The rounds of one batch of rolling_scenarios (LiveForecaster.scenarios runs the same on its head window):
     window [Bo,W,N] -> (bands [Bo,Q,horizon,N], paths [Bo,S,horizon,N]).  coupling: "independent", "path", or a fitted
-    math_utils.GaussianCopula, whose correlated uniforms (one ops.copula_uniforms launch per round) then drive the draws."""
+    math_utils.GaussianCopula (or SpaceTimeCopula, which couples the steps of a round as well), whose correlated uniforms (one
+    ops.copula_uniforms launch per round) then drive the draws."""
     quantiles = model.quantiles
     Bo, _, N = window.shape
     copula = None if isinstance(coupling, str) else coupling
@@ -957,6 +958,9 @@ def scenario_rounds(model, window, horizon, paths, origin0, seed, coupling, tail
         if copula.tails != tails:
             raise ValueError(f"scenario_rounds: the copula's tails are {copula.tails!r}, the call's {tails!r}: the transform of "
                              "the fit and the draw must be inverses")
+        coupled = getattr(copula, "steps", None)                # a SpaceTimeCopula: every step of a round needs its row of T
+        if coupled is not None and coupled < model.horizon:
+            raise ValueError(f"scenario_rounds: the copula couples {coupled} steps, a round of the model has {model.horizon}")
     steps = torch.empty(Bo, paths, horizon, N, device=window.device)
     bands = torch.empty(Bo, len(quantiles), horizon, N, device=window.device)
     done, L = 0, None

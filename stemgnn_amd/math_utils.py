@@ -994,7 +994,13 @@ class GaussianCopula:
         return ops.copula_pit(y.contiguous(), y_hat.contiguous(), self.quantiles, self.tails)
 
     def fit(self, y, y_hat):
-        pairs, (s, a, q) = ops.copula_gram(self.pit(y, y_hat))
+        shrunk, R, pairs, factor = self._estimate(self.pit(y, y_hat), self.shrinkage, "GaussianCopula.fit")
+        self._take(shrunk, R, pairs, factor, R.device)
+        return self
+
+    def _estimate(self, u, shrinkage, who):
+        """(shrunk, raw, pairs, fp64 host factor) over the columns of u [.., K]: the estimator of the class docstring"""
+        pairs, (s, a, q) = ops.copula_gram(u)
         m = pairs.double()
         mean = a / m                                                    # mean_i|j; its transpose is mean_j|i (m is symmetric)
         var = q / m - mean * mean
@@ -1003,10 +1009,8 @@ class GaussianCopula:
         R.fill_diagonal_(1.0)
         R = (R + R.T) / 2
         eye = torch.eye(R.shape[0], dtype=R.dtype, device=R.device)
-        shrunk = (1.0 - self.shrinkage) * R + self.shrinkage * eye
-        factor = self._factor(shrunk.cpu().numpy(), "GaussianCopula.fit")
-        self._take(shrunk, R, pairs, factor, R.device)
-        return self
+        shrunk = (1.0 - shrinkage) * R + shrinkage * eye
+        return shrunk, R, pairs, self._factor(shrunk.cpu().numpy(), who)
 
     @staticmethod
     def _factor(R, who):
@@ -1029,27 +1033,31 @@ class GaussianCopula:
     def from_correlation(cls, R, quantiles, tails="linear", device=None):
         """A copula from a prior correlation matrix (numpy or tensor): square, finite, symmetric and of unit diagonal to 1e-6,
         positive definite.  device: where factor_t goes (default: R's when it is a device tensor, else the current HIP device)."""
+        R, factor, device = cls._prior(R, "GaussianCopula.from_correlation", device)
+        self = cls(quantiles, shrinkage=0.0, tails=tails)
+        dev_R = torch.from_numpy(R.copy()).to(device)
+        self._take(dev_R, dev_R.clone(), None, factor, device)
+        return self
+
+    @classmethod
+    def _prior(cls, R, who, device):
+        """A prior correlation matrix validated on the host -> (fp64 numpy matrix, its fp64 factor, the device to use)"""
         if torch.is_tensor(R):
             device = R.device if device is None and R.is_cuda else device
             R = R.detach().cpu().numpy()
         R = np.asarray(R, dtype=np.float64)
         if R.ndim != 2 or R.shape[0] != R.shape[1] or R.shape[0] < 1:
-            raise ValueError(f"GaussianCopula.from_correlation: a square matrix is needed, got shape {R.shape}")
+            raise ValueError(f"{who}: a square matrix is needed, got shape {R.shape}")
         if not np.isfinite(R).all():
-            raise ValueError("GaussianCopula.from_correlation: the matrix has entries that are not finite")
+            raise ValueError(f"{who}: the matrix has entries that are not finite")
         if np.abs(R - R.T).max() > 1e-6:
-            raise ValueError(f"GaussianCopula.from_correlation: the matrix is not symmetric (max |R - R^T| = "
-                             f"{np.abs(R - R.T).max():.3e})")
+            raise ValueError(f"{who}: the matrix is not symmetric (max |R - R^T| = {np.abs(R - R.T).max():.3e})")
         if np.abs(np.diag(R) - 1.0).max() > 1e-6:
-            raise ValueError(f"GaussianCopula.from_correlation: the diagonal is not 1 (max |R_ii - 1| = "
-                             f"{np.abs(np.diag(R) - 1.0).max():.3e})")
-        self = cls(quantiles, shrinkage=0.0, tails=tails)
-        factor = cls._factor(R, "GaussianCopula.from_correlation")
+            raise ValueError(f"{who}: the diagonal is not 1 (max |R_ii - 1| = {np.abs(np.diag(R) - 1.0).max():.3e})")
+        factor = cls._factor(R, who)
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-        dev_R = torch.from_numpy(R.copy()).to(device)
-        self._take(dev_R, dev_R.clone(), None, factor, device)
-        return self
+        return R, factor, device
 
     def uniforms(self, Bo, S, L, step, horizon, origin0, seed, offset=0):
         if self.factor_t is None:
@@ -1062,6 +1070,9 @@ class GaussianCopula:
                     factor_t=self.factor_t)
 
     def load_state_dict(self, state, device=None):
+        if "step_factor" in state:
+            raise ValueError("GaussianCopula.load_state_dict: the state was saved by a SpaceTimeCopula (it holds step_factor); "
+                             "loading it here would drop the step coupling")
         q = tuple(float(t) for t in state["quantiles"])
         if q != self.quantiles or state["tails"] != self.tails:
             raise ValueError(f"GaussianCopula.load_state_dict: saved for levels {q}, tails={state['tails']!r}; this one has "
@@ -1084,6 +1095,139 @@ class GaussianCopula:
     @classmethod
     def from_state_dict(cls, state, device=None):
         return cls(state["quantiles"], state["shrinkage"], state["tails"], state["min_pairs"]).load_state_dict(state, device)
+
+
+class SpaceTimeCopula(GaussianCopula):
+    """The dependence between nodes AND between the steps of one round: a separable Gaussian copula over (step, node).
+
+    `GaussianCopula` couples the nodes of one (path, step) row; the H = model.horizon steps a path draws in one round are still
+    independent of one another, although real h-step errors from one origin are strongly correlated.  Here the normal scores of
+    one round of one path have correlation T[j, j'] * R[n, n']: R the node matrix of `GaussianCopula`, T an H x H matrix over the
+    steps.  Every (step, node) keeps exactly the predicted marginal.  Between rounds the dependence stays what the roll creates
+    (the next round is conditioned on the drawn window).  It goes wherever a `GaussianCopula` goes as `coupling=`;
+    `path_energy_score` is the score that ranks it (CRPS and the per-step `EnsembleScores.energy` do not see steps).
+
+    fit(y, y_hat): the node part is `GaussianCopula.fit`'s, bit for bit.  The step part takes the same u = pit(y, y_hat)
+    [count, H, N] with rows (origin, node) and columns h -- `ops.copula_gram(u.transpose(1, 2))` -- through the same
+    elementwise estimator; step_correlation = (1 - step_shrinkage) T + step_shrinkage I, its fp64 Cholesky factor taken on the
+    host and cast to fp32 as step_factor [H, H].
+    from_correlations(R, T, quantiles, tails): prior matrices instead of a fit, both validated on the host.
+    uniforms(Bo, S, L, ...): L <= steps; the leading L x L block of step_factor (the factor of T's leading block) goes to
+    `ops.copula_uniforms(..., step_factor=)`.
+    New attributes: step_correlation (fp64 [H, H], device), step_correlation_raw, step_pairs (int64; None from a prior),
+    step_factor (fp32 [H, H], lower triangular), steps (= H)."""
+
+    def __init__(self, quantiles, shrinkage=0.05, step_shrinkage=0.0, tails="linear", min_pairs=8):
+        super().__init__(quantiles, shrinkage=shrinkage, tails=tails, min_pairs=min_pairs)
+        if not 0.0 <= float(step_shrinkage) <= 1.0:
+            raise ValueError(f"SpaceTimeCopula: step_shrinkage must be within [0, 1], got {step_shrinkage}")
+        self.step_shrinkage = float(step_shrinkage)
+        self.step_correlation = self.step_correlation_raw = self.step_pairs = self.step_factor = self.steps = None
+        self._blocks = {}
+
+    def fit(self, y, y_hat):
+        u = self.pit(y, y_hat)
+        shrunk, R, pairs, factor = self._estimate(u, self.shrinkage, "SpaceTimeCopula.fit")
+        steps = self._estimate(u.transpose(1, 2).contiguous(), self.step_shrinkage, "SpaceTimeCopula.fit, the step matrix")
+        self._take(shrunk, R, pairs, factor, R.device)
+        self._take_steps(*steps, R.device)
+        return self
+
+    def _take_steps(self, correlation, raw, pairs, factor, device):
+        self.step_correlation, self.step_correlation_raw, self.step_pairs = correlation, raw, pairs
+        self.step_factor = torch.from_numpy(np.ascontiguousarray(factor.astype(np.float32))).to(device)
+        self.steps = int(factor.shape[0])
+        self._blocks = {}
+
+    @classmethod
+    def from_correlation(cls, R, quantiles, tails="linear", device=None):
+        raise TypeError("SpaceTimeCopula.from_correlation: a step matrix is needed too; call from_correlations(R, T, ...)")
+
+    @classmethod
+    def from_correlations(cls, R, T, quantiles, tails="linear", device=None):
+        """A copula from prior matrices (numpy or tensor): R over the nodes, T over the steps, each square, finite, symmetric
+        and of unit diagonal to 1e-6, positive definite.  device: as for `GaussianCopula.from_correlation`."""
+        R, factor, device = cls._prior(R, "SpaceTimeCopula.from_correlations", device)
+        T, step_factor, _ = cls._prior(T, "SpaceTimeCopula.from_correlations, the step matrix", device)
+        self = cls(quantiles, shrinkage=0.0, step_shrinkage=0.0, tails=tails)
+        dev_R, dev_T = torch.from_numpy(R.copy()).to(device), torch.from_numpy(T.copy()).to(device)
+        self._take(dev_R, dev_R.clone(), None, factor, device)
+        self._take_steps(dev_T, dev_T.clone(), None, step_factor, device)
+        return self
+
+    def uniforms(self, Bo, S, L, step, horizon, origin0, seed, offset=0):
+        if self.factor_t is None or self.step_factor is None:
+            raise ValueError("SpaceTimeCopula.uniforms: not fitted (call fit, from_correlations or load_state_dict first)")
+        L = int(L)
+        if not 1 <= L <= self.steps:
+            raise ValueError(f"SpaceTimeCopula.uniforms: {L} steps in a round, the copula couples {self.steps}")
+        block = self._blocks.get(L)
+        if block is None:                                               # the factor of T's leading block
+            block = self._blocks[L] = self.step_factor[:L, :L].contiguous()
+        return ops.copula_uniforms(self.factor_t, Bo, S, L, step, horizon, origin0=origin0, seed=seed, offset=offset,
+                                   step_factor=block)
+
+    def state_dict(self):
+        return dict(super().state_dict(), step_shrinkage=self.step_shrinkage, steps=self.steps,
+                    step_correlation=self.step_correlation, step_correlation_raw=self.step_correlation_raw,
+                    step_pairs=self.step_pairs, step_factor=self.step_factor)
+
+    STEP_KEYS = ("step_shrinkage", "steps", "step_correlation", "step_correlation_raw", "step_pairs", "step_factor")
+
+    def load_state_dict(self, state, device=None):
+        missing = [k for k in self.STEP_KEYS if k not in state]
+        if missing:
+            raise ValueError(f"SpaceTimeCopula.load_state_dict: the state has no {', '.join(missing)}: it was saved by a "
+                             "GaussianCopula, which couples no steps")
+        f = state["step_factor"]
+        if f is not None and (f.dim() != 2 or f.shape[0] != f.shape[1] or
+                              tuple(state["step_correlation"].shape) != tuple(f.shape)):
+            raise ValueError(f"SpaceTimeCopula.load_state_dict: step_factor {tuple(f.shape)} / step_correlation "
+                             f"{tuple(state['step_correlation'].shape)} are not one square shape")
+        GaussianCopula.load_state_dict(self, {k: v for k, v in state.items() if k not in self.STEP_KEYS}, device)
+
+        def put(t, dtype):
+            if t is None:
+                return None
+            return t.detach().to(device=t.device if device is None else device, dtype=dtype).contiguous().clone()
+
+        self.step_correlation = put(state["step_correlation"], torch.float64)
+        self.step_correlation_raw = put(state["step_correlation_raw"], torch.float64)
+        self.step_pairs, self.step_factor = put(state["step_pairs"], torch.int64), put(f, torch.float32)
+        self.steps = None if f is None else int(f.shape[0])
+        self._blocks = {}
+        return self
+
+    @classmethod
+    def from_state_dict(cls, state, device=None):
+        if "step_shrinkage" not in state:
+            raise ValueError("SpaceTimeCopula.from_state_dict: the state has no step_shrinkage: it was saved by a "
+                             "GaussianCopula, which couples no steps")
+        return cls(state["quantiles"], state["shrinkage"], state["step_shrinkage"], state["tails"],
+                   state["min_pairs"]).load_state_dict(state, device)
+
+
+def path_energy_score(target, paths, mul=None, add=None, ignore_nan=False, fair=False):
+    """The energy score of whole trajectories: target [count, H, N] and paths [count, S, H, N] scored as count rows of H * N
+    values, so that the dependence across steps counts as the dependence across nodes does in `EnsembleScores.energy` -- the
+    one score that ranks step couplings (`SpaceTimeCopula` against `GaussianCopula`).  `ops.ensemble_scores` on the views
+    [count, 1, H * N] and [count, S, 1, H * N]; mul / add [N] are repeated for every step.  Returns the mean over the origins
+    as a numpy float64 (one sync).  ignore_nan, fair: as for `EnsembleScores`."""
+    paths = _as_f32(paths)
+    target = _as_f32(target, like=paths)
+    if target.dim() != 3 or paths.dim() != 4 or (paths.shape[0],) + tuple(paths.shape[2:]) != tuple(target.shape):
+        raise ValueError(f"path_energy_score: target must be [count, H, N] and paths [count, S, H, N], got "
+                         f"{tuple(target.shape)} / {tuple(paths.shape)}")
+    count, S, H, N = paths.shape
+    if (mul is None) != (add is None):
+        raise ValueError("path_energy_score: mul and add go together")
+    if mul is not None:
+        mul, add = (torch.as_tensor(v).reshape(-1).repeat(H) for v in (mul, add))
+        if mul.numel() != H * N or add.numel() != H * N:
+            raise ValueError(f"path_energy_score: mul and add must hold {N} values")
+    out, _ = ops.ensemble_scores(target.contiguous().view(count, 1, H * N), paths.contiguous().view(count, S, 1, H * N), mul, add,
+                                 ignore_nan=bool(ignore_nan), fair=bool(fair))
+    return np.float64(out[1].item())
 
 
 class ConformalCalibrator:

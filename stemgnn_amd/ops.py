@@ -2005,21 +2005,36 @@ def copula_gram(u):
     return pairs, sums
 
 
-def copula_uniforms(factor_t, Bo, S, L, step, horizon, origin0=0, seed=0, offset=0):
+def copula_uniforms(factor_t, Bo, S, L, step, horizon, origin0=0, seed=0, offset=0, step_factor=None):
     """The correlated uniforms of one round (``stemgnn_copula_uniforms``): factor_t [N,N] float32 with factor_t[k, n] = L[n, k],
     L the lower Cholesky factor of the nodes' correlation matrix (the entries with k > n are never read into the result) ->
     u [Bo,S,L,N] = normcdf(L e) clamped to [2^-24, 1 - 2^-24], e the standard normal of the Philox word that
-    coupling="independent" takes for that (global origin, path, step, node)."""
+    coupling="independent" takes for that (global origin, path, step, node).  step_factor: a contiguous float32 [L,L] tensor on
+    factor_t's device, the lower Cholesky factor A of a correlation over the round's steps (entries above the diagonal are never
+    read); the L steps of a path are then coupled as well, e <- A e along the steps ahead of the node sum
+    (``stemgnn_copula_uniforms_steps``; L <= 16 for N <= 512, L <= 4 beyond)."""
     lib = _lib.load()
     _require_gpu(factor_t, "factor_t")
     if factor_t.dim() != 2 or factor_t.shape[0] != factor_t.shape[1] or not factor_t.is_contiguous():
         raise _lib.StemGNNHipError(f"copula_uniforms: factor_t must be a contiguous [N,N] tensor, got {tuple(factor_t.shape)}")
     N = factor_t.shape[0]
+    if step_factor is not None and (not torch.is_tensor(step_factor) or tuple(step_factor.shape) != (int(L), int(L)) or
+                                    step_factor.dtype != torch.float32 or step_factor.device != factor_t.device or
+                                    not step_factor.is_contiguous()):
+        got = f"{step_factor.dtype} {tuple(step_factor.shape)} on {step_factor.device}" if torch.is_tensor(step_factor) else \
+            type(step_factor).__name__
+        raise _lib.StemGNNHipError(f"copula_uniforms: step_factor must be a contiguous float32 {(int(L), int(L))} tensor on "
+                                   f"factor_t's device, got {got}")
     u = torch.empty(int(Bo), int(S), int(L), N, device=factor_t.device, dtype=torch.float32)
     mask = (1 << 64) - 1
-    _lib.check(lib.stemgnn_copula_uniforms(factor_t.data_ptr(), int(Bo), int(S), int(L), N, int(step), int(horizon),
-                                           int(origin0), int(seed) & mask, int(offset) & mask, u.data_ptr(), _stream()),
-               "copula_uniforms")
+    if step_factor is None:
+        _lib.check(lib.stemgnn_copula_uniforms(factor_t.data_ptr(), int(Bo), int(S), int(L), N, int(step), int(horizon),
+                                               int(origin0), int(seed) & mask, int(offset) & mask, u.data_ptr(), _stream()),
+                   "copula_uniforms")
+    else:
+        _lib.check(lib.stemgnn_copula_uniforms_steps(factor_t.data_ptr(), step_factor.data_ptr(), int(Bo), int(S), int(L), N,
+                                                     int(step), int(horizon), int(origin0), int(seed) & mask, int(offset) & mask,
+                                                     u.data_ptr(), _stream()), "copula_uniforms")
     return u
 
 
